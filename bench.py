@@ -4,6 +4,7 @@ clips (BASELINE.json: 64x64, 16-frame clips; cfg2 = MNIST f4 VQ-VAE + MAGE, batc
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3] [--scaling weak|strong]
                     [--batch 64] [--global-batch 256] [--frames 16] [--precision bf16|fp32] [--ar-mode full|incremental]
+                    [--dump-outputs DIR]
 
 One "step" = one autoregressive_generate(batch) call: VQ-VAE encode of the first frames + text encoder +
 motion-anchor encoder + the reference's L-1 full decoder recomputes + VQ-VAE decode of the L-1 generated
@@ -514,7 +515,35 @@ def parse():
     ap.add_argument("--trained-steps", type=int, default=300, help="training steps of the trained-weights token-agreement leg (0 = skip; rank 0 at N = 1, with the CPU baseline)")
     ap.add_argument("--cpu-clips", type=int, default=4, help="clips of the CPU baseline sample (4 = SURVEY cfg1, the reference's CPU-runnable batch)")
     ap.add_argument("--trained-clips", type=int, default=16, help="held-out clips of the trained-weights token-agreement leg (each costs ~6 s of CPU oracle)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed autoregressive_generate call returned as DIR/<name>.npy "
+                         "(float32: video [B,L,C,H,W], tokens [B,L-1,16,16]; rank r > 0 of a multi-GPU run adds _rank<r>).  The inputs "
+                         "and weights are seeded, so two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """The timed path's outputs as float32 .npy files (at the default shapes 16.8 MB of video + 61 KB of tokens per rank)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.detach().to("cpu", torch.float32).contiguous().numpy())
+
+
+def without_notes(obj):
+    """The result line without its prose ("note", "*_note" and the kernel legend): every number stays, and the line stays short
+    enough for drivers that read a bounded tail of the output."""
+    if isinstance(obj, dict):
+        return {k: without_notes(v) for k, v in obj.items() if not (k == "note" or k.endswith("_note"))}
+    if isinstance(obj, list):
+        return [without_notes(v) for v in obj]
+    return obj
 
 
 def main():
@@ -604,6 +633,8 @@ def main():
     dt = D.max_over_ranks(dt, dev)
     assert tuple(out.shape) == (B, L, 1, 64, 64)
     tok_main = model.last_tokens.clone()
+    if args.dump_outputs:                      # outside the timed region, before any other call can touch the model's buffers
+        dump_outputs(args.dump_outputs, {"video": out, "tokens": tok_main}, rank, world)
     prof = ops.PROFILE.summary()
     replayed = getattr(model, "last_call_mode", "eager") == "graph"
 
@@ -850,7 +881,7 @@ def main():
                           "launches_per_step": g2["calls"] // (args.steps if src2 is gemms else 1),
                           "avg_launch_us": round(g2["ms"] * 1e3 / g2["calls"], 2), "flops_per_launch": g2["flops"] / g2["calls"],
                           "hbm_view": hbm_view(rest[0], g2)}
-            roofline = {"bound": "mfma", "kernel": dom_key + legend,
+            roofline = {"bound": "mfma", "kernel": dom_key, "kernel_note": legend.strip(),
                         "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
                         "traffic": traffic, "traffic_source": traffic_source, "launches_per_step": dom["calls"] // args.steps,
                         "avg_launch_us": round(dom["ms"] * 1e3 / dom["calls"], 2),
@@ -973,7 +1004,7 @@ def main():
                                                                      if "f16" in gtt else None)
         res["cfg4_bf16_incremental_ms_per_call"] = ((cfg4 or {}).get("bf16", {}).get("incremental", {}).get("ms_per_call")
                                                     if isinstance(cfg4, dict) and "bf16" in cfg4 else None)
-        print(json.dumps(res))
+        print(json.dumps(without_notes(res)))
     if world > 1:
         D.barrier()
         torch.distributed.destroy_process_group()
