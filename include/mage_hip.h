@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MAGE_ABI_VERSION 8
+#define MAGE_ABI_VERSION 9
 
 /* MAGE_BF16X3 / MAGE_F16X3: SPLIT-PRECISION operands -- the fast parity mode.  A logical fp32 matrix [rows, C] (C % 64 == 0, base
  * 256-byte aligned) is stored as two 16-bit pieces per element, x ~ hi + lo, per row as 64-column slabs [hi(64) | lo(64)] (so a row
@@ -72,7 +72,8 @@ int mage_check_device_errors(void* stream);
  *   gemm_no_4w, gemm_no_4h, gemm_4h_plain, gemm4_train_forms, gemm_no_8phase, gemm_no_taps8, gemm_no_narrow, gemm_no_narrow_few, gemm_no_small, gemm_small_m,
  *   gemm_stagger_groups / _percent / _forced (MAGE_GEMM_STAGGER="G,percent"), gemm4_stagger_groups / _percent
  *   (MAGE_GEMM4_STAGGER), attn_no_mfma, attn_no_fewq, vq_no_mfma          -- what each one does: struct MageOptions in csrc/common.h and
- *   the table in INTEGRATION.md.  Unknown name: MAGE_EINVAL. */
+ *   the table in INTEGRATION.md.  Unknown name: MAGE_EINVAL.  Values: switches 0 | 1, stagger groups 0..64, percentages 0..400, gemm_small_m
+ *   0..2^20; mage_set_option refuses others (MAGE_EINVAL), a value from the environment is clamped into its range. */
 int mage_set_option(const char* name, int32_t value);
 int mage_get_option(const char* name, int32_t* value);
 
@@ -200,6 +201,10 @@ typedef struct mage_gemm_desc {
 } mage_gemm_desc;
 
 int mage_gemm(const mage_gemm_desc* desc, void* stream);
+/* The symbol of the kernel mage_gemm(desc, .) launches, as rocprofv3's kernel statistics name it without "void ", "(anonymous namespace)::"
+ * and the parameter list (e.g. "gemm4h_kernel<2, 2, false>"), written NUL-terminated into buf[len].  Runs mage_gemm's own checks and selection
+ * on the current device and launches nothing; an invalid descriptor returns what mage_gemm returns, with the same mage_last_error(). */
+int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int32_t len);
 /* 1 if a bf16 plain GEMM of this size (lean epilogue: bias / x + Linear(.) / the LayerNorm-folded forms) runs on the few-rows kernel
  * on the current device (one clip per call), 0 if on the tiled kernels, < 0 on error */
 int mage_gemm_is_small(int32_t M, int32_t N, int32_t K);

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MAGE_HIP_LIB", os.path.join(_HERE, "lib", "libmage_hi
 
 F32, BF16, BF16X3, F16X3, F16 = 0, 1, 2, 3, 4  # BF16X3 / F16X3: split-precision operands; F16: single-pass half operands (include/mage_hip.h)
 ACT_NONE, ACT_RELU, ACT_QUICKGELU, ACT_GELU_ERF, ACT_TANH, ACT_QUICKGELU_GRAD = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -60,6 +60,7 @@ SIGNATURES = {
     "mage_set_option": (C.c_int, [C.c_char_p, i32]),
     "mage_get_option": (C.c_int, [C.c_char_p, C.POINTER(i32)]),
     "mage_gemm": (C.c_int, [C.POINTER(GemmDesc), vp]),
+    "mage_gemm_kernel_name": (C.c_int, [C.POINTER(GemmDesc), C.c_char_p, i32]),
     "mage_gemm_is_small": (C.c_int, [i32, i32, i32]),
     "mage_ln_stats": (C.c_int, [vp, i64, i32, i32, f32, vp, vp]),
     "mage_row_stats": (C.c_int, [vp, i32, i64, i32, i64, f32, vp, vp]),

@@ -76,6 +76,30 @@ __device__ __forceinline__ void mage_raise(int* word, int code, long value, int 
         }                                                                               \
     } while (0)
 
+// ---- the one launch path of the kernels mage_gemm dispatches to (gemm_impl.h, gemm4.hip, gemm4h.hip, conv_tile.hip)
+int mage_gemm_cu_count();                  // CUs of the current device rounded down to a multiple of 8 (256 if unknown): the GEMM schedulers' grid
+// Set by mage_gemm_kernel_name for the duration of one mage_gemm call: the launch that call selects stores its kernel here instead of running.
+extern thread_local const void** mage_gemm_plan;
+// Sets the kernel's dynamic-LDS limit once per device, launches it, checks the launch.  The flags are per DEVICE (a process may drive several
+// GPUs, e.g. nn.DataParallel, main_mage.py:106); setting one twice from two threads is harmless.
+template <auto KERNEL, typename Args>
+int mage_gemm_launch(unsigned grid, unsigned block, unsigned lds, hipStream_t s, const Args& a) {
+    if (mage_gemm_plan) {
+        *mage_gemm_plan = (const void*)KERNEL;
+        return MAGE_OK;
+    }
+    static bool attr[MAGE_MAX_DEVICES] = {false};
+    const int dev = mage_device_index();
+    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
+    if (!attr[dev]) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        attr[dev] = true;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, s, a);
+    MAGE_CHECK_LAUNCH("mage_gemm");
+    return MAGE_OK;
+}
+
 // round-to-nearest-even fp32 -> bf16 (same rounding as torch's .to(torch.bfloat16))
 __device__ __forceinline__ unsigned short f2bf_bits(float f) {
     unsigned int u = __float_as_uint(f);

@@ -188,21 +188,9 @@ int mage_conv3x3_c64_try(const mage_gemm_desc* d, hipStream_t s) {
     if (d->M % plane) return 0;
     const long n_img = d->M / plane;
     if ((d->y_off * d->ldy) % 8 || (d->y_mul_y * d->ldy) % 8 || (d->y_img_stride * d->ldy) % 8) return 0;
-    const int dev = mage_device_index();
-    if (dev < 0) return 0;
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    static bool attr[MAGE_MAX_DEVICES] = {false};
-    if (!n_cu_dev[dev]) {
-        hipDeviceProp_t p;
-        n_cu_dev[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) ? (p.multiProcessorCount & ~7) : 256;
-    }
-    const int n_cu = n_cu_dev[dev];
+    const int n_cu = mage_gemm_cu_count();
     const long ntiles = n_img * (d->out_h / 16) * (d->out_w / 16);
     if (ntiles < n_cu || ntiles >= (1L << 31) || mage_zero_page() == nullptr) return 0;
-    if (!attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_c64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
-        attr[dev] = true;
-    }
     Conv64Args a;
     a.A = (const unsigned short*)d->A;
     a.W = (const unsigned short*)d->W;
@@ -222,7 +210,6 @@ int mage_conv3x3_c64_try(const mage_gemm_desc* d, hipStream_t s) {
     a.tiles_x = d->out_w / 16;
     a.tiles_per_img = (d->out_h / 16) * a.tiles_x;
     a.ntiles = (int)ntiles;
-    hipLaunchKernelGGL(conv3x3_c64_kernel, dim3(n_cu), dim3(256), C64_LDS, s, a);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return 1;
+    const int r = mage_gemm_launch<conv3x3_c64_kernel>(n_cu, 256, C64_LDS, s, a);
+    return r < 0 ? r : 1;
 }

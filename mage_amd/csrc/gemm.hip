@@ -1,5 +1,10 @@
 // mage_gemm / mage_gemm_is_small: argument checks and dispatch for the fp32, bf16 and split-precision GEMMs (the kernel templates and their
 // launchers live in gemm_impl.h; the f16 instantiations are compiled in gemm_f16.hip, the one-wave-per-SIMD kernel in gemm4.hip).
+#include <cxxabi.h>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <unordered_map>
 #include "gemm_impl.h"
 
 int mage_gemm_f16(const mage_gemm_desc* d, hipStream_t s);     // gemm_f16.hip
@@ -27,16 +32,8 @@ extern "C" int mage_debug_read(void* dst, size_t bytes) {
 
 
 extern "C" int mage_gemm_is_small(int32_t M, int32_t N, int32_t K) {
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0 && M > 0 && N > 0 && K > 0, "mage_gemm_is_small: no current device / bad sizes");
-    hipDeviceProp_t p;
-    int n_cu = 256;
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    if (!n_cu_dev[dev]) {
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) n_cu = p.multiProcessorCount & ~7;
-        n_cu_dev[dev] = n_cu;
-    }
-    return small_shape(M, N, K, n_cu_dev[dev]) ? 1 : 0;
+    MAGE_CHECK_ARG(mage_device_index() >= 0 && M > 0 && N > 0 && K > 0, "mage_gemm_is_small: no current device / bad sizes");
+    return small_shape(M, N, K, mage_gemm_cu_count()) ? 1 : 0;
 }
 
 extern "C" int mage_gemm(const mage_gemm_desc* d_in, void* stream) {
@@ -113,4 +110,48 @@ extern "C" int mage_gemm(const mage_gemm_desc* d_in, void* stream) {
                         d->in_w != d->out_w || d->a_half;
     if (d->dtype == MAGE_BF16) return gather ? launch<MAGE_BF16, true>(d, s) : launch<MAGE_BF16, false>(d, s);
     return gather ? launch<MAGE_F32, true>(d, s) : launch<MAGE_F32, false>(d, s);
+}
+
+thread_local const void** mage_gemm_plan = nullptr;
+
+// The kernel mage_gemm would launch for `desc`, by its symbol: mage_gemm itself runs with mage_gemm_plan set, so every argument check, default
+// and selection rule is the dispatch's own and nothing is enqueued.  The name comes from the runtime (hipGetFuncBySymbol + hipKernelNameRef:
+// no stream involved, so also safe while a graph is being captured), demangled, normalised as the kernel statistics of rocprofv3 are read
+// (tools/kernel_stats_summary.py: no "void ", no "(anonymous namespace)::", no parameter list) and cached per kernel.
+extern "C" int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int32_t len) {
+    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_kernel_name: no buffer");
+    const void* kernel = nullptr;
+    mage_gemm_plan = &kernel;
+    const int r = mage_gemm(desc, nullptr);
+    mage_gemm_plan = nullptr;
+    if (r != MAGE_OK) return r;
+    static std::mutex mu;
+    static std::unordered_map<const void*, std::string> names;
+    std::string name;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = names.find(kernel);
+        if (it == names.end()) {
+            hipFunction_t f = nullptr;
+            const char* raw = hipGetFuncBySymbol(&f, kernel) == hipSuccess ? hipKernelNameRef(f) : nullptr;
+            if (!raw) {
+                mage_set_error("mage_gemm_kernel_name: the runtime has no name for the selected kernel");
+                return MAGE_EHIP;
+            }
+            std::string n = raw;
+            int status = -1;
+            if (char* dm = n.compare(0, 2, "_Z") == 0 ? abi::__cxa_demangle(raw, nullptr, nullptr, &status) : nullptr) {
+                if (status == 0) n = dm;
+                free(dm);
+            }
+            for (const char* drop : {"void ", "(anonymous namespace)::"})
+                for (size_t at; (at = n.find(drop)) != std::string::npos;) n.erase(at, strlen(drop));
+            n = n.substr(0, n.find('('));
+            it = names.emplace(kernel, n).first;
+        }
+        name = it->second;
+    }
+    MAGE_CHECK_ARG((int32_t)name.size() < len, "mage_gemm_kernel_name: %d bytes are too few for '%s'", (int)len, name.c_str());
+    memcpy(buf, name.c_str(), name.size() + 1);
+    return MAGE_OK;
 }

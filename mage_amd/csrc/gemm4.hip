@@ -467,13 +467,6 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
 
 template <int ACT, int EK, int LN, bool RB, bool HF = false>
 int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
-    static bool attr[MAGE_MAX_DEVICES] = {false};
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    if (!attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm4_kernel<ACT, EK, LN, RB, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS);
-        attr[dev] = true;
-    }
     Gemm4Args a;
     a.A = d->A;
     a.W = d->W;
@@ -508,9 +501,8 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
         a.stagger_groups = st_groups;
         a.stagger_sleeps = (int)(period * st_percent / 100 / st_groups / 1024);
     }
-    hipLaunchKernelGGL((gemm4_kernel<ACT, EK, LN, RB, HF>), dim3(grid), dim3(256), G4_LDS, s, a);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return 1;
+    const int r = mage_gemm_launch<gemm4_kernel<ACT, EK, LN, RB, HF>>(grid, 256, G4_LDS, s, a);
+    return r < 0 ? r : 1;
 }
 
 }  // namespace
@@ -768,14 +760,7 @@ int mage_gemm4_try(const mage_gemm_desc* d, hipStream_t s) {
     if (d->y_dtype != MAGE_F32 && d->y_dtype != d->dtype) return 0;
     if (hf && (dual || gbwd)) return 0;
     if (d->ldy % 8 || d->lda % 8 || (((uintptr_t)d->bias | (uintptr_t)d->ln_colsum) & 15) || (((uintptr_t)d->ln_stats) & 7)) return 0;
-    const int dev = mage_device_index();
-    if (dev < 0) return 0;
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    if (!n_cu_dev[dev]) {
-        hipDeviceProp_t p;
-        n_cu_dev[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) ? (p.multiProcessorCount & ~7) : 256;
-    }
-    const int n_cu = n_cu_dev[dev];
+    const int n_cu = mage_gemm_cu_count();
     // at least four tiles per CU: with two (the incremental loop's c_fc at 16 k rows) the prologue's un-overlapped slab pair and the single
     // tile boundary cost more than the K loop gains (47.5 vs 41 us per launch there): those sizes stay on the lockstep kernel
     const long ntiles = (long)(d->M / 256) * (d->N / 256);

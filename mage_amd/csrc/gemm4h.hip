@@ -470,13 +470,6 @@ __global__ __launch_bounds__(256) void gemm4h_kernel(const Gemm4hArgs g) {
 
 template <int ACT, int LN, bool HF>
 int launch4h(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
-    static bool attr[MAGE_MAX_DEVICES] = {false};
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    if (!attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm4h_kernel<ACT, LN, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, H_LDS);
-        attr[dev] = true;
-    }
     Gemm4hArgs a;
     a.A = d->A;
     a.W = d->W;
@@ -494,9 +487,8 @@ int launch4h(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
     a.ntiles_n = d->N / 256;
     a.ntiles = (d->M / 256) * a.ntiles_n;
     const int grid = a.ntiles >= n_cu ? n_cu : ((a.ntiles + 7) & ~7);
-    hipLaunchKernelGGL((gemm4h_kernel<ACT, LN, HF>), dim3(grid), dim3(256), H_LDS, s, a);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return 1;
+    const int r = mage_gemm_launch<gemm4h_kernel<ACT, LN, HF>>(grid, 256, H_LDS, s, a);
+    return r < 0 ? r : 1;
 }
 
 }  // namespace

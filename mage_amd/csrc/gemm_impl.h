@@ -1330,26 +1330,14 @@ int launch_small(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
     // rows per workgroup: as many as still leave ~2 workgroups per CU (fewer re-reads of W from L2)
     const int rw = ((long)((d->M + 63) / 64) * p64 >= 2L * n_cu) ? 4 : ((long)((d->M + 31) / 32) * p64 >= 2L * n_cu) ? 2 : 1;
     const unsigned grid = (unsigned)(((d->M + 16 * rw - 1) / (16 * rw)) * p64);
-    if (rw == 4) hipLaunchKernelGGL((gemm_small_kernel<ACT, EK, LN, RB, 4, SPL, HF>), dim3(grid), dim3(256), 0, s, *d);
-    else if (rw == 2) hipLaunchKernelGGL((gemm_small_kernel<ACT, EK, LN, RB, 2, SPL, HF>), dim3(grid), dim3(256), 0, s, *d);
-    else hipLaunchKernelGGL((gemm_small_kernel<ACT, EK, LN, RB, 1, SPL, HF>), dim3(grid), dim3(256), 0, s, *d);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return MAGE_OK;
+    if (rw == 4) return mage_gemm_launch<gemm_small_kernel<ACT, EK, LN, RB, 4, SPL, HF>>(grid, 256, 0, s, *d);
+    if (rw == 2) return mage_gemm_launch<gemm_small_kernel<ACT, EK, LN, RB, 2, SPL, HF>>(grid, 256, 0, s, *d);
+    return mage_gemm_launch<gemm_small_kernel<ACT, EK, LN, RB, 1, SPL, HF>>(grid, 256, 0, s, *d);
 }
 
 template <int DT, bool GATHER, int ACT, int MT, int EK, bool SPLIT = false, int LN = LN_NONE, int NW = 4, int SPL = 0, bool RB = false>
 int launch_tile(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
     typedef Tile<MT, NW, ring_stages<DT, GATHER, MT, EK, SPLIT, NW>()> TL;
-    // launch attributes are per DEVICE (a process may drive several GPUs, e.g. nn.DataParallel, main_mage.py:106): cached per
-    // device index; setting one twice from two threads is harmless
-    static bool attr_set[MAGE_MAX_DEVICES] = {false};
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm_kernel<DT, GATHER, ACT, MT, EK, SPLIT, LN, NW, SPL, RB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  TL::LDS_BYTES);
-        attr_set[dev] = true;
-    }
     GemmArgs a;
     a.d = *d;
     a.zero = (const char*)mage_zero_page();
@@ -1388,21 +1376,10 @@ int launch_tile(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
         const long a_rows = (long)((d->M + d->out_h * d->out_w - 1) / (d->out_h * d->out_w)) * d->a_img_stride + d->a_off + 1;
         const long a_span = a_rows * d->lda + (long)(d->n_split - 1) * d->a_split_stride;       // elements reachable from A / W
         const long w_span = (long)d->N * d->ldw + (long)(d->n_split - 1) * d->w_split_stride;
-        if (use8 && d->K % 64 == 0 && a_span * 2 < (1L << 32) && w_span * 2 < (1L << 32)) {
-            static bool attr8[MAGE_MAX_DEVICES] = {false};
-            if (!attr8[dev]) {
-                (void)hipFuncSetAttribute((const void*)gemm8_kernel<ACT, EK, SPLIT, false, LN, SPL, RB, HF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024);
-                attr8[dev] = true;
-            }
-            hipLaunchKernelGGL((gemm8_kernel<ACT, EK, SPLIT, false, LN, SPL, RB, HF>), dim3(grid), dim3(512), 160 * 1024, s, a);
-            MAGE_CHECK_LAUNCH("mage_gemm");
-            return MAGE_OK;
-        }
+        if (use8 && d->K % 64 == 0 && a_span * 2 < (1L << 32) && w_span * 2 < (1L << 32))
+            return mage_gemm_launch<gemm8_kernel<ACT, EK, SPLIT, false, LN, SPL, RB, HF>>(grid, 512, 160 * 1024, s, a);
     }
-    hipLaunchKernelGGL((gemm_kernel<DT, GATHER, ACT, MT, EK, SPLIT, LN, NW, SPL, RB>), dim3(grid), dim3(512), TL::LDS_BYTES, s, a);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return MAGE_OK;
+    return mage_gemm_launch<gemm_kernel<DT, GATHER, ACT, MT, EK, SPLIT, LN, NW, SPL, RB>>(grid, 512, TL::LDS_BYTES, s, a);
 }
 
 
@@ -1410,13 +1387,6 @@ int launch_tile(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
 // eligible (the caller falls through to the generic gather kernel), < 0 on error.
 template <int ACT, int EK, int SPL = 0, int LN = LN_NONE, bool HF = false, bool RB = false>
 int launch_taps8(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    static bool attr[MAGE_MAX_DEVICES] = {false};
-    if (!attr[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm8_kernel<ACT, EK, false, true, LN, SPL, RB, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr[dev] = true;
-    }
     GemmArgs a;
     a.d = *d;
     a.zero = (const char*)mage_zero_page();
@@ -1427,9 +1397,8 @@ int launch_taps8(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
     a.stagger_groups = 0;
     a.stagger_sleeps = 0;
     const int grid = a.ntiles >= n_cu ? n_cu : ((a.ntiles + 7) & ~7);
-    hipLaunchKernelGGL((gemm8_kernel<ACT, EK, false, true, LN, SPL, RB, HF>), dim3(grid), dim3(512), 160 * 1024, s, a);
-    MAGE_CHECK_LAUNCH("mage_gemm");
-    return 1;
+    const int r = mage_gemm_launch<gemm8_kernel<ACT, EK, false, true, LN, SPL, RB, HF>>(grid, 512, 160 * 1024, s, a);
+    return r < 0 ? r : 1;
 }
 
 template <int SPL = 0, bool HF = false>
@@ -1447,12 +1416,7 @@ int try_taps8(const mage_gemm_desc* d, hipStream_t s) {
     // starts inside the padding -- the sub-pixel phases of a transposed convolution -- comes with a_off and a wider pitch)
     if (d->in_h < d->out_h + d->taps_h - 1 || d->in_w < d->out_w + d->taps_w - 1) return 0;
     if (d->cin % 64 != 0 || d->K % 64 != 0 || d->scale || d->post_relu) return 0;
-    int dev = mage_device_index();
-    if (dev < 0) return 0;
-    hipDeviceProp_t p;
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    if (!n_cu_dev[dev]) n_cu_dev[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) ? (p.multiProcessorCount & ~7) : 256;
-    const int n_cu = n_cu_dev[dev];
+    const int n_cu = mage_gemm_cu_count();
     // any tile count (also the 64-image conv of the incremental AR mode: both modes must run the SAME arithmetic, their tokens
     // are compared bitwise), but only the widths the 8-phase kernel is exercised at
     if (d->N % 256 != 0 || d->M % 256 != 0) return 0;
@@ -1504,16 +1468,7 @@ bool small_shape(int M, int N, int K, int n_cu) {
 // Split-precision GEMMs (dtype MAGE_BF16X3 / MAGE_F16X3): the decoder's Linear layers and frame convolution in the fast parity mode.
 template <int SPL>
 int launch_spl(const mage_gemm_desc* d, hipStream_t s) {
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    if (!n_cu_dev[dev]) {
-        hipDeviceProp_t p;
-        int n = 256;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) n = p.multiProcessorCount & ~7;
-        n_cu_dev[dev] = n;
-    }
-    const int n_cu = n_cu_dev[dev];
+    const int n_cu = mage_gemm_cu_count();
     MAGE_CHECK_ARG(!d->scale && !d->post_relu && !d->y2 && !d->ln_stats && d->n_split == 1 && !d->a_half && !d->res_half,
                    "mage_gemm: split-precision form: epilogue y = act(acc + bias) | residual + acc + bias | rowadd[..] + acc only");
     MAGE_CHECK_ARG(!d->rowadd, "mage_gemm: split-precision form: row tables only in the padded-taps form");
@@ -1546,16 +1501,7 @@ int launch_spl(const mage_gemm_desc* d, hipStream_t s) {
 
 template <int DT, bool GATHER, int ACT, int EK, int LN = LN_NONE, bool RB = false>
 int launch_ek(const mage_gemm_desc* d, hipStream_t s) {
-    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
-    const int dev = mage_device_index();
-    MAGE_CHECK_ARG(dev >= 0, "mage_gemm: no current device");
-    if (!n_cu_dev[dev]) {
-        hipDeviceProp_t p;
-        int n = 256;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) n = p.multiProcessorCount & ~7;
-        n_cu_dev[dev] = n;
-    }
-    const int n_cu = n_cu_dev[dev];
+    const int n_cu = mage_gemm_cu_count();
     if constexpr (DT != MAGE_F32 && !GATHER && EK != EK_GENERAL && LN != LN_DUAL && LN != LN_GELUBWD && (ACT == MAGE_ACT_NONE || ACT == MAGE_ACT_QUICKGELU)) {
         if (d->n_split == 1 && !d->a_relu && small_shape(d->M, d->N, d->K, n_cu)) return launch_small<ACT, EK, LN, RB, 0, DT == MAGE_F16>(d, s, n_cu);
     }

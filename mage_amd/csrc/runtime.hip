@@ -32,19 +32,22 @@ int* mage_error_word() {
     return dev < 0 ? nullptr : g_flag[dev];
 }
 
-// ---- options: one table, read once from the environment, changed through mage_set_option
+// ---- options: one table, read once from the environment, changed through mage_set_option.  Every value lies in [0, hi]: switches 0 | 1,
+// counts and percentages have ranges (a negative row bound or group count would index nothing sensible).  The environment's values are
+// clamped into it, mage_set_option refuses what lies outside (so that config.lib_option can always restore what it read).
 static MageOptions g_opt;
 static std::once_flag g_opt_once;             // the first mage_gemm calls of several host threads race for the table otherwise
-struct OptField { const char* name; int MageOptions::*field; };
+struct OptField { const char* name; int MageOptions::*field; int hi; };
 static const OptField g_opt_fields[] = {
-    {"gemm_no_4w", &MageOptions::gemm_no_4w}, {"gemm_no_4h", &MageOptions::gemm_no_4h}, {"gemm_4h_plain", &MageOptions::gemm_4h_plain}, {"gemm4_train_forms", &MageOptions::gemm4_train_forms},
-    {"gemm_no_8phase", &MageOptions::gemm_no_8phase}, {"gemm_no_taps8", &MageOptions::gemm_no_taps8},
-    {"gemm_no_narrow", &MageOptions::gemm_no_narrow}, {"gemm_no_narrow_few", &MageOptions::gemm_no_narrow_few},
-    {"gemm_no_small", &MageOptions::gemm_no_small}, {"gemm_small_m", &MageOptions::gemm_small_m},
-    {"gemm_stagger_groups", &MageOptions::gemm_stagger_groups},
-    {"gemm_stagger_percent", &MageOptions::gemm_stagger_percent}, {"gemm_stagger_forced", &MageOptions::gemm_stagger_forced},
-    {"gemm4_stagger_groups", &MageOptions::gemm4_stagger_groups}, {"gemm4_stagger_percent", &MageOptions::gemm4_stagger_percent},
-    {"attn_no_mfma", &MageOptions::attn_no_mfma}, {"attn_no_fewq", &MageOptions::attn_no_fewq}, {"vq_no_mfma", &MageOptions::vq_no_mfma}, {"conv_no_tile", &MageOptions::conv_no_tile},
+    {"gemm_no_4w", &MageOptions::gemm_no_4w, 1}, {"gemm_no_4h", &MageOptions::gemm_no_4h, 1}, {"gemm_4h_plain", &MageOptions::gemm_4h_plain, 1},
+    {"gemm4_train_forms", &MageOptions::gemm4_train_forms, 1}, {"gemm_no_8phase", &MageOptions::gemm_no_8phase, 1}, {"gemm_no_taps8", &MageOptions::gemm_no_taps8, 1},
+    {"gemm_no_narrow", &MageOptions::gemm_no_narrow, 1}, {"gemm_no_narrow_few", &MageOptions::gemm_no_narrow_few, 1},
+    {"gemm_no_small", &MageOptions::gemm_no_small, 1}, {"gemm_small_m", &MageOptions::gemm_small_m, 1 << 20},
+    {"gemm_stagger_groups", &MageOptions::gemm_stagger_groups, 64},
+    {"gemm_stagger_percent", &MageOptions::gemm_stagger_percent, 400}, {"gemm_stagger_forced", &MageOptions::gemm_stagger_forced, 1},
+    {"gemm4_stagger_groups", &MageOptions::gemm4_stagger_groups, 64}, {"gemm4_stagger_percent", &MageOptions::gemm4_stagger_percent, 400},
+    {"attn_no_mfma", &MageOptions::attn_no_mfma, 1}, {"attn_no_fewq", &MageOptions::attn_no_fewq, 1}, {"vq_no_mfma", &MageOptions::vq_no_mfma, 1},
+    {"conv_no_tile", &MageOptions::conv_no_tile, 1},
 };
 static int env_flag(const char* name) {
     const char* e = getenv(name);
@@ -68,19 +71,20 @@ const MageOptions& mage_options() {
         if (const char* e = getenv("MAGE_GEMM_STAGGER")) {
             o.gemm_stagger_forced = 1;
             if (sscanf(e, "%d,%d", &o.gemm_stagger_groups, &o.gemm_stagger_percent) < 2) o.gemm_stagger_percent = 60;
-            if (o.gemm_stagger_groups < 0) o.gemm_stagger_groups = 0;
         }
         o.gemm4_stagger_groups = 8;
         o.gemm4_stagger_percent = 100;
         if (const char* e = getenv("MAGE_GEMM4_STAGGER")) {
             if (sscanf(e, "%d,%d", &o.gemm4_stagger_groups, &o.gemm4_stagger_percent) < 2) o.gemm4_stagger_percent = 100;
-            if (o.gemm4_stagger_groups < 0) o.gemm4_stagger_groups = 0;
         }
         o.attn_no_mfma = env_flag("MAGE_ATTN_NO_MFMA");
         o.attn_no_fewq = env_flag("MAGE_ATTN_NO_FEWQ");
         o.vq_no_mfma = env_flag("MAGE_VQ_NO_MFMA");
         o.conv_no_tile = env_flag("MAGE_CONV_NO_TILE");
-        if (o.gemm_small_m < 0) o.gemm_small_m = 0;
+        for (const OptField& f : g_opt_fields) {
+            int& v = o.*(f.field);
+            v = v < 0 ? 0 : v > f.hi ? f.hi : v;
+        }
         g_opt = o;
     });
     return g_opt;
@@ -88,16 +92,10 @@ const MageOptions& mage_options() {
 extern "C" int mage_set_option(const char* name, int32_t value) {
     MAGE_CHECK_ARG(name != nullptr, "mage_set_option: null name");
     (void)mage_options();
-    // values: switches are 0 / 1, counts and percentages have ranges (a negative row bound or group count would index nothing sensible).
     // Changing an option while another host thread is inside a dispatch function is the caller's race: set options before the threads start.
-    const bool is_count = strstr(name, "stagger_groups") != nullptr, is_percent = strstr(name, "stagger_percent") != nullptr;
-    const bool is_rows = strcmp(name, "gemm_small_m") == 0;
     for (const OptField& f : g_opt_fields)
         if (strcmp(f.name, name) == 0) {
-            MAGE_CHECK_ARG(is_count ? (value >= 0 && value <= 64) : is_percent ? (value >= 0 && value <= 400) : is_rows ? (value >= 0 && value <= (1 << 20))
-                                                                                                                    : (value == 0 || value == 1),
-                           "mage_set_option: value %d out of range for '%s' (switches: 0 | 1; stagger groups 0..64, percent 0..400; gemm_small_m 0..2^20)",
-                           (int)value, name);
+            MAGE_CHECK_ARG(value >= 0 && value <= f.hi, "mage_set_option: value %d out of range for '%s' (0..%d)", (int)value, name, f.hi);
             g_opt.*(f.field) = value;
             return MAGE_OK;
         }
@@ -114,6 +112,17 @@ extern "C" int mage_get_option(const char* name, int32_t* value) {
         }
     mage_set_error("mage_get_option: unknown option '%s'", name);
     return MAGE_EINVAL;
+}
+
+int mage_gemm_cu_count() {
+    static int n_cu_dev[MAGE_MAX_DEVICES] = {0};
+    const int dev = mage_device_index();
+    if (dev < 0) return 256;
+    if (!n_cu_dev[dev]) {
+        hipDeviceProp_t p;
+        n_cu_dev[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount >= 8) ? (p.multiProcessorCount & ~7) : 256;
+    }
+    return n_cu_dev[dev];
 }
 
 extern "C" int mage_abi_version(void) { return MAGE_ABI_VERSION; }

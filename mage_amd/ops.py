@@ -118,15 +118,12 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _lib_opts(l) -> dict:
-    """The library's kernel-selection options that the profile keys mirror (mage_get_option; read only while profiling)."""
-    out = {}
-    v = C.c_int32(0)
-    for name in ("gemm_no_narrow", "gemm_no_narrow_few", "gemm_no_8phase", "gemm_no_taps8", "gemm4_train_forms", "gemm_no_4w", "gemm_no_4h", "gemm_4h_plain",
-                 "conv_no_tile"):
-        _lib.check(l.mage_get_option(name.encode(), C.byref(v)), l)
-        out[name] = int(v.value)
-    return out
+def _kernel_name(l, d) -> str:
+    """The symbol of the kernel mage_gemm picks for descriptor d (mage_gemm_kernel_name: the library's own dispatch, nothing launched), as
+    rocprofv3's per-symbol statistics name it: the profile keys line up with them."""
+    buf = C.create_string_buffer(256)
+    _lib.check(l.mage_gemm_kernel_name(C.byref(d), buf, len(buf)), l)
+    return buf.value.decode()
 
 
 class _Profile:
@@ -279,80 +276,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, M: int, N: int, K
     d.res_half = int(res_half)
     d.a_half = int(a_half)
     d.a_relu = int(a_relu)
-    ln = 2 if (ln_stats is not None or ln_colsum is not None) else (1 if (y2 is not None or ln_part is not None) else 0)      # LN_CONSUME / LN_PRODUCE
-    h16 = d.dtype in (BF16, F16)                                                             # 16-bit operands: the same kernels, bf16 or f16 MFMA
-    hf = "true" if d.dtype == F16 else "false"                                               # HF, the kernels' last template argument
-    rb = residual is not None and residual.dtype == a.dtype and h16                          # 16-bit residual stream (RB in csrc/gemm_impl.h)
-    if y2 is not None and ln_part is None and ln_stats is None and ln_colsum is None and act == ACT_QUICKGELU:
-        ln = 3                                                                                  # LN_DUAL: pre-activation + activated rows
-    act_k = act
-    if act == ACT_QUICKGELU_GRAD:                                                               # y = acc * QuickGELU'(y2): LN_GELUBWD, act none
-        ln, act_k = 4, ACT_NONE
     if PROFILE.enabled:
-        # key = the kernel instantiation mage_gemm dispatches to (mirrors launch_act in csrc/gemm_impl.h, incl. the library's options), so
-        # that the per-kernel averages line up with rocprofv3's per-symbol statistics
-        lo = _lib_opts(l)
-        gather = taps_h * taps_w > 1 or stride != 1 or dy0 != 0 or dx0 != 0 or d.in_h != d.out_h or d.in_w != d.out_w or a_half
-        n_cu = torch.cuda.get_device_properties(a.device).multi_processor_count & ~7
-        mt = 8 if (h16 and ((M + 255) // 256) * ((N + 255) // 256) * max(n_split, 1) >= 2 * n_cu) else 4
-        if scale is None and rowadd is None and residual is None and not post_relu:
-            ek = 0
-        elif (not gather and act == ACT_NONE and residual is not None and (residual.dtype == torch.float32 or rb) and scale is None
-              and rowadd is None and not post_relu and out_h == 1 and out_w >= M and residual.data_ptr() % 16 == 0 and not res_half):
-            ek = 1
-        else:
-            ek = 2
-        sp = "true" if n_split > 1 else "false"
-        nw = 4
-        if (ek != 1 and ln == 0 and N <= 128 and n_split == 1 and ((M + 255) // 256) * ((N + 63) // 64) >= n_cu
-                and not lo["gemm_no_narrow"]):
-            mt, nw = 2, 1                                   # the narrow 256 x 64 tile (launch_ek in csrc/gemm.hip)
-        if (ek == 1 and h16 and not gather and act == ACT_NONE and n_split == 1 and N % 64 == 0
-                and ((M + 127) // 128) * ((N + 255) // 256) < n_cu and not lo["gemm_no_narrow"]
-                and not lo["gemm_no_narrow_few"]):
-            mt, nw = 2, 1                                   # few rows: x + Linear(.) of the incremental loop on the narrow tile
-        rbs = ", true" if (rb and ek == 1) else ", false"       # rocprofv3 prints every template argument: the keys match its symbols
-        key = f"gemm_kernel<{d.dtype}, {'true' if gather else 'false'}, {act_k}, {mt}, {ek}, {sp}, {ln}, {nw}, 0{rbs}>"
-        a_rows = ((M + out_h * out_w - 1) // (out_h * out_w)) * d.a_img_stride + a_off + 1
-        if (h16 and not gather and mt == 8 and ek != 2 and K % 64 == 0 and a_rows * lda * 2 < 2 ** 32
-                and N * K * 2 < 2 ** 32 and not lo["gemm_no_8phase"]):
-            key = f"gemm8_kernel<{act_k}, {ek}, {sp}, false, {ln}, 0{rbs}, {hf}>"    # the 8-phase ping-pong variant (launch_tile in csrc/gemm_impl.h)
-        # padded-taps convolutions and row-table Linears on the 8-phase kernel (try_taps8 in csrc/gemm.hip)
-        ntaps = taps_h * taps_w
-        table, plain = rowadd is not None and residual is None, rowadd is None and residual is None
-        if (h16 and n_split == 1 and (ntaps > 1 or table) and stride == 1 and dys == 1 and dxs == 1 and dy0 == 0 and dx0 == 0
-                and d.in_h >= out_h + taps_h - 1 and d.in_w >= out_w + taps_w - 1 and d.cin % 64 == 0 and K % 64 == 0 and scale is None
-                and not post_relu and N % 256 == 0 and M % 256 == 0
-                and not lo["gemm_no_8phase"] and not lo["gemm_no_taps8"]):
-            if table and act == ACT_NONE:
-                key = f"gemm8_kernel<0, 1, false, true, 0, 0, false, {hf}>"
-            elif (plain or (head_w is not None and rowadd is None)) and act in (ACT_NONE, ACT_RELU) and d.dtype == BF16:
-                key = f"gemm8_kernel<{act}, 0, false, true, {5 if head_w is not None else 0}, 0, false, false>"
-            elif (rowadd is None and residual is not None and residual.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and act == ACT_NONE
-                  and d.dtype == BF16 and bias is not None and y_mul_x == 1):
-                key = "gemm8_kernel<0, 0, false, true, 0, 0, true, false>"       # the convolution adds a residual tensor in its epilogue
-        # 64 -> 64 channel 3x3 convolutions over whole 16 x 16 pixel tiles (mage_conv3x3_c64_try in csrc/conv_tile.hip)
-        tile_conv = (d.dtype == BF16 and y.dtype == torch.bfloat16 and N == 64 and d.cin == 64 and taps_h == 3 and taps_w == 3 and stride == 1 and dy0 == -1
-                     and dx0 == -1 and dys == 1 and dxs == 1 and d.in_h == out_h and d.in_w == out_w and out_h % 16 == 0 and out_w % 16 == 0 and ek == 0
-                     and act in (ACT_NONE, ACT_RELU) and y_mul_x == 1 and a_off == 0 and n_split == 1 and M % (out_h * out_w) == 0
-                     and (M // 256) >= n_cu and not lo["conv_no_tile"])
-        if tile_conv:
-            key = "conv3x3_c64_kernel"
-        # the one-wave-per-SIMD kernel (mage_gemm4_try in csrc/gemm4.hip): QKV / c_fc at full-loop sizes
-        if (h16 and not gather and n_split <= 1 and M % 256 == 0 and N % 256 == 0 and K % 128 == 0 and 256 <= K <= 1024
-                and out_h == 1 and out_w >= M and y_mul_x == 1 and ek == 0 and not res_half and ln_part is None
-                and (bias is not None or (N <= 4096 and ln_stats is None)) and (ln_stats is None) == (ln_colsum is None)
-                and (act in (ACT_NONE, ACT_QUICKGELU) if y2 is None else (ln in (3, 4) and y.dtype == torch.bfloat16 and ldy2 % 8 == 0
-                                                                          and bool(lo["gemm4_train_forms"])))
-                and lda % 8 == 0 and ldy % 8 == 0 and not lo["gemm_no_4w"]):
-            nt4 = (M // 256) * (N // 256)
-            if nt4 >= 4 * n_cu:
-                key = f"gemm4_kernel<{act_k}, 0, {ln}, false, {hf}>"
-            # its split-half form (mage_gemm4h_try in csrc/gemm4h.hip): K = 512, 16-bit rows out; at >= 4 tiles per CU the QuickGELU forms
-            # (c_fc), from 3/4 tile per CU up to there (the incremental loop's step) every form
-            if (K == 512 and y.dtype == a.dtype and y2 is None and ln in (0, 2) and not lo["gemm_no_4h"] and nt4 * 4 >= 3 * n_cu
-                    and (nt4 < 4 * n_cu or act == ACT_QUICKGELU or lo["gemm_4h_plain"]) and (ln_stats is None or ln_stats.data_ptr() % 16 == 0)):
-                key = f"gemm4h_kernel<{act_k}, {ln}, {hf}>"
+        key = _kernel_name(l, d)
         if PROFILE.wants(key):
             ev = PROFILE.begin()
             _lib.check(l.mage_gemm(C.byref(d), s), l)
@@ -413,7 +338,7 @@ def _gemm_split(l, s, a, w, y, *, M, N, K, lda, ldy, out_h, out_w, in_h, in_w, a
     d.residual, d.ldr, d.res_dtype = _p(residual), ldr, F32
     d.ldw, d.n_split = ldw, 1
     if PROFILE.enabled:
-        key = f"gemm_split<{split_kind}, {act}, {1 if residual is not None else 0}, {taps_h * taps_w}>"
+        key = _kernel_name(l, d)
         if PROFILE.wants(key):
             ev = PROFILE.begin()
             _lib.check(l.mage_gemm(C.byref(d), s), l)

@@ -2,6 +2,8 @@
 import json
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -163,3 +165,23 @@ def test_config_is_read_once_and_library_options_round_trip(monkeypatch):
     offenders = [str(p.relative_to(root)) for p in root.rglob("*.py")
                  if "os.environ" in p.read_text() and p.name not in ("config.py", "_lib.py", "dist.py")]
     assert offenders == [], offenders
+
+
+def test_library_options_from_the_environment_are_clamped_to_their_ranges():
+    """The environment's values go through the ranges mage_set_option enforces: an out-of-range MAGE_GEMM_STAGGER / MAGE_GEMM_SMALL_M is
+    clamped when the table is filled, so that config.lib_option can always restore what it read.  A child process: the table is read once."""
+    code = ("import json\n"
+            "from mage_amd import config\n"
+            "before = config.lib_options()\n"
+            "with config.lib_option('gemm_stagger_groups', 3):\n"
+            "    assert config.lib_flag('gemm_stagger_groups') == 3\n"
+            "print(json.dumps([before, config.lib_options()]))\n")
+    env = dict(os.environ, MAGE_GEMM_STAGGER="100,900", MAGE_GEMM_SMALL_M="99999999", MAGE_GEMM4_STAGGER="-3,-7", MAGE_GEMM_NO_4W="1")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    before, after = json.loads(r.stdout.strip().splitlines()[-1])
+    assert (before["gemm_stagger_groups"], before["gemm_stagger_percent"], before["gemm_stagger_forced"]) == (64, 400, 1)
+    assert before["gemm_small_m"] == 1 << 20
+    assert (before["gemm4_stagger_groups"], before["gemm4_stagger_percent"]) == (0, 0)
+    assert before["gemm_no_4w"] == 1                     # in-range values as given
+    assert after == before

@@ -1178,3 +1178,159 @@ def test_gemm_split_half_kernel_row_offsets(M, N, act):
     torch.cuda.synchronize()
     assert torch.equal(outs[0], outs[1])
     assert (outs[1][:y_off] == 7.0).all() and (outs[1][M + y_off:] == 7.0).all() and not (outs[1][y_off:M + y_off] == 7.0).all()
+
+
+# ---- mage_gemm_kernel_name: the library names the kernel its own dispatch picks (the profile keys of ops.gemm; bench.py's roofline)
+def _z(*shape, dt=torch.bfloat16):
+    return torch.zeros(*shape, device=DEV, dtype=dt)
+
+
+def _kernel_named(monkeypatch, **kw):
+    """The symbol mage_gemm_kernel_name returns for the descriptor ops.gemm builds from kw: mage_gemm is swapped for the query, so nothing
+    is launched (and no buffer is touched)."""
+    from mage_amd import _lib
+    o = ops()
+    l = _lib.lib(0)
+    names = []
+    with monkeypatch.context() as m:
+        m.setattr(l, "mage_gemm", lambda d, s: names.append(o._kernel_name(l, d._obj)) or 0)
+        o.gemm(**kw)
+    assert len(names) == 1
+    return names[0]
+
+
+def _linear(M, N, K, dt=torch.bfloat16, y_dt=None, **kw):
+    return dict(a=_z(M, K, dt=dt), w=_z(N, K, dt=dt), y=_z(M, N, dt=y_dt or dt), M=M, N=N, K=K, lda=K, ldy=N, **kw)
+
+
+def _split_linear(M, N, K, kind, **kw):
+    o = ops()
+    return dict(a=o.split_empty(M, K, kind, DEV, zero=True), w=o.split_empty(N, K, kind, DEV, zero=True), y=_z(M, N, dt=torch.float32),
+                M=M, N=N, K=K, lda=2 * K, ldy=N, split_kind=kind, **kw)
+
+
+def _conv3x3_padded(N=256, **kw):
+    """16 x 16 output pixels of one image over a zero-padded 18 x 18 input, 64 -> N channels: the padded-taps form."""
+    return dict(a=_z(18 * 18, 64), w=_z(N, 576), M=256, N=N, K=576, lda=64, out_h=16, out_w=16, in_h=18, in_w=18, taps_h=3, taps_w=3,
+                bias=_z(N, dt=torch.float32), **kw)
+
+
+def _gemm_family_cases():
+    """(family, ops.gemm arguments, the symbol).  The tile-count rules assume the MI355X's 256 CUs; the symbols are rocprofv3's
+    (profiles/r06_*_kernel_stats.csv where the family appears there)."""
+    o = ops()
+    f32, b16 = torch.float32, torch.bfloat16
+    bias = lambda n: _z(n, dt=f32)                                                            # noqa: E731
+    return [
+        ("few_rows", _linear(256, 512, 512, bias=bias(512)), "gemm_small_kernel<0, 0, 0, false, 1, 0, false>"),
+        ("few_rows_f16x3", _split_linear(256, 512, 512, o.F16X3, bias=bias(512)), "gemm_small_kernel<0, 0, 0, false, 1, 2, false>"),
+        ("narrow", _linear(65536, 64, 64, bias=bias(64)), "gemm_kernel<1, false, 0, 2, 0, false, 0, 1, 0, false>"),
+        ("narrow_few", _linear(8192, 512, 512, y_dt=f32, bias=bias(512), residual=_z(8192, 512, dt=f32), ldr=512),
+         "gemm_kernel<1, false, 0, 2, 1, false, 0, 1, 0, false>"),
+        ("lockstep_mt4", _linear(1024, 256, 64, dt=f32, bias=bias(256)), "gemm_kernel<0, false, 0, 4, 0, false, 0, 4, 0, false>"),
+        ("lockstep_mt8", _linear(65536, 512, 64, bias=bias(512), scale=bias(512), shift=bias(512)),
+         "gemm_kernel<1, false, 0, 8, 2, false, 0, 4, 0, false>"),
+        ("gemm8_plain", _linear(65536, 512, 64, bias=bias(512)), "gemm8_kernel<0, 0, false, false, 0, 0, false, false>"),
+        ("gemm8_residual", _linear(65536, 512, 64, bias=bias(512), residual=_z(65536, 512), ldr=512),
+         "gemm8_kernel<0, 1, false, false, 0, 0, true, false>"),
+        ("taps8_table", _linear(256, 256, 64, y_dt=f32, rowadd=_z(16, 256, dt=f32), rowadd_mod=16),
+         "gemm8_kernel<0, 1, false, true, 0, 0, false, false>"),
+        ("taps8_plain", dict(_conv3x3_padded(), y=_z(256, 256), ldy=256, act=o.ACT_RELU), "gemm8_kernel<1, 0, false, true, 0, 0, false, false>"),
+        ("taps8_residual", dict(_conv3x3_padded(), y=_z(256, 256), ldy=256, residual=_z(256, 256), ldr=256),
+         "gemm8_kernel<0, 0, false, true, 0, 0, true, false>"),
+        ("taps8_head", dict(_conv3x3_padded(), y=_z(256, 16, dt=f32), ldy=16, act=o.ACT_RELU, head_w=_z(16, 256)),
+         "gemm8_kernel<1, 0, false, true, 5, 0, false, false>"),
+        ("conv3x3_c64", dict(a=_z(16 * 4096, 64), w=_z(64, 576), y=_z(16 * 4096, 64), M=16 * 4096, N=64, K=576, lda=64, ldy=64, out_h=64, out_w=64,
+                             taps_h=3, taps_w=3, dy0=-1, dx0=-1, bias=bias(64), act=o.ACT_RELU), "conv3x3_c64_kernel"),
+        ("gemm4", _linear(65536, 1024, 256, bias=bias(1024)), "gemm4_kernel<0, 0, 0, false, false>"),
+        ("gemm4h", _linear(32768, 2048, 512, bias=bias(2048), act=o.ACT_QUICKGELU), "gemm4h_kernel<2, 0, false>"),
+        ("gemm4h_f16", _linear(32768, 2048, 512, dt=torch.float16, bias=bias(2048), act=o.ACT_QUICKGELU), "gemm4h_kernel<2, 0, true>"),
+        ("split_bf16x3", _split_linear(1024, 256, 64, o.BF16X3, bias=bias(256)), "gemm_kernel<1, false, 0, 4, 0, false, 0, 4, 1, false>"),
+        ("split_f16x3", _split_linear(1024, 256, 64, o.F16X3, bias=bias(256)), "gemm_kernel<1, false, 0, 4, 0, false, 0, 4, 2, false>"),
+        ("split_f16x3_residual", _split_linear(1024, 256, 64, o.F16X3, bias=bias(256), residual=_z(1024, 256, dt=f32), ldr=256),
+         "gemm_kernel<1, false, 0, 4, 1, false, 0, 4, 2, false>"),
+    ]
+
+
+def test_gemm_kernel_name_per_family(monkeypatch):
+    cases = _gemm_family_cases()
+    got = {fam: _kernel_named(monkeypatch, **kw) for fam, kw, _ in cases}
+    want = {fam: sym for fam, _, sym in cases}
+    assert got == want, {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+
+
+def test_gemm_kernel_name_follows_the_options(monkeypatch):
+    """The c_fc shape (QuickGELU, K = 512, 4 tiles per CU): gemm4h_kernel; gemm_no_4h -> gemm4_kernel; gemm_no_4w -> the 8-phase kernel;
+    gemm_no_4w + gemm_no_8phase -> the lockstep one."""
+    o = ops()
+    kw = _linear(32768, 2048, 512, bias=_z(2048, dt=torch.float32), act=o.ACT_QUICKGELU)
+    assert _kernel_named(monkeypatch, **kw) == "gemm4h_kernel<2, 0, false>"
+    with config.lib_option("gemm_no_4h", 1):
+        assert _kernel_named(monkeypatch, **kw) == "gemm4_kernel<2, 0, 0, false, false>"
+    with config.lib_option("gemm_no_4w", 1):
+        assert _kernel_named(monkeypatch, **kw) == "gemm8_kernel<2, 0, false, false, 0, 0, false, false>"
+        with config.lib_option("gemm_no_8phase", 1):
+            assert _kernel_named(monkeypatch, **kw) == "gemm_kernel<1, false, 2, 8, 0, false, 0, 4, 0, false>"
+    assert _kernel_named(monkeypatch, **kw) == "gemm4h_kernel<2, 0, false>"
+
+
+def _plain_desc(a, w, y, bias):
+    from mage_amd import _lib
+    M, K, N = a.shape[0], a.shape[1], w.shape[0]
+    d = _lib.GemmDesc()
+    d.dtype, d.M, d.N, d.K, d.A, d.W, d.Y, d.lda, d.ldy, d.y_dtype = _lib.BF16, M, N, K, a.data_ptr(), w.data_ptr(), y.data_ptr(), K, N, _lib.BF16
+    d.out_h, d.out_w, d.in_h, d.in_w, d.a_img_stride, d.y_img_stride, d.y_mul_y, d.y_mul_x = 1, M, 1, M, M, M, M, 1
+    d.taps_h, d.taps_w, d.cin, d.stride, d.dys, d.dxs = 1, 1, K, 1, 1, 1
+    d.bias, d.act = bias.data_ptr(), _lib.ACT_QUICKGELU
+    return d
+
+
+def test_gemm_kernel_name_launches_nothing_and_checks_like_mage_gemm():
+    """The query enqueues nothing (Y keeps its sentinel across a sync), a real mage_gemm right after writes the product, and an invalid
+    descriptor gets mage_gemm's own code and message."""
+    import ctypes as C
+    from mage_amd import _lib
+    o = ops()
+    l = _lib.lib(0)
+    M, N, K = 32768, 2048, 512                                   # c_fc: gemm4h_kernel
+    a, w, b = rnd(M, K, seed=71).bfloat16().to(DEV), rnd(N, K, seed=72, scale=K ** -0.5).bfloat16().to(DEV), rnd(N, seed=73).to(DEV)
+    y = torch.full((M, N), 3.0, device=DEV, dtype=torch.bfloat16)
+    d = _plain_desc(a, w, y, b)
+    torch.cuda.synchronize()
+    assert o._kernel_name(l, d) == "gemm4h_kernel<2, 0, false>"
+    torch.cuda.synchronize()
+    assert (y == 3.0).all()
+    _lib.check(l.mage_gemm(C.byref(d), torch.cuda.current_stream().cuda_stream), l)
+    torch.cuda.synchronize()
+    v = a[:512].float() @ w.float().t() + b
+    ref = (v * torch.sigmoid(1.702 * v)).bfloat16()
+    torch.testing.assert_close(y[:512].float(), ref.float(), **TOL[torch.bfloat16])
+    # invalid descriptors: the same code and mage_last_error() as mage_gemm
+    buf = C.create_string_buffer(256)
+    for field, bad in (("N", 12), ("K", 500), ("act", 9), ("lda", 7)):
+        e = _plain_desc(a, w, y, b)
+        setattr(e, field, bad)
+        r_gemm = l.mage_gemm(C.byref(e), None)
+        msg_gemm = l.mage_last_error()
+        r_name = l.mage_gemm_kernel_name(C.byref(e), buf, len(buf))
+        assert r_gemm < 0 and (r_name, l.mage_last_error()) == (r_gemm, msg_gemm), (field, r_gemm, r_name, msg_gemm)
+    assert l.mage_gemm_kernel_name(None, buf, len(buf)) == l.mage_gemm(None, None) < 0
+    assert l.mage_gemm_kernel_name(C.byref(d), buf, 4) < 0 and b"too few" in l.mage_last_error()
+
+
+def test_gemm_profile_key_is_the_launched_kernel():
+    """ops.PROFILE keys a GEMM by the library's name for it; the bracketed launch computes what an unprofiled one does."""
+    o = ops()
+    M, N, K = 32768, 2048, 512
+    a, w, b = rnd(M, K, seed=74).bfloat16().to(DEV), rnd(N, K, seed=75, scale=K ** -0.5).bfloat16().to(DEV), rnd(N, seed=76).to(DEV)
+    y0, y1 = (torch.empty(M, N, device=DEV, dtype=torch.bfloat16) for _ in range(2))
+    kw = dict(M=M, N=N, K=K, lda=K, ldy=N, bias=b, act=o.ACT_QUICKGELU)
+    o.gemm(a, w, y0, **kw)
+    o.PROFILE.reset(enabled=True)
+    try:
+        o.gemm(a, w, y1, **kw)
+        prof = o.PROFILE.summary()
+    finally:
+        o.PROFILE.reset()
+    assert list(prof) == ["gemm4h_kernel<2, 0, false>"] and prof["gemm4h_kernel<2, 0, false>"]["calls"] == 1
+    assert torch.equal(y0, y1)
