@@ -244,7 +244,10 @@ int mage_layernorm(const float* x, const float* gamma, const float* beta, void* 
  *   key   j  -> row  outer*kv_outer_stride + in + j*kv_axis_stride    of k, v
  * Head h uses columns [h*32, h*32+32).  causal: key j visible to query i iff j <= i + (nk - nq) (the mask is aligned to
  * the LAST key, so nq == nk is the usual lower triangle and nq < nk is a query block appended to a key cache).
- * kv_len (optional, int32 [ceil(n_seq / kv_len_div)]): only keys j < kv_len[s / kv_len_div] are visible.
+ * kv_len (optional, int32 [ceil(n_seq / kv_len_div)]): only keys j < kv_len[s / kv_len_div] are visible.  A query row that sees
+ * no key (kv_len 0, or a causal row of nq > nk) is NaN, as torch's softmax over an all -inf row gives; an f16x3 output stores it
+ * clamped like any value outside the f16 range: -65504.
+ * q, k, v and out must be 16-byte aligned (every kernel moves them in 16-byte vectors): MAGE_EINVAL otherwise, nothing launched.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mage_attn_desc {
     int32_t dtype;                     /* element type of q, k, v and out; MAGE_F16X3: q, k, v are SPLIT rows (ld* in 16-bit elements; head h's

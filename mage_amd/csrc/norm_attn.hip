@@ -852,9 +852,8 @@ int ln_launch(const float* x, const float* g, const float* b, void* y, int64_t r
 template <typename T>
 int attn_launch(const mage_attn_desc* d, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
-        // the axial attentions: short sequences on the matrix cores (16-byte aligned 64-byte head segments)
-        if (d->nq <= 32 && d->nk <= 32 && d->n_head <= 32 && !mage_options().attn_no_mfma &&
-            ((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->out) & 15) == 0)) {
+        // the axial attentions: short sequences on the matrix cores
+        if (d->nq <= 32 && d->nk <= 32 && d->n_head <= 32 && !mage_options().attn_no_mfma) {
             const int nkb = d->nk <= 16 ? 1 : 2;
             if (d->nq <= 2 && d->n_seq >= 1024 && !mage_options().attn_no_fewq) {      // the incremental step's temporal attention
                 const dim3 grid((unsigned)((d->n_seq + 3) / 4));
@@ -873,9 +872,16 @@ int attn_launch(const mage_attn_desc* d, hipStream_t s) {
             return MAGE_OK;
         }
     }
-    // heads per workgroup: all of them if K,V fit 64 KiB of LDS, else the largest power of two that does
+    // heads per workgroup: all of them if K,V fit 64 KiB of LDS, else halved while even; an odd group that still does not fit takes
+    // its largest divisor that does (1 always does: nk <= 64), so every head count runs
+    auto too_big = [&](int g) { return (long)d->nk * g * 32 * 2 * sizeof(T) > 64 * 1024; };
     int hg = d->n_head;
-    while ((long)d->nk * hg * 32 * 2 * sizeof(T) > 64 * 1024 && hg > 1 && hg % 2 == 0) hg /= 2;
+    while (too_big(hg) && hg > 1 && hg % 2 == 0) hg /= 2;
+    if (too_big(hg)) {
+        int g = hg - 1;
+        while (hg % g != 0 || too_big(g)) --g;
+        hg = g;
+    }
     const size_t lds = (size_t)d->nk * hg * 32 * 2 * sizeof(T);
     MAGE_CHECK_ARG(lds <= 64 * 1024 && d->n_head % hg == 0, "mage_attention: nk=%d too large for LDS staging", d->nk);
     const dim3 grid(d->n_seq, d->n_head / hg), blk(256);
@@ -1020,6 +1026,8 @@ extern "C" int mage_attention(const mage_attn_desc* d, void* stream) {
     MAGE_CHECK_ARG(d->nk >= 1 && d->nk <= 64, "mage_attention: nk=%d outside [1, 64]", d->nk);
     MAGE_CHECK_ARG(d->nq >= 1 && d->n_seq >= 1 && d->n_head >= 1 && d->inner >= 1, "mage_attention: bad sizes");
     MAGE_CHECK_ARG((d->ldq | d->ldk | d->ldv | d->ldo) % 8 == 0, "mage_attention: leading dims must be multiples of 8");
+    MAGE_CHECK_ARG((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->out) & 15) == 0,
+                   "mage_attention: q, k, v and out must be 16-byte aligned (every kernel reads and writes them in 16-byte vectors)");
     MAGE_CHECK_ARG(!d->kv_len || d->kv_len_div >= 1, "mage_attention: kv_len_div must be >= 1");
     MAGE_CHECK_ARG((d->o_axis_stride == 0 && d->o_outer_stride == 0) || d->o_axis_stride > 0, "mage_attention: o_axis_stride must be > 0 when an output row map is given");
     MAGE_CHECK_ARG(d->drop_p >= 0.f && d->drop_p < 1.f && (d->drop_p == 0.f || (d->dtype == MAGE_F32 && d->out_split == 0)),

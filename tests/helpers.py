@@ -51,3 +51,12 @@ def assert_tokens(got, want, margin, tol, what):
     assert not hard.any(), f"{what}: {hard.sum()} index mismatches where the reference margin > {tol} " \
                            f"(first at {np.flatnonzero(hard)[:5]}, margins {margin[hard][:5]})"
     return int(bad.sum())
+
+
+def unsplit(y, kind):
+    """Split-precision rows [rows, 2C] (MAGE_F16X3 / MAGE_BF16X3 pieces, include/mage_hip.h) -> the fp64 values they represent [rows, C]."""
+    from mage_amd import ops
+    rows, c2 = y.shape
+    v = y.reshape(rows, c2 // 128, 2, 64).float()
+    lo = v[:, :, 1] / (2048.0 if kind == ops.F16X3 else 1.0)
+    return (v[:, :, 0].double() + lo.double()).reshape(rows, c2 // 2)

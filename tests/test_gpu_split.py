@@ -11,7 +11,7 @@ import torch
 
 from mage_amd import ops
 from mage_amd.utils import synth
-from tests.helpers import assert_tokens, build_mage, chk, golden, t
+from tests.helpers import assert_tokens, build_mage, chk, golden, t, unsplit
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -21,13 +21,6 @@ KINDS = [pytest.param(ops.F16X3, id="f16x3"), pytest.param(ops.BF16X3, id="bf16x
 # measured worst |error| of a K = 512..2048 product of unit-scale operands (tools/split_probe.py, profiles/r03_split_probe.txt):
 # f16x3 5e-6 .. 9e-6 (the exact-fp32 MFMA chain: 9e-6 .. 2e-5), bf16x3 2.3e-5 .. 2.6e-5
 GEMM_TOL = {ops.F16X3: 2e-5, ops.BF16X3: 6e-5}
-
-
-def unsplit(y, kind):
-    rows, c2 = y.shape
-    v = y.view(rows, c2 // 128, 2, 64).float()
-    lo = v[:, :, 1] / (2048.0 if kind == ops.F16X3 else 1.0)
-    return (v[:, :, 0].double() + lo.double()).reshape(rows, c2 // 2)
 
 
 def dev_batch(batch):
