@@ -4,7 +4,13 @@ clips (BASELINE.json: 64x64, 16-frame clips; cfg2 = MNIST f4 VQ-VAE + MAGE, batc
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3] [--scaling weak|strong]
                     [--batch 64] [--global-batch 256] [--frames 16] [--precision bf16|fp32] [--ar-mode full|incremental]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: it sets up, runs the W warm-up calls and the K timed calls, writes --dump-outputs and
+prints the line (frames/s, ms_per_step, and the roofline and per-kernel figures read from the HIP events of the last warm-up call
+and of the timed calls).  --full adds the secondary measurements, each of which takes runs of its own (minutes in all; the --no-*
+options skip single ones): the other AR mode, the f16x3 / fp32 parity modes and the f16 mode, the VQ-VAE decode roofline, the
+training step, the cfg4 object, the B = 1 latency table, the CPU baseline and the GPU-vs-oracle token agreement.
 
 One "step" = one autoregressive_generate(batch) call: VQ-VAE encode of the first frames + text encoder +
 motion-anchor encoder + the reference's L-1 full decoder recomputes + VQ-VAE decode of the L-1 generated
@@ -505,6 +511,8 @@ def parse():
                     help="HIP events inside the timed region: around the dominant GEMM symbol's launches only (it is found, "
                          "and the per-kernel table filled, in the last warm-up call, which brackets every launch), or around "
                          "every GEMM / attention / LayerNorm launch (~1 %% slower)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the secondary measurements below (a plain run times the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-mode", action="store_true", help="skip the second AR mode (clean rocprofv3 runs)")
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the fp32 (parity-gated) pass and the bf16-vs-fp32 token agreement")
@@ -588,7 +596,7 @@ def main():
     model = instantiate_from_config(cfg).eval()
     synth.fill_state_dict(model, 0)
     cpu_sd = ({k: v.detach().clone() for k, v in model.state_dict().items()}
-              if rank == 0 and world == 1 and not args.no_cpu_baseline else None)      # CPU baseline: rank 0 at N=1 only
+              if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline else None)      # CPU baseline: rank 0 at N=1 only
     model = model.to(dev).set_precision(args.precision)
     model.ar_mode = args.ar_mode
     model.streams = args.streams
@@ -642,7 +650,7 @@ def main():
     other_mode = "incremental" if args.ar_mode == "full" else "full"
     other = None
     tick("build_warmup_and_timed_headline")
-    if not args.no_other_mode:
+    if args.full and not args.no_other_mode:
         model.ar_mode = other_mode
         model.streams = 1 if other_mode == "incremental" else args.streams     # small launches: concurrency only adds gaps
         model.autoregressive_generate(batch)
@@ -663,7 +671,7 @@ def main():
     # every fp32-mode golden gate of tests/ -- reference token sequences bit-exact, logits within 1e-4) timed in both AR modes, the
     # exact-fp32 MFMA mode beside it, and how far the free-running bf16 token sequence is from them
     parity = None
-    if args.precision == "bf16" and not args.no_parity_mode:
+    if args.full and args.precision == "bf16" and not args.no_parity_mode:
         def timed(n):
             prime()
             sync_all()
@@ -720,7 +728,7 @@ def main():
 
     # the single-pass f16 mode on the same batch: the bf16 kernels with IEEE half operands (same MFMA rate, 8x smaller roundings)
     f16m = None
-    if args.precision == "bf16" and not args.no_parity_mode:
+    if args.full and args.precision == "bf16" and not args.no_parity_mode:
         try:
             nf = max(1, min(args.steps, 5))
             model.set_precision("f16")
@@ -767,7 +775,7 @@ def main():
     # VQ-VAE decode of this call's B*(L-1) generated frames on its own: HBM roofline under SURVEY 8d's traffic model + MFMA fraction
     decode = None
     tick("other_ar_mode_parity_mode_f16_mode")
-    if not args.no_decode_roofline:
+    if args.full and not args.no_decode_roofline:
         gen = tok_main.view(B, L - 1, 16, 16)
         model.first_stage_decode(gen)
         torch.cuda.synchronize()
@@ -811,7 +819,7 @@ def main():
     # This is the only place of the path with a real exchange step, so it is what an N > 1 run of this script measures RCCL with.
     train = None
     tick("decode_roofline")
-    if args.precision == "bf16" and not args.no_train_step:
+    if args.full and args.precision == "bf16" and not args.no_train_step:
         try:
             train = train_step_probe(args, dev, rank, world, B, L, wl_kw, D)
         except Exception as e:                                   # never lets the secondary measurement take the bench line down
@@ -819,7 +827,7 @@ def main():
 
     lat = cfg4 = None
     tick("train_step")
-    if rank == 0 and world == 1 and args.precision == "bf16" and not (args.no_latency_b1 and args.no_cfg4):
+    if args.full and rank == 0 and world == 1 and args.precision == "bf16" and not (args.no_latency_b1 and args.no_cfg4):
         m4 = None
         try:
             m4 = build_cfg4_model(dev)

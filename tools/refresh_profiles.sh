@@ -7,7 +7,7 @@ mkdir -p $OUT
 # the bench line first, on a rested chip (the PMC passes before it cost the line 3-6 % on some boxes); roofline.traffic comes from the
 # committed PMC summary (profiles/<tag>_pmc_traffic.json), refreshed by the passes at the end of this script for the next commit
 cd $GRAFT_REPO_ROOT
-python bench.py 2> $OUT/bench_$TAG.err | tail -1 > $OUT/${TAG}_bench_cfg2_bf16.json
+python bench.py --full 2> $OUT/bench_$TAG.err | tail -1 > $OUT/${TAG}_bench_cfg2_bf16.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o k -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-other-mode --no-parity-mode --no-decode-roofline --no-train-step --no-latency-b1 --no-cfg4 2> /dev/null | tail -1 > $OUT/${TAG}_bench_cfg2_bf16_under_rocprof.json
