@@ -483,15 +483,15 @@ class FlatAxialDecoder(nn.Module):
         bf16 GEMM noise.  The incremental loop uses the same kernels on the same rows: still bit-identical to the full loop."""
         return getattr(self, "stream_bf16", True) and config.get().stream_16bit
 
-    def _ln_linear(self, d, p, lin, xb, stats, y, *, M, N, lo=0, hi=None, part=None, **kw):
-        """y = Linear(LN(x)) from the bf16 copy of x and its row statistics (rows lo:hi of the Linear's outputs).  part (instead of
-        stats): the producer's partial sums -- few-rows GEMMs reduce them in their prologue (_stats_inline), no mage_ln_stats launch."""
-        Cc = self.model_channels
-        hi = N + lo if hi is None else hi
-        src = dict(ln_part=part, ln_eps=1e-5) if part is not None else dict(ln_stats=stats)
+    def _ln_linear(self, d, p, lin, xn, xb, ln, y, *, M, N, **kw):
+        """y = Linear(LN(x)) for block p's in_proj / c_fc.  ln None: from xn, the output of a standalone layernorm.  Otherwise from the
+        16-bit rows xb, gamma folded into the weights and the normalisation finished in the epilogue; ln names the row statistics
+        (ln_stats) or the producer's partial sums that the few-rows kernel reduces in its prologue (ln_part; _stats_inline)."""
+        Cc, name = self.model_channels, f"{p}.{lin}"
+        if ln is None:
+            return ops.gemm(xn, _wdt(d, name, self.compute_dtype), y, M=M, N=N, K=Cc, lda=Cc, ldy=N, bias=d[name + ".b"], **kw)
         lnw, lns = self._ln_fold_w(d, p, lin, xb.dtype)
-        return ops.gemm(xb, lnw[lo:hi], y, M=M, N=hi - lo, K=Cc, lda=Cc, ldy=kw.pop("ldy", hi - lo),
-                        bias=d[f"{p}.{lin}.lnc"][lo:hi], ln_colsum=lns[lo:hi], **src, **kw)
+        return ops.gemm(xb, lnw, y, M=M, N=N, K=Cc, lda=Cc, ldy=N, bias=d[name + ".lnc"], ln_colsum=lns, **ln, **kw)
 
     @staticmethod
     def _ln_fold_w(d, p, lin, dt):
@@ -513,225 +513,173 @@ class FlatAxialDecoder(nn.Module):
         Cc = self.model_channels
         return all(ops.gemm_is_small(xb, M, n, Cc) for n in (Cc, 2 * Cc, 3 * Cc, 4 * Cc))
 
+    # ------------------------------------------------------------------ the two loops: one pass per operand form serves both
+    # A pass computes positions p0 .. p0+P-1 of the L slots: the motion anchor goes to slot 0 when the window starts there, the nf new
+    # frames to the last nf slots of the window.  The reference's full-recompute loop is p0 = 0, P = L, nf = L-1 (_run); the incremental
+    # loop appends one frame per step (_inc_step).  Both loops run the same body on the same per-row arithmetic, so their tokens are
+    # bit-identical by construction.
     @torch.no_grad()
     def _run(self, motion: torch.Tensor, imgs: torch.Tensor, *, B: int, hh: int, ww: int) -> torch.Tensor:
         """motion [B*hw, Cc], imgs [B*(L-1)*hw, Ci] in the compute dtype -> logits [B*(L-1)*hw, K] fp32
         (use_cids=False: predicted latents [B*(L-1)*hw, 8] fp32 whose first out_channels columns are valid)."""
-        if self._split_on():
-            return self._run_split(motion, imgs, B=B, hh=hh, ww=ww)
-        d = self._derived.get(self._build)
-        dt, Cc, L, dev = self.compute_dtype, self.model_channels, self.frames_length, motion.device
-        hw = hh * ww
-        M = B * L * hw
-        H = Cc // 32
-        fold, have_stats = self._fold(dt, B, hw), False
-        sb = fold and self._stream_bf16()
-        inl = fill_stats = False
-        if fold:
-            xb = torch.empty(M, Cc, device=dev, dtype=dt)                          # the bf16 stream (or the bf16 copy of the fp32 one)
-            part = torch.empty(Cc // 64, M, 2, device=dev, dtype=F32)       # slice-major (mage_gemm_desc::ln_part_rows)
-            stats = torch.empty(M, 2, device=dev, dtype=F32)
-            inl = self._stats_inline(xb, M)
-        # the stream starts in bf16 too: context_linear and the frame fill write bf16 rows, their LayerNorm statistics come from one pass
-        # over those rows (mage_row_stats), block 0 then runs like every other block (no fp32 rows, no LayerNorm launch)
-        x0 = xb if sb else torch.empty(M, Cc, device=dev, dtype=F32)               # residual stream as assembled by :375-378
-        x = x0 if not sb else None
-        # context_linear -> slot 0, in_linear -> slots 1..L-1, + T_positional_embedding, no concat copy (:375-378)
-        _linear(motion, d, "context_linear", x0, dt, M=B * hw, N=Cc, K=self.context_channels, out_w=hw, y_img_stride=L * hw,
-                rowadd=d["tpos"], rowadd_div=hw, rowadd_mod=L)
-        if isinstance(imgs, FrameTokens):
-            imgs.fill(x0, n_img=B * (L - 1), per_clip=L - 1, P=L, y_off=hw, tp=d["tpos"])
-        else:
-            _linear(imgs, d, "in_linear", x0, dt, M=B * (L - 1) * hw, N=Cc, K=self.in_channels, out_w=(L - 1) * hw,
-                    y_img_stride=L * hw, y_off=hw, rowadd=d["tpos"], rowadd_div=hw, rowadd_mod=L)
-        if sb:
-            ops.row_stats(xb, 1e-5, stats)
-            have_stats = fill_stats = True
-        xn = torch.empty(M, Cc, device=dev, dtype=dt)
-        qkv = torch.empty(M, 3 * Cc, device=dev, dtype=dt)
-        ao = torch.empty(M, Cc, device=dev, dtype=dt)
-        hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
-        for i in range(self.layers):
-            p = f"b{i}"
-            axis = i % 3                                                            # 0: L (causal), 1: H, 2: W  (:344,:382)
-            if axis == 0:
-                geo = dict(n_seq=B * hw, inner=hw, nq=L, nk=L, q_outer_stride=L * hw, q_axis_stride=hw, causal=True)
-            elif axis == 1:
-                geo = dict(n_seq=B * L * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww, causal=False)
-            else:
-                geo = dict(n_seq=B * L * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1, causal=False)
-            if have_stats:
-                self._ln_linear(d, p, "in_proj", xb, stats, qkv, M=M, N=3 * Cc, part=part if (inl and not (fill_stats and i == 0)) else None)
-            else:
-                ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5)
-                _linear(xn, d, p + ".in_proj", qkv, dt, M=M, N=3 * Cc, K=Cc)
-            ops.attention(qkv, qkv[:, Cc:], qkv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, n_head=H,
-                          kv_outer_stride=geo["q_outer_stride"], kv_axis_stride=geo["q_axis_stride"], **geo)
-            if fold:
-                if sb:
-                    _linear(ao, d, p + ".out_proj", xb, dt, M=M, N=Cc, K=Cc, residual=xb, ldr=Cc, ln_part=part)
-                else:
-                    _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, residual=x, ldr=Cc, y2=xb, ldy2=Cc, ln_part=part)
-                if not inl:
-                    ops.ln_stats(part, Cc, 1e-5, stats)
-                self._ln_linear(d, p, "c_fc", xb, stats, hdn, M=M, N=4 * Cc, act=ops.ACT_QUICKGELU, part=part if inl else None)
-            else:
-                _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, residual=x, ldr=Cc)
-                ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5)
-                _linear(xn, d, p + ".c_fc", hdn, dt, M=M, N=4 * Cc, K=Cc, act=ops.ACT_QUICKGELU)
-            last = i == self.layers - 1
-            if last and self.use_cids and dt != F32:
-                # the last block's x + c_proj(.) is only read by the head GEMM: the epilogue rounds it to the compute dtype on the
-                # way out (same fp32 sum, same round-to-nearest-even as a separate cast pass: bit-identical) instead of writing
-                # the fp32 stream and converting it in another launch
-                _linear(hdn, d, p + ".c_proj", xn, dt, M=M, N=Cc, K=4 * Cc, residual=xb if sb else x, ldr=Cc)
-            elif fold and not last:
-                if sb:
-                    _linear(hdn, d, p + ".c_proj", xb, dt, M=M, N=Cc, K=4 * Cc, residual=xb, ldr=Cc, ln_part=part)
-                else:
-                    _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y2=xb, ldy2=Cc, ln_part=part)
-                if not inl:
-                    ops.ln_stats(part, Cc, 1e-5, stats)
-                have_stats = True
-            else:
-                if x is None:                                            # bf16 stream, MAGE+ head: its GroupNorm reads fp32 rows
-                    x = torch.empty(M, Cc, device=dev, dtype=F32)
-                _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, residual=xb if sb else x, ldr=Cc)
-        if not self.use_cids:
-            # GroupNorm statistics span all L-1 frames of a clip (:387-388): this head is NOT causal along L
-            y = ops.groupnorm_silu(x, d["gn.w"], d["gn.b"], torch.empty(B * (L - 1) * hw, Cc, device=dev, dtype=dt), n_samples=B,
-                                   rows_per_sample=(L - 1) * hw, sample_stride_rows=L * hw, row_off=hw, groups=32,
-                                   eps=self.out[0].eps)
-            n8 = d["out.f32"].shape[0]
-            pred = torch.empty(B * (L - 1) * hw, n8, device=dev, dtype=F32)
-            return _linear(y, d, "out", pred, dt, M=B * (L - 1) * hw, N=n8, K=Cc)
-        xa = x if dt == F32 else xn
-        logits = torch.empty(B * (L - 1) * hw, self.out_channels, device=dev, dtype=F32)
-        _linear(xa, d, "out", logits, dt, M=B * (L - 1) * hw, N=self.out_channels, K=Cc, out_w=(L - 1) * hw,
-                a_img_stride=L * hw, a_off=hw)                                      # head on x[:, 1:]  (:385)
-        return logits
+        L = self.frames_length
+        run = self._pass_split if self._split_on() else self._pass
+        return run(motion, imgs, B=B, hh=hh, ww=ww, p0=0, P=L, nf=L - 1, cache=None)
 
-    # ------------------------------------------------------------------ incremental (temporal KV cache) decoding
     # SURVEY.md 8f-1: the decoder is causal along L (temporal blocks masked, spatial blocks per frame), so the logits of
     # frame k do not depend on later slots.  Instead of recomputing all L positions in each of the L-1 iterations
     # (mage_model.py:673-684) only the NEW position(s) run through the stack; the temporal blocks keep their K,V of
-    # earlier positions in a cache.  Same kernels, same per-row arithmetic: the tokens are bit-identical to the full loop.
-    @torch.no_grad()
-    def _inc_begin(self, B: int, hh: int, ww: int, device) -> dict:
-        dt, Cc, L = self.compute_dtype, self.model_channels, self.frames_length
-        if self._split_on() and self._attn_split():        # f16x3: K, V cached as split rows (what the attention kernel reads)
-            caches = {i: ops.split_empty(B * L * hh * ww, 2 * Cc, self.split_kind, device) for i in range(self.layers) if i % 3 == 0}
-            return {"B": B, "hh": hh, "ww": ww, "kv": caches, "p": 0}
-        if self._split_on():                                # the other split forms (_inc_step_split with fp32 rows): [K | V] only, q stays in qkv
-            caches = {i: torch.empty(B * L * hh * ww, 2 * Cc, device=device, dtype=dt) for i in range(self.layers) if i % 3 == 0}
-            return {"B": B, "hh": hh, "ww": ww, "kv": caches, "p": 0}
-        # temporal blocks: one row [q | k | v] per (clip, slot, pixel) -- the new positions' QKV projection is ONE launch writing straight into
-        # the slots (q is read back from there by the attention of the same step; 1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)
-        caches = {i: torch.empty(B * L * hh * ww, 3 * Cc, device=device, dtype=dt) for i in range(self.layers) if i % 3 == 0}
-        return {"B": B, "hh": hh, "ww": ww, "kv": caches, "p": 0}
+    # earlier positions in a cache.
+    def _inc_begin(self, B: int, hh: int, ww: int) -> dict:
+        """State of one incremental decode: the next position, and the temporal blocks' caches (laid out by the pass of the first step)."""
+        return {"B": B, "hh": hh, "ww": ww, "kv": {}, "p": 0}
 
     @torch.no_grad()
     def _inc_step(self, st: dict, motion: Optional[torch.Tensor], imgs: torch.Tensor) -> torch.Tensor:
         """Append position(s): the first call takes the motion anchor (slot 0) and frame 0's features (slot 1); later calls
         take the features of the newest frame only.  Returns the logits of the last appended slot, [B*hw, K] fp32."""
-        if self._split_on():
-            return self._inc_step_split(st, motion, imgs)
-        d = self._derived.get(self._build)
-        dt, Cc, L = self.compute_dtype, self.model_channels, self.frames_length
-        dev = imgs.tokens.device if isinstance(imgs, FrameTokens) else imgs.device
-        B, hh, ww = st["B"], st["hh"], st["ww"]
-        hw, H = hh * ww, Cc // 32
         p0 = st["p"]
         P = 2 if motion is not None else 1                                  # new positions p0 .. p0+P-1
-        assert (p0 == 0) == (motion is not None) and p0 + P <= L
+        # (the MAGE+ head's GroupNorm spans all frames of a clip: only the full loop is valid there)
+        assert self.use_cids and (p0 == 0) == (motion is not None) and p0 + P <= self.frames_length
+        run = self._pass_split if self._split_on() else self._pass
+        logits = run(motion, imgs, B=st["B"], hh=st["hh"], ww=st["ww"], p0=p0, P=P, nf=1, cache=st["kv"])
+        st["p"] = p0 + P
+        return logits
+
+    def _axial_geo(self, axis: int, B: int, hh: int, ww: int, P: int, p0: int = 0, *, cached: bool = False,
+                   q_cached: bool = False) -> dict:
+        """Row map of the axial attention of a block attending along `axis` (0: L, causal; 1: H; 2: W -- :344,382) at positions
+        p0 .. p0+P-1 of B clips of hh x ww frames, as keyword arguments of ops.attention / ops.attention_bwd.  Temporal blocks: q, K, V
+        are the window's own rows [B, P, hh, ww] unless `cached`: K, V of positions 0 .. p0+P-1 then come from the [B, L, hh, ww] cache,
+        and so does q with `q_cached` (the output keeps the window's row map)."""
+        hw, H = hh * ww, self.model_channels // 32
+        if axis == 1:
+            return dict(n_seq=B * P * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww, causal=False,
+                        kv_outer_stride=hw, kv_axis_stride=ww, n_head=H)
+        if axis == 2:
+            return dict(n_seq=B * P * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1, causal=False,
+                        kv_outer_stride=ww, kv_axis_stride=1, n_head=H)
+        kvo = (self.frames_length if cached else P) * hw
+        geo = dict(n_seq=B * hw, inner=hw, nq=P, nk=p0 + P, q_outer_stride=kvo if q_cached else P * hw, q_axis_stride=hw, causal=True,
+                   kv_outer_stride=kvo, kv_axis_stride=hw, n_head=H)
+        if q_cached:
+            geo.update(o_outer_stride=P * hw, o_axis_stride=hw)
+        return geo
+
+    def _embed(self, d, x, motion, imgs, *, B: int, hw: int, P: int, nf: int, tp: torch.Tensor, sk: int = 0) -> None:
+        """The window's input rows of x [B*P*hw, C] (:375-378, no concat copy): context_linear(motion) -> slot 0 (if motion), in_linear
+        (frames) -> the last nf slots, + the window's T positions tp.  imgs: rows in the compute dtype, or FrameTokens.  sk (split modes):
+        motion is fp32 rows, split here where the padded-taps GEMM takes them; imgs split rows (_frame_features) or fp32 rows."""
+        dt, Cc = self.compute_dtype, self.model_channels
+        if motion is not None:
+            if sk and self._taps_ok(B * hw):
+                self._lin_s(ops.split(motion, sk), d, "context_linear", x, M=B * hw, N=Cc, K=self.context_channels, out_w=hw,
+                            y_img_stride=P * hw, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+            else:
+                _linear(motion, d, "context_linear", x, dt, M=B * hw, N=Cc, K=self.context_channels, out_w=hw, y_img_stride=P * hw,
+                        rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+        off = (P - nf) * hw
+        if isinstance(imgs, FrameTokens):
+            imgs.fill(x, n_img=B * nf, per_clip=nf, P=P, y_off=off, tp=tp)
+        elif sk and imgs.dtype != F32:
+            self._lin_s(imgs, d, "in_linear", x, M=B * nf * hw, N=Cc, K=self.in_channels, out_w=nf * hw, y_img_stride=P * hw, y_off=off,
+                        rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+        else:
+            _linear(imgs, d, "in_linear", x, dt, M=B * nf * hw, N=Cc, K=self.in_channels, out_w=nf * hw, y_img_stride=P * hw, y_off=off,
+                    rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+
+    def _head(self, d, xa, *, B: int, hw: int, P: int, nf: int, split: bool = False) -> torch.Tensor:
+        """The head on the window's last nf slots (:385), reading the last block's output xa: logits [B*nf*hw, K] fp32 from rows in the
+        compute dtype (split: split rows); use_cids=False: predicted latents [B*nf*hw, 8] fp32 (first out_channels columns valid) from fp32 rows."""
+        dt, Cc, rows = self.compute_dtype, self.model_channels, B * nf * hw
+        if not self.use_cids:
+            # MAGE+: GroupNorm + SiLU + Conv3d 1x1x1 (:350-354); the GroupNorm statistics span all frames of a clip (:387-388): NOT causal along L
+            y = ops.groupnorm_silu(xa, d["gn.w"], d["gn.b"], torch.empty(rows, Cc, device=xa.device, dtype=dt), n_samples=B,
+                                   rows_per_sample=nf * hw, sample_stride_rows=P * hw, row_off=(P - nf) * hw, groups=32, eps=self.out[0].eps)
+            n8 = d["out.f32"].shape[0]
+            return _linear(y, d, "out", torch.empty(rows, n8, device=xa.device, dtype=F32), dt, M=rows, N=n8, K=Cc)
+        logits = torch.empty(rows, self.out_channels, device=xa.device, dtype=F32)
+        if split:
+            return self._lin_s(xa, d, "out", logits, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
+        return _linear(xa, d, "out", logits, dt, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
+
+    def _pass(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict]) -> torch.Tensor:
+        """fp32 / bf16 / f16: one window (see above) through the stack.  cache (incremental loop): block -> its [B, L, hw, q|k|v] rows."""
+        d = self._derived.get(self._build)
+        dt, Cc, L = self.compute_dtype, self.model_channels, self.frames_length
+        dev = (imgs.tokens if isinstance(imgs, FrameTokens) else imgs).device
+        hw = hh * ww
         M = B * P * hw
-        fold, have_stats = self._fold(dt, B, hw), False
+        # The LayerNorm in front of in_proj and c_fc, decided once per pass.  Without the fold (_fold): a standalone layernorm of the fp32
+        # rows x into xn (ln None).  With it, every x + Linear(.) (res) also leaves per-row partial sums `part` and the 16-bit rows xb, and
+        # the Linear normalises xb itself (_ln_linear): from (mean, rstd) rows `stats` that an ln_stats launch reduces from `part`, or, on
+        # the few-rows kernel (inl), from `part` directly.  Block 0's in_proj (ln0) follows the fill: the statistics of one row_stats pass
+        # over the 16-bit stream (sb), else a layernorm of the fp32 rows.
+        fold = self._fold(dt, B, hw)
         sb = fold and self._stream_bf16()
-        inl = fill_stats = False
-        if fold:                                                             # see _run
-            xb = torch.empty(M, Cc, device=dev, dtype=dt)
+        xb = part = stats = None
+        if fold:
+            xb = torch.empty(M, Cc, device=dev, dtype=dt)                          # the 16-bit stream (or the 16-bit copy of the fp32 one)
             part = torch.empty(Cc // 64, M, 2, device=dev, dtype=F32)       # slice-major (mage_gemm_desc::ln_part_rows)
             stats = torch.empty(M, 2, device=dev, dtype=F32)
-            inl = self._stats_inline(xb, M)
-        x0 = xb if sb else torch.empty(M, Cc, device=dev, dtype=F32)
-        x = x0 if not sb else None
-        tp = d["tpos"][p0:]
-        if motion is not None:
-            _linear(motion, d, "context_linear", x0, dt, M=B * hw, N=Cc, K=self.context_channels, out_w=hw, y_img_stride=P * hw,
-                    rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-        if isinstance(imgs, FrameTokens):
-            imgs.fill(x0, n_img=B, per_clip=1, P=P, y_off=(P - 1) * hw, tp=tp)
-        else:
-            _linear(imgs, d, "in_linear", x0, dt, M=B * hw, N=Cc, K=self.in_channels, out_w=hw, y_img_stride=P * hw,
-                    y_off=(P - 1) * hw, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+        inl = fold and self._stats_inline(xb, M)
+        ln = None if not fold else dict(ln_part=part, ln_eps=1e-5) if inl else dict(ln_stats=stats)
+        ln0 = dict(ln_stats=stats) if sb else None
+        x = xb if sb else torch.empty(M, Cc, device=dev, dtype=F32)                # the residual stream
+        res = dict(residual=x, ldr=Cc)                  # every x + Linear(.) but the last: in place on the stream
+        if fold:                                        # ... leaving the partial sums (and, fp32 stream, the 16-bit copy xb)
+            res["ln_part"] = part
+            if not sb:
+                res.update(y2=xb, ldy2=Cc)
+        self._embed(d, x, motion, imgs, B=B, hw=hw, P=P, nf=nf, tp=d["tpos"][p0:])
         if sb:
             ops.row_stats(xb, 1e-5, stats)
-            have_stats = fill_stats = True
         xn = torch.empty(M, Cc, device=dev, dtype=dt)
         qkv = torch.empty(M, 3 * Cc, device=dev, dtype=dt)
         ao = torch.empty(M, Cc, device=dev, dtype=dt)
         hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
+        geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
         for i in range(self.layers):
             p = f"b{i}"
-            axis = i % 3
-            if not have_stats:
+            ln1 = ln if i else ln0
+            if ln1 is None:
                 ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5)
-            w, b = _wdt(d, p + ".in_proj", dt), d[p + ".in_proj.b"]
-            pin = part if (inl and not (fill_stats and i == 0)) else None        # block 0: the statistics of the fill, not partial sums
-            if axis == 0:
-                kv = st["kv"][i]                                             # [B, L, hw, Q|K|V]
-                if have_stats:                                               # q, k, v of the new positions -> their cache slots, one launch
-                    self._ln_linear(d, p, "in_proj", xb, stats, kv, M=M, N=3 * Cc, out_w=P * hw, y_img_stride=L * hw, y_off=p0 * hw, part=pin)
-                else:
-                    ops.gemm(xn, w, kv, M=M, N=3 * Cc, K=Cc, lda=Cc, ldy=3 * Cc, bias=b, out_w=P * hw, y_img_stride=L * hw, y_off=p0 * hw)
-                ops.attention(kv[p0 * hw:], kv[:, Cc:], kv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, n_seq=B * hw, inner=hw,
-                              nq=P, nk=p0 + P, n_head=H, q_outer_stride=L * hw, q_axis_stride=hw, kv_outer_stride=L * hw,
-                              kv_axis_stride=hw, causal=True, o_outer_stride=P * hw, o_axis_stride=hw)
+            if i % 3 == 0 and cache is not None:
+                # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
+                # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)
+                if p0 == 0:
+                    cache[i] = torch.empty(B * L * hw, 3 * Cc, device=dev, dtype=dt)
+                kv = cache[i]
+                self._ln_linear(d, p, "in_proj", xn, xb, ln1, kv, M=M, N=3 * Cc, out_w=P * hw, y_img_stride=L * hw, y_off=p0 * hw)
+                q = kv[p0 * hw:]
             else:
-                if have_stats:
-                    self._ln_linear(d, p, "in_proj", xb, stats, qkv, M=M, N=3 * Cc, part=pin)
-                else:
-                    ops.gemm(xn, w, qkv, M=M, N=3 * Cc, K=Cc, lda=Cc, ldy=3 * Cc, bias=b)
-                if axis == 1:
-                    geo = dict(n_seq=B * P * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww)
-                else:
-                    geo = dict(n_seq=B * P * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1)
-                ops.attention(qkv, qkv[:, Cc:], qkv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, n_head=H,
-                              kv_outer_stride=geo["q_outer_stride"], kv_axis_stride=geo["q_axis_stride"], **geo)
-            if fold:
-                if sb:
-                    _linear(ao, d, p + ".out_proj", xb, dt, M=M, N=Cc, K=Cc, residual=xb, ldr=Cc, ln_part=part)
-                else:
-                    _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, residual=x, ldr=Cc, y2=xb, ldy2=Cc, ln_part=part)
-                if not inl:
-                    ops.ln_stats(part, Cc, 1e-5, stats)
-                self._ln_linear(d, p, "c_fc", xb, stats, hdn, M=M, N=4 * Cc, act=ops.ACT_QUICKGELU, part=part if inl else None)
-            else:
-                _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, residual=x, ldr=Cc)
+                q = kv = qkv
+                self._ln_linear(d, p, "in_proj", xn, xb, ln1, qkv, M=M, N=3 * Cc)
+            ops.attention(q, kv[:, Cc:], kv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, **geo[i % 3])
+            _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, **res)
+            if fold and not inl:
+                ops.ln_stats(part, Cc, 1e-5, stats)
+            if ln is None:
                 ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5)
-                _linear(xn, d, p + ".c_fc", hdn, dt, M=M, N=4 * Cc, K=Cc, act=ops.ACT_QUICKGELU)
-            last = i == self.layers - 1
-            if last and dt != F32:                                  # see _run: the head's input straight from the epilogue
-                _linear(hdn, d, p + ".c_proj", xn, dt, M=M, N=Cc, K=4 * Cc, residual=xb if sb else x, ldr=Cc)
-            elif fold and not last:
-                if sb:
-                    _linear(hdn, d, p + ".c_proj", xb, dt, M=M, N=Cc, K=4 * Cc, residual=xb, ldr=Cc, ln_part=part)
-                else:
-                    _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y2=xb, ldy2=Cc, ln_part=part)
-                if not inl:
+            self._ln_linear(d, p, "c_fc", xn, xb, ln, hdn, M=M, N=4 * Cc, act=ops.ACT_QUICKGELU)
+            if i < self.layers - 1:
+                _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, **res)
+                if fold and not inl:
                     ops.ln_stats(part, Cc, 1e-5, stats)
-                have_stats = True
             else:
-                _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, residual=xb if sb else x, ldr=Cc)
-        xa = x if dt == F32 else xn
-        logits = torch.empty(B * hw, self.out_channels, device=dev, dtype=F32)
-        _linear(xa, d, "out", logits, dt, M=B * hw, N=self.out_channels, K=Cc, out_w=hw, a_img_stride=P * hw, a_off=(P - 1) * hw)
-        st["p"] = p0 + P
-        return logits
-
+                # the last x + c_proj(.) is only read by the head.  16-bit logits head: the epilogue rounds it to the compute dtype on the way
+                # out (same fp32 sum, same round-to-nearest-even as a separate cast pass: bit-identical) instead of writing fp32 rows and
+                # converting them in another launch.  MAGE+ head: its GroupNorm reads fp32 rows (fresh ones behind the 16-bit stream).
+                if self.use_cids and dt != F32:
+                    xa = xn
+                else:
+                    xa = torch.empty(M, Cc, device=dev, dtype=F32) if sb else x
+                _linear(hdn, d, p + ".c_proj", xa, dt, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
+        return self._head(d, xa, B=B, hw=hw, P=P, nf=nf)
 
     # ------------------------------------------------------------------ the fast parity modes ('f16x3' / 'bf16x3')
-    # The stack of _run / _inc_step with fp32 everywhere EXCEPT the operands of the Linear layers: those are split-precision
+    # The stack of _pass with fp32 everywhere EXCEPT the operands of the Linear layers: those are split-precision
     # tensors (two 16-bit pieces per element, ops.split_empty) written directly by their producers -- LayerNorm, the attention
     # kernel, the c_fc epilogue (QuickGELU), the last c_proj epilogue -- and multiplied as three f16 / bf16 MFMA products per K
     # slab (include/mage_hip.h, MAGE_F16X3).  Residual stream, q / k / v, softmax and logits are fp32 as in 'fp32' mode.
@@ -767,58 +715,39 @@ class FlatAxialDecoder(nn.Module):
         return ops.gemm(a, w, y, M=M, N=N, K=K, lda=kw.pop("lda", 2 * K), ldy=kw.pop("ldy", 2 * N if y_split else N), bias=b,
                         split_kind=sk, y_split=y_split, **kw)
 
-    def _embed_inputs_split(self, d, x, motion, imgs, *, B, hw, P, tp, n_img_rows):
-        """context_linear -> slot 0 (if motion), in_linear -> the other slot(s), + T positions: rows of x [B*P*hw, C] fp32.
-        motion fp32 rows; imgs split rows (from _frame_features in split mode) or fp32 rows."""
-        sk, Cc = self.split_kind, self.model_channels
-        img_tok = isinstance(imgs, FrameTokens)
-        img_split = (not img_tok) and imgs.dtype != F32
-        if motion is not None:
-            if self._taps_ok(B * hw):
-                self._lin_s(ops.split(motion, sk), d, "context_linear", x, M=B * hw, N=Cc, K=self.context_channels, out_w=hw,
-                            y_img_stride=P * hw, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-            else:
-                _linear(motion, d, "context_linear", x, F32, M=B * hw, N=Cc, K=self.context_channels, out_w=hw, y_img_stride=P * hw,
-                        rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-        off = hw if motion is not None else 0
-        if img_tok:
-            imgs.fill(x, n_img=n_img_rows // hw, per_clip=n_img_rows // hw // B, P=P, y_off=off, tp=tp)
-        elif img_split:
-            self._lin_s(imgs, d, "in_linear", x, M=n_img_rows, N=Cc, K=self.in_channels, out_w=n_img_rows // B, y_img_stride=P * hw,
-                        y_off=off, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-        else:
-            _linear(imgs, d, "in_linear", x, F32, M=n_img_rows, N=Cc, K=self.in_channels, out_w=n_img_rows // B, y_img_stride=P * hw,
-                    y_off=off, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-
-    @torch.no_grad()
-    def _run_split(self, motion: torch.Tensor, imgs: torch.Tensor, *, B: int, hh: int, ww: int) -> torch.Tensor:
+    def _pass_split(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict]) -> torch.Tensor:
+        """f16x3 / bf16x3: one window through the stack.  cache (incremental loop): block -> its [B, L, hw, K|V] rows, fp32 or (when the
+        attention reads split operands) split rows; q of the new positions stays packed in qkv."""
         d = self._derived.get(self._build)
-        sk, Cc, L, dev = self.split_kind, self.model_channels, self.frames_length, motion.device
+        sk, Cc, L = self.split_kind, self.model_channels, self.frames_length
+        dev = (imgs.tokens if isinstance(imgs, FrameTokens) else imgs).device
         hw = hh * ww
-        M = B * L * hw
-        H = Cc // 32
+        M = B * P * hw
         x = torch.empty(M, Cc, device=dev, dtype=F32)
-        self._embed_inputs_split(d, x, motion, imgs, B=B, hw=hw, P=L, tp=d["tpos"], n_img_rows=B * (L - 1) * hw)
+        self._embed(d, x, motion, imgs, B=B, hw=hw, P=P, nf=nf, tp=d["tpos"][p0:], sk=sk)
         xn = ops.split_empty(M, Cc, sk, dev)
         qs = self._attn_split()                # f16x3: q, k, v leave the QKV epilogue as split rows, attention on the matrix cores
+        m_ = 2 if qs else 1                    # split rows: 2 16-bit elements per logical column
         qkv = ops.split_empty(M, 3 * Cc, sk, dev) if qs else torch.empty(M, 3 * Cc, device=dev, dtype=F32)
         ao = ops.split_empty(M, Cc, sk, dev)
         hdn = ops.split_empty(M, 4 * Cc, sk, dev)
+        geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None) for a in range(3)]
         for i in range(self.layers):
             p = f"b{i}"
-            axis = i % 3
-            if axis == 0:
-                geo = dict(n_seq=B * hw, inner=hw, nq=L, nk=L, q_outer_stride=L * hw, q_axis_stride=hw, causal=True)
-            elif axis == 1:
-                geo = dict(n_seq=B * L * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww, causal=False)
-            else:
-                geo = dict(n_seq=B * L * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1, causal=False)
             ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5, split_kind=sk)
-            self._lin_s(xn, d, p + ".in_proj", qkv, M=M, N=3 * Cc, K=Cc, y_split=qs)
-            m_ = 2 if qs else 1                                                      # split rows: 2 16-bit elements per logical column
-            ops.attention(qkv, qkv[:, m_ * Cc:], qkv[:, m_ * 2 * Cc:], ao, ldq=m_ * 3 * Cc, ldk=m_ * 3 * Cc, ldv=m_ * 3 * Cc, ldo=2 * Cc, n_head=H,
-                          kv_outer_stride=geo["q_outer_stride"], kv_axis_stride=geo["q_axis_stride"], out_split=sk, split_kind=sk if qs else 0,
-                          **geo)
+            if i % 3 == 0 and cache is not None:
+                if p0 == 0:
+                    cache[i] = ops.split_empty(B * L * hw, 2 * Cc, sk, dev) if qs else torch.empty(B * L * hw, 2 * Cc, device=dev, dtype=F32)
+                kv = cache[i]
+                q = qkv.view(-1)[:M * m_ * Cc].view(M, m_ * Cc)             # q of the new positions, packed [M, C]
+                self._lin_s(xn, d, p + ".in_proj", q, M=M, N=Cc, K=Cc, lo=0, hi=Cc, ldy=m_ * Cc, y_split=qs)
+                self._lin_s(xn, d, p + ".in_proj", kv, M=M, N=2 * Cc, K=Cc, lo=Cc, hi=3 * Cc, ldy=m_ * 2 * Cc, out_w=P * hw,
+                            y_img_stride=L * hw, y_off=p0 * hw, y_split=qs)
+                k, v, ldq, ldkv = kv, kv[:, m_ * Cc:], m_ * Cc, m_ * 2 * Cc
+            else:
+                self._lin_s(xn, d, p + ".in_proj", qkv, M=M, N=3 * Cc, K=Cc, y_split=qs)
+                q, k, v, ldq, ldkv = qkv, qkv[:, m_ * Cc:], qkv[:, m_ * 2 * Cc:], m_ * 3 * Cc, m_ * 3 * Cc
+            ops.attention(q, k, v, ao, ldq=ldq, ldk=ldkv, ldv=ldkv, ldo=2 * Cc, out_split=sk, split_kind=sk if qs else 0, **geo[i % 3])
             self._lin_s(ao, d, p + ".out_proj", x, M=M, N=Cc, K=Cc, residual=x, ldr=Cc)
             ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5, split_kind=sk)
             self._lin_s(xn, d, p + ".c_fc", hdn, M=M, N=4 * Cc, K=Cc, act=ops.ACT_QUICKGELU, y_split=True)
@@ -826,70 +755,7 @@ class FlatAxialDecoder(nn.Module):
                 self._lin_s(hdn, d, p + ".c_proj", xn, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y_split=True)
             else:
                 self._lin_s(hdn, d, p + ".c_proj", x, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
-        if not self.use_cids:                                 # MAGE+ head (N = 8 columns): GroupNorm + SiLU, fp32 GEMM
-            y = ops.groupnorm_silu(x, d["gn.w"], d["gn.b"], torch.empty(B * (L - 1) * hw, Cc, device=dev, dtype=F32), n_samples=B,
-                                   rows_per_sample=(L - 1) * hw, sample_stride_rows=L * hw, row_off=hw, groups=32,
-                                   eps=self.out[0].eps)
-            n8 = d["out.f32"].shape[0]
-            pred = torch.empty(B * (L - 1) * hw, n8, device=dev, dtype=F32)
-            return _linear(y, d, "out", pred, F32, M=B * (L - 1) * hw, N=n8, K=Cc)
-        logits = torch.empty(B * (L - 1) * hw, self.out_channels, device=dev, dtype=F32)
-        self._lin_s(xn, d, "out", logits, M=B * (L - 1) * hw, N=self.out_channels, K=Cc, out_w=(L - 1) * hw, a_img_stride=L * hw,
-                    a_off=hw)
-        return logits
-
-    @torch.no_grad()
-    def _inc_step_split(self, st: dict, motion: Optional[torch.Tensor], imgs: torch.Tensor) -> torch.Tensor:
-        d = self._derived.get(self._build)
-        sk, Cc, L = self.split_kind, self.model_channels, self.frames_length
-        dev = imgs.tokens.device if isinstance(imgs, FrameTokens) else imgs.device
-        B, hh, ww = st["B"], st["hh"], st["ww"]
-        hw, H = hh * ww, Cc // 32
-        p0 = st["p"]
-        P = 2 if motion is not None else 1
-        assert (p0 == 0) == (motion is not None) and p0 + P <= L
-        M = B * P * hw
-        x = torch.empty(M, Cc, device=dev, dtype=F32)
-        self._embed_inputs_split(d, x, motion, imgs, B=B, hw=hw, P=P, tp=d["tpos"][p0:], n_img_rows=B * hw)
-        xn = ops.split_empty(M, Cc, sk, dev)
-        qs = self._attn_split()
-        m_ = 2 if qs else 1                                                  # split rows: 2 16-bit elements per logical column
-        ask = sk if qs else 0
-        qkv = ops.split_empty(M, 3 * Cc, sk, dev) if qs else torch.empty(M, 3 * Cc, device=dev, dtype=F32)
-        ao = ops.split_empty(M, Cc, sk, dev)
-        hdn = ops.split_empty(M, 4 * Cc, sk, dev)
-        for i in range(self.layers):
-            p = f"b{i}"
-            axis = i % 3
-            ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5, split_kind=sk)
-            if axis == 0:
-                kv = st["kv"][i]                                             # [B, L, hw, K|V] fp32 (f16x3: split rows)
-                qv = qkv.view(-1)[:M * m_ * Cc].view(M, m_ * Cc)             # q of the new positions, packed [M, C]
-                self._lin_s(xn, d, p + ".in_proj", qv, M=M, N=Cc, K=Cc, lo=0, hi=Cc, ldy=m_ * Cc, y_split=qs)
-                self._lin_s(xn, d, p + ".in_proj", kv, M=M, N=2 * Cc, K=Cc, lo=Cc, hi=3 * Cc, ldy=m_ * 2 * Cc, out_w=P * hw,
-                            y_img_stride=L * hw, y_off=p0 * hw, y_split=qs)
-                ops.attention(qv, kv, kv[:, m_ * Cc:], ao, ldq=m_ * Cc, ldk=m_ * 2 * Cc, ldv=m_ * 2 * Cc, ldo=2 * Cc, n_seq=B * hw, inner=hw, nq=P,
-                              nk=p0 + P, n_head=H, q_outer_stride=P * hw, q_axis_stride=hw, kv_outer_stride=L * hw,
-                              kv_axis_stride=hw, causal=True, out_split=sk, split_kind=ask)
-            else:
-                self._lin_s(xn, d, p + ".in_proj", qkv, M=M, N=3 * Cc, K=Cc, y_split=qs)
-                if axis == 1:
-                    geo = dict(n_seq=B * P * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww)
-                else:
-                    geo = dict(n_seq=B * P * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1)
-                ops.attention(qkv, qkv[:, m_ * Cc:], qkv[:, m_ * 2 * Cc:], ao, ldq=m_ * 3 * Cc, ldk=m_ * 3 * Cc, ldv=m_ * 3 * Cc, ldo=2 * Cc, n_head=H,
-                              kv_outer_stride=geo["q_outer_stride"], kv_axis_stride=geo["q_axis_stride"], out_split=sk, split_kind=ask, **geo)
-            self._lin_s(ao, d, p + ".out_proj", x, M=M, N=Cc, K=Cc, residual=x, ldr=Cc)
-            ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5, split_kind=sk)
-            self._lin_s(xn, d, p + ".c_fc", hdn, M=M, N=4 * Cc, K=Cc, act=ops.ACT_QUICKGELU, y_split=True)
-            if i == self.layers - 1:
-                self._lin_s(hdn, d, p + ".c_proj", xn, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y_split=True)
-            else:
-                self._lin_s(hdn, d, p + ".c_proj", x, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
-        logits = torch.empty(B * hw, self.out_channels, device=dev, dtype=F32)
-        self._lin_s(xn, d, "out", logits, M=B * hw, N=self.out_channels, K=Cc, out_w=hw, a_img_stride=P * hw, a_off=(P - 1) * hw)
-        st["p"] = p0 + P
-        return logits
+        return self._head(d, xn if self.use_cids else x, B=B, hw=hw, P=P, nf=nf, split=True)
 
     def forward(self, motion: torch.Tensor, imgs: torch.Tensor) -> torch.Tensor:
         """motion [B,H,W,Cc], imgs [B,L-1,H,W,Ci] -> logits [B,L-1,H,W,out] fp32."""
@@ -1410,7 +1276,7 @@ class MAGE(nn.Module):
         gen = torch.empty(B, Lm1, R, R, device=images.device, dtype=torch.int64)
         if self.ar_mode == "incremental":
             # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
-            st = self.generate_model._inc_begin(B, R, R, images.device)
+            st = self.generate_model._inc_begin(B, R, R)
             prev = tok0.contiguous()
             gen_t = torch.empty(Lm1, B, hw, device=images.device, dtype=torch.int64)         # frame-major: a frame's tokens are contiguous,
             for i in range(Lm1):                                                              # the argmax writes them where the next step reads them

@@ -174,7 +174,7 @@ def _dec_forward(gm, run: _Run, motion, feats, B: int, hh: int, ww: int):
     d = gm._derived.get(gm._build)
     dt, Cc, L, dev = run.dt, gm.model_channels, gm.frames_length, motion.device
     hw = hh * ww
-    M, H = B * L * hw, Cc // 32
+    M = B * L * hw
     x = torch.empty(M, Cc, device=dev, dtype=F32)
     ops.gemm(motion, d["context_linear" + _sfx(dt)], x, M=B * hw, N=Cc, K=gm.context_channels, lda=gm.context_channels, ldy=Cc,
              bias=d["context_linear.b"], out_w=hw, y_img_stride=L * hw, rowadd=d["tpos"], rowadd_div=hw, rowadd_mod=L)
@@ -184,14 +184,7 @@ def _dec_forward(gm, run: _Run, motion, feats, B: int, hh: int, ww: int):
     xn1 = xa = None
     for i in range(gm.layers):
         p = f"b{i}"
-        axis = i % 3
-        if axis == 0:
-            geo = dict(n_seq=B * hw, inner=hw, nq=L, nk=L, q_outer_stride=L * hw, q_axis_stride=hw, causal=True)
-        elif axis == 1:
-            geo = dict(n_seq=B * L * ww, inner=ww, nq=hh, nk=hh, q_outer_stride=hw, q_axis_stride=ww, causal=False)
-        else:
-            geo = dict(n_seq=B * L * hh, inner=1, nq=ww, nk=ww, q_outer_stride=ww, q_axis_stride=1, causal=False)
-        geo.update(kv_outer_stride=geo["q_outer_stride"], kv_axis_stride=geo["q_axis_stride"], n_head=H)
+        geo = gm._axial_geo(i % 3, B, hh, ww, L)
         if xn1 is None:                              # later blocks: written with the previous block's residual add
             xn1 = ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], torch.empty(M, Cc, device=dev, dtype=dt), 1e-5)
         qkv = ops.gemm(xn1, d[p + ".in_proj" + _sfx(dt)], torch.empty(M, 3 * Cc, device=dev, dtype=dt), M=M, N=3 * Cc, K=Cc, lda=Cc,
