@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MAGE_ABI_VERSION 9
+#define MAGE_ABI_VERSION 10
 
 /* MAGE_BF16X3 / MAGE_F16X3: SPLIT-PRECISION operands -- the fast parity mode.  A logical fp32 matrix [rows, C] (C % 64 == 0, base
  * 256-byte aligned) is stored as two 16-bit pieces per element, x ~ hi + lo, per row as 64-column slabs [hi(64) | lo(64)] (so a row
@@ -345,6 +345,19 @@ int mage_vq_prepare(const float* codebook, int32_t K, int32_t D, float* codebook
  * without copies.  margin (optional, [rows] fp32) receives best minus second-best. */
 int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
                 int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, float* margin, void* stream);
+
+/* Seeded token sampling: temperature, top-k, top-p (nucleus), Gumbel-max on a stateless counter -- the stochastic counterpart of
+ * mage_argmax, with its row addressing (ld, group, in_group_stride, in_off, out_group_stride, out_off).  Row i draws with
+ * seeds[i / group] (int64 [>= rows / group], device) at token position pos = pos_off + i % group (frame * h*w + pixel).  The rule
+ * (vq.hip states it in full): s = logits * (float)(1.0 / temperature); top_k in [0, K] (0 or K: off) keeps every code whose s is >= the
+ * top_k-th largest; top_p in (0, 1] (1: off) keeps, of those, every code whose s is >= the largest value whose softmax mass from above
+ * reaches top_p; the token is the smallest j of that set maximising s_j - log(-log(u_j)), u_j from hash32 of (seed, pos, j).  NaN logits
+ * are never drawn.  top_k == 1 is greedy: mage_argmax.  K % 4 == 0, K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0, ld >= K, logits 16-byte aligned;
+ * temperature finite and > 0: MAGE_EINVAL otherwise, nothing launched. */
+#define MAGE_SAMPLE_MAX_K 4096
+int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
+                       int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, const int64_t* seeds,
+                       int64_t pos_off, float temperature, int32_t top_k, float top_p, void* stream);
 
 /* Mean cross entropy over rows (F.cross_entropy, mage_model.py:618): row_loss[i] = logsumexp(logits[i]) -
  * logits[i, target[i]] (workspace, [rows] fp32), loss_mean[0] = mean_i row_loss[i] (fixed-order fp64 sum:

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MAGE_HIP_LIB", os.path.join(_HERE, "lib", "libmage_hi
 
 F32, BF16, BF16X3, F16X3, F16 = 0, 1, 2, 3, 4  # BF16X3 / F16X3: split-precision operands; F16: single-pass half operands (include/mage_hip.h)
 ACT_NONE, ACT_RELU, ACT_QUICKGELU, ACT_GELU_ERF, ACT_TANH, ACT_QUICKGELU_GRAD = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -81,6 +81,7 @@ SIGNATURES = {
     "mage_vq_nearest": (C.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
     "mage_vq_prepare": (C.c_int, [vp, i32, i32, vp, vp, vp]),
     "mage_argmax": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
+    "mage_sample_tokens": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, i64, f32, i32, f32, vp]),
     "mage_cross_entropy": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
     "mage_conv_in": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mage_split_rows": (C.c_int, [vp, i64, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, vp, vp]),

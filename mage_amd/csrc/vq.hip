@@ -254,6 +254,148 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
     }
 }
 
+// ---- seeded token sampling (mage_sample_tokens): temperature, top-k, top-p, Gumbel-max.  The rule, for one row:
+//   inputs: fp32 logits z[0..K), inv_t = (float)(1.0 / temperature) (host), top_k (0 = off), top_p in (0, 1] (1 = off), the row's clip
+//   seed (uint64) and the token position pos = frame * h*w + pixel (frame = index of the generated frame, 0 .. L-2).
+//   1. s_j = z_j * inv_t (one fp32 multiply).  A NaN logit is never selected (it is in no set below).
+//   2. top-k: if 0 < top_k < K, A = { j : s_j >= the top_k-th largest s } (ties at the boundary kept: |A| may exceed top_k; fewer than
+//      top_k non-NaN logits: A = all of them); otherwise A = every code.
+//   3. top-p: if top_p < 1, w_j = exp(s_j - max_A s) for j in A, W = sum_A w_j, tau = the largest value v among { s_j : j in A } with
+//      sum_{j in A, s_j >= v} w_j >= top_p * W, N = { j in A : s_j >= tau } (ties kept); otherwise N = A.
+//   4. Gumbel-max on a stateless counter (hash32, common.h):
+//      u_j = ((hash32(seed * 0x9e3779b97f4a7c15 + (pos * K + j)) >> 8) + 0.5) * 2^-24   (uint64 wrap-around arithmetic),
+//      g_j = -log(-log(u_j)), token = the smallest j in N that maximises s_j + g_j (no selectable code at all: token 0).
+// A token's random stream depends on its clip's seed, frame, pixel and code only: not on the batch size, the clip's place in the batch,
+// the AR mode, the number of streams or graph replay.  top_k == 1 is greedy by definition: mage_argmax's kernel (first maximum wins).
+// One wave per row, the row in registers (NV values per lane, 16-byte loads; code k = c*256 + lane*4 + e of chunk c).  The selections are
+// bit-by-bit bisections over order-preserving uint keys of s: top-k counts with ballots (a scalar count, no shuffles), top-p sums the w_j
+// with fixed-order butterflies (every lane holds the same bits).  Where the sums are rounded (W, the masses) a row whose boundary mass is
+// within fp32 rounding of top_p * W may keep one value more or less than the exact rule; nothing else is approximate.
+__device__ __forceinline__ unsigned sample_key(float s) {       // order-preserving; -0 == +0; NaN -> 0 (below every number: never kept)
+    unsigned u = __float_as_uint(s);
+    if (s != s) return 0u;
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sample_key_value(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// g = -log(-log(u)) with u = (m + 0.5) 2^-24 never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
+__device__ __forceinline__ float sample_gumbel(unsigned long long ctr) {
+    const unsigned m = hash32(ctr) >> 8;
+    const float e = m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f)
+                                   : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
+    return -logf(e);
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+
+template <int NV, bool TOPK, bool TOPP>
+__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
+                                                     long in_stride, long in_off, int64_t* __restrict__ out, long out_stride,
+                                                     long out_off, const int64_t* __restrict__ seeds, long pos_off, float inv_t,
+                                                     int top_k, float top_p) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long gi = i / group, gr = i - gi * group;
+    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
+    float s[NV];
+    unsigned key[NV];                                   // 0: not selectable (NaN, or past K)
+#pragma unroll
+    for (int c = 0; c < NV / 4; ++c) {
+        const int k = c * 256 + lane * 4;
+        const f32x4 v = k < K ? *(const f32x4*)(p + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s[c * 4 + e] = __fmul_rn(v[e], inv_t);
+            key[c * 4 + e] = k < K ? sample_key(s[c * 4 + e]) : 0u;
+        }
+    }
+    unsigned lo = 1u;                                   // the candidate set: key >= lo
+    if constexpr (TOPK) {                               // the largest t with #{key >= t} >= top_k: the top_k-th largest key
+        unsigned t = 0u;
+        for (int b = 31; b >= 0; --b) {
+            const unsigned c = t | (1u << b);
+            int n = 0;
+#pragma unroll
+            for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= c));
+            if (n >= top_k) t = c;
+        }
+        lo = max(t, 1u);
+    }
+    if constexpr (TOPP) {
+        unsigned km = 0u;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) km = max(km, key[e]);
+        km = wave_max_u32(km);
+        if (km >= lo) {                                 // else: nothing selectable
+            const float smax = sample_key_value(km);
+            float w[NV], wl = 0.f;
+#pragma unroll
+            for (int e = 0; e < NV; ++e) {
+                w[e] = key[e] >= lo ? expf(s[e] - smax) : 0.f;
+                wl += w[e];
+            }
+            const float target = __fmul_rn(top_p, wave_sum(wl));
+            // the largest key t in [lo, km] with mass(key >= t) >= target; mass(>= lo) = W >= target.  The bits above the highest one in which
+            // lo and km differ are common to every key in between: the bisection starts below them (mass(>= t) = W there too).
+            const unsigned d = lo ^ km;
+            const int hb = d ? 31 - __builtin_clz(d) : -1;
+            unsigned t = hb >= 0 ? (km & ~((2u << hb) - 1u)) : km;
+            for (int b = hb; b >= 0; --b) {
+                const unsigned c = t | (1u << b);
+                float ml = 0.f;
+#pragma unroll
+                for (int e = 0; e < NV; ++e) ml += key[e] >= c ? w[e] : 0.f;
+                const float m = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_sum(ml))));
+                if (m >= target) t = c;
+            }
+            lo = max(t, lo);
+        }
+    }
+    const unsigned long long ctr = (unsigned long long)seeds[gi] * 0x9e3779b97f4a7c15ULL
+                                   + (unsigned long long)(pos_off + gr) * (unsigned long long)K;
+    float best = -INFINITY;
+    int bj = 0x7fffffff;
+    if constexpr (TOPK || TOPP) {
+        // a filtered set is small: each lane draws for its own candidates one at a time (the wave runs as many rounds as the fullest lane
+        // holds), instead of paying the Gumbel transform -- the dominant cost -- in every slot some lane of the wave needs
+        unsigned long long pend = 0;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) pend |= (unsigned long long)(key[e] >= lo) << e;
+        while (pend) {
+            const int e0 = __builtin_ctzll(pend);
+            pend &= pend - 1;
+            float sv = 0.f;
+#pragma unroll
+            for (int e = 0; e < NV; ++e) sv = e == e0 ? s[e] : sv;
+            const int j = (e0 >> 2) * 256 + lane * 4 + (e0 & 3);
+            const float v = sv + sample_gumbel(ctr + (unsigned long long)j);
+            if (v > best || (v == best && j < bj)) { best = v; bj = j; }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            if (key[e] >= lo) {
+                const int j = (e >> 2) * 256 + lane * 4 + (e & 3);
+                const float v = s[e] + sample_gumbel(ctr + (unsigned long long)j);
+                if (v > best || (v == best && j < bj)) { best = v; bj = j; }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oj = __shfl_xor(bj, o, 64);
+        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+    }
+    if (lane == 0) out[gi * out_stride + gr + out_off] = bj == 0x7fffffff ? 0 : bj;
+}
+
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                       long rows, int K, float* __restrict__ row_loss, int* __restrict__ err) {
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -562,6 +704,49 @@ extern "C" int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t
                        K, (long)ld, (long)group, (long)in_group_stride, (long)in_off, out, (long)out_group_stride,
                        (long)out_off, margin);
     MAGE_CHECK_LAUNCH("mage_argmax");
+    return MAGE_OK;
+}
+
+template <int NV>
+static void sample_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, long group,
+                          long in_stride, long in_off, int64_t* out, long out_stride, long out_off, const int64_t* seeds, long pos_off,
+                          float inv_t, int top_k, float top_p) {
+#define MAGE_SAMPLE(TK, TP)                                                                                                          \
+    hipLaunchKernelGGL((sample_kernel<NV, TK, TP>), grid, dim3(256), 0, s, logits, rows, K, ld, group, in_stride, in_off, out,   \
+                       out_stride, out_off, seeds, pos_off, inv_t, top_k, top_p)
+    if (topk && topp) MAGE_SAMPLE(true, true);
+    else if (topk) MAGE_SAMPLE(true, false);
+    else if (topp) MAGE_SAMPLE(false, true);
+    else MAGE_SAMPLE(false, false);
+#undef MAGE_SAMPLE
+}
+
+extern "C" int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
+                                  int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, const int64_t* seeds,
+                                  int64_t pos_off, float temperature, int32_t top_k, float top_p, void* stream) {
+    MAGE_CHECK_ARG(logits && out && seeds, "mage_sample_tokens: null pointer");
+    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && pos_off >= 0 &&
+                   (((uintptr_t)logits) & 15) == 0,
+                   "mage_sample_tokens: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K,
+                   (long)ld, MAGE_SAMPLE_MAX_K);
+    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "mage_sample_tokens: top_k=%d outside [0, K=%d]", top_k, K);
+    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mage_sample_tokens: top_p=%g outside (0, 1]", (double)top_p);
+    const float inv_t = (float)(1.0 / (double)temperature);
+    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
+                   "mage_sample_tokens: temperature=%g must be finite and > 0", (double)temperature);
+    if (top_k == 1)                                     // greedy by definition: first maximum of the logits
+        return mage_argmax(logits, rows, K, ld, group, in_group_stride, in_off, out, out_group_stride, out_off, nullptr, stream);
+    const bool topk = top_k > 0 && top_k < K, topp = top_p < 1.f;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    const long a[] = {(long)rows, (long)ld, (long)group, (long)in_group_stride, (long)in_off, (long)out_group_stride, (long)out_off,
+                      (long)pos_off};
+    if (K <= 256) sample_launch<4>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
+    else if (K <= 512) sample_launch<8>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
+    else if (K <= 1024) sample_launch<16>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
+    else if (K <= 2048) sample_launch<32>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
+    else sample_launch<64>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
+    MAGE_CHECK_LAUNCH("mage_sample_tokens");
     return MAGE_OK;
 }
 

@@ -16,10 +16,12 @@ products per K slab, fp32 accumulation -- include/mage_hip.h): fp32-class logits
 """
 from __future__ import annotations
 
+import ctypes
 import gc
+import math
 from collections import OrderedDict
 from math import exp
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import nn
@@ -848,6 +850,8 @@ class MAGE(nn.Module):
         self._graphs: dict = {}
         self._derived = _Derived(self)
         self.last_tokens: Optional[torch.Tensor] = None
+        self.sampling: Optional[Tuple[float, int, float]] = None   # (temperature, top_k, top_p) of set_sampling; None: greedy (the reference)
+        self.last_sample_seeds: Optional[torch.Tensor] = None     # the per-clip seeds of the last sampled call
 
     # ------------------------------------------------------------------ construction helpers
     def instantiate_first_stage(self, config):
@@ -871,6 +875,48 @@ class MAGE(nn.Module):
         if hasattr(self.first_stage_model, "set_precision"):     # an external latent first stage (MAGE+) has no such switch
             self.first_stage_model.set_precision(precision)
         return self
+
+    def set_sampling(self, temperature: Optional[float] = 1.0, top_k: int = 0, top_p: float = 1.0) -> "MAGE":
+        """Seeded stochastic decoding of the VQ tokens in autoregressive_generate: temperature, top-k (0: off), top-p (1: off), one seed per
+        clip (batch['sample_seed'], int64 [B]; drawn from torch's default CPU generator when absent).  The rule is mage_sample_tokens'
+        (include/mage_hip.h); top_k = 1 is greedy.  set_sampling(None): greedy argmax, the reference's decoding (the default)."""
+        if temperature is None:
+            self.sampling = None
+            return self
+        if not self.use_cids:
+            raise ValueError("set_sampling: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
+        t, k, p = float(temperature), int(top_k), float(top_p)
+        t32 = ctypes.c_float(t).value if math.isfinite(t) and abs(t) < 3e38 else math.inf     # the library takes it as fp32
+        if not (math.isfinite(t32) and t32 > 0 and 1.0 / t32 < 3.4e38):
+            raise ValueError(f"set_sampling: temperature must be finite and > 0 (in fp32, and so must 1 / temperature), got {temperature}")
+        if int(top_k) != top_k or not 0 <= k <= self.codebook_size:
+            raise ValueError(f"set_sampling: top_k must be an integer in [0, {self.codebook_size}], got {top_k}")
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"set_sampling: top_p must be in (0, 1], got {top_p}")
+        self.sampling = (t, k, p)
+        return self
+
+    def _sample_seeds(self, batch) -> dict:
+        """The batch with its 'sample_seed' entry as int64 [B] on the images' device (drawn here when absent); kept as last_sample_seeds."""
+        images = batch["images"]
+        B = images.shape[0]
+        seeds = batch.get("sample_seed")
+        if seeds is None:
+            seeds = torch.randint(-2 ** 63, 2 ** 63 - 1, (B,), dtype=torch.int64)
+        seeds = torch.as_tensor(seeds)
+        if seeds.dtype != torch.int64 or tuple(seeds.shape) != (B,):
+            raise ValueError(f"batch['sample_seed'] must be int64 [{B}], got {seeds.dtype} {tuple(seeds.shape)}")
+        seeds = seeds.to(images.device).contiguous()
+        self.last_sample_seeds = seeds
+        return {**batch, "sample_seed": seeds}
+
+    def _pick(self, logits, out, seeds: Optional[torch.Tensor], *, rows: int, K: int, pos_off: int, **kw) -> None:
+        """Tokens of `rows` logits rows: the sampler with the clip seeds when sampling is on, argmax otherwise (argmax's row addressing)."""
+        if seeds is None:
+            ops.argmax(logits, out, rows=rows, K=K, **kw)
+        else:
+            t, k, p = self.sampling
+            ops.sample_tokens(logits, out, seeds, rows=rows, K=K, temperature=t, top_k=k, top_p=p, pos_off=pos_off, **kw)
 
     def _dt(self) -> torch.dtype:
         return PRECISIONS[self.precision][0]
@@ -1074,13 +1120,18 @@ class MAGE(nn.Module):
     @torch.no_grad()
     def autoregressive_generate(self, batch):
         """batch {'images' [B,L,C,H,W] (only frame 0 is read), 'text' int64 [B,S], 'speed' [B] optional,
-        'video_noise' [B,64,h,w] optional (injects the randomness-branch noise instead of torch.randn)} -> [B,L,C,H,W].
+        'video_noise' [B,64,h,w] optional (injects the randomness-branch noise instead of torch.randn), 'sample_seed' int64 [B] optional
+        (one seed per clip when set_sampling is on; drawn from torch's default CPU generator when absent, kept as last_sample_seeds)}
+        -> [B,L,C,H,W].
 
         With ``self.streams = n > 1`` the clips are processed as n independent groups on n HIP streams: clips never
         interact, so the results are bit-identical, and the HBM-bound kernels of one group (LayerNorm, attention, casts)
         run under the MFMA-bound GEMMs of the other instead of in front of them."""
         images = batch["images"]
         _need_gpu(images, "MAGE.autoregressive_generate")
+        self.last_sample_seeds = None
+        if getattr(self, "sampling", None) is not None and self.use_cids:
+            batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
         with torch.cuda.device(images.device), weights_frozen():
             ug = self._graph_auto(batch) if self.use_graph is None else bool(self.use_graph)
@@ -1109,7 +1160,7 @@ class MAGE(nn.Module):
         return (int(getattr(self, "streams", 1)), bool(getattr(self, "frame_table", True)), self.generate_model._stream_bf16(), bool(getattr(self.ma_encoder, "mage_plus", False)),
                 getattr(self.ma_encoder, "split_kind", 0), getattr(self.text_encoder, "split_kind", 0),
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
-                config.get(), tuple(sorted(config.lib_options().items())))
+                config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None))
 
     def _generate_eager(self, batch):
         if not self.use_cids:
@@ -1274,6 +1325,7 @@ class MAGE(nn.Module):
         ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
         ma_dt = _to_dt(ma, dt)
         gen = torch.empty(B, Lm1, R, R, device=images.device, dtype=torch.int64)
+        seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
         if self.ar_mode == "incremental":
             # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
             st = self.generate_model._inc_begin(B, R, R)
@@ -1283,7 +1335,10 @@ class MAGE(nn.Module):
                 feats = self._frame_source(prev, dt)                                          # newest frame only
                 step_logits = self.generate_model._inc_step(st, ma_dt if i == 0 else None, feats)
                 prev = gen_t[i]
-                ops.argmax(step_logits, prev, rows=B * hw, K=K)
+                if seeds is None:
+                    ops.argmax(step_logits, prev, rows=B * hw, K=K)
+                else:                                                                         # clip = row // hw, position i*hw + pixel
+                    self._pick(step_logits, prev, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw)
             gen = gen_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else gen_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # index plumbing, once
             self.last_tokens, self.last_logits = gen, None
             video = self.first_stage_decode(gen)
@@ -1297,9 +1352,15 @@ class MAGE(nn.Module):
             if ev is not None:
                 ops.PROFILE.end("decoder_step", ev, 0.0)
             if i != Lm1 - 1:                                                                  # argmax of frame i -> slot i+1
-                ops.argmax(logits, cur, rows=B * hw, K=K, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw,
+                self._pick(logits, cur, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw,
                            out_group_stride=Lm1 * hw, out_off=(i + 1) * hw)
-        ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                       # :687
+        if seeds is None:
+            ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                   # :687
+        else:
+            # sampled: frames 0..L-3 are the tokens the loop conditioned on (slots 1..L-2); only the last frame is drawn from these logits
+            gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:, 1:])
+            self._pick(logits, gen, seeds, rows=B * hw, K=K, pos_off=(Lm1 - 1) * hw, group=hw, in_group_stride=Lm1 * hw,
+                       in_off=(Lm1 - 1) * hw, out_group_stride=Lm1 * hw, out_off=(Lm1 - 1) * hw)
         self.last_tokens, self.last_logits = gen, logits.view(B, Lm1, R, R, K)
         video = self.first_stage_decode(gen)                                                  # :690
         return _assemble(images, video)                         # :691

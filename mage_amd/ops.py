@@ -518,6 +518,23 @@ def argmax(logits: torch.Tensor, out: torch.Tensor, *, rows: int, K: int, ld: Op
     return out
 
 
+def sample_tokens(logits: torch.Tensor, out: torch.Tensor, seeds: torch.Tensor, *, rows: int, K: int, temperature: float = 1.0,
+                  top_k: int = 0, top_p: float = 1.0, pos_off: int = 0, ld: Optional[int] = None, group: Optional[int] = None,
+                  in_group_stride: Optional[int] = None, in_off: int = 0, out_group_stride: Optional[int] = None,
+                  out_off: int = 0) -> torch.Tensor:
+    """argmax's row addressing; row i draws with seeds[i // group] at position pos_off + i % group (mage_sample_tokens)."""
+    l, s = _dev(logits)
+    assert logits.dtype == torch.float32 and out.dtype == torch.int64 and seeds.dtype == torch.int64 and seeds.is_contiguous()
+    group = rows if group is None else group
+    in_group_stride = group if in_group_stride is None else in_group_stride
+    out_group_stride = group if out_group_stride is None else out_group_stride
+    assert seeds.device == logits.device and seeds.numel() >= (rows + group - 1) // group
+    _lib.check(l.mage_sample_tokens(logits.data_ptr(), rows, K, K if ld is None else ld, group, in_group_stride, in_off,
+                                    out.data_ptr(), out_group_stride, out_off, seeds.data_ptr(), pos_off, float(temperature),
+                                    int(top_k), float(top_p), s), l)
+    return out
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     l, s = _dev(logits)
     assert logits.dtype == torch.float32 and logits.is_contiguous() and target.dtype == torch.int64
