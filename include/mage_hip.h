@@ -91,6 +91,9 @@ int mage_get_option(const char* name, int32_t* value);
  * per CU), the one-wave-per-SIMD variant (bf16, bias or LayerNorm-consuming epilogue, K in [256, 1024], >= 4 tiles per CU: the decoder's QKV and
  * c_fc; option gemm_no_4w disables it) and its split-half form with the epilogue under the K loop (csrc/gemm4h.hip: K = 512, 16-bit rows out;
  * by default the QuickGELU forms = c_fc; gemm_no_4h disables it, gemm_4h_plain sends QKV there too), the few-rows kernel (M <= 1024), the padded-taps forms and the split-precision forms.
+ * (Same bits: the plain-row kernels among each other, and a padded-taps convolution with cin = 64 -- a K slab is one tap -- against the generic gather
+ * kernel.  Not the row-table form, which loads the table into its accumulators where the generic kernel adds it after the product, and not
+ * padded taps with cin > 64, whose slabs of one tap are summed in another order: equal up to fp32 rounding.)
  *
  * Row geometry.  A GEMM row m in [0, M) is decoded as img = m / (out_h*out_w),
  * oy = (m / out_w) % out_h, ox = m % out_w.  K = taps_h*taps_w*cin; k -> (ky, kx, ci), ci fastest:
@@ -117,7 +120,8 @@ int mage_get_option(const char* name, int32_t* value);
  * result, i.e. the next GEMM's A operand, directly.
  *
  * Requirements: lda and cin multiples of 8 (bf16) / 4 (f32); N multiple of 8; ldy/ldr multiples of 4 (fp32) / 8 (bf16);
- * A, W, Y 16-byte aligned; W is [N][K] row-major in `dtype`.
+ * A, W, Y 16-byte aligned; W is [N][K] row-major in `dtype`, packed (ldw = 0 or K) except in the split-K and split-precision
+ * forms, which take ldw >= K (2K); ldw < K, and ldw != K on any other form, is MAGE_EINVAL (checked before mage_init's own check).
  * ------------------------------------------------------------------------------------------- */
 typedef struct mage_gemm_desc {
     int32_t dtype;                     /* MAGE_F32 | MAGE_BF16 | MAGE_BF16X3 | MAGE_F16X3: type of A and W and of the MFMA */
@@ -141,7 +145,9 @@ typedef struct mage_gemm_desc {
     const void* residual;
     int32_t ldr, res_dtype;
     int32_t post_relu;
-    int32_t ldw;                       /* row stride of W in elements; 0 = K (W packed [N][K]) */
+    int32_t ldw;                       /* row stride of W in elements; 0 = K (W packed [N][K]; split operands: 2K).  A stride other than that is
+                                        * accepted only by the forms whose kernels read it -- split-K (n_split > 1) and split-precision operands;
+                                        * every other descriptor with ldw != K is refused (MAGE_EINVAL), never run with K in its place */
     /* Split-K (the weight-gradient GEMMs dW = dY^T X of the training path, whose contraction runs over all M tokens while the
      * output is only [N_out, K_out]): n_split > 1 computes n_split independent products in ONE launch,
      *     Y + s*y_split_stride  =  (A + s*a_split_stride) (*) (W + s*w_split_stride)^T      s = 0 .. n_split-1

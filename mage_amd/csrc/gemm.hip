@@ -44,6 +44,10 @@ extern "C" int mage_gemm(const mage_gemm_desc* d_in, void* stream) {
     if (dn.n_split <= 0) dn.n_split = 1;
     const mage_gemm_desc* d = &dn;
     MAGE_CHECK_ARG(d->ldw >= (spl ? 2 * d->K : d->K), "mage_gemm: ldw=%d < K=%d", d->ldw, d->K);
+    // only the split-K and the split-precision kernels carry the W row stride (gemm_impl.h, above gemm_kernel: in the generation path's kernels
+    // it costs the 8-phase kernel 11 spilled SGPRs): every other kernel indexes W with K, so a wider stride is refused, not ignored
+    MAGE_CHECK_ARG(d->ldw == d->K || d->n_split > 1 || spl,
+                   "mage_gemm: ldw=%d != K=%d: a W row stride other than K is read only by the split-K (n_split > 1) and split-precision forms", d->ldw, d->K);
     MAGE_CHECK_ARG(mage_zero_page() != nullptr, "mage_gemm: mage_init() has not been called");
     const bool h16 = d->dtype == MAGE_F16;
     MAGE_CHECK_ARG(d->dtype == MAGE_F32 || d->dtype == MAGE_BF16 || h16 || spl, "mage_gemm: bad dtype %d", d->dtype);

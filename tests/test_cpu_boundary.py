@@ -167,6 +167,38 @@ def test_config_is_read_once_and_library_options_round_trip(monkeypatch):
     assert offenders == [], offenders
 
 
+def test_gemm_refuses_a_w_row_stride_its_kernel_would_ignore():
+    """mage_gemm_desc::ldw: a W row stride other than K is read only by the split-K and the split-precision kernels; every other descriptor
+    with ldw != K is MAGE_EINVAL, decided before the mage_init check (so without a device), and mage_gemm_kernel_name inherits it.
+    The accepted forms get past the rule: without an initialised device they stop at the mage_init check that follows it."""
+    import ctypes as C
+    lib = _lib.load()
+    buf = (C.c_char * 4096)()                                   # never read: every call below returns before anything looks at the operands
+    p = C.addressof(buf)
+
+    def err(dtype, K, ldw, n_split=1, name=False):
+        d = _lib.GemmDesc(dtype=dtype, M=256, N=256, K=K, A=p, W=p, Y=p, lda=4 * K, ldy=256, y_dtype=_lib.F32, out_h=1, out_w=256, in_h=1,
+                          in_w=256, a_img_stride=256, taps_h=1, taps_w=1, cin=K, stride=1, dys=1, dxs=1, y_img_stride=256, y_mul_y=256,
+                          y_mul_x=1, ldw=ldw, n_split=n_split, a_split_stride=K, w_split_stride=K, y_split_stride=256 * 256)
+        out = C.create_string_buffer(256)
+        r = lib.mage_gemm_kernel_name(C.byref(d), out, len(out)) if name else lib.mage_gemm(C.byref(d), None)
+        return r, lib.mage_last_error().decode()
+
+    for dtype in (_lib.F32, _lib.BF16, _lib.F16):
+        for name in (False, True):
+            r, msg = err(dtype, 64, 72, name=name)
+            assert r == -1 and "ldw=72 != K=64" in msg and "split-K" in msg and "split-precision" in msg, (dtype, r, msg)
+            r, msg = err(dtype, 64, 56, name=name)
+            assert r == -1 and "ldw=56 < K=64" in msg, (dtype, r, msg)
+    for kw in (dict(dtype=_lib.F32, K=64, ldw=0), dict(dtype=_lib.BF16, K=64, ldw=64), dict(dtype=_lib.BF16, K=64, ldw=128, n_split=2),
+               dict(dtype=_lib.F32, K=64, ldw=128, n_split=2), dict(dtype=_lib.F16X3, K=64, ldw=0), dict(dtype=_lib.F16X3, K=64, ldw=128),
+               dict(dtype=_lib.BF16X3, K=64, ldw=192)):
+        r, msg = err(**kw, name=True)                            # (the query: nothing is launched where a device has been initialised)
+        assert r == 0 or (r == -1 and "ldw" not in msg and "mage_init" in msg), (kw, r, msg)
+    r, msg = err(_lib.BF16X3, 64, 120)                           # split operands: ldw counts 16-bit elements, 2K at least
+    assert r == -1 and "ldw=120 < K=64" in msg, (r, msg)
+
+
 def test_library_options_from_the_environment_are_clamped_to_their_ranges():
     """The environment's values go through the ranges mage_set_option enforces: an out-of-range MAGE_GEMM_STAGGER / MAGE_GEMM_SMALL_M is
     clamped when the table is filled, so that config.lib_option can always restore what it read.  A child process: the table is read once."""
