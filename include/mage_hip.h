@@ -525,7 +525,19 @@ int mage_group_rowsum(const void* x, int32_t dtype, int64_t rows, int32_t C, int
                       int64_t row_scale_div, float* out, int32_t n_chunk, void* stream);
 /* Backward of mage_attention: same descriptor (q, k, v as in the forward call; desc->out is unused), dout addressed like the
  * forward's out (ldo), gradients written with the addressing of q (dq, ld_dq) and of k / v (dk, dv, ld_dk, ld_dv) in desc->dtype.
- * P is recomputed in fp32; fixed-order sums (deterministic). */
+ * P is recomputed in fp32; fixed-order sums (deterministic).
+ *   dtype      MAGE_F32 or MAGE_BF16 (f16 and the split kinds: MAGE_EINVAL); drop_p > 0 with MAGE_F32 only; no output row map
+ *              (o_outer_stride = o_axis_stride = 0).
+ *   kernels    bf16 with nq <= 32, nk <= 32 and q, k, v, dout, dq, dk, dv and all seven leading dimensions multiples of 16 bytes
+ *              runs on the matrix cores.  Everything else -- fp32, longer bf16, and bf16 with a misaligned base or leading dimension, which
+ *              is NOT refused -- runs on the thread-per-query kernel, which needs
+ *                  16 * (2 * nk * 32 + 2 * qb * 33 + 2 * qb * (nk + 1)) <= 163840 bytes of LDS,  qb = min(nq, 64)
+ *              (nk = 64 up to nq = 31; any nq up to nk = 30): MAGE_EINVAL beyond it.
+ *   key rows   dk and dv are STORED, not accumulated: the key rows of different sequences must be distinct.  kv_outer_stride = 0 with
+ *              n_seq > inner (every outer block reading the same keys, which the forward accepts) is refused with MAGE_EINVAL.
+ *   no key     a query that sees no key (kv_len 0, or a causal query i < nq - nk) has an all -inf score row, as in the forward: its dq
+ *              is NaN, and dk and dv of EVERY key row of its (sequence, head) are NaN -- what torch.autograd returns through
+ *              softmax(scores + mask).  Other sequences and heads are unaffected.  Keys that no query of a sequence sees get dk = dv = 0. */
 int mage_attention_bwd(const mage_attn_desc* desc, const void* dout, void* dq, void* dk, void* dv, int32_t ld_dq, int32_t ld_dk,
                        int32_t ld_dv, void* stream);
 /* nn.Dropout in training mode as a stateless mask: y = (accumulate ? y : 0) + x * keep(seed, i) / (1 - p).  The backward pass

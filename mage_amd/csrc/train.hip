@@ -635,7 +635,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const mage_attn_desc
                 float p = ps[i * nkp + lane];
                 if (drop_thresh) {
                     const unsigned long long idx = (((unsigned long long)s * d.n_head + h) * d.nq + (i0 + i)) * d.nk + lane;
-                    p = hash32(d.drop_seed * 0x9e3779b97f4a7c15ULL + idx) >= drop_thresh ? p * inv_keep : 0.f;
+                    // a product, not a select: the NaN of a query that sees no key survives a dropped (i, j) (NaN * 0), as in torch
+                    p *= hash32(d.drop_seed * 0x9e3779b97f4a7c15ULL + idx) >= drop_thresh ? inv_keep : 0.f;
                 }
 #pragma unroll
                 for (int c = 0; c < 32; ++c) {
@@ -1262,7 +1263,8 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
             tshort4 phi, plo, dhi, dlo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float p = (kb * 16 + r < jmq[e]) ? expf(s2[e] * d.scale - mxq[e]) * invq[e] : 0.f;
+                // a query that sees no key (jmq <= 0) has P = NaN on every key, as in the query-major half (0 * (1 / 0)): dv is NaN too
+                const float p = (kb * 16 + r < jmq[e]) ? expf(s2[e] * d.scale - mxq[e]) * invq[e] : (jmq[e] > 0 ? 0.f : NAN);
                 short hi, lo;
                 split_hi_lo(p, hi, lo);
                 phi[e] = hi;
@@ -1321,6 +1323,11 @@ extern "C" int mage_attention_bwd(const mage_attn_desc* d, const void* dout, voi
     MAGE_CHECK_ARG(d->drop_p >= 0.f && d->drop_p < 1.f && (d->drop_p == 0.f || d->dtype == MAGE_F32),
                    "mage_attention_bwd: drop_p=%g needs the fp32 kernels and 0 <= p < 1", (double)d->drop_p);
     MAGE_CHECK_ARG(d->o_axis_stride == 0 && d->o_outer_stride == 0, "mage_attention_bwd: dout is addressed like q (no separate output row map)");
+    MAGE_CHECK_ARG(d->dtype == MAGE_F32 || d->dtype == MAGE_BF16, "mage_attention_bwd: bad dtype %d (fp32 and bf16 only)", d->dtype);
+    // dk / dv are stored, not accumulated: sequences that share key rows would overwrite each other's gradients
+    MAGE_CHECK_ARG(d->kv_outer_stride != 0 || d->n_seq <= d->inner,
+                   "mage_attention_bwd: kv_outer_stride 0 with n_seq=%d > inner=%d: sequences share key rows, their dk / dv would overwrite each other",
+                   d->n_seq, d->inner);
     if (d->dtype == MAGE_BF16 && d->nq <= 32 && d->nk <= 32 && !mage_options().attn_no_mfma && d->ldq % 8 == 0 && d->ldk % 8 == 0 &&
         d->ldv % 8 == 0 && d->ldo % 8 == 0 && ld_dq % 8 == 0 && ld_dk % 8 == 0 && ld_dv % 8 == 0 &&
         ((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) == 0)) {
@@ -1337,7 +1344,7 @@ extern "C" int mage_attention_bwd(const mage_attn_desc* d, const void* dout, voi
     const int qb = d->nq < 64 ? d->nq : 64;
     const size_t per_wave = (size_t)(2 * d->nk * 32 + 2 * qb * 33 + 2 * qb * (d->nk + 1)) * 4;
     const size_t lds = 4 * per_wave;
-    MAGE_CHECK_ARG(lds <= 160 * 1024, "mage_attention_bwd: LDS budget");
+    MAGE_CHECK_ARG(lds <= 160 * 1024, "mage_attention_bwd: LDS budget: nq=%d nk=%d need %zu bytes of 163840", d->nq, d->nk, lds);
     const dim3 grid(d->n_seq, (d->n_head + 3) / 4), blk(256);
     static bool attr_set[MAGE_MAX_DEVICES][2] = {{false}};
     const int dev = mage_device_index();
@@ -1349,16 +1356,13 @@ extern "C" int mage_attention_bwd(const mage_attn_desc* d, const void* dout, voi
         }
         hipLaunchKernelGGL((attention_bwd_kernel<float>), grid, blk, lds, s, *d, (const float*)dout, (float*)dq, (float*)dk, (float*)dv, ld_dq,
                            ld_dk, ld_dv, qb);
-    } else if (d->dtype == MAGE_BF16) {
+    } else {                                         // MAGE_BF16 (checked above)
         if (!attr_set[dev][1]) {
             (void)hipFuncSetAttribute((const void*)attention_bwd_kernel<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr_set[dev][1] = true;
         }
         hipLaunchKernelGGL((attention_bwd_kernel<unsigned short>), grid, blk, lds, s, *d, (const unsigned short*)dout, (unsigned short*)dq,
                            (unsigned short*)dk, (unsigned short*)dv, ld_dq, ld_dk, ld_dv, qb);
-    } else {
-        mage_set_error("mage_attention_bwd: bad dtype %d", d->dtype);
-        return MAGE_EINVAL;
     }
     MAGE_CHECK_LAUNCH("mage_attention_bwd");
     return MAGE_OK;

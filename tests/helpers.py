@@ -2,6 +2,7 @@
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from mage_amd.utils import synth
@@ -60,3 +61,66 @@ def unsplit(y, kind):
     v = y.reshape(rows, c2 // 128, 2, 64).float()
     lo = v[:, :, 1] / (2048.0 if kind == ops.F16X3 else 1.0)
     return (v[:, :, 0].double() + lo.double()).reshape(rows, c2 // 2)
+
+
+# ---------------------------------------------------------------- attention cases (tests/test_gpu_attention.py, tests/attention_bwd_ref.py)
+# NaN sentinels with a payload no kernel produces (negative sign, nonzero payload): 0 * inf gives the default NaN
+SENTINEL = {torch.float32: (torch.int32, 0xFFC0DEAD - 2 ** 32), torch.bfloat16: (torch.int16, 0xFFDE - 2 ** 16),
+            torch.float16: (torch.int16, 0xFE5A - 2 ** 16)}
+
+
+def attn_case(name, kind, nq, nk, H, n_seq, inner=1, causal=False, geo="sep", lens=None, div=1, omap=False, spread=1, scale=None,
+              kv_shared=False):
+    """geo 'axial': q, k, v side by side in one [rows, 3C] buffer, query i and key i on one row (the decoder's axial blocks; nq == nk);
+    'sep': three buffers with different leading dimensions.  spread 2 leaves a row gap between consecutive queries; omap gives out a row
+    map of its own (gaps between queries and between outer blocks); kv_shared: every outer block reads the same keys (kv_outer_stride 0).
+    lens: per-sequence key lengths 'edge' (nk, 1, nk - 1, a middle value, nk + 3) or 'edge0' (the same after a 0), indexed by s / div."""
+    return pytest.param(dict(name=name, kind=kind, nq=nq, nk=nk, H=H, n_seq=n_seq, inner=inner, causal=causal, geo=geo, lens=lens, div=div,
+                             omap=omap, spread=spread, scale=scale, kv_shared=kv_shared), id=name)
+
+
+def attn_lens(c):
+    nk, n = c["nk"], -(-c["n_seq"] // c["div"])
+    pat = [nk, 1, max(nk - 1, 0), (nk + 1) // 2, nk + 3]
+    if c["lens"] == "edge0":
+        pat = [0] + pat
+    g = torch.Generator().manual_seed(n * 7 + nk)
+    rnd = torch.randint(0, nk + 1, (n,), generator=g)
+    return torch.tensor([pat[i] if i < len(pat) else int(rnd[i]) for i in range(n)], dtype=torch.int32)
+
+
+def ulp(x, dt):
+    """The spacing of dt's values at |x| (bf16: 8 significand bits down to fp32's normal range; f16: 11 bits, subnormals below 2^-14)."""
+    _, e = torch.frexp(x.abs())
+    e = torch.where(x == 0, -1000.0, e.to(torch.float64) - 1)               # floor(log2 |x|)
+    if dt == torch.bfloat16:
+        return torch.exp2(e.clamp(min=-126) - 7)
+    return torch.exp2(e.clamp(min=-14) - 10)
+
+
+def attn_geometry(c):
+    nq, nk, inner, n_seq = c["nq"], c["nk"], c["inner"], c["n_seq"]
+    n_outer = -(-n_seq // inner)
+    if c["geo"] == "axial":
+        assert nq == nk and c["spread"] == 1
+        g = dict(q_outer_stride=nk * inner, q_axis_stride=inner, kv_outer_stride=nk * inner, kv_axis_stride=inner)
+        q_rows = kv_rows = n_outer * nk * inner
+    else:
+        qas = inner * c["spread"]
+        g = dict(q_outer_stride=nq * qas, q_axis_stride=qas, kv_outer_stride=0 if c["kv_shared"] else nk * inner, kv_axis_stride=inner)
+        q_rows, kv_rows = n_outer * nq * qas, (1 if c["kv_shared"] else n_outer) * nk * inner
+    if c["omap"]:
+        g.update(o_outer_stride=nq * 2 * inner + inner, o_axis_stride=2 * inner)
+        o_rows = n_outer * g["o_outer_stride"]
+    else:
+        o_rows = q_rows
+    return g, q_rows, kv_rows, o_rows + 3                                   # 3 rows past the last mapped one
+
+
+def attn_row_maps(c, g):
+    s = torch.arange(c["n_seq"])
+    outer, inn = s // c["inner"], s % c["inner"]
+    qr = (outer * g["q_outer_stride"] + inn)[:, None] + torch.arange(c["nq"])[None] * g["q_axis_stride"]
+    kr = (outer * g["kv_outer_stride"] + inn)[:, None] + torch.arange(c["nk"])[None] * g["kv_axis_stride"]
+    orr = (outer * g["o_outer_stride"] + inn)[:, None] + torch.arange(c["nq"])[None] * g["o_axis_stride"] if c["omap"] else qr
+    return qr, kr, orr
