@@ -365,6 +365,22 @@ int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, int64_t ld,
                        int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, const int64_t* seeds,
                        int64_t pos_off, float temperature, int32_t top_k, float top_p, void* stream);
 
+/* Log-probability of a given token under each row's logits: logprob = z_t - logsumexp_j z_j (log-softmax gathered at t).  Row i reads K fp32
+ * logits with mage_argmax's input addressing (ld, group, in_group_stride, in_off), token t = tokens[(i / group)*tok_group_stride + i % group
+ * + tok_off] (int64) and writes the fp32 result to the same index of logprob: the tokens mage_argmax / mage_sample_tokens wrote into the
+ * token buffer are scored where they lie.  The sum has a fixed order: a row's bits do not depend on rows or on its place in the launch.
+ * -inf logits contribute nothing; a NaN logit or a row with no finite logit gives NaN; z_t = -inf gives -inf.  A token outside [0, K) is
+ * recorded for mage_check_device_errors (and clamped).  Sizes and alignment as mage_sample_tokens: K % 4 == 0, K <= MAGE_SAMPLE_MAX_K,
+ * ld % 4 == 0, ld >= K, logits 16-byte aligned, strides and offsets >= 0; MAGE_EINVAL otherwise, nothing launched. */
+int mage_token_logprob(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride, int64_t in_off,
+                       const int64_t* tokens, float* logprob, int64_t tok_group_stride, int64_t tok_off, void* stream);
+
+/* Per-clip totals of token log-probabilities and the best-of-N pick.  logprob [n_clips * n_cand, per_clip] fp32 (the candidates of a clip
+ * adjacent) -> scores [n_clips, n_cand] fp32: each the fixed-order fp64 sum of a candidate's per_clip values rounded once (a clip's scores
+ * are bitwise independent of the batch).  n_cand > 1: best [n_clips] int64 = the candidate with the largest score, the smallest index on
+ * ties; a NaN score wins only if every score of the clip is NaN (then candidate 0).  n_cand == 1: best may be null and is not written. */
+int mage_clip_scores(const float* logprob, int64_t n_clips, int32_t n_cand, int64_t per_clip, float* scores, int64_t* best, void* stream);
+
 /* Mean cross entropy over rows (F.cross_entropy, mage_model.py:618): row_loss[i] = logsumexp(logits[i]) -
  * logits[i, target[i]] (workspace, [rows] fp32), loss_mean[0] = mean_i row_loss[i] (fixed-order fp64 sum:
  * deterministic).  A target outside [0, K) is recorded for mage_check_device_errors. */

@@ -82,6 +82,8 @@ SIGNATURES = {
     "mage_vq_prepare": (C.c_int, [vp, i32, i32, vp, vp, vp]),
     "mage_argmax": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
     "mage_sample_tokens": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, i64, f32, i32, f32, vp]),
+    "mage_token_logprob": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, vp, i64, i64, vp]),
+    "mage_clip_scores": (C.c_int, [vp, i64, i32, i64, vp, vp, vp]),
     "mage_cross_entropy": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
     "mage_conv_in": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mage_split_rows": (C.c_int, [vp, i64, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, vp, vp]),

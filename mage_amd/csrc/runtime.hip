@@ -178,6 +178,7 @@ extern "C" int mage_check_device_errors(void* stream) {
     (void)hipMemsetAsync(flag, 0, 16, (hipStream_t)stream);
     const char* what = host[0] == MAGE_DEVERR_EMBEDDING_ID ? "mage_embedding: index out of range"
                        : host[0] == MAGE_DEVERR_CE_TARGET ? "mage_cross_entropy: target out of range"
+                       : host[0] == MAGE_DEVERR_TOKEN_ID ? "mage_token_logprob: token out of range"
                                                           : "device-side argument error";
     mage_set_error("%s (value %d, valid range [0, %d))", what, host[1], host[2]);
     return MAGE_EINVAL;

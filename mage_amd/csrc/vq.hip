@@ -433,6 +433,77 @@ __global__ __launch_bounds__(1024) void sum_kernel(const float* __restrict__ v, 
     }
 }
 
+// ---- token log-probabilities (mage_token_logprob) and per-clip scores (mage_clip_scores).
+// lp = z_t - (m + log sum_j exp(z_j - m)), m = max_j z_j: the log-softmax of a row gathered at its token.  One wave per row, the row in
+// registers in sample_kernel's layout (code k = c*256 + lane*4 + e of chunk c).  Every reduction has a fixed order (a lane adds its own
+// terms in register order, the lanes meet in an xor butterfly), so a row's bits depend on the row alone.  -inf logits add exp(-inf) = 0;
+// a NaN logit, or a row whose maximum is not finite (inf - inf), makes the sum NaN and so the result; z_t = -inf gives -inf.  expf / logf
+// are the accurate ones.
+template <int NV>
+__global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
+                                                            long in_stride, long in_off, const int64_t* __restrict__ tokens,
+                                                            float* __restrict__ logprob, long tok_stride, long tok_off,
+                                                            int* __restrict__ err) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long gi = i / group, gr = i - gi * group;
+    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
+    float z[NV];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < NV / 4; ++c) {
+        const int k = c * 256 + lane * 4;
+        const f32x4 v = k < K ? *(const f32x4*)(p + k) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            z[c * 4 + e] = v[e];
+            mx = fmaxf(mx, v[e]);                       // (a NaN is skipped here and caught by the sum)
+        }
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) s = __fadd_rn(s, expf(z[e] - mx));
+    s = wave_sum(s);
+    if (lane == 0) {
+        const long ti = gi * tok_stride + gr + tok_off;
+        long tg = tokens[ti];
+        if (tg < 0 || tg >= K) {                        // reported by mage_check_device_errors, as mage_cross_entropy's targets are
+            mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
+            tg = tg < 0 ? 0 : K - 1;
+        }
+        logprob[ti] = p[tg] - (mx + logf(s));
+    }
+}
+
+// One workgroup per clip: wave w sums candidates w, w + 4, ... (a lane adds values lane, lane + 64, ... in fp64, the lanes meet in an xor
+// butterfly, one rounding to fp32), then thread 0 picks the largest score: first on ties, a NaN only if every score is NaN.
+__global__ __launch_bounds__(256) void clip_scores_kernel(const float* __restrict__ logprob, int n_cand, long per_clip,
+                                                          float* __restrict__ scores, int64_t* __restrict__ best) {
+    const long clip = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int c = wave; c < n_cand; c += 4) {
+        const float* v = logprob + (clip * n_cand + c) * per_clip;
+        double s = 0.0;
+        for (long j = lane; j < per_clip; j += 64) s += (double)v[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) scores[clip * n_cand + c] = (float)s;
+    }
+    if (!best) return;
+    __syncthreads();                                    // (workgroup-uniform: `best` is a kernel argument)
+    if (threadIdx.x == 0) {
+        int bi = 0;
+        float bs = scores[clip * n_cand];
+        for (int c = 1; c < n_cand; ++c) {
+            const float sc = scores[clip * n_cand + c];
+            if (sc > bs || (bs != bs && sc == sc)) { bs = sc; bi = c; }
+        }
+        best[clip] = bi;
+    }
+}
+
 }  // namespace
 
 extern "C" int mage_vq_prepare(const float* codebook, int32_t K, int32_t D, float* codebook_t, float* c2, void* stream) {
@@ -747,6 +818,43 @@ extern "C" int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, 
     else if (K <= 2048) sample_launch<32>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
     else sample_launch<64>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
     MAGE_CHECK_LAUNCH("mage_sample_tokens");
+    return MAGE_OK;
+}
+
+extern "C" int mage_token_logprob(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
+                                  int64_t in_off, const int64_t* tokens, float* logprob, int64_t tok_group_stride, int64_t tok_off,
+                                  void* stream) {
+    MAGE_CHECK_ARG(logits && tokens && logprob, "mage_token_logprob: null pointer");
+    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
+                   in_off >= 0 && tok_group_stride >= 0 && tok_off >= 0 && (((uintptr_t)logits) & 15) == 0,
+                   "mage_token_logprob: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K, (long)ld,
+                   MAGE_SAMPLE_MAX_K);
+    int* err = mage_error_word();
+    MAGE_CHECK_ARG(err != nullptr, "mage_token_logprob: mage_init() has not been called");
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+#define MAGE_LOGPROB(NV)                                                                                                             \
+    hipLaunchKernelGGL((token_logprob_kernel<NV>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, (long)group,              \
+                       (long)in_group_stride, (long)in_off, tokens, logprob, (long)tok_group_stride, (long)tok_off, err)
+    if (K <= 256) MAGE_LOGPROB(4);
+    else if (K <= 512) MAGE_LOGPROB(8);
+    else if (K <= 1024) MAGE_LOGPROB(16);
+    else if (K <= 2048) MAGE_LOGPROB(32);
+    else MAGE_LOGPROB(64);
+#undef MAGE_LOGPROB
+    MAGE_CHECK_LAUNCH("mage_token_logprob");
+    return MAGE_OK;
+}
+
+extern "C" int mage_clip_scores(const float* logprob, int64_t n_clips, int32_t n_cand, int64_t per_clip, float* scores, int64_t* best,
+                                void* stream) {
+    MAGE_CHECK_ARG(logprob && scores, "mage_clip_scores: null pointer");
+    MAGE_CHECK_ARG(n_clips > 0 && n_clips <= 0x7fffffffL && n_cand > 0 && per_clip > 0, "mage_clip_scores: bad sizes n_clips=%ld n_cand=%d per_clip=%ld",
+                   (long)n_clips, n_cand, (long)per_clip);
+    MAGE_CHECK_ARG(n_cand == 1 || best, "mage_clip_scores: n_cand=%d > 1 needs `best`", n_cand);
+    hipLaunchKernelGGL(clip_scores_kernel, dim3((unsigned)n_clips), dim3(256), 0, (hipStream_t)stream, logprob, n_cand, (long)per_clip, scores,
+                       n_cand > 1 ? best : nullptr);
+    MAGE_CHECK_LAUNCH("mage_clip_scores");
     return MAGE_OK;
 }
 

@@ -852,6 +852,12 @@ class MAGE(nn.Module):
         self.last_tokens: Optional[torch.Tensor] = None
         self.sampling: Optional[Tuple[float, int, float]] = None   # (temperature, top_k, top_p) of set_sampling; None: greedy (the reference)
         self.last_sample_seeds: Optional[torch.Tensor] = None     # the per-clip seeds of the last sampled call
+        self.logprobs = False          # set_logprobs: autoregressive_generate also leaves the log-probabilities of the tokens it generated
+        self.candidates = 1            # set_sampling(candidates=N): N sampled candidates per clip, the most likely one kept
+        self.last_token_logprobs: Optional[torch.Tensor] = None   # fp32 [B, L-1, h, w] (set_logprobs, candidates > 1, score)
+        self.last_clip_logprob: Optional[torch.Tensor] = None     # fp32 [B]: their per-clip totals
+        self.last_candidate_scores: Optional[torch.Tensor] = None  # candidates > 1: fp32 [B, N], every candidate's total
+        self.last_candidate_index: Optional[torch.Tensor] = None   # candidates > 1: int64 [B], the candidate kept
 
     # ------------------------------------------------------------------ construction helpers
     def instantiate_first_stage(self, config):
@@ -876,12 +882,20 @@ class MAGE(nn.Module):
             self.first_stage_model.set_precision(precision)
         return self
 
-    def set_sampling(self, temperature: Optional[float] = 1.0, top_k: int = 0, top_p: float = 1.0) -> "MAGE":
+    def set_sampling(self, temperature: Optional[float] = 1.0, top_k: int = 0, top_p: float = 1.0, candidates: int = 1) -> "MAGE":
         """Seeded stochastic decoding of the VQ tokens in autoregressive_generate: temperature, top-k (0: off), top-p (1: off), one seed per
         clip (batch['sample_seed'], int64 [B]; drawn from torch's default CPU generator when absent).  The rule is mage_sample_tokens'
-        (include/mage_hip.h); top_k = 1 is greedy.  set_sampling(None): greedy argmax, the reference's decoding (the default)."""
+        (include/mage_hip.h); top_k = 1 is greedy.  set_sampling(None): greedy argmax, the reference's decoding (the default).
+        candidates = N > 1: every clip is drawn N times behind ONE prologue (candidate c with seed sample_seed + c, int64 wrap-around; candidate
+        0 is the candidates = 1 result) and only the candidate with the largest log-probability (unfiltered softmax, temperature 1) is decoded:
+        last_tokens / last_token_logprobs / last_clip_logprob are the winner's, last_candidate_scores [B, N] and last_candidate_index [B]
+        tell the rest."""
+        if isinstance(candidates, bool) or int(candidates) != candidates or candidates < 1:
+            raise ValueError(f"set_sampling: candidates must be an integer >= 1, got {candidates}")
         if temperature is None:
-            self.sampling = None
+            if candidates > 1:
+                raise ValueError("set_sampling: candidates > 1 needs sampling on (greedy candidates would all be the same clip)")
+            self.sampling, self.candidates = None, 1
             return self
         if not self.use_cids:
             raise ValueError("set_sampling: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
@@ -893,8 +907,42 @@ class MAGE(nn.Module):
             raise ValueError(f"set_sampling: top_k must be an integer in [0, {self.codebook_size}], got {top_k}")
         if not 0.0 < p <= 1.0:
             raise ValueError(f"set_sampling: top_p must be in (0, 1], got {top_p}")
-        self.sampling = (t, k, p)
+        self.sampling, self.candidates = (t, k, p), int(candidates)
         return self
+
+    def set_logprobs(self, on: bool = True) -> "MAGE":
+        """on: autoregressive_generate leaves last_token_logprobs (fp32 [B, L-1, h, w]: the log-probability of each generated token under the
+        logits it was picked from -- the model's full softmax at temperature 1, not the filtered set of set_sampling) and last_clip_logprob
+        (fp32 [B], their per-clip totals).  Off (the default): both are None and the call launches nothing more."""
+        if on and not self.use_cids:
+            raise ValueError("set_logprobs: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        self.logprobs = bool(on)
+        return self
+
+    def _n_cand(self) -> int:
+        return int(getattr(self, "candidates", 1)) if getattr(self, "sampling", None) is not None and self.use_cids else 1
+
+    def _want_logprobs(self) -> bool:
+        return self.use_cids and (bool(getattr(self, "logprobs", False)) or self._n_cand() > 1)
+
+    @torch.no_grad()
+    def score(self, batch) -> torch.Tensor:
+        """Teacher-forced log-likelihood of the batch's own video under its caption: fp32 [B], the sum over frames 1 .. L-1 of the
+        log-probabilities of the frames' VQ tokens given the frames before them (last_token_logprobs [B, L-1, h, w] keeps the terms)."""
+        if not self.use_cids:
+            raise ValueError("score: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        images = batch["images"]
+        _need_gpu(images, "MAGE.score")
+        with torch.cuda.device(images.device), weights_frozen():
+            tok, logits = self.teacher_forced_logits(batch)
+            B, L, K = images.shape[0], self.frames_length, self.codebook_size
+            tgt = tok[:, 1:L].contiguous()
+            lp = torch.empty(tgt.shape, device=images.device, dtype=F32)
+            ops.token_logprob(logits, tgt, lp, rows=tgt.numel(), K=K)
+            scores, _ = ops.clip_scores(lp, n_clips=B)
+            self.last_token_logprobs = lp
+            ops.check_device_errors(images.device)
+        return scores.view(B)
 
     def _sample_seeds(self, batch) -> dict:
         """The batch with its 'sample_seed' entry as int64 [B] on the images' device (drawn here when absent); kept as last_sample_seeds."""
@@ -1130,6 +1178,7 @@ class MAGE(nn.Module):
         images = batch["images"]
         _need_gpu(images, "MAGE.autoregressive_generate")
         self.last_sample_seeds = None
+        self.last_token_logprobs = self.last_clip_logprob = self.last_candidate_scores = self.last_candidate_index = None
         if getattr(self, "sampling", None) is not None and self.use_cids:
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
@@ -1160,7 +1209,8 @@ class MAGE(nn.Module):
         return (int(getattr(self, "streams", 1)), bool(getattr(self, "frame_table", True)), self.generate_model._stream_bf16(), bool(getattr(self.ma_encoder, "mage_plus", False)),
                 getattr(self.ma_encoder, "split_kind", 0), getattr(self.text_encoder, "split_kind", 0),
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
-                config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None))
+                config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None),
+                self._want_logprobs(), self._n_cand())
 
     def _generate_eager(self, batch):
         if not self.use_cids:
@@ -1216,6 +1266,7 @@ class MAGE(nn.Module):
                 with torch.cuda.graph(g):
                     out = self._generate_eager(static)
                     toks, logits = self.last_tokens, self.last_logits
+                    lps = self._logprob_results()
             except Exception:
                 if self.use_graph:                       # asked for explicitly: loud
                     raise
@@ -1226,7 +1277,7 @@ class MAGE(nn.Module):
                 if gc_was:
                     gc.enable()
                 recs = ops.PROFILE.capture_end(saved)
-            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "tok": toks, "logits": logits, "recs": recs}
+            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "tok": toks, "logits": logits, "lps": lps, "recs": recs}
         else:
             for k, v in batch.items():
                 ent["in"][k].copy_(v)
@@ -1239,7 +1290,17 @@ class MAGE(nn.Module):
         # cloned like the tokens and the output: graph replay is the DEFAULT for small calls (use_graph = None), and a caller that keeps
         # last_logits across two generations must not find the first one overwritten by the second (0.5 MB per clip at cfg2)
         self.last_logits = None if ent["logits"] is None else ent["logits"].clone()
+        self._set_logprob_results([None if t_ is None else t_.clone() for t_ in ent["lps"]])
         return ent["out"].clone()
+
+    _LOGPROB_RESULTS = ("last_token_logprobs", "last_clip_logprob", "last_candidate_scores", "last_candidate_index")
+
+    def _logprob_results(self) -> list:
+        return [getattr(self, a, None) for a in self._LOGPROB_RESULTS]
+
+    def _set_logprob_results(self, vals) -> None:
+        for a, v in zip(self._LOGPROB_RESULTS, vals):
+            setattr(self, a, v)
 
     def _warm_derived(self) -> None:
         """Build every derived weight cache (bf16 copies, transposed codebook, folded BatchNorm vectors, summed positional
@@ -1270,18 +1331,20 @@ class MAGE(nn.Module):
         main = torch.cuda.current_stream(batch["images"].device)
         if getattr(self, "_side_streams", None) is None or len(self._side_streams) != n:
             self._side_streams = [torch.cuda.Stream(device=batch["images"].device) for _ in range(n)]
-        outs, toks = [None] * n, [None] * n
+        outs, toks, lps = [None] * n, [None] * n, [None] * n
         for g, st in enumerate(self._side_streams):
             st.wait_stream(main)                                      # inputs were produced on the caller's stream
             with torch.cuda.stream(st):
                 sub = {k: v[g * per:(g + 1) * per] for k, v in batch.items()}
                 outs[g] = self._generate_one(sub)
                 toks[g] = self.last_tokens
+                lps[g] = self._logprob_results()
         for st in self._side_streams:
             main.wait_stream(st)
-        for t_ in outs + toks:
+        for t_ in outs + toks + [t_ for l_ in lps for t_ in l_ if t_ is not None]:
             t_.record_stream(main)                                    # allocator plumbing: consumed on the caller's stream
         self.last_tokens, self.last_logits = torch.cat(toks, 0), None
+        self._set_logprob_results([None if col[0] is None else torch.cat(col, 0) for col in zip(*lps)])
         return torch.cat(outs, 0)
 
     @torch.no_grad()
@@ -1323,13 +1386,23 @@ class MAGE(nn.Module):
         dt = self._dt()
         tok0 = self.first_stage_encode(images[:, 0:1])[:, 0].reshape(B, hw)                   # :642
         ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
+        seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
+        N, Bc = self._n_cand(), B
+        if N > 1:
+            # best of N: the once-per-clip prologue above ran once; from here every clip is N adjacent rows of a batch of B * N, candidate c
+            # drawing with seed + c (int64 wrap-around), and only the winners are decoded
+            B = Bc * N
+            tok0 = tok0[:, None, :].expand(Bc, N, hw).reshape(B, hw)
+            ma = ma.view(Bc, 1, hw, -1).expand(Bc, N, hw, ma.shape[-1]).reshape(B * hw, -1)
+            seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
         ma_dt = _to_dt(ma, dt)
         gen = torch.empty(B, Lm1, R, R, device=images.device, dtype=torch.int64)
-        seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
+        want_lp = self._want_logprobs()
         if self.ar_mode == "incremental":
             # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
             st = self.generate_model._inc_begin(B, R, R)
             prev = tok0.contiguous()
+            lp_t = torch.empty(Lm1, B, hw, device=images.device, dtype=F32) if want_lp else None
             gen_t = torch.empty(Lm1, B, hw, device=images.device, dtype=torch.int64)         # frame-major: a frame's tokens are contiguous,
             for i in range(Lm1):                                                              # the argmax writes them where the next step reads them
                 feats = self._frame_source(prev, dt)                                          # newest frame only
@@ -1339,12 +1412,17 @@ class MAGE(nn.Module):
                     ops.argmax(step_logits, prev, rows=B * hw, K=K)
                 else:                                                                         # clip = row // hw, position i*hw + pixel
                     self._pick(step_logits, prev, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw)
+                if want_lp:                                                                   # the tokens just picked, under the logits they came from
+                    ops.token_logprob(step_logits, prev, lp_t[i], rows=B * hw, K=K)
             gen = gen_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else gen_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # index plumbing, once
-            self.last_tokens, self.last_logits = gen, None
-            video = self.first_stage_decode(gen)
-            return _assemble(images, video)
+            lp = None
+            if want_lp:
+                lp = lp_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else lp_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)
+            return self._finish(images, gen, None, lp, Bc, N)
         cur = tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                                 # :670 future slots hold frame 0
         logits = None
+        lp = torch.empty(B, Lm1, R, R, device=images.device, dtype=F32) if want_lp else None
+        frame = dict(rows=B * hw, K=K, group=hw, in_group_stride=Lm1 * hw)                  # frame i of every clip: (in_ / tok_) off = i * hw
         for i in range(Lm1):                                                                  # :673-684
             feats = self._frame_source(cur, dt)
             ev = ops.PROFILE.begin() if ops.PROFILE.wants("decoder_step") else None          # bench.py: the transformer step on its own
@@ -1354,16 +1432,38 @@ class MAGE(nn.Module):
             if i != Lm1 - 1:                                                                  # argmax of frame i -> slot i+1
                 self._pick(logits, cur, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw,
                            out_group_stride=Lm1 * hw, out_off=(i + 1) * hw)
+                if want_lp and seeds is not None:         # sampled: frame i's tokens (slot i+1 of cur) under the logits they were drawn from
+                    ops.token_logprob(logits, cur.view(-1)[hw:], lp.view(-1), in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
         if seeds is None:
             ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                   # :687
+            if want_lp:
+                ops.token_logprob(logits, gen, lp, rows=B * Lm1 * hw, K=K)
         else:
             # sampled: frames 0..L-3 are the tokens the loop conditioned on (slots 1..L-2); only the last frame is drawn from these logits
             gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:, 1:])
             self._pick(logits, gen, seeds, rows=B * hw, K=K, pos_off=(Lm1 - 1) * hw, group=hw, in_group_stride=Lm1 * hw,
                        in_off=(Lm1 - 1) * hw, out_group_stride=Lm1 * hw, out_off=(Lm1 - 1) * hw)
-        self.last_tokens, self.last_logits = gen, logits.view(B, Lm1, R, R, K)
-        video = self.first_stage_decode(gen)                                                  # :690
-        return _assemble(images, video)                         # :691
+            if want_lp:
+                ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
+        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N)
+
+    def _finish(self, images, gen, logits, lp, Bc: int, N: int):
+        """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
+        of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691)."""
+        if lp is not None:
+            scores, best = ops.clip_scores(lp, n_clips=Bc, n_cand=N)
+            if N > 1:
+                win = best + torch.arange(Bc, device=best.device, dtype=torch.int64) * N
+                gen, lp = gen.index_select(0, win), lp.index_select(0, win)
+                logits = None if logits is None else logits.index_select(0, win)
+                self.last_candidate_scores, self.last_candidate_index = scores, best
+                self.last_clip_logprob = scores.gather(1, best[:, None]).view(Bc)
+            else:
+                self.last_clip_logprob = scores.view(Bc)
+            self.last_token_logprobs = lp
+        self.last_tokens, self.last_logits = gen, logits
+        video = self.first_stage_decode(gen)
+        return _assemble(images, video)
 
     # ------------------------------------------------------------------ teacher-forced pass (mage_model.py:575-639)
     @torch.no_grad()

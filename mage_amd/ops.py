@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -533,6 +533,35 @@ def sample_tokens(logits: torch.Tensor, out: torch.Tensor, seeds: torch.Tensor, 
                                     out.data_ptr(), out_group_stride, out_off, seeds.data_ptr(), pos_off, float(temperature),
                                     int(top_k), float(top_p), s), l)
     return out
+
+
+def token_logprob(logits: torch.Tensor, tokens: torch.Tensor, logprob: torch.Tensor, *, rows: int, K: int, ld: Optional[int] = None,
+                  group: Optional[int] = None, in_group_stride: Optional[int] = None, in_off: int = 0,
+                  tok_group_stride: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
+    """argmax's input addressing; row i scores tokens[(i // group) * tok_group_stride + i % group + tok_off] and writes the same index of
+    logprob (mage_token_logprob).  tokens / logprob are addressed from their first element: pass a flat slice to shift one against the other."""
+    l, s = _dev(logits)
+    assert logits.dtype == torch.float32 and tokens.dtype == torch.int64 and logprob.dtype == torch.float32
+    assert tokens.device == logits.device and logprob.device == logits.device
+    group = rows if group is None else group
+    in_group_stride = group if in_group_stride is None else in_group_stride
+    tok_group_stride = group if tok_group_stride is None else tok_group_stride
+    last = ((rows - 1) // group) * tok_group_stride + (rows - 1) % group + tok_off          # the largest index addressed
+    assert tok_off >= 0 and last < tokens.numel() and last < logprob.numel()
+    _lib.check(l.mage_token_logprob(logits.data_ptr(), rows, K, K if ld is None else ld, group, in_group_stride, in_off, tokens.data_ptr(),
+                                    logprob.data_ptr(), tok_group_stride, tok_off, s), l)
+    return logprob
+
+
+def clip_scores(logprob: torch.Tensor, *, n_clips: int, n_cand: int = 1):
+    """(scores [n_clips, n_cand] fp32, best [n_clips] int64 or None when n_cand == 1) of logprob [n_clips * n_cand, ...] fp32
+    (mage_clip_scores)."""
+    l, s = _dev(logprob)
+    assert logprob.dtype == torch.float32 and logprob.is_contiguous() and logprob.numel() % (n_clips * n_cand) == 0
+    scores = torch.empty(n_clips, n_cand, device=logprob.device, dtype=torch.float32)
+    best = torch.empty(n_clips, device=logprob.device, dtype=torch.int64) if n_cand > 1 else None
+    _lib.check(l.mage_clip_scores(logprob.data_ptr(), n_clips, n_cand, logprob.numel() // (n_clips * n_cand), scores.data_ptr(), _p(best), s), l)
+    return scores, best
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
