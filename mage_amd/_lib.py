@@ -1,4 +1,4 @@
-"""ctypes binding of libmage_hip.so (the C ABI in include/mage_hip.h).
+"""ctypes binding of libmage_hip.so (the C ABI in include/mage_hip.h and include/mage_hip_ext.h).
 
 The product path has no fallback: if the shared library is missing or the device
 is not a gfx950 GPU, ``lib()`` raises and every op fails loudly.
@@ -125,6 +125,11 @@ SIGNATURES = {
     "mage_adam": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, vp]),
 }
 
+# The core table above is frozen at 69 entry points (ABI 10); additions are declared in include/mage_hip_ext.h and bound from this one.
+EXT_SIGNATURES = {
+    "mage_token_stats": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, f32, i32, f32, vp, vp, vp, vp, vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 _inited_devices = set()
 
@@ -146,7 +151,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     # that owns torch's streams and allocations (two HIP runtimes in one process do not see each other's devices).
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the .so is stale / missing a symbol
         fn.restype, fn.argtypes = res, args
     if lib.mage_abi_version() != ABI_VERSION:

@@ -2,6 +2,7 @@
 // Integer/index outputs here must be bit-exact against the reference, so the distance follows the
 // reference FORMULA (vqvae_model.py:14-21): fl32(fl32(|c|^2 + |z|^2) - 2*<z,c>), first minimum wins.
 #include "common.h"
+#include "../../include/mage_hip_ext.h"
 
 namespace {
 
@@ -293,22 +294,23 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return v;
 }
 
-template <int NV, bool TOPK, bool TOPP>
-__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
-                                                     long in_stride, long in_off, int64_t* __restrict__ out, long out_stride,
-                                                     long out_off, const int64_t* __restrict__ seeds, long pos_off, float inv_t,
-                                                     int top_k, float top_p) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const long gi = i / group, gr = i - gi * group;
-    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
-    float s[NV];
-    unsigned key[NV];                                   // 0: not selectable (NaN, or past K)
+// Chunk c of a row in sample_kernel's layout: one 16-byte load, codes k = c*256 + lane*4 + e, 0 past K.
+__device__ __forceinline__ f32x4 sample_row_chunk(const float* __restrict__ p, int lane, int K, int c) {
+    const int k = c * 256 + lane * 4;
+    return k < K ? *(const f32x4*)(p + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Steps 1-3 of the rule for one row: s (the scaled logits), key (0: not selectable -- NaN, or past K) and the returned threshold lo >= 1
+// with N = { j : key_j >= lo }.  row(c) gives chunk c of the row (sample_kernel loads it there and then, token_stats_kernel hands over the
+// registers it read once).  THE filter: mage_sample_tokens draws from this set and mage_token_stats reports on it, so the two agree bit
+// for bit on every row, the ones whose rounded top-p masses keep a value more or less than the exact rule included.
+template <int NV, bool TOPK, bool TOPP, typename ROW>
+__device__ __forceinline__ unsigned sample_filter(ROW row, int lane, int K, float inv_t, int top_k, float top_p, float (&s)[NV],
+                                                  unsigned (&key)[NV]) {
 #pragma unroll
     for (int c = 0; c < NV / 4; ++c) {
         const int k = c * 256 + lane * 4;
-        const f32x4 v = k < K ? *(const f32x4*)(p + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 v = row(c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             s[c * 4 + e] = __fmul_rn(v[e], inv_t);
@@ -318,12 +320,20 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     unsigned lo = 1u;                                   // the candidate set: key >= lo
     if constexpr (TOPK) {                               // the largest t with #{key >= t} >= top_k: the top_k-th largest key
         unsigned t = 0u;
-        for (int b = 31; b >= 0; --b) {
+        auto bit = [&](int b) {
             const unsigned c = t | (1u << b);
             int n = 0;
 #pragma unroll
             for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= c));
             if (n >= top_k) t = c;
+        };
+        // NV = 4, 32 x 4 ballots: straight-line code, which the compiler chose by itself while this loop stood in sample_kernel (K = 256,
+        // top-k only: 40 against 43 us as a loop); every other instance is the loop it always was
+        if constexpr (NV == 4) {
+#pragma unroll
+            for (int b = 31; b >= 0; --b) bit(b);
+        } else {
+            for (int b = 31; b >= 0; --b) bit(b);
         }
         lo = max(t, 1u);
     }
@@ -357,6 +367,23 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
             lo = max(t, lo);
         }
     }
+    return lo;
+}
+
+template <int NV, bool TOPK, bool TOPP>
+__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
+                                                     long in_stride, long in_off, int64_t* __restrict__ out, long out_stride,
+                                                     long out_off, const int64_t* __restrict__ seeds, long pos_off, float inv_t,
+                                                     int top_k, float top_p) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long gi = i / group, gr = i - gi * group;
+    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
+    float s[NV];
+    unsigned key[NV];
+    const unsigned lo = sample_filter<NV, TOPK, TOPP>([=](int c) { return sample_row_chunk(p, lane, K, c); }, lane, K, inv_t, top_k, top_p,
+                                                      s, key);                                    // the candidate set: key >= lo
     const unsigned long long ctr = (unsigned long long)seeds[gi] * 0x9e3779b97f4a7c15ULL
                                    + (unsigned long long)(pos_off + gr) * (unsigned long long)K;
     float best = -INFINITY;
@@ -378,10 +405,12 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
             if (v > best || (v == best && j < bj)) { best = v; bj = j; }
         }
     } else {
+        // nothing filtered: lo == 1, and key >= 1 says no more than "a code of the row, not NaN" (sample_key) -- asked of s itself, so that
+        // this instance holds no key registers through the Gumbel transforms
 #pragma unroll
         for (int e = 0; e < NV; ++e) {
-            if (key[e] >= lo) {
-                const int j = (e >> 2) * 256 + lane * 4 + (e & 3);
+            const int j = (e >> 2) * 256 + lane * 4 + (e & 3);
+            if (j < K && s[e] == s[e]) {
                 const float v = s[e] + sample_gumbel(ctr + (unsigned long long)j);
                 if (v > best || (v == best && j < bj)) { best = v; bj = j; }
             }
@@ -474,6 +503,121 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restr
             tg = tg < 0 ? 0 : K - 1;
         }
         logprob[ti] = p[tg] - (mx + logf(s));
+    }
+}
+
+// ---- per-token statistics of the sampling policy (mage_token_stats, include/mage_hip_ext.h): what mage_sample_tokens' filter kept and how
+// the kept set weighs the given token.  Per row, with s, A, N of steps 1-3 of the sampling rule above (sample_filter: the sampler's own code,
+// so N is the sampler's bit for bit), s_max = max_N s, w_j = exp(s_j - s_max), Z = sum_{j in N} w_j:
+//   kept           = |N|                                                (a ballot count: exact)
+//   policy_logprob = s_t - (s_max + log Z) for t in N, -inf otherwise   (s_t = z_t * inv_t, the sampler's multiply)
+//   policy_entropy = log Z - (sum_{j in N} w_j (s_j - s_max)) / Z       (nats; exactly 0 when |N| = 1)
+//   entropy        = the same formula over the whole row of z itself: temperature 1, no filter -- the distribution mage_token_logprob scores under
+// top_k == 1 is greedy by definition, as in the sampler: N = { mage_argmax's first maximum of z }, kept = 1, policy_logprob = 0 for that code
+// and -inf for any other, policy_entropy = 0.
+// Special values: a NaN logit is in no set and adds nothing to Z (it makes `entropy` NaN, as it does mage_token_logprob's result); a -inf
+// logit in N counts in `kept` and adds a zero term to both sums (never 0 * inf); a row with no selectable code (every logit NaN) gives
+// kept = 0 and NaN for policy_logprob and policy_entropy; s_max = +-inf (a +inf logit, a row of -inf only) gives NaN through
+// inf - inf, as in mage_token_logprob; a token outside [0, K) is raised (MAGE_DEVERR_TOKEN_ID) and clamped.
+// One wave per row, the row read once into registers in sample_kernel's layout whatever outputs are asked for (a null output costs a
+// wave-uniform branch), one instance per filter combination.  Every sum has a fixed order: a lane adds its own terms in register order (adding
+// 0 for a code outside N), the lanes meet in an xor butterfly; expf / logf are the accurate ones.  With temperature 1 and no filter, s = z,
+// s_max = the row maximum and Z is token_logprob_kernel's sum operation for operation: policy_logprob equals mage_token_logprob's result bit
+// for bit on NaN-free rows.
+enum { STATS_TOPK = 1, STATS_TOPP = 2, STATS_GREEDY = 4 };
+template <int NV, int MODE>
+__global__ __launch_bounds__(256) void token_stats_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group, long in_stride,
+                                                          long in_off, const int64_t* __restrict__ tokens, long tok_stride, long tok_off,
+                                                          float inv_t, int top_k, float top_p, float* __restrict__ policy_logprob,
+                                                          float* __restrict__ policy_entropy, int32_t* __restrict__ kept,
+                                                          float* __restrict__ entropy, int* __restrict__ err) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long gi = i / group, gr = i - gi * group;
+    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
+    const long ti = gi * tok_stride + gr + tok_off;
+    f32x4 zc[NV / 4];
+#pragma unroll
+    for (int c = 0; c < NV / 4; ++c) zc[c] = sample_row_chunk(p, lane, K, c);
+    if (entropy) {                                      // the whole row at temperature 1: token_logprob_kernel's maximum and sum
+        float mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < NV; ++e)
+            if ((e >> 2) * 256 + lane * 4 < K) mx = fmaxf(mx, zc[e >> 2][e & 3]);          // (a NaN is skipped here and caught by the sum)
+        mx = wave_max(mx);
+        float zs = 0.f, ts = 0.f;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            const float d = zc[e >> 2][e & 3] - mx;
+            const float w = (e >> 2) * 256 + lane * 4 < K ? expf(d) : 0.f;
+            zs = __fadd_rn(zs, w);
+            ts = w == 0.f ? ts : __fmaf_rn(w, d, ts);   // exp(-inf) = 0 adds nothing: not 0 * inf
+        }
+        zs = wave_sum(zs);
+        ts = wave_sum(ts);
+        if (lane == 0) entropy[ti] = logf(zs) - ts / zs;
+    }
+    if (!policy_logprob && !policy_entropy && !kept) return;
+    float s[NV];
+    unsigned key[NV];
+    const unsigned lo = sample_filter<NV, (MODE & STATS_TOPK) != 0, (MODE & STATS_TOPP) != 0>([&](int c) { return zc[c]; }, lane, K, inv_t, top_k,
+                                                                                              top_p, s, key);
+    unsigned km = 0u;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) km = max(km, key[e]);
+    km = wave_max_u32(km);                              // km >= lo unless nothing is selectable (then every key is 0)
+    if constexpr (MODE == STATS_GREEDY) {               // (inv_t = 1 here: s = z) N = the first maximum, NaNs skipped: argmax_kernel's pick
+        int bj = 0x7fffffff;
+#pragma unroll
+        for (int e = NV - 1; e >= 0; --e)
+            if (key[e] == km) bj = (e >> 2) * 256 + lane * 4 + (e & 3);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bj = min(bj, __shfl_xor(bj, o, 64));
+        if (lane == 0) {
+            const bool any = km != 0u;
+            if (kept) kept[ti] = any ? 1 : 0;
+            if (policy_entropy) policy_entropy[ti] = any ? 0.f : __builtin_nanf("");
+            if (policy_logprob) {
+                long tg = tokens[ti];
+                if (tg < 0 || tg >= K) {
+                    mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
+                    tg = tg < 0 ? 0 : K - 1;
+                }
+                policy_logprob[ti] = !any ? __builtin_nanf("") : tg == bj ? 0.f : -INFINITY;
+            }
+        }
+    } else {
+        int n = 0;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= lo));
+        float zs = 0.f, ts = 0.f;
+        const float smax = sample_key_value(km);
+        if (policy_logprob || policy_entropy) {
+#pragma unroll
+            for (int e = 0; e < NV; ++e) {
+                const float d = s[e] - smax;
+                const float w = key[e] >= lo ? expf(d) : 0.f;
+                zs = __fadd_rn(zs, w);
+                ts = w == 0.f ? ts : __fmaf_rn(w, d, ts);
+            }
+            zs = wave_sum(zs);
+            if (policy_entropy) ts = wave_sum(ts);
+        }
+        if (lane == 0) {
+            if (kept) kept[ti] = n;
+            const float lz = logf(zs);
+            if (policy_entropy) policy_entropy[ti] = n ? lz - ts / zs : __builtin_nanf("");
+            if (policy_logprob) {
+                long tg = tokens[ti];
+                if (tg < 0 || tg >= K) {
+                    mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
+                    tg = tg < 0 ? 0 : K - 1;
+                }
+                const float st = __fmul_rn(p[tg], inv_t);
+                policy_logprob[ti] = !n ? __builtin_nanf("") : sample_key(st) >= lo ? st - (smax + lz) : -INFINITY;
+            }
+        }
     }
 }
 
@@ -843,6 +987,53 @@ extern "C" int mage_token_logprob(const float* logits, int64_t rows, int32_t K, 
     else MAGE_LOGPROB(64);
 #undef MAGE_LOGPROB
     MAGE_CHECK_LAUNCH("mage_token_logprob");
+    return MAGE_OK;
+}
+
+template <int NV>
+static void stats_launch(int mode, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, long group, long in_stride, long in_off,
+                         const int64_t* tokens, long tok_stride, long tok_off, float inv_t, int top_k, float top_p, float* policy_logprob,
+                         float* policy_entropy, int32_t* kept, float* entropy, int* err) {
+#define MAGE_STATS(M)                                                                                                                 \
+    hipLaunchKernelGGL((token_stats_kernel<NV, M>), grid, dim3(256), 0, s, logits, rows, K, ld, group, in_stride, in_off, tokens, tok_stride, \
+                       tok_off, inv_t, top_k, top_p, policy_logprob, policy_entropy, kept, entropy, err)
+    if (mode == STATS_GREEDY) MAGE_STATS(STATS_GREEDY);
+    else if (mode == (STATS_TOPK | STATS_TOPP)) MAGE_STATS(STATS_TOPK | STATS_TOPP);
+    else if (mode == STATS_TOPK) MAGE_STATS(STATS_TOPK);
+    else if (mode == STATS_TOPP) MAGE_STATS(STATS_TOPP);
+    else MAGE_STATS(0);
+#undef MAGE_STATS
+}
+
+extern "C" int mage_token_stats(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride, int64_t in_off,
+                                const int64_t* tokens, int64_t tok_group_stride, int64_t tok_off, float temperature, int32_t top_k, float top_p,
+                                float* policy_logprob, float* policy_entropy, int32_t* kept, float* entropy, void* stream) {
+    MAGE_CHECK_ARG(logits && (policy_logprob || policy_entropy || kept || entropy), "mage_token_stats: null logits, or no output asked for");
+    MAGE_CHECK_ARG(tokens || !policy_logprob, "mage_token_stats: policy_logprob needs tokens");
+    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
+                   in_off >= 0 && tok_group_stride >= 0 && tok_off >= 0 && (((uintptr_t)logits) & 15) == 0,
+                   "mage_token_stats: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K, (long)ld,
+                   MAGE_SAMPLE_MAX_K);
+    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "mage_token_stats: top_k=%d outside [0, K=%d]", top_k, K);
+    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mage_token_stats: top_p=%g outside (0, 1]", (double)top_p);
+    const float inv_t = (float)(1.0 / (double)temperature);
+    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
+                   "mage_token_stats: temperature=%g must be finite and > 0", (double)temperature);
+    int* err = mage_error_word();
+    MAGE_CHECK_ARG(err != nullptr, "mage_token_stats: mage_init() has not been called");
+    const int mode = top_k == 1 ? STATS_GREEDY : (top_k > 0 && top_k < K ? STATS_TOPK : 0) | (top_p < 1.f ? STATS_TOPP : 0);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+#define MAGE_STATS_NV(NV)                                                                                                              \
+    stats_launch<NV>(mode, grid, s, logits, (long)rows, K, (long)ld, (long)group, (long)in_group_stride, (long)in_off, tokens,         \
+                     (long)tok_group_stride, (long)tok_off, mode == STATS_GREEDY ? 1.f : inv_t, top_k, top_p, policy_logprob, policy_entropy, kept, entropy, err)
+    if (K <= 256) MAGE_STATS_NV(4);
+    else if (K <= 512) MAGE_STATS_NV(8);
+    else if (K <= 1024) MAGE_STATS_NV(16);
+    else if (K <= 2048) MAGE_STATS_NV(32);
+    else MAGE_STATS_NV(64);
+#undef MAGE_STATS_NV
+    MAGE_CHECK_LAUNCH("mage_token_stats");
     return MAGE_OK;
 }
 

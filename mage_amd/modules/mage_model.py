@@ -858,6 +858,14 @@ class MAGE(nn.Module):
         self.last_clip_logprob: Optional[torch.Tensor] = None     # fp32 [B]: their per-clip totals
         self.last_candidate_scores: Optional[torch.Tensor] = None  # candidates > 1: fp32 [B, N], every candidate's total
         self.last_candidate_index: Optional[torch.Tensor] = None   # candidates > 1: int64 [B], the candidate kept
+        self.logprob_policy = False    # set_logprobs(policy=True): the same under the sampler's own filtered distribution (mage_token_stats)
+        self.logprob_entropy = False   # set_logprobs(entropy=True): per-token entropies
+        self.last_token_policy_logprobs: Optional[torch.Tensor] = None   # policy: fp32 [B, L-1, h, w], -inf where the sampler could not draw the token
+        self.last_clip_policy_logprob: Optional[torch.Tensor] = None     # policy: fp32 [B], their per-clip totals
+        self.last_token_kept: Optional[torch.Tensor] = None              # policy: int32 [B, L-1, h, w], the size of the set the sampler drew from
+        self.last_candidate_policy_scores: Optional[torch.Tensor] = None  # policy, candidates > 1: fp32 [B, N]
+        self.last_token_entropy: Optional[torch.Tensor] = None           # entropy: fp32 [B, L-1, h, w], the full softmax at temperature 1 (nats)
+        self.last_token_policy_entropy: Optional[torch.Tensor] = None    # entropy, sampling on: the filtered distribution's
 
     # ------------------------------------------------------------------ construction helpers
     def instantiate_first_stage(self, config):
@@ -910,13 +918,23 @@ class MAGE(nn.Module):
         self.sampling, self.candidates = (t, k, p), int(candidates)
         return self
 
-    def set_logprobs(self, on: bool = True) -> "MAGE":
+    def set_logprobs(self, on: bool = True, *, policy: bool = False, entropy: bool = False) -> "MAGE":
         """on: autoregressive_generate leaves last_token_logprobs (fp32 [B, L-1, h, w]: the log-probability of each generated token under the
         logits it was picked from -- the model's full softmax at temperature 1, not the filtered set of set_sampling) and last_clip_logprob
-        (fp32 [B], their per-clip totals).  Off (the default): both are None and the call launches nothing more."""
+        (fp32 [B], their per-clip totals).  Off (the default): both are None and the call launches nothing more.
+        policy (needs on, and set_sampling on when a generation or score starts): also the sampler's own view (mage_token_stats: the filter
+        of mage_sample_tokens run again in the same arithmetic) -- last_token_policy_logprobs (fp32 [B, L-1, h, w]: the log-probability under
+        the temperature-scaled softmax renormalised over the kept top-k / top-p set, -inf for a token outside it), last_clip_policy_logprob
+        (fp32 [B]), last_token_kept (int32 [B, L-1, h, w]: the size of the kept set) and, with candidates = N > 1, last_candidate_policy_scores
+        [B, N] (the winner is still picked by the model log-probability).
+        entropy (needs on; works with greedy decoding): last_token_entropy (fp32 [B, L-1, h, w], nats: the full softmax at temperature 1) and,
+        with sampling on, last_token_policy_entropy (the kept set's).  score honours both flags for the batch's own tokens.
+        set_logprobs(False) clears all three switches."""
+        if (policy or entropy) and not on:
+            raise ValueError("set_logprobs: policy / entropy need on=True")
         if on and not self.use_cids:
             raise ValueError("set_logprobs: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
-        self.logprobs = bool(on)
+        self.logprobs, self.logprob_policy, self.logprob_entropy = bool(on), bool(policy), bool(entropy)
         return self
 
     def _n_cand(self) -> int:
@@ -925,14 +943,44 @@ class MAGE(nn.Module):
     def _want_logprobs(self) -> bool:
         return self.use_cids and (bool(getattr(self, "logprobs", False)) or self._n_cand() > 1)
 
+    def _want_stats(self) -> Tuple[bool, bool]:
+        """(policy, entropy) of set_logprobs; policy without a sampler to describe is refused here, where a generation or score starts."""
+        if not (self.use_cids and getattr(self, "logprobs", False)):
+            return False, False
+        pol, ent = bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False))
+        if pol and getattr(self, "sampling", None) is None:
+            raise ValueError("set_logprobs(policy=True) reports the sampler's distribution: switch sampling on with set_sampling first")
+        return pol, ent
+
+    def _stats_alloc(self, shape, device) -> Optional[dict]:
+        """The output buffers of mage_token_stats the switches ask for (by its argument names), None when they ask for nothing."""
+        pol, ent = self._want_stats()
+        if not (pol or ent):
+            return None
+        sampled = getattr(self, "sampling", None) is not None
+        mk = lambda want, dt: torch.empty(shape, device=device, dtype=dt) if want else None      # noqa: E731
+        return {"policy_logprob": mk(pol, F32), "kept": mk(pol, torch.int32), "entropy": mk(ent, F32), "policy_entropy": mk(ent and sampled, F32)}
+
+    def _stats(self, logits, tokens, bufs: dict, sel, **kw) -> None:
+        """One mage_token_stats launch beside a mage_token_logprob one (same addressing kw), under the current sampler (greedy: the plain
+        softmax); sel picks the launch's view of each buffer."""
+        t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
+        ops.token_stats(logits, tokens, temperature=t, top_k=k, top_p=p, **{n: None if b is None else sel(b) for n, b in bufs.items()}, **kw)
+
+    _STATS_RESULTS = (("policy_logprob", "last_token_policy_logprobs"), ("kept", "last_token_kept"), ("entropy", "last_token_entropy"),
+                      ("policy_entropy", "last_token_policy_entropy"))
+
     @torch.no_grad()
     def score(self, batch) -> torch.Tensor:
         """Teacher-forced log-likelihood of the batch's own video under its caption: fp32 [B], the sum over frames 1 .. L-1 of the
-        log-probabilities of the frames' VQ tokens given the frames before them (last_token_logprobs [B, L-1, h, w] keeps the terms)."""
+        log-probabilities of the frames' VQ tokens given the frames before them (last_token_logprobs [B, L-1, h, w] keeps the terms).
+        With set_logprobs(policy=, entropy=) it leaves their results for the batch's own tokens too; every result of theirs that this call
+        does not compute is None afterwards, last_candidate_policy_scores included (score has no candidates)."""
         if not self.use_cids:
             raise ValueError("score: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
         images = batch["images"]
         _need_gpu(images, "MAGE.score")
+        self._want_stats()                                # (refuses policy without sampling before anything runs)
         with torch.cuda.device(images.device), weights_frozen():
             tok, logits = self.teacher_forced_logits(batch)
             B, L, K = images.shape[0], self.frames_length, self.codebook_size
@@ -941,6 +989,16 @@ class MAGE(nn.Module):
             ops.token_logprob(logits, tgt, lp, rows=tgt.numel(), K=K)
             scores, _ = ops.clip_scores(lp, n_clips=B)
             self.last_token_logprobs = lp
+            st = self._stats_alloc(tgt.shape, images.device)   # the batch's own tokens under the current sampler: -inf where it could never draw one
+            for _, attr in self._STATS_RESULTS:
+                setattr(self, attr, None)
+            self.last_clip_policy_logprob = self.last_candidate_policy_scores = None
+            if st is not None:
+                self._stats(logits, tgt, st, lambda b: b, rows=tgt.numel(), K=K)
+                for name, attr in self._STATS_RESULTS:
+                    setattr(self, attr, st[name])
+                if st["policy_logprob"] is not None:
+                    self.last_clip_policy_logprob = ops.clip_scores(st["policy_logprob"], n_clips=B)[0].view(B)
             ops.check_device_errors(images.device)
         return scores.view(B)
 
@@ -1178,7 +1236,8 @@ class MAGE(nn.Module):
         images = batch["images"]
         _need_gpu(images, "MAGE.autoregressive_generate")
         self.last_sample_seeds = None
-        self.last_token_logprobs = self.last_clip_logprob = self.last_candidate_scores = self.last_candidate_index = None
+        self._set_logprob_results([None] * len(self._LOGPROB_RESULTS))
+        self._want_stats()                               # (refuses policy without sampling before anything runs)
         if getattr(self, "sampling", None) is not None and self.use_cids:
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
@@ -1210,7 +1269,7 @@ class MAGE(nn.Module):
                 getattr(self.ma_encoder, "split_kind", 0), getattr(self.text_encoder, "split_kind", 0),
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
                 config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None),
-                self._want_logprobs(), self._n_cand())
+                self._want_logprobs(), self._n_cand(), bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False)))
 
     def _generate_eager(self, batch):
         if not self.use_cids:
@@ -1293,7 +1352,9 @@ class MAGE(nn.Module):
         self._set_logprob_results([None if t_ is None else t_.clone() for t_ in ent["lps"]])
         return ent["out"].clone()
 
-    _LOGPROB_RESULTS = ("last_token_logprobs", "last_clip_logprob", "last_candidate_scores", "last_candidate_index")
+    _LOGPROB_RESULTS = ("last_token_logprobs", "last_clip_logprob", "last_candidate_scores", "last_candidate_index",
+                        "last_token_policy_logprobs", "last_clip_policy_logprob", "last_token_kept", "last_candidate_policy_scores",
+                        "last_token_entropy", "last_token_policy_entropy")
 
     def _logprob_results(self) -> list:
         return [getattr(self, a, None) for a in self._LOGPROB_RESULTS]
@@ -1403,6 +1464,7 @@ class MAGE(nn.Module):
             st = self.generate_model._inc_begin(B, R, R)
             prev = tok0.contiguous()
             lp_t = torch.empty(Lm1, B, hw, device=images.device, dtype=F32) if want_lp else None
+            st_t = self._stats_alloc((Lm1, B, hw), images.device)
             gen_t = torch.empty(Lm1, B, hw, device=images.device, dtype=torch.int64)         # frame-major: a frame's tokens are contiguous,
             for i in range(Lm1):                                                              # the argmax writes them where the next step reads them
                 feats = self._frame_source(prev, dt)                                          # newest frame only
@@ -1414,14 +1476,18 @@ class MAGE(nn.Module):
                     self._pick(step_logits, prev, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw)
                 if want_lp:                                                                   # the tokens just picked, under the logits they came from
                     ops.token_logprob(step_logits, prev, lp_t[i], rows=B * hw, K=K)
+                if st_t is not None:
+                    self._stats(step_logits, prev, st_t, lambda b: b[i], rows=B * hw, K=K)
             gen = gen_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else gen_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # index plumbing, once
-            lp = None
-            if want_lp:
-                lp = lp_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else lp_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)
-            return self._finish(images, gen, None, lp, Bc, N)
+            clip_major = lambda t_: t_.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # noqa: E731
+            lp = clip_major(lp_t) if want_lp else None
+            st = None if st_t is None else {n: None if b is None else clip_major(b) for n, b in st_t.items()}
+            return self._finish(images, gen, None, lp, Bc, N, st)
         cur = tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                                 # :670 future slots hold frame 0
         logits = None
         lp = torch.empty(B, Lm1, R, R, device=images.device, dtype=F32) if want_lp else None
+        st = self._stats_alloc((B, Lm1, R, R), images.device)
+        flat = lambda b: b.view(-1)      # noqa: E731
         frame = dict(rows=B * hw, K=K, group=hw, in_group_stride=Lm1 * hw)                  # frame i of every clip: (in_ / tok_) off = i * hw
         for i in range(Lm1):                                                                  # :673-684
             feats = self._frame_source(cur, dt)
@@ -1434,10 +1500,14 @@ class MAGE(nn.Module):
                            out_group_stride=Lm1 * hw, out_off=(i + 1) * hw)
                 if want_lp and seeds is not None:         # sampled: frame i's tokens (slot i+1 of cur) under the logits they were drawn from
                     ops.token_logprob(logits, cur.view(-1)[hw:], lp.view(-1), in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
+                if st is not None and seeds is not None:
+                    self._stats(logits, cur.view(-1)[hw:], st, flat, in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
         if seeds is None:
             ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                   # :687
             if want_lp:
                 ops.token_logprob(logits, gen, lp, rows=B * Lm1 * hw, K=K)
+            if st is not None:
+                self._stats(logits, gen, st, flat, rows=B * Lm1 * hw, K=K)
         else:
             # sampled: frames 0..L-3 are the tokens the loop conditioned on (slots 1..L-2); only the last frame is drawn from these logits
             gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:, 1:])
@@ -1445,22 +1515,38 @@ class MAGE(nn.Module):
                        in_off=(Lm1 - 1) * hw, out_group_stride=Lm1 * hw, out_off=(Lm1 - 1) * hw)
             if want_lp:
                 ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N)
+            if st is not None:
+                self._stats(logits, gen, st, flat, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
+        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N, st)
 
-    def _finish(self, images, gen, logits, lp, Bc: int, N: int):
+    def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None):
         """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
-        of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691)."""
+        of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691).  st: the
+        mage_token_stats buffers of set_logprobs(policy=, entropy=), [B * N, L-1, h, w] each (None: off); the winner's rows are kept."""
         if lp is not None:
             scores, best = ops.clip_scores(lp, n_clips=Bc, n_cand=N)
+            pscores = None
+            if st is not None and st["policy_logprob"] is not None:
+                pscores = ops.clip_scores(st["policy_logprob"], n_clips=Bc, n_cand=N)[0]
             if N > 1:
                 win = best + torch.arange(Bc, device=best.device, dtype=torch.int64) * N
                 gen, lp = gen.index_select(0, win), lp.index_select(0, win)
                 logits = None if logits is None else logits.index_select(0, win)
                 self.last_candidate_scores, self.last_candidate_index = scores, best
                 self.last_clip_logprob = scores.gather(1, best[:, None]).view(Bc)
+                if st is not None:
+                    st = {n: None if b is None else b.index_select(0, win) for n, b in st.items()}
+                if pscores is not None:
+                    self.last_candidate_policy_scores = pscores
+                    self.last_clip_policy_logprob = pscores.gather(1, best[:, None]).view(Bc)
             else:
                 self.last_clip_logprob = scores.view(Bc)
+                if pscores is not None:
+                    self.last_clip_policy_logprob = pscores.view(Bc)
             self.last_token_logprobs = lp
+            if st is not None:
+                for name, attr in self._STATS_RESULTS:
+                    setattr(self, attr, st[name])
         self.last_tokens, self.last_logits = gen, logits
         video = self.first_stage_decode(gen)
         return _assemble(images, video)

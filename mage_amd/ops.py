@@ -553,6 +553,28 @@ def token_logprob(logits: torch.Tensor, tokens: torch.Tensor, logprob: torch.Ten
     return logprob
 
 
+def token_stats(logits: torch.Tensor, tokens: Optional[torch.Tensor], *, rows: int, K: int, temperature: float = 1.0, top_k: int = 0,
+                top_p: float = 1.0, policy_logprob: Optional[torch.Tensor] = None, policy_entropy: Optional[torch.Tensor] = None,
+                kept: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, ld: Optional[int] = None,
+                group: Optional[int] = None, in_group_stride: Optional[int] = None, in_off: int = 0,
+                tok_group_stride: Optional[int] = None, tok_off: int = 0) -> None:
+    """token_logprob's addressing and sample_tokens' parameters; row i writes index (i // group) * tok_group_stride + i % group + tok_off of
+    every output given (mage_token_stats): policy_logprob fp32 (needs tokens), policy_entropy fp32, kept int32 -- under the set the sampler
+    draws from -- and entropy fp32 (the whole row at temperature 1).  At least one output."""
+    l, s = _dev(logits)
+    assert logits.dtype == torch.float32 and (tokens is None or (tokens.dtype == torch.int64 and tokens.device == logits.device))
+    group = rows if group is None else group
+    in_group_stride = group if in_group_stride is None else in_group_stride
+    tok_group_stride = group if tok_group_stride is None else tok_group_stride
+    last = ((rows - 1) // group) * tok_group_stride + (rows - 1) % group + tok_off          # the largest index addressed
+    assert tok_off >= 0 and (tokens is None or last < tokens.numel())
+    for o, dt in ((policy_logprob, torch.float32), (policy_entropy, torch.float32), (kept, torch.int32), (entropy, torch.float32)):
+        assert o is None or (o.dtype == dt and o.device == logits.device and last < o.numel())
+    _lib.check(l.mage_token_stats(logits.data_ptr(), rows, K, K if ld is None else ld, group, in_group_stride, in_off, _p(tokens),
+                                  tok_group_stride, tok_off, float(temperature), int(top_k), float(top_p), _p(policy_logprob),
+                                  _p(policy_entropy), _p(kept), _p(entropy), s), l)
+
+
 def clip_scores(logprob: torch.Tensor, *, n_clips: int, n_cand: int = 1):
     """(scores [n_clips, n_cand] fp32, best [n_clips] int64 or None when n_cand == 1) of logprob [n_clips * n_cand, ...] fp32
     (mage_clip_scores)."""
