@@ -522,7 +522,9 @@ int mage_layernorm_bwd(const float* x, const float* gamma, const void* dy, int32
 int mage_act(const void* x, void* y, int32_t dtype, int64_t n, int32_t act, void* stream);
 int mage_act_bwd(const void* x, const void* dy, void* dx, int32_t dtype, int64_t n, int32_t act, void* stream);
 /* F.cross_entropy backward (mage_model.py:618): dlogits = (softmax(logits) - onehot(target)) * grad_out[0] / rows, written in
- * dl_dtype (the A operand of the head's dX / dW GEMMs).  grad_out: device pointer to the upstream scalar gradient. */
+ * dl_dtype (MAGE_F32 or MAGE_BF16: the A operand of the head's dX / dW GEMMs).  grad_out: device pointer to the upstream scalar gradient.
+ * A target outside [0, K) is reported by the forward kernel (mage_cross_entropy); here it has no one-hot: its row's gradient is
+ * softmax(logits) * grad_out[0] / rows.  A -inf logit has probability 0 and gradient 0 exactly. */
 int mage_cross_entropy_bwd(const float* logits, const int64_t* target, int64_t rows, int32_t K, const float* grad_out, void* dlogits,
                            int32_t dl_dtype, void* stream);
 /* nn.Embedding backward: dtable[ids[i], :] += dout[orow(i), :] (orow as in mage_embedding; ids equal to padding_idx (< 0: none)
