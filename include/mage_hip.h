@@ -468,7 +468,8 @@ int mage_reparam_kl(const float* mu, const float* logvar, const float* eps, floa
                     void* stream);
 
 /* out[0] = mean over rows x cols of (a[r*lda + c] - b[r*ldb + c])^2, fp32 inputs, fp64 fixed-order accumulation
- * (F.mse_loss of the MAGE+ latent prediction, mage_model.py:620).  workspace: 256 doubles. */
+ * (F.mse_loss of the MAGE+ latent prediction, mage_model.py:620).  workspace: 256 doubles.  lda and ldb are row strides in elements
+ * and must be at least cols; a smaller one is refused with MAGE_EINVAL (mage_mse_bwd likewise). */
 int mage_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t cols, double* workspace, float* out,
              void* stream);
 
@@ -610,7 +611,7 @@ int mage_reparam_kl_bwd(const float* mu, const float* logvar, const float* eps, 
 int mage_maxpool2_bwd(const float* x, const float* dy, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 int mage_upsample2_bwd(const float* dy, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 /* da = d mean((a - b)^2) / da * gout[0] over the first `cols` columns (zeros in the padding columns up to ld_da): backward of mage_mse
- * (F.mse_loss of the MAGE+ latent prediction, mage_model.py:620). */
+ * (F.mse_loss of the MAGE+ latent prediction, mage_model.py:620).  lda, ldb >= cols and ld_da >= cols, or the call is refused. */
 int mage_mse_bwd(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t cols, const float* gout, float* da,
                  int64_t ld_da, void* stream);
 

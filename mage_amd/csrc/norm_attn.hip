@@ -1180,6 +1180,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 int gn_launch(const char* who, const float* x, int64_t sample_stride_rows, int64_t row_off, int32_t n_samples, int32_t rows_per_sample,
               int32_t C, int32_t groups, const float* gamma, const float* beta, float eps, float* stats, const float* residual,
               int32_t act, void* y, int32_t y_dtype, int64_t y_sample_stride_rows, int64_t y_row_off, hipStream_t s) {
+    if (y_dtype != MAGE_F32 && y_dtype != MAGE_BF16 && y_dtype != MAGE_F16) {      // refuse before the statistics kernel writes stats
+        mage_set_error("%s: bad y_dtype %d", who, y_dtype);
+        return MAGE_EINVAL;
+    }
     hipLaunchKernelGGL(gn_stats_kernel, dim3(n_samples, groups), dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
                        rows_per_sample, C, groups, eps, stats);
     const long total = (long)n_samples * rows_per_sample * C;
@@ -1191,14 +1195,10 @@ int gn_launch(const char* who, const float* x, int64_t sample_stride_rows, int64
         hipLaunchKernelGGL((gn_apply_kernel<unsigned short>), grid, dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
                            rows_per_sample, C, groups, stats, gamma, beta, residual, act, (unsigned short*)y,
                            (long)y_sample_stride_rows, (long)y_row_off, total);
-    else if (y_dtype == MAGE_F16)                      // the f16 mode on the latent (MAGE+) path: the GroupNorm + SiLU head's rows (round 6)
+    else                                               // the f16 mode on the latent (MAGE+) path: the GroupNorm + SiLU head's rows (round 6)
         hipLaunchKernelGGL((gn_apply_kernel<f16_t>), grid, dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
                            rows_per_sample, C, groups, stats, gamma, beta, residual, act, (f16_t*)y,
                            (long)y_sample_stride_rows, (long)y_row_off, total);
-    else {
-        mage_set_error("%s: bad y_dtype %d", who, y_dtype);
-        return MAGE_EINVAL;
-    }
     MAGE_CHECK_LAUNCH(who);
     return MAGE_OK;
 }
@@ -1285,6 +1285,7 @@ __global__ void mse_final_kernel(const double* __restrict__ partial, int n, doub
 extern "C" int mage_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t cols, double* workspace,
                         float* out, void* stream) {
     MAGE_CHECK_ARG(a && b && workspace && out && rows > 0 && cols > 0, "mage_mse: bad arguments");
+    MAGE_CHECK_ARG(lda >= cols && ldb >= cols, "mage_mse: lda=%ld ldb=%ld must be at least cols=%d", (long)lda, (long)ldb, cols);
     const int nblk = (int)((rows * cols + 255) / 256 < 256 ? (rows * cols + 255) / 256 : 256);
     hipLaunchKernelGGL(mse_partial_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, (long)lda, b, (long)ldb, (long)rows, cols,
                        workspace);

@@ -1605,6 +1605,7 @@ __global__ void mse_bwd_kernel(const float* __restrict__ a, long lda, const floa
 extern "C" int mage_mse_bwd(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t cols, const float* gout, float* da,
                             int64_t ld_da, void* stream) {
     MAGE_CHECK_ARG(a && b && gout && da && rows > 0 && cols > 0 && ld_da >= cols, "mage_mse_bwd: bad arguments");
+    MAGE_CHECK_ARG(lda >= cols && ldb >= cols, "mage_mse_bwd: lda=%ld ldb=%ld must be at least cols=%d", (long)lda, (long)ldb, cols);
     const long n = rows * ld_da;
     hipLaunchKernelGGL(mse_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, (long)lda, b, (long)ldb, (long)rows,
                        cols, gout, da, (long)ld_da, (float)(1.0 / ((double)rows * cols)));

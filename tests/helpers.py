@@ -124,3 +124,58 @@ def attn_row_maps(c, g):
     kr = (outer * g["kv_outer_stride"] + inn)[:, None] + torch.arange(c["nk"])[None] * g["kv_axis_stride"]
     orr = (outer * g["o_outer_stride"] + inn)[:, None] + torch.arange(c["nq"])[None] * g["o_axis_stride"] if c["omap"] else qr
     return qr, kr, orr
+
+
+# ---------------------------------------------------------------- kernel-against-fp64 tests (tests/test_gpu_train_kernels.py, tests/test_gpu_norm_kernels.py)
+DEV = "cuda:0"
+WORST = {}
+
+
+def lib():
+    from mage_amd import ops
+    return ops._dev(torch.empty(1, device=DEV))
+
+
+def sent(shape, dt):
+    it, val = SENTINEL[dt]
+    return torch.full(shape if isinstance(shape, tuple) else (shape,), val, dtype=it, device=DEV).view(dt)
+
+
+def untouched(t):
+    it, val = SENTINEL[t.dtype]
+    return bool((t.view(it) == val).all())
+
+
+def written(t):
+    it, val = SENTINEL[t.dtype]
+    return bool((t.view(it) != val).all())
+
+
+def bits(t):
+    return t.view(SENTINEL[t.dtype][0])
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def within(entry, name, got, ref, bound):
+    """Every element finite and inside its bound; keeps the largest |err| / bound per entry point for the report."""
+    got = got.double().cpu()
+    assert bool(torch.isfinite(got).all()), f"{name}: non-finite output"
+    err = (got - ref).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    w = int(ratio.flatten().argmax()) if ratio.numel() else 0
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    WORST[entry] = max(WORST.get(entry, 0.0), worst)
+    print(f"{entry} {name}: worst |err| / bound {worst:.3f} (largest so far {WORST[entry]:.3f})")
+    assert worst <= 1.0, (f"{entry} {name}: |err| {float(err.flatten()[w]):.3e} > bound {float(bound.expand_as(err).flatten()[w]):.3e} at flat index {w} "
+                          f"(ref {float(ref.expand_as(err).flatten()[w]):.9e}, got {float(got.flatten()[w]):.9e})")
+
+
+def refused(call, *outs):
+    with pytest.raises(ValueError):
+        call()
+    torch.cuda.synchronize()
+    for o in outs:
+        assert untouched(o), "a refused call wrote to an output"

@@ -33,66 +33,15 @@ import torch
 
 from mage_amd import _lib, ops
 from tests import train_ref as R
-from tests.helpers import SENTINEL, unsplit
+from tests.helpers import DEV, bits, lib, ptr, refused, sent, untouched, unsplit, within, written
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 GOLD = 0x9E3779B97F4A7C15
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 CODE = {"f32": ops.F32, "bf16": ops.BF16, "f16": ops.F16, "bf16x3": ops.BF16X3, "f16x3": ops.F16X3}
 LN_ROWS = {4: 5, 252: 4, 256: 5, 260: 5, 512: 4, 516: 5, 1024: 4, 1028: 5, 2044: 4, 2048: 5, 64: 5}
 LN_EPS = {516: 1e-8}
-WORST = {}
-
-
-def lib():
-    return ops._dev(torch.empty(1, device=DEV))
-
-
-def sent(shape, dt):
-    it, val = SENTINEL[dt]
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), val, dtype=it, device=DEV).view(dt)
-
-
-def untouched(t):
-    it, val = SENTINEL[t.dtype]
-    return bool((t.view(it) == val).all())
-
-
-def written(t):
-    it, val = SENTINEL[t.dtype]
-    return bool((t.view(it) != val).all())
-
-
-def bits(t):
-    return t.view(SENTINEL[t.dtype][0])
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def within(entry, name, got, ref, bound):
-    """Every element finite and inside its bound; keeps the largest |err| / bound per entry point for the report."""
-    got = got.double().cpu()
-    assert bool(torch.isfinite(got).all()), f"{name}: non-finite output"
-    err = (got - ref).abs()
-    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)
-    w = int(ratio.flatten().argmax()) if ratio.numel() else 0
-    worst = float(ratio.max()) if ratio.numel() else 0.0
-    WORST[entry] = max(WORST.get(entry, 0.0), worst)
-    print(f"{entry} {name}: worst |err| / bound {worst:.3f} (largest so far {WORST[entry]:.3f})")
-    assert worst <= 1.0, (f"{entry} {name}: |err| {float(err.flatten()[w]):.3e} > bound {float(bound.expand_as(err).flatten()[w]):.3e} at flat index {w} "
-                          f"(ref {float(ref.expand_as(err).flatten()[w]):.9e}, got {float(got.flatten()[w]):.9e})")
-
-
-def refused(call, *outs):
-    with pytest.raises(ValueError):
-        call()
-    torch.cuda.synchronize()
-    for o in outs:
-        assert untouched(o), "a refused call wrote to an output"
 
 
 # ------------------------------------------------------------------------------------------------ mage_layernorm
