@@ -42,6 +42,50 @@ int mage_token_stats(const float* logits, int64_t rows, int32_t K, int64_t ld, i
                      const int64_t* tokens, int64_t tok_group_stride, int64_t tok_off, float temperature, int32_t top_k, float top_p,
                      float* policy_logprob, float* policy_entropy, int32_t* kept, float* entropy, void* stream);
 
+/* Policy-gradient loss over given tokens, and its gradient with respect to the logits: no site in the reference (its only objective is the
+ * mean cross-entropy).  Serves MAGE.policy_loss (mage_amd/modules/mage_train.py: train_forward / train_backward with a policy).
+ * Row i is the K fp32 logits z at logits + i*ld with its token t = tokens[i] (int64), its advantage A = advantage[i / adv_div] (fp32;
+ * adv_div = 1: one per row, adv_div = rows per clip: one per clip) and, when behaviour_logprob is given, b = behaviour_logprob[i] (fp32:
+ * the log-probability under which the token was drawn).  The policy is mage_sample_tokens' under (temperature, top_k, top_p): with
+ * s = z * (float)(1.0 / temperature) and N the set it draws from -- the sampler's own filter code runs again in the same arithmetic, as in
+ * mage_token_stats -- the forward call writes, per row,
+ *   cut      (uint32)  the filter's threshold on the order-preserving key of s: j is in N iff key(s_j) >= cut[i] (what the backward call reads
+ *                      instead of running the filter again);
+ *   logprob  (fp32)    s_t - (s_max + log Z), Z = sum_{j in N} exp(s_j - s_max); -inf for t outside N: mage_token_stats' policy_logprob,
+ *                      bit for bit (the same operations in the same order);
+ *   entropy  (fp32)    log Z - (sum_{j in N} exp(s_j - s_max) (s_j - s_max)) / Z: mage_token_stats' policy_entropy, bit for bit;
+ *   row_loss (fp32)    l_i = -A logprob - entropy_coef entropy                                       (behaviour_logprob null: the
+ *                      reward-weighted likelihood; A = 1, temperature 1, no filter, entropy_coef 0: cross-entropy's row loss), or
+ *                      l_i = -min(rho A, clamp(rho, 1 - clip_lo, 1 + clip_hi) A) - entropy_coef entropy,  rho = expf(logprob - b)
+ *                      (the clipped surrogate).  rho is one fp32 value, the bounds are (float)(1.0 - clip_lo) and (float)(1.0 + clip_hi);
+ *                      the products and the sum are taken in fp64 and rounded once.
+ * A row whose token lies outside a non-empty N (off-policy data the current filter could never draw) is an outside row: logprob -inf,
+ * l_i = 0, a zero gradient row.  summary[0..5) are five means over `rows`, each summed in fp64 in a fixed order and rounded once to fp32:
+ * l, entropy, b - logprob (0 without behaviour_logprob), the share of rows whose gradient the clip switched off (g_i = 0 below), the share of
+ * outside rows; an outside row counts in the last one only.  Two launches on the same inputs give the same bits.  The partial sums pass
+ * through one per-device buffer of the library: calls of mage_policy_loss on one device must be ordered (one stream, or events).
+ * The backward call writes dlogits [rows, K] (contiguous; dl_dtype MAGE_F32 or MAGE_BF16, as mage_cross_entropy_bwd's):
+ *   dlogits_ij = grad_out[0] / rows * inv_t * [ g_i (1[j = t] - p_j) + entropy_coef p_j (log p_j + entropy_i) ]   for j in N,
+ *   exactly 0 for j outside N and for every j of an outside row; p = softmax of s over N, a p_j = 0 term counts as 0 (never 0 * inf);
+ *   g_i = -A without behaviour_logprob; with it g_i = -A rho where the unclipped term of the min is the active one (A >= 0 and
+ *   rho <= 1 + clip_hi, or A < 0 and rho >= 1 - clip_lo) and 0 otherwise.  It recomputes Z, entropy and rho with the forward call's
+ *   operations, so both passes take the same branch; pass it the forward call's arguments.
+ * Special values: a NaN logit is in no set; a row with no selectable code (every logit NaN) gives NaN for logprob, entropy and row_loss and
+ * a zero gradient row; a row whose largest kept s is not finite gives NaN throughout (inf - inf), as mage_token_logprob does.  A token
+ * outside [0, K) is recorded for mage_check_device_errors by the forward call and clamped by both.
+ * top_k == 1 is refused: a greedy policy has log-probability 0 and no gradient, and its one-element set is not a threshold.  clip_lo in
+ * [0, 1], clip_hi >= 0, entropy_coef finite, adv_div > 0; otherwise mage_token_stats' rules: K % 4 == 0, K <= MAGE_SAMPLE_MAX_K,
+ * ld % 4 == 0, ld >= K, logits (and dlogits) 16-byte aligned, top_k in [0, K], top_p in (0, 1], temperature (and its reciprocal) finite
+ * and > 0; every output required.  MAGE_EINVAL otherwise, nothing launched.
+ * One wave per row, the row in registers in the sampler's layout (4 .. 64 values per lane by K), one kernel instance per filter
+ * combination, every sum in a fixed order, accurate expf / logf. */
+int mage_policy_loss(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage, int64_t adv_div,
+                     const float* behaviour_logprob, float temperature, int32_t top_k, float top_p, float clip_lo, float clip_hi,
+                     float entropy_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* summary, void* stream);
+int mage_policy_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                         int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature, float clip_lo,
+                         float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

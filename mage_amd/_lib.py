@@ -128,6 +128,8 @@ SIGNATURES = {
 # The core table above is frozen at 69 entry points (ABI 10); additions are declared in include/mage_hip_ext.h and bound from this one.
 EXT_SIGNATURES = {
     "mage_token_stats": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, f32, i32, f32, vp, vp, vp, vp, vp]),
+    "mage_policy_loss": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, f32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "mage_policy_loss_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

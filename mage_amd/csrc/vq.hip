@@ -621,6 +621,219 @@ __global__ __launch_bounds__(256) void token_stats_kernel(const float* __restric
     }
 }
 
+// ---- policy-gradient loss over given tokens (mage_policy_loss / mage_policy_loss_bwd, include/mage_hip_ext.h states the rule).  The policy
+// is the sampler's: s, N of steps 1-3 of the sampling rule above by sample_filter itself, logprob and entropy by token_stats_kernel's
+// operations in token_stats_kernel's order, so on the same inputs they carry mage_token_stats' bits.  One wave per row, the row read once
+// into registers in sample_kernel's layout, one instance per filter combination; the forward kernel leaves the filter's threshold in cut[i]
+// and the backward kernel keeps j iff sample_key(s_j) >= cut[i]: no second bisection, and the same set bit for bit.
+
+// w_j = exp(s_j - smax) over the kept set (0 outside it), Z = sum w_j and sum w_j (s_j - smax): token_stats_kernel's sums, term for term
+template <int NV>
+__device__ __forceinline__ void policy_sums(const float (&s)[NV], const unsigned (&key)[NV], unsigned lo, float smax, float (&w)[NV], float& zs,
+                                            float& ts) {
+    zs = 0.f;
+    ts = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) {
+        const float d = s[e] - smax;
+        w[e] = key[e] >= lo ? expf(d) : 0.f;
+        zs = __fadd_rn(zs, w[e]);
+        ts = w[e] == 0.f ? ts : __fmaf_rn(w[e], d, ts);
+    }
+    zs = wave_sum(zs);
+    ts = wave_sum(ts);
+}
+
+// One row's loss term and the factor g of its gradient from logprob lp, entropy H, advantage A and (clipped form) the behaviour
+// log-probability b.  rho = expf(lp - b) is the one fp32 value both passes use to decide which branch of the surrogate is active; the
+// products and the final sum are taken in fp64 and rounded once.  An outside row (lp = -inf: a token the filter cannot draw) gives 0, 0.
+struct PolicyTerm { float loss, g; bool outside, off; };
+__device__ __forceinline__ PolicyTerm policy_term(float lp, float H, float A, bool clipped, float b, float cmin, float cmax, float ent_coef) {
+    PolicyTerm t{0.f, 0.f, lp == -INFINITY, false};
+    if (t.outside) return t;
+    double surr;
+    if (!clipped) {
+        surr = (double)A * (double)lp;
+        t.g = -A;
+    } else {
+        const float rho = expf(lp - b);
+        const bool active = (A >= 0.f && rho <= cmax) || (A < 0.f && rho >= cmin);
+        const double u = (double)rho * (double)A, c = (double)fminf(fmaxf(rho, cmin), cmax) * (double)A;
+        surr = u < c ? u : (c < u ? c : (u != u ? u : c));              // min; a NaN stays a NaN
+        t.g = active ? -(A * rho) : 0.f;
+        t.off = !active;
+    }
+    t.loss = (float)(-surr - (double)ent_coef * (double)H);
+    return t;
+}
+
+__device__ __forceinline__ long policy_token(const int64_t* __restrict__ tokens, long i, int K, int* err) {
+    long tg = tokens[i];
+    if (tg < 0 || tg >= K) {
+        if (err) mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);          // (the backward pass clamps alike and leaves the report to the forward one)
+        tg = tg < 0 ? 0 : K - 1;
+    }
+    return tg;
+}
+
+template <int NV, bool TOPK, bool TOPP>
+__global__ __launch_bounds__(256) void policy_loss_kernel(const float* __restrict__ logits, long rows, int K, long ld,
+                                                          const int64_t* __restrict__ tokens, const float* __restrict__ adv, long adv_div,
+                                                          const float* __restrict__ blp, float inv_t, int top_k, float top_p, float cmin,
+                                                          float cmax, float ent_coef, float* __restrict__ row_loss,
+                                                          float* __restrict__ logprob, float* __restrict__ entropy,
+                                                          unsigned* __restrict__ cut, int* __restrict__ err) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + i * ld;
+    float s[NV], w[NV];
+    unsigned key[NV];
+    const unsigned lo = sample_filter<NV, TOPK, TOPP>([=](int c) { return sample_row_chunk(p, lane, K, c); }, lane, K, inv_t, top_k, top_p, s,
+                                                      key);
+    unsigned km = 0u;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) km = max(km, key[e]);
+    km = wave_max_u32(km);                              // km >= lo unless nothing is selectable (then every key is 0)
+    int n = 0;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= lo));
+    const float smax = sample_key_value(km);
+    float zs, ts;
+    policy_sums<NV>(s, key, lo, smax, w, zs, ts);
+    if (lane == 0) {
+        const float lz = logf(zs);
+        const float H = n ? lz - ts / zs : __builtin_nanf("");
+        const long tg = policy_token(tokens, i, K, err);
+        const float st = __fmul_rn(p[tg], inv_t);
+        const float lp = !n ? __builtin_nanf("") : sample_key(st) >= lo ? st - (smax + lz) : -INFINITY;
+        cut[i] = lo;
+        logprob[i] = lp;
+        entropy[i] = H;
+        row_loss[i] = policy_term(lp, H, adv[i / adv_div], blp != nullptr, blp ? blp[i] : 0.f, cmin, cmax, ent_coef).loss;
+    }
+}
+
+// summary, stage 1 of 2: workgroup b owns rows [b * chunk, (b + 1) * chunk) and leaves five fp64 sums in part[b * 5 ..]: the loss terms, the
+// entropies, b - logprob, the rows whose gradient the clip switched off, the outside rows (an outside row counts in the last one only).
+// A thread adds its rows in ascending order, the lanes meet in an xor butterfly, thread 0 adds the four waves in order: a fixed order.
+enum { POLICY_PARTS = 256 };
+__device__ double g_policy_part[POLICY_PARTS * 5];      // stage 1 -> stage 2, within one mage_policy_loss call (stream order)
+__global__ __launch_bounds__(256) void policy_part_kernel(const float* __restrict__ row_loss, const float* __restrict__ logprob,
+                                                          const float* __restrict__ entropy, const float* __restrict__ adv, long adv_div,
+                                                          const float* __restrict__ blp, float cmin, float cmax, long rows, long chunk) {
+    __shared__ double red[4][5];
+    const long r0 = (long)blockIdx.x * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long i = r0 + threadIdx.x; i < r1; i += 256) {
+        const float lp = logprob[i];
+        if (lp == -INFINITY) {
+            a[4] += 1.0;
+            continue;
+        }
+        a[0] += (double)row_loss[i];
+        a[1] += (double)entropy[i];
+        if (blp) {
+            const float b = blp[i];
+            a[2] += (double)b - (double)lp;
+            a[3] += policy_term(lp, 0.f, adv[i / adv_div], true, b, cmin, cmax, 0.f).off ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int q = threadIdx.x;
+        g_policy_part[blockIdx.x * 5 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// stage 2: thread t holds workgroup t's sums; the same butterfly and wave order, one multiply by 1 / rows, one rounding to fp32
+__global__ __launch_bounds__(256) void policy_summary_kernel(float* __restrict__ summary, double inv) {
+    __shared__ double red[4][5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        double v = g_policy_part[threadIdx.x * 5 + q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int q = threadIdx.x;
+        summary[q] = (float)((((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) * inv);
+    }
+}
+
+// dlogits_ij = scale * [ g_i (1[j = t] - p_j) + ent_coef p_j (log p_j + H_i) ] for j in N, 0 outside N and in outside rows; scale =
+// grad_out[0] / rows * inv_t, p_j = w_j / Z, log p_j + H_i = (s_j - smax) - (sum_N w (s - smax)) / Z; a p_j = 0 term is 0.  Z, H, logprob are
+// recomputed with the forward kernel's operations (policy_sums), so g_i is decided by the forward pass's rho.
+template <int NV, typename OT>
+__global__ __launch_bounds__(256) void policy_loss_bwd_kernel(const float* __restrict__ logits, long rows, int K, long ld,
+                                                              const int64_t* __restrict__ tokens, const float* __restrict__ adv, long adv_div,
+                                                              const float* __restrict__ blp, const unsigned* __restrict__ cut, float inv_t,
+                                                              float cmin, float cmax, float ent_coef, const float* __restrict__ gout,
+                                                              float inv_rows, OT* __restrict__ dl) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + i * ld;
+    OT* o = dl + i * (long)K;
+    const unsigned lo = cut[i];
+    float s[NV], w[NV];
+    unsigned key[NV];
+    unsigned km = 0u;
+#pragma unroll
+    for (int c = 0; c < NV / 4; ++c) {
+        const int k = c * 256 + lane * 4;
+        const f32x4 v = sample_row_chunk(p, lane, K, c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s[c * 4 + e] = __fmul_rn(v[e], inv_t);                      // sample_filter's s and key
+            key[c * 4 + e] = k < K ? sample_key(s[c * 4 + e]) : 0u;
+            km = max(km, key[c * 4 + e]);
+        }
+    }
+    km = wave_max_u32(km);
+    const float smax = sample_key_value(km);
+    float zs, ts;
+    policy_sums<NV>(s, key, lo, smax, w, zs, ts);
+    const long tg = policy_token(tokens, i, K, nullptr);
+    const float st = __fmul_rn(p[tg], inv_t);
+    const bool out_n = sample_key(st) < lo;                             // t outside N (or no selectable code at all: st is NaN, key 0)
+    const float lz = logf(zs);
+    const float H = lz - ts / zs;
+    const float lp = st - (smax + lz);
+    const PolicyTerm t = policy_term(lp, H, adv[i / adv_div], blp != nullptr, blp ? blp[i] : 0.f, cmin, cmax, ent_coef);
+    // 1 - p_t = (Z - w_t) / Z from the sum of the OTHER kept terms (same fixed order): no cancellation where the token holds nearly all the mass
+    float zo = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) zo = __fadd_rn(zo, (e >> 2) * 256 + lane * 4 + (e & 3) == tg ? 0.f : w[e]);
+    zo = wave_sum(zo);
+    const float scale = gout[0] * inv_rows * inv_t, inv_z = 1.0f / zs;
+    const float hx = ts / zs;                                           // log p_j + H = (s_j - smax) - hx: log Z drops out
+    const bool zero = out_n || t.outside;                               // an outside row (t.outside: a kept token of logit -inf)
+#pragma unroll
+    for (int c = 0; c < NV / 4; ++c) {
+        const int k = c * 256 + lane * 4;
+        if (k >= K) break;
+        f32x4 d;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = c * 4 + e;
+            const float pj = w[j] * inv_z;
+            float v = t.g * (k + e == tg ? zo * inv_z : -pj);
+            if (ent_coef != 0.f && pj != 0.f) v += ent_coef * pj * ((s[j] - smax) - hx);
+            d[e] = (zero || key[j] < lo) ? 0.f : v * scale;
+        }
+        store4(o + k, d);
+    }
+}
+
 // One workgroup per clip: wave w sums candidates w, w + 4, ... (a lane adds values lane, lane + 64, ... in fp64, the lanes meet in an xor
 // butterfly, one rounding to fp32), then thread 0 picks the largest score: first on ties, a NaN only if every score is NaN.
 __global__ __launch_bounds__(256) void clip_scores_kernel(const float* __restrict__ logprob, int n_cand, long per_clip,
@@ -1059,5 +1272,96 @@ extern "C" int mage_cross_entropy(const float* logits, const int64_t* target, in
     hipLaunchKernelGGL(ce_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, target, (long)rows, K, row_loss, err);
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, s, row_loss, (long)rows, loss_mean, 1.0 / (double)rows);
     MAGE_CHECK_LAUNCH("mage_cross_entropy");
+    return MAGE_OK;
+}
+
+// the argument rules mage_policy_loss and mage_policy_loss_bwd share (mage_token_stats' sizes and temperature, the clip and the entropy weight)
+static int policy_check(const char* who, const void* logits, int64_t rows, int32_t K, int64_t ld, int64_t adv_div, float temperature,
+                        float inv_t, float clip_lo, float clip_hi, float entropy_coef) {
+    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && adv_div > 0 &&
+                   (((uintptr_t)logits) & 15) == 0,
+                   "%s: bad sizes rows=%ld K=%d ld=%ld adv_div=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", who, (long)rows, K, (long)ld,
+                   (long)adv_div, MAGE_SAMPLE_MAX_K);
+    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
+                   "%s: temperature=%g must be finite and > 0", who, (double)temperature);
+    MAGE_CHECK_ARG(clip_lo >= 0.f && clip_lo <= 1.f && clip_hi >= 0.f, "%s: clip_lo=%g outside [0, 1] or clip_hi=%g < 0", who, (double)clip_lo,
+                   (double)clip_hi);
+    MAGE_CHECK_ARG(__builtin_isfinite(entropy_coef), "%s: entropy_coef=%g must be finite", who, (double)entropy_coef);
+    return MAGE_OK;
+}
+
+template <int NV>
+static void policy_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, const int64_t* tokens,
+                          const float* adv, long adv_div, const float* blp, float inv_t, int top_k, float top_p, float cmin, float cmax,
+                          float ent_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, int* err) {
+#define MAGE_POLICY(TK, TP)                                                                                                            \
+    hipLaunchKernelGGL((policy_loss_kernel<NV, TK, TP>), grid, dim3(256), 0, s, logits, rows, K, ld, tokens, adv, adv_div, blp, inv_t, \
+                       top_k, top_p, cmin, cmax, ent_coef, row_loss, logprob, entropy, cut, err)
+    if (topk && topp) MAGE_POLICY(true, true);
+    else if (topk) MAGE_POLICY(true, false);
+    else if (topp) MAGE_POLICY(false, true);
+    else MAGE_POLICY(false, false);
+#undef MAGE_POLICY
+}
+
+extern "C" int mage_policy_loss(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                int64_t adv_div, const float* behaviour_logprob, float temperature, int32_t top_k, float top_p, float clip_lo,
+                                float clip_hi, float entropy_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut,
+                                float* summary, void* stream) {
+    MAGE_CHECK_ARG(logits && tokens && advantage && row_loss && logprob && entropy && cut && summary, "mage_policy_loss: null pointer");
+    const float inv_t = (float)(1.0 / (double)temperature);
+    if (int rc = policy_check("mage_policy_loss", logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
+    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "mage_policy_loss: top_k=%d outside [0, K=%d]", top_k, K);
+    MAGE_CHECK_ARG(top_k != 1, "mage_policy_loss: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient");
+    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mage_policy_loss: top_p=%g outside (0, 1]", (double)top_p);
+    int* err = mage_error_word();
+    MAGE_CHECK_ARG(err != nullptr, "mage_policy_loss: mage_init() has not been called");
+    const bool topk = top_k > 0 && top_k < K, topp = top_p < 1.f;
+    const float cmin = (float)(1.0 - (double)clip_lo), cmax = (float)(1.0 + (double)clip_hi);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+#define MAGE_POLICY_NV(NV)                                                                                                             \
+    policy_launch<NV>(topk, topp, grid, s, logits, (long)rows, K, (long)ld, tokens, advantage, (long)adv_div, behaviour_logprob, inv_t, \
+                      top_k, top_p, cmin, cmax, entropy_coef, row_loss, logprob, entropy, cut, err)
+    if (K <= 256) MAGE_POLICY_NV(4);
+    else if (K <= 512) MAGE_POLICY_NV(8);
+    else if (K <= 1024) MAGE_POLICY_NV(16);
+    else if (K <= 2048) MAGE_POLICY_NV(32);
+    else MAGE_POLICY_NV(64);
+#undef MAGE_POLICY_NV
+    hipLaunchKernelGGL(policy_part_kernel, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage, (long)adv_div,
+                       behaviour_logprob, cmin, cmax, (long)rows, (long)((rows + POLICY_PARTS - 1) / POLICY_PARTS));
+    hipLaunchKernelGGL(policy_summary_kernel, dim3(1), dim3(POLICY_PARTS), 0, s, summary, 1.0 / (double)rows);
+    MAGE_CHECK_LAUNCH("mage_policy_loss");
+    return MAGE_OK;
+}
+
+extern "C" int mage_policy_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                    int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature, float clip_lo,
+                                    float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream) {
+    MAGE_CHECK_ARG(logits && tokens && advantage && cut && grad_out && dlogits, "mage_policy_loss_bwd: null pointer");
+    const float inv_t = (float)(1.0 / (double)temperature);
+    if (int rc = policy_check("mage_policy_loss_bwd", logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
+    MAGE_CHECK_ARG((dl_dtype == MAGE_F32 || dl_dtype == MAGE_BF16) && (((uintptr_t)dlogits) & 15) == 0,
+                   "mage_policy_loss_bwd: dlogits must be 16-byte aligned fp32 or bf16 (dtype %d)", dl_dtype);
+    const float cmin = (float)(1.0 - (double)clip_lo), cmax = (float)(1.0 + (double)clip_hi);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+#define MAGE_POLICY_BWD(NV, OT)                                                                                                        \
+    hipLaunchKernelGGL((policy_loss_bwd_kernel<NV, OT>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, tokens, advantage,   \
+                       (long)adv_div, behaviour_logprob, cut, inv_t, cmin, cmax, entropy_coef, grad_out, 1.0f / (float)rows, (OT*)dlogits)
+#define MAGE_POLICY_BWD_NV(NV)                                  \
+    do {                                                        \
+        if (dl_dtype == MAGE_F32) MAGE_POLICY_BWD(NV, float);   \
+        else MAGE_POLICY_BWD(NV, unsigned short);               \
+    } while (0)
+    if (K <= 256) MAGE_POLICY_BWD_NV(4);
+    else if (K <= 512) MAGE_POLICY_BWD_NV(8);
+    else if (K <= 1024) MAGE_POLICY_BWD_NV(16);
+    else if (K <= 2048) MAGE_POLICY_BWD_NV(32);
+    else MAGE_POLICY_BWD_NV(64);
+#undef MAGE_POLICY_BWD_NV
+#undef MAGE_POLICY_BWD
+    MAGE_CHECK_LAUNCH("mage_policy_loss_bwd");
     return MAGE_OK;
 }

@@ -866,6 +866,8 @@ class MAGE(nn.Module):
         self.last_candidate_policy_scores: Optional[torch.Tensor] = None  # policy, candidates > 1: fp32 [B, N]
         self.last_token_entropy: Optional[torch.Tensor] = None           # entropy: fp32 [B, L-1, h, w], the full softmax at temperature 1 (nats)
         self.last_token_policy_entropy: Optional[torch.Tensor] = None    # entropy, sampling on: the filtered distribution's
+        self.last_policy_token_logprobs: Optional[torch.Tensor] = None   # policy_loss: fp32 [B, L-1, h, w], the given tokens under the current policy
+        self._last_policy_out = None
 
     # ------------------------------------------------------------------ construction helpers
     def instantiate_first_stage(self, config):
@@ -1001,6 +1003,75 @@ class MAGE(nn.Module):
                     self.last_clip_policy_logprob = ops.clip_scores(st["policy_logprob"], n_clips=B)[0].view(B)
             ops.check_device_errors(images.device)
         return scores.view(B)
+
+    def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0):
+        """Policy-gradient loss of given tokens under the policy set_sampling currently describes (sampling off: temperature 1, no filter):
+        (loss, info) of one teacher-forced pass over frame 0 of batch['images'] (plus batch['text'] and the optional batch['speed'], as
+        autoregressive_generate reads them) followed by `tokens` (int64 [B, L-1, h, w], e.g. last_tokens), ending in mage_policy_loss
+        (include/mage_hip_ext.h states the rule).  advantages: fp32 [B] (one per clip) or [B, L-1, h, w] (one per token).
+        behaviour_logprobs None: the reward-weighted likelihood, mean of -A logprob - entropy_coef entropy.  behaviour_logprobs fp32
+        [B, L-1, h, w] (e.g. last_token_policy_logprobs of the call that drew the tokens): the clipped surrogate with the importance ratio
+        rho = exp(logprob - behaviour), clipped to [1 - lo, 1 + hi]; clip is a float (lo = hi) or a (lo, hi) pair.  A token the current
+        filter could never draw contributes 0 and no gradient and is counted in info['outside_fraction'].
+        In grad mode (any parameter requiring grad) the loss carries one autograd node over the trainable parameters backed by the HIP
+        backward kernels, as forward's does: loss.backward(); optimizer.step() works.  Under torch.no_grad(): values only.
+        info = {'loss', 'entropy', 'approx_kl' (mean of behaviour - logprob), 'clip_fraction', 'outside_fraction'} as floats;
+        last_policy_token_logprobs keeps the per-token log-probabilities (fp32 [B, L-1, h, w]).
+        Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
+        from . import mage_train
+        L, R, K = self.frames_length, self.image_resolution, self.codebook_size
+        if not self.use_cids:
+            raise ValueError("policy_loss: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        if self.randomness:
+            raise ValueError("policy_loss: randomness=True draws generation-time noise that has no backward here; not supported")
+        if self._dt() == torch.float16:
+            raise ValueError("policy_loss: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
+        t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
+        if k == 1:
+            raise ValueError("policy_loss: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient")
+        images = batch["images"]
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[1] >= 1):
+            raise ValueError("policy_loss: batch['images'] must be [B, >= 1, C, H, W]")
+        B = images.shape[0]
+        tshape = (B, L - 1, R, R)
+        if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
+            raise ValueError(f"policy_loss: tokens must be int64 {list(tshape)}")
+        if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape)):
+            raise ValueError(f"policy_loss: advantages must be fp32 [{B}] or {list(tshape)}")
+        b = behaviour_logprobs
+        if b is not None and not (torch.is_tensor(b) and b.dtype == F32 and tuple(b.shape) == tshape):
+            raise ValueError(f"policy_loss: behaviour_logprobs must be fp32 {list(tshape)} or None")
+        try:
+            lo, hi = (float(clip), float(clip)) if not isinstance(clip, (tuple, list)) else (float(clip[0]), float(clip[1]))
+            if isinstance(clip, (tuple, list)) and len(clip) != 2:
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"policy_loss: clip must be a float or a (lo, hi) pair, got {clip!r}") from None
+        if not (0.0 <= lo <= 1.0 and hi >= 0.0):
+            raise ValueError(f"policy_loss: clip lo={lo} must lie in [0, 1] and hi={hi} must be >= 0")
+        if not math.isfinite(float(entropy_coef)):
+            raise ValueError(f"policy_loss: entropy_coef must be finite, got {entropy_coef}")
+        for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("advantages", advantages),
+                        ("behaviour_logprobs", b)):
+            if x is not None and not (x.is_cuda and x.device == images.device):
+                raise ValueError(f"policy_loss: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        policy = dict(tokens=tokens.contiguous(), advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo,
+                      clip_hi=hi, entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
+        with torch.cuda.device(images.device):
+            if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+                names = mage_train.trainable_names(self)
+                byname = dict(self.named_parameters())
+                loss = mage_train.MagePolicyLossFn.apply(self, batch, policy, names, *[byname[n] for n in names])
+                info, lp = self._last_policy_out
+                self._last_policy_out = None
+            else:
+                with torch.no_grad():
+                    loss, tape = mage_train.train_forward(self, batch, policy)
+                info, lp = tape["parts"], tape["policy"]["logprob"]
+                loss, tape = loss.clone(), None
+            self.last_policy_token_logprobs = lp.view(tshape)
+            ops.check_device_errors(images.device)
+        return loss, info
 
     def _sample_seeds(self, batch) -> dict:
         """The batch with its 'sample_seed' entry as int64 [B] on the images' device (drawn here when absent); kept as last_sample_seeds."""

@@ -575,9 +575,18 @@ def _text_backward(te, run32: _Run, tape, dout, grads, pre: str = "text_encoder"
 
 
 # ----------------------------------------------------------------------------------------------------------------- whole model
-def train_forward(model, batch):
+def _policy_scalars(policy: dict) -> dict:
+    """The scalar arguments mage_policy_loss and mage_policy_loss_bwd share."""
+    return {k: policy[k] for k in ("temperature", "clip_lo", "clip_hi", "entropy_coef")}
+
+
+def train_forward(model, batch, policy: Optional[dict] = None):
     """Teacher-forced pass of MAGE.forward (mage_model.py:575-639) with the activations the backward pass needs.
-    Returns (loss 0-dim fp32 tensor, tape)."""
+    Returns (loss 0-dim fp32 tensor, tape).
+    policy (MAGE.policy_loss; use_cids models without the randomness branch): the pass runs over GIVEN tokens and ends in the policy-gradient
+    loss instead of the cross-entropy -- frame 0 is still first_stage_encode(images[:, 0:1]), frames 1 .. L-1 are policy['tokens']
+    (int64 [B, L-1, h, w]); policy['advantage'] (fp32, one per clip or per token), policy['behaviour'] (fp32 per token, or None) and the
+    scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h)."""
     images = batch["images"]
     B = images.shape[0]
     R, L, Cc = model.image_resolution, model.frames_length, model.vision_width
@@ -596,7 +605,10 @@ def train_forward(model, batch):
     dev = images.device
     tok = tok_in = tok0 = lat_all = lat_in = lat0 = None
     if model.use_cids:
-        tok = model.first_stage_encode(images).reshape(B, -1, hw)                     # frozen first stage: no gradient
+        if policy is None:
+            tok = model.first_stage_encode(images).reshape(B, -1, hw)                 # frozen first stage: no gradient
+        else:
+            tok = torch.cat([model.first_stage_encode(images[:, 0:1]).reshape(B, 1, hw), policy["tokens"].reshape(B, L - 1, hw)], 1)
         tok_in = tok[:, :L - 1].contiguous()
         tok0 = tok[:, 0].contiguous()
         # frame features for the decoder (compute dtype) and, as the inference prologue does, frame 0's in fp32 for the MA encoder
@@ -639,13 +651,24 @@ def train_forward(model, batch):
         ops.add_scaled_rowvec(ma, speed, d["speed"], B=B, P=hw, Cc=Cc)
     ma_dt = ma if dt == F32 else ma.to(dt)
     logits, t_dec = _dec_forward(model.generate_model, run, ma_dt, feats, B, R, R)
-    if model.use_cids:
+    if policy is not None:
+        target = tok[:, 1:L].reshape(-1).contiguous()
+        res = ops.policy_loss(logits, target, policy["advantage"], policy["behaviour"], **_policy_scalars(policy), top_k=policy["top_k"],
+                              top_p=policy["top_p"])
+        recon = res["summary"][0]
+        policy = dict(policy, cut=res["cut"], logprob=res["logprob"], summary=res["summary"])
+    elif model.use_cids:
         target = tok[:, 1:L].reshape(-1).contiguous()
         recon = ops.cross_entropy(logits, target)                                                            # :618
     else:
         target = lat_all[:, 1:L].contiguous().view(-1, 8)
         recon = ops.mse(logits, target, rows=B * (L - 1) * hw, cols=model.first_stage_model.embed_dim, lda=logits.shape[1], ldb=8)   # :620
         model.last_logits = logits
+    if policy is not None:
+        parts = dict(zip(("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction"), policy["summary"].tolist()))
+        tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
+                    logits=logits, target=target, speed=speed, B=B, rand=None, beta=0.0, alpha=0.0, parts=parts, policy=policy)
+        return recon, tape
     loss, parts = recon, {"prediction": recon.item()}
     beta = alpha = 0.0
     if model.randomness:                                                     # :622-632 ([B]-element reductions and scalars)
@@ -678,7 +701,11 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
     dev = tape["logits"].device
     grads: Dict[str, torch.Tensor] = {}
     gout = grad_out.detach().to(device=dev, dtype=F32).reshape(1).contiguous()
-    if model.use_cids:
+    pol = tape.get("policy")
+    if pol is not None:
+        dlogits = ops.policy_loss_bwd(tape["logits"], tape["target"], pol["advantage"], pol["behaviour"], pol["cut"], gout,
+                                      torch.empty(tape["logits"].shape, device=dev, dtype=dt), **_policy_scalars(pol))
+    elif model.use_cids:
         dlogits = ops.cross_entropy_bwd(tape["logits"], tape["target"], gout, torch.empty(tape["logits"].shape, device=dev, dtype=dt))
     else:
         pred = tape["logits"]
@@ -750,3 +777,20 @@ class MageLossFn(torch.autograd.Function):
             g = grads.get(n)
             out.append(g.reshape(shp) if g is not None else torch.zeros(shp, device=dev, dtype=F32))     # ln_q / ln_kv: unused -> 0
         return (None, None, None, *out)
+
+
+class MagePolicyLossFn(torch.autograd.Function):
+    """loss = MagePolicyLossFn.apply(model, batch, policy, names, *params): MageLossFn's node over train_forward(model, batch, policy)."""
+
+    @staticmethod
+    def forward(ctx, model, batch, policy, names, *params):
+        with torch.no_grad():
+            loss, tape = train_forward(model, batch, policy)
+        model._last_policy_out = (tape["parts"], tape["policy"]["logprob"])  # for MAGE.policy_loss: the summary and the per-token log-probabilities
+        ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
+        ctx.devices = [p.device for p in params]
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (None, *MageLossFn.backward(ctx, grad_out))

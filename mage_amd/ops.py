@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "policy_loss", "policy_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -573,6 +573,58 @@ def token_stats(logits: torch.Tensor, tokens: Optional[torch.Tensor], *, rows: i
     _lib.check(l.mage_token_stats(logits.data_ptr(), rows, K, K if ld is None else ld, group, in_group_stride, in_off, _p(tokens),
                                   tok_group_stride, tok_off, float(temperature), int(top_k), float(top_p), _p(policy_logprob),
                                   _p(policy_entropy), _p(kept), _p(entropy), s), l)
+
+
+def _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div):
+    """The asserts policy_loss and policy_loss_bwd share; returns (rows, K, ld, adv_div).  adv_div None: advantage's entries share the rows
+    out equally (one per row, or one per clip)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows, K = logits.shape
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() == rows and tokens.device == logits.device
+    assert advantage.dtype == torch.float32 and advantage.is_contiguous() and advantage.device == logits.device
+    if adv_div is None:
+        assert advantage.numel() > 0 and rows % advantage.numel() == 0, "one advantage per row, or per equal group of consecutive rows"
+        adv_div = rows // advantage.numel()
+    assert adv_div > 0 and (rows - 1) // adv_div < advantage.numel()         # the largest index addressed
+    if behaviour_logprob is not None:
+        assert behaviour_logprob.dtype == torch.float32 and behaviour_logprob.is_contiguous() and behaviour_logprob.numel() == rows
+        assert behaviour_logprob.device == logits.device
+    return rows, K, logits.stride(0), adv_div
+
+
+def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor] = None, *,
+                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, clip_lo: float = 0.2, clip_hi: float = 0.2,
+                entropy_coef: float = 0.0, adv_div: Optional[int] = None) -> dict:
+    """mage_policy_loss over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows]; advantage fp32, row i using entry i // adv_div
+    (default: rows / numel consecutive rows per entry); behaviour_logprob fp32 [rows] selects the clipped surrogate, None the reward-weighted likelihood.  Returns the per-row
+    fp32 tensors 'row_loss', 'logprob', 'entropy', the uint32 thresholds 'cut' (kept as int32 storage: policy_loss_bwd's input) and
+    'summary' fp32 [5]: the means of the loss, the entropy, b - logprob, the clipped share and the outside share."""
+    l, s = _dev(logits)
+    rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
+    mk = lambda n, dt: torch.empty(n, device=logits.device, dtype=dt)      # noqa: E731
+    out = dict(row_loss=mk(rows, torch.float32), logprob=mk(rows, torch.float32), entropy=mk(rows, torch.float32), cut=mk(rows, torch.int32),
+               summary=mk(5, torch.float32))
+    _lib.check(l.mage_policy_loss(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
+                                  float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef),
+                                  out["row_loss"].data_ptr(), out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(),
+                                  out["summary"].data_ptr(), s), l)
+    return out
+
+
+def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor],
+                    cut: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *, temperature: float = 1.0, clip_lo: float = 0.2,
+                    clip_hi: float = 0.2, entropy_coef: float = 0.0, adv_div: Optional[int] = None) -> torch.Tensor:
+    """mage_policy_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16 from policy_loss' inputs and its 'cut'; grad_out fp32 [1]."""
+    l, s = _dev(logits)
+    rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
+    assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.numel() == rows and cut.device == logits.device
+    assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
+    assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
+    assert dlogits.device == logits.device
+    _lib.check(l.mage_policy_loss_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
+                                      cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef),
+                                      grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
+    return dlogits
 
 
 def clip_scores(logprob: torch.Tensor, *, n_clips: int, n_cand: int = 1):

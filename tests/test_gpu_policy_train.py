@@ -1,0 +1,277 @@
+"""GPU: MAGE.policy_loss -- its gradients against autograd through the oracle (oracle/mage_oracle.py's motion_anchor, _frame_features and
+flat_axial_decoder over frame 0's encoded tokens plus given tokens, with the policy loss written in torch on the CPU), its consistency
+with the log-probabilities a generation reports, the filter plumbing, bf16 against fp32, a short optimisation loop and the refusals."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from mage_amd import _lib
+from mage_amd.optim import FlatAdam
+from mage_amd.utils import synth
+from oracle import mage_oracle as O
+from tests.helpers import build_mage, cpu_sd
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GRAD_TOL = 1e-4             # tests/test_gpu_train.py's: relative to the largest entry of the reference gradient tensor
+SMALL = dict(width=64, layers=3, vq_dim=32, K=64)
+
+
+def dev_batch(b):
+    return {k: v.to(DEV) for k, v in b.items()}
+
+
+def rel(a, b):
+    return (a.detach().float().cpu() - b.detach().float().cpu()).abs().max().item() / max(b.detach().abs().max().item(), 1e-30)
+
+
+def oracle_policy(sd, batch, L, tokens, adv_rows, T, clip, c, seed):
+    """The clipped surrogate through the oracle on the CPU: (loss, gradients by name, b, info).  b = the oracle's own log-probability plus
+    noise of +-0.4 (so some rows clip), rows within 1e-2 of a clip edge drawn again."""
+    sd = {k: (v.clone().requires_grad_() if v.is_floating_point() and not k.startswith("first_stage_model.") else v) for k, v in sd.items()}
+    images = batch["images"]
+    tok0 = O.vqvae_encode(sd, "first_stage_model.", images[:, 0])
+    tok = torch.cat([tok0[:, None], tokens], 1)
+    ma = O.motion_anchor(sd, tok0, batch["text"], batch.get("speed"))
+    logits = O.flat_axial_decoder(sd, "generate_model.", ma, O._frame_features(sd, tok[:, :L - 1]))
+    K = logits.shape[-1]
+    s = logits.reshape(-1, K) * float(np.float32(1.0 / float(np.float32(T))))
+    logp = torch.log_softmax(s, -1)
+    lp = logp.gather(1, tokens.reshape(-1, 1))[:, 0]
+    ent = -(logp.exp() * logp).sum(-1)
+    lo, hi = 1.0 - clip, 1.0 + clip
+    g = torch.Generator().manual_seed(seed)
+    noise = (torch.rand(lp.shape, generator=g) * 2 - 1) * 0.4
+    for _ in range(8):
+        rho = (-noise).exp()
+        near = ((rho / lo - 1).abs() < 1e-2) | ((rho / hi - 1).abs() < 1e-2)
+        noise[near] = ((torch.rand(lp.shape, generator=g) * 2 - 1) * 0.4)[near]
+    assert not near.any()
+    b = (lp.detach() + noise).float()
+    rho = (lp - b).exp()
+    loss = (-torch.minimum(rho * adv_rows, rho.clamp(lo, hi) * adv_rows) - c * ent).mean()
+    names = [k for k, v in sd.items() if v.requires_grad]
+    gs = torch.autograd.grad(loss, [sd[k] for k in names], allow_unused=True)
+    active = ((adv_rows >= 0) & (rho <= hi)) | ((adv_rows < 0) & (rho >= lo))
+    info = dict(loss=loss.item(), entropy=ent.mean().item(), approx_kl=(b - lp).mean().item(), clip_fraction=(~active).float().mean().item())
+    return loss.item(), dict(zip(names, gs)), b, info
+
+
+@pytest.mark.parametrize("cfg_kw,B,L,seed,batch_kw,per_token,c", [
+    (SMALL, 3, 5, 31, dict(text_len=9, ragged_text=True), False, 0.01),
+    (dict(), 1, 4, 33, dict(digits=2, caption_lengths=(16, 18, 20)), True, 0.0),                     # full width (d=512, 6 blocks)
+])
+def test_policy_gradients_match_oracle_autograd(cfg_kw, B, L, seed, batch_kw, per_token, c):
+    """fp32 mode, eval(): temperature 1.3 and no filter (a kept-set boundary would be decided by logits that differ by 1e-5 between the two
+    sides; the filter is covered at kernel level, where both sides see the same logits)."""
+    T, clip = 1.3, 0.2
+    m = build_mage(synth.mnist_model_config(frames_length=L, **cfg_kw), seed, DEV)
+    batch = synth.synth_batch_mnist(B, L, seed=seed, **batch_kw)
+    R, K = m.image_resolution, m.codebook_size
+    g = torch.Generator().manual_seed(seed + 1)
+    tokens = torch.randint(0, K, (B, L - 1, R, R), generator=g)
+    adv = torch.randn((B, L - 1, R, R) if per_token else (B,), generator=g)
+    if not per_token:
+        adv[0], adv[1] = adv[0].abs() + 0.1, -adv[1].abs() - 0.1                                     # mixed signs
+    adv_rows = adv.reshape(-1) if per_token else adv.repeat_interleave((L - 1) * R * R)
+    want_loss, want, b, want_info = oracle_policy(cpu_sd(m), batch, L, tokens, adv_rows, T, clip, c, seed + 2)
+    assert 0.02 < want_info["clip_fraction"] < 0.9
+    m.set_sampling(T)
+    loss, info = m.policy_loss(dev_batch(batch), tokens.to(DEV), adv.to(DEV), b.view(B, L - 1, R, R).to(DEV), clip=clip, entropy_coef=c)
+    m.set_sampling(None)
+    print(f"loss {loss.item():.6f} want {want_loss:.6f}; info {info}; oracle {want_info}")
+    assert abs(loss.item() - want_loss) < 1e-4 and loss.requires_grad and info["loss"] == loss.item()
+    assert abs(info["entropy"] - want_info["entropy"]) < 1e-4 and abs(info["approx_kl"] - want_info["approx_kl"]) < 1e-4
+    assert abs(info["clip_fraction"] - want_info["clip_fraction"]) < 1e-6 and info["outside_fraction"] == 0.0
+    assert m.last_policy_token_logprobs.shape == tokens.shape
+    loss.backward()
+    worst, n_checked = ("", 0.0), 0
+    for name, p in m.named_parameters():
+        if name.startswith("first_stage_model."):
+            assert p.grad is None
+            continue
+        g_ref = want.get(name)
+        assert p.grad is not None, name
+        if g_ref is None or g_ref.abs().max().item() == 0.0:
+            assert p.grad.abs().max().item() == 0.0, name
+            continue
+        r = rel(p.grad, g_ref)
+        n_checked += 1
+        if r > worst[1]:
+            worst = (name, r)
+    print(f"{n_checked} gradients checked, worst relative error {worst[1]:.2e} at {worst[0]}")
+    assert worst[1] < GRAD_TOL, worst
+    assert n_checked >= 90
+
+
+@pytest.fixture(scope="module")
+def small():
+    L = 5
+    m = build_mage(synth.mnist_model_config(frames_length=L, **SMALL), 41, DEV)
+    return m, synth.synth_batch_mnist(3, L, seed=41, text_len=9, ragged_text=True)
+
+
+def _reset(m):
+    m.set_sampling(None).set_logprobs(False).set_precision("fp32")
+    m.eval()
+    m.zero_grad(set_to_none=True)
+
+
+def _sample(m, batch, T, seeds, **kw):
+    m.set_sampling(T, **kw).set_logprobs(True, policy=True)
+    m.autoregressive_generate(dev_batch({**batch, "sample_seed": torch.tensor(seeds, dtype=torch.int64)}))
+    return m.last_tokens.clone(), m.last_token_policy_logprobs.clone()
+
+
+def test_on_policy_ratios_are_one(small):
+    """The log-probabilities of the teacher-forced pass against the ones the generation reported for the same tokens: both passes are held to
+    1e-4 logits against the oracle, two paths x (logit + log-sum-exp) = 4e-4, with 2.5x margin: 1e-3."""
+    m, batch = small
+    _reset(m)
+    tokens, blp = _sample(m, batch, 0.9, [5, 6, 7])
+    adv = torch.tensor([1.0, -0.5, 0.25], device=DEV)
+    with torch.no_grad():
+        loss, info = m.policy_loss(dev_batch(batch), tokens, adv, blp)
+    got = m.last_policy_token_logprobs
+    _reset(m)
+    assert not loss.requires_grad and got.shape == blp.shape == tokens.shape
+    d = (got - blp).abs().max().item()
+    print(f"max |teacher-forced - generated| policy log-probability {d:.3e}; info {info}")
+    assert d < 1e-3
+    assert info["clip_fraction"] == 0.0 and info["outside_fraction"] == 0.0 and abs(info["approx_kl"]) < 1e-3
+    assert set(info) == {"loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction"} and all(isinstance(v, float) for v in info.values())
+
+
+def test_filter_parameters_reach_the_kernel(small):
+    m, batch = small
+    _reset(m)
+    m.autoregressive_generate(dev_batch(batch))                      # greedy tokens: the row maximum, which both filters always keep
+    tokens = m.last_tokens.clone()
+    adv = torch.tensor([1.0, -0.5, 0.25], device=DEV)
+    with torch.no_grad():
+        _, plain = m.policy_loss(dev_batch(batch), tokens, adv)
+        m.set_sampling(1.0, top_k=8, top_p=0.9)
+        _, info = m.policy_loss(dev_batch(batch), tokens, adv)
+    _reset(m)
+    assert all(np.isfinite(v) for v in info.values()) and info["outside_fraction"] == 0.0
+    assert info["approx_kl"] == 0.0 and info["clip_fraction"] == 0.0                                # the weighted form
+    assert info["entropy"] < plain["entropy"]                        # the filtered distribution's: something was cut
+
+
+def test_bf16_policy_gradients_track_fp32(small):
+    m, batch = small
+    _reset(m)
+    tokens, blp = _sample(m, batch, 0.9, [8, 9, 10])
+    m.set_logprobs(False)
+    adv = torch.tensor([1.0, -0.5, 0.25], device=DEV)
+    b = dev_batch(batch)
+    m.policy_loss(b, tokens, adv, blp, entropy_coef=0.01)[0].backward()
+    g32 = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+    m.zero_grad(set_to_none=True)
+    m.set_precision("bf16")
+    m.policy_loss(b, tokens, adv, blp, entropy_coef=0.01)[0].backward()
+    cos = []
+    for n, p in m.named_parameters():
+        if p.grad is not None and g32[n].abs().max() > 0:
+            cos.append(F.cosine_similarity(p.grad.flatten(), g32[n].flatten(), dim=0).item())
+    _reset(m)
+    print(f"bf16 vs fp32 policy gradients: min cosine {min(cos):.4f}, mean {np.mean(cos):.4f}")
+    assert len(cos) >= 90 and min(cos) > 0.98
+
+
+def _loop(seed):
+    L = 5
+    m = build_mage(synth.mnist_model_config(frames_length=L, **SMALL), seed, DEV)
+    batch = synth.synth_batch_mnist(3, L, seed=seed, text_len=9, ragged_text=True)
+    tokens, _ = _sample(m, batch, 1.0, [1, 2, 3])
+    m.set_logprobs(False)
+    reward = (tokens == 0).float().flatten(1).mean(1)
+    adv = (reward - reward.mean()).contiguous()
+    assert adv.abs().max().item() > 0
+    opt = FlatAdam(m.parameters(), lr=1e-3)
+    b = dev_batch(batch)
+    losses = []
+    for _ in range(20):
+        opt.zero_grad()
+        loss, _ = m.policy_loss(b, tokens, adv)
+        loss.backward()
+        opt.step()
+        losses.append(loss.item())
+    with torch.no_grad():
+        losses.append(m.policy_loss(b, tokens, adv)[0].item())
+    return losses
+
+
+def test_twenty_steps_lower_the_loss_and_repeat_bit_for_bit():
+    a = _loop(43)
+    print(f"weighted policy loss over 20 FlatAdam steps: first {a[0]:.6e}, last {a[-1]:.6e}")
+    assert a[-1] < a[0]
+    assert _loop(43)[-1] == a[-1]
+
+
+def test_refusals_launch_nothing_and_leave_forward_alone(small, monkeypatch):
+    m, batch = small
+    _reset(m)
+    b = dev_batch(batch)
+    B, L, R = 3, m.frames_length, m.image_resolution
+    tokens = torch.zeros(B, L - 1, R, R, dtype=torch.int64, device=DEV)
+    adv = torch.ones(B, device=DEV)
+    blp = torch.zeros(B, L - 1, R, R, device=DEV)
+
+    def forward_bits():
+        m.zero_grad(set_to_none=True)
+        loss, _ = m(b)
+        loss.backward()
+        return loss.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+    loss0, g0 = forward_bits()
+    m.set_sampling(0.9, top_k=8, top_p=0.9)
+    m.policy_loss(b, tokens, adv, blp, clip=(0.1, 0.3), entropy_coef=0.01)[0].backward()
+    m.set_sampling(None)
+    loss1, g1 = forward_bits()
+    assert torch.equal(loss0, loss1) and g0.keys() == g1.keys() and all(torch.equal(g0[n], g1[n]) for n in g0)       # no state leaks
+    m.zero_grad(set_to_none=True)
+
+    lib = _lib.lib(0)
+    calls = []
+
+    def counted(name, fn):
+        def f(*a):
+            calls.append(name)
+            return fn(*a)
+        return f
+    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
+        if name not in ("mage_last_error", "mage_abi_version"):
+            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+
+    def refused(match, *a, **kw):
+        with pytest.raises(ValueError, match=match):
+            m.policy_loss(*a, **kw)
+        assert calls == []
+    m.use_cids = False
+    refused("use_cids=False", b, tokens, adv)
+    m.use_cids = True
+    m.randomness = True
+    refused("randomness=True", b, tokens, adv)
+    m.randomness = False
+    m.set_sampling(1.0, top_k=1)
+    refused("top_k=1", b, tokens, adv)
+    m.set_sampling(None)
+    m.set_precision("f16")
+    refused("f16", b, tokens, adv)
+    m.set_precision("fp32")
+    refused("tokens", b, tokens[:, 1:], adv)
+    refused("tokens", b, tokens.int(), adv)
+    refused("advantages", b, tokens, adv[:2])
+    refused("advantages", b, tokens, adv.double())
+    refused("behaviour_logprobs", b, tokens, adv, blp[:, :, 1:])
+    refused("behaviour_logprobs", b, tokens, adv, blp.double())
+    refused("clip", b, tokens, adv, blp, clip=-0.1)
+    refused("clip", b, tokens, adv, blp, clip=(0.1, 0.2, 0.3))
+    refused("entropy_coef", b, tokens, adv, entropy_coef=float("nan"))
+    refused("GPU", b, tokens.cpu(), adv)
+    refused("GPU", b, tokens, adv.cpu())
+    refused("GPU", b, tokens, adv, blp.cpu())
+    refused("GPU", {k: v.cpu() for k, v in b.items()}, tokens, adv)
+    monkeypatch.undo()
+    _reset(m)
