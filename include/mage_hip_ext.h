@@ -86,6 +86,41 @@ int mage_policy_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t l
                          int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature, float clip_lo,
                          float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream);
 
+/* Per-frame MSE, PSNR and SSIM between generated frames and their targets: no site in the reference (it reports no metric).  Serves
+ * MAGE.video_metrics and the built-in rewards of MAGE.rollout (mage_amd/modules/mage_model.py).
+ * video and target are fp32 [clips, T, C, H, W] with a frame's C*H*W values contiguous, frames of a clip T*C*H*W apart and clip r of video
+ * at video + r*video_clip_stride (elements); video clip r is compared with target clip r / tgt_div at target + (r / tgt_div) *
+ * target_clip_stride (tgt_div = N: the N candidates of a clip share one ground truth; a target that is frames 1 .. L-1 of an [B, L, C, H, W]
+ * batch is the pointer advanced one frame with target_clip_stride = L*C*H*W).  Outputs are fp32 [clips*T], entry r*T + t for frame t of
+ * clip r; each is optional (null: not computed), at least one must be given:
+ *   mse   the mean over C*H*W of (x - y)^2: differences, squares and the sum in fp64, rounded once;
+ *   psnr  10 log10(data_range^2 / mse) from the fp64 mean; +inf where mse is 0;
+ *   ssim  the mean over channels and window positions of
+ *           ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2)),  C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2,
+ *         with the local moments under an 11 x 11 Gaussian window (sigma 1.5, normalised to sum 1, applied separably) at the (H-10) x (W-10)
+ *         positions where the window lies inside the frame, biased: sx^2 = E[x^2] - mx^2, sxy = E[xy] - mx my.  All of it in fp64, rounded
+ *         once (x*x, y*y and x*y of fp32 values are exact there).
+ * Every sum has a fixed order and there are no floating-point atomics: two launches give the same bits, and a frame's bits depend on its own
+ * pixels only -- not on clips, tgt_div or its place in the launch.  Both sides go through the same operations, so metrics(x, y) equals
+ * metrics(y, x) bit for bit and metrics(x, x) is mse 0, psnr +inf, ssim 1 exactly.  A NaN pixel makes its own frame's outputs NaN.
+ * ssim needs H >= 11 and W >= 11; clips, T, C, H, W > 0 with clips*T and C*H*W below 2^31; tgt_div >= 1; data_range finite and > 0; both
+ * strides >= T*C*H*W; pointers 4-byte aligned: MAGE_EINVAL otherwise, nothing launched.
+ * One workgroup per frame, which walks the frame in tiles of up to 28 x 30 window positions: a tile's pixels come from memory once into LDS
+ * (only the 10-pixel halo is read again by the neighbouring tile), a row pass and a column pass form the five windowed moments through LDS. */
+int mage_video_metrics(const float* video, int64_t video_clip_stride, const float* target, int64_t target_clip_stride, int64_t clips, int32_t T,
+                       int32_t C, int32_t H, int32_t W, int64_t tgt_div, float data_range, float* mse, float* psnr, float* ssim, void* stream);
+
+/* Per-clip rewards and group-relative advantages from per-frame rewards: no site in the reference.  Serves MAGE.rollout.
+ * frame_reward is fp32 [groups*N*T]: T frame rewards for each of the N candidates of each group (clip).  reward (fp32 [groups*N]) is each
+ * candidate's mean over its T frames, added in fp64 in order and rounded once.  With mean_g and std_g the mean and the population standard
+ * deviation of a group's N rewards (fp64, fixed order), advantage (fp32 [groups*N]) is
+ *   mode 0:  r - mean_g;          mode 1:  (r - mean_g) / (std_g + eps).
+ * A reward equal to its group's mean gets exactly 0 in both modes (so a group of equal rewards is all zeros, also with eps = 0).  A group
+ * holding a NaN or infinite reward gets NaN advantages throughout; nothing is checked on the host.  Two launches give the same bits.
+ * groups > 0, N >= 2, T >= 1, mode 0 or 1, eps finite and >= 0, pointers non-null and 4-byte aligned: MAGE_EINVAL otherwise, nothing launched. */
+int mage_group_advantages(const float* frame_reward, int64_t groups, int32_t N, int32_t T, int32_t mode, float eps, float* reward,
+                          float* advantage, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,8 @@ EXT_SIGNATURES = {
     "mage_token_stats": (C.c_int, [vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, f32, i32, f32, vp, vp, vp, vp, vp]),
     "mage_policy_loss": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, f32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "mage_policy_loss_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, vp, i32, vp]),
+    "mage_video_metrics": (C.c_int, [vp, i64, vp, i64, i64, i32, i32, i32, i32, i64, f32, vp, vp, vp, vp]),
+    "mage_group_advantages": (C.c_int, [vp, i64, i32, i32, i32, f32, vp, vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

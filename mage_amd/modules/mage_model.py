@@ -1073,6 +1073,113 @@ class MAGE(nn.Module):
             ops.check_device_errors(images.device)
         return loss, info
 
+    @torch.no_grad()
+    def video_metrics(self, video, target, data_range: float = 2.0) -> dict:
+        """Per-frame quality of `video` against `target`, both fp32 [B, T, C, H, W] on the model's GPU: {'mse', 'psnr', 'ssim'}, fp32 [B, T]
+        each (mage_video_metrics, include/mage_hip_ext.h: the standard 11 x 11 Gaussian-window SSIM over the valid region, PSNR = 10 log10(
+        data_range^2 / mse), +inf for identical frames).  data_range is the span of the pixel values: the models' frames lie in (-1, 1), so
+        2.0.  Works for any model (use_cids or not): it only looks at frames.  Either side may be a view along the frame axis, e.g.
+        batch['images'][:, 1:]."""
+        for name, x in (("video", video), ("target", target)):
+            if not (torch.is_tensor(x) and x.dim() == 5 and x.dtype == F32 and x.numel() > 0):
+                raise ValueError(f"video_metrics: {name} must be a non-empty fp32 [B, T, C, H, W] tensor")
+        if tuple(video.shape) != tuple(target.shape):
+            raise ValueError(f"video_metrics: video {list(video.shape)} and target {list(target.shape)} must have the same shape")
+        if video.shape[-2] < 11 or video.shape[-1] < 11:
+            raise ValueError(f"video_metrics: SSIM's 11 x 11 window needs H and W >= 11, got {video.shape[-2]} x {video.shape[-1]}")
+        dr = float(data_range)
+        if not (math.isfinite(dr) and dr > 0 and dr < 3.4e38):
+            raise ValueError(f"video_metrics: data_range must be finite and > 0, got {data_range}")
+        try:
+            _need_gpu(video, "MAGE.video_metrics")
+            _need_gpu(target, "MAGE.video_metrics")
+        except RuntimeError as e:                        # (a refusal like the ones above: the same words, as a ValueError)
+            raise ValueError(str(e)) from None
+        if video.device != target.device:
+            raise ValueError("video_metrics: video and target must be on the same GPU")
+        with torch.cuda.device(video.device):
+            video, target = (x if ops._frames_ok(x) else x.contiguous() for x in (video, target))
+            return ops.video_metrics(video, target, data_range=dr)
+
+    _ROLLOUT_REWARDS = ("ssim", "psnr", "neg_mse")
+
+    @torch.no_grad()
+    def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6) -> dict:
+        """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
+        under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
+        rewarded on the device, and the rewards turned into group-relative advantages:
+            out = m.rollout(batch, 8); loss, info = m.policy_loss(out['batch'], out['tokens'], out['advantages'], out['behaviour_logprobs'])
+        batch is autoregressive_generate's ('sample_seed' int64 [B] optional: candidate c of a clip draws with seed + c, so candidate 0 is
+        the candidates = 1 sample).  reward: 'ssim', 'psnr' or 'neg_mse' -- the mean over the L-1 generated frames of that metric against
+        frames 1 .. L-1 of batch['images'], which must then hold all L frames (mage_video_metrics, data_range 2) -- or a callable
+        (video [B*N, L, C, H, W], batch) -> fp32 [B*N] on the GPU, one reward per clip (batch: the returned one).  normalize: 'std'
+        ((r - mean) / (std + eps) over a clip's N candidates), 'mean' (r - mean) or None (the rewards themselves) (mage_group_advantages; a
+        group holding a non-finite reward -- a PSNR of identical frames -- gets NaN advantages, unchecked: a check would be a sync).
+        Returns {'video' [B*N, L, C, H, W], 'tokens' int64 [B*N, L-1, h, w], 'behaviour_logprobs' fp32 like tokens (the policy
+        log-probabilities: last_token_policy_logprobs of a generation), 'token_logprobs' (the model's, temperature 1, unfiltered), 'rewards'
+        fp32 [B, N], 'advantages' fp32 [B*N], 'frame_metrics' {'mse', 'psnr', 'ssim'} fp32 [B*N, L-1] each (None for a callable reward),
+        'seeds' int64 [B*N], 'batch': the input with every per-clip tensor repeated N times along dim 0, 'images' cut to frame 0 (all
+        policy_loss reads)}; row b*N + c is candidate c of clip b throughout.
+        One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
+        (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
+        if not self.use_cids:
+            raise ValueError("rollout: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
+        if getattr(self, "sampling", None) is None:
+            raise ValueError("rollout: candidates are drawn by the sampler: switch sampling on with set_sampling first")
+        if isinstance(candidates, bool) or not isinstance(candidates, int) or candidates < 2:
+            raise ValueError(f"rollout: candidates must be an integer >= 2 (a group of one has no relative advantage), got {candidates!r}")
+        if not (callable(reward) or reward in self._ROLLOUT_REWARDS):
+            raise ValueError(f"rollout: reward must be one of {list(self._ROLLOUT_REWARDS)} or a callable, got {reward!r}")
+        if normalize not in ("std", "mean", None):
+            raise ValueError(f"rollout: normalize must be 'std', 'mean' or None, got {normalize!r}")
+        if not (isinstance(eps, (int, float)) and math.isfinite(eps) and 0 <= eps < 3.4e38):
+            raise ValueError(f"rollout: eps must be finite and >= 0, got {eps!r}")
+        N, L = int(candidates), self.frames_length
+        images = batch["images"]
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1 and images.shape[1] >= 1):
+            raise ValueError("rollout: batch['images'] must be [B, >= 1, C, H, W]")
+        builtin = not callable(reward)
+        if builtin and not (images.shape[1] >= L and images.dtype == F32 and min(images.shape[-2:]) >= 11):
+            raise ValueError(f"rollout: reward '{reward}' compares with the ground truth: batch['images'] must be fp32 [B, {L}, C, H, W] with "
+                             "H, W >= 11")
+        for name, x in batch.items():
+            if torch.is_tensor(x) and name != "sample_seed" and not (x.is_cuda and x.device == images.device):
+                raise ValueError(f"rollout: batch['{name}'] must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        Bc = images.shape[0]
+        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
+        settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
+        try:
+            self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
+            b = self._sample_seeds(batch)
+            with torch.cuda.device(images.device), weights_frozen():
+                out = self._generate_one(b, keep_all=True)
+                seeds = (b["sample_seed"][:, None] + torch.arange(N, device=images.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
+                rep = {k: (v.repeat_interleave(N, 0) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == Bc else v) for k, v in batch.items()
+                       if k not in ("images", "sample_seed")}
+                out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": seeds}
+                out["seeds"] = seeds
+                video = out["video"]
+                if builtin:
+                    gen = video[:, 1:] if video.dtype == F32 else video[:, 1:].float()
+                    fm = out["frame_metrics"] = ops.video_metrics(gen, images[:, 1:L], tgt_div=N, data_range=2.0)
+                    fr = fm[reward] if reward != "neg_mse" else -fm["mse"]
+                else:
+                    out["frame_metrics"] = None
+                    fr = reward(video, out["batch"])
+                    if not (torch.is_tensor(fr) and fr.dtype == F32 and tuple(fr.shape) == (Bc * N,) and fr.device == images.device):
+                        raise ValueError(f"rollout: the reward callable must return fp32 [{Bc * N}] on the model's GPU")
+                    fr = fr.contiguous()
+                out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
+                out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
+                ops.check_device_errors(images.device)
+        finally:
+            self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings
+            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
+                delattr(self, a)
+            for a, v in keep.items():
+                setattr(self, a, v)
+        return out
+
     def _sample_seeds(self, batch) -> dict:
         """The batch with its 'sample_seed' entry as int64 [B] on the images' device (drawn here when absent); kept as last_sample_seeds."""
         images = batch["images"]
@@ -1510,7 +1617,7 @@ class MAGE(nn.Module):
         return _assemble(images, video)
 
     @torch.no_grad()
-    def _generate_one(self, batch):
+    def _generate_one(self, batch, keep_all: bool = False):
         images = batch["images"]
         B = images.shape[0]
         R, L, K = self.image_resolution, self.frames_length, self.codebook_size
@@ -1553,7 +1660,7 @@ class MAGE(nn.Module):
             clip_major = lambda t_: t_.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # noqa: E731
             lp = clip_major(lp_t) if want_lp else None
             st = None if st_t is None else {n: None if b is None else clip_major(b) for n, b in st_t.items()}
-            return self._finish(images, gen, None, lp, Bc, N, st)
+            return self._finish(images, gen, None, lp, Bc, N, st, keep_all)
         cur = tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                                 # :670 future slots hold frame 0
         logits = None
         lp = torch.empty(B, Lm1, R, R, device=images.device, dtype=F32) if want_lp else None
@@ -1588,12 +1695,18 @@ class MAGE(nn.Module):
                 ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
             if st is not None:
                 self._stats(logits, gen, st, flat, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N, st)
+        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all)
 
-    def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None):
+    def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None, keep_all: bool = False):
         """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
         of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691).  st: the
-        mage_token_stats buffers of set_logprobs(policy=, entropy=), [B * N, L-1, h, w] each (None: off); the winner's rows are kept."""
+        mage_token_stats buffers of set_logprobs(policy=, entropy=), [B * N, L-1, h, w] each (None: off); the winner's rows are kept.
+        keep_all (MAGE.rollout only): no winner is picked -- all B * N candidates are decoded and handed back with their tokens and
+        log-probabilities as a dict, and no result attribute is written."""
+        if keep_all:
+            first = images[:, 0:1] if N == 1 else images[:, 0:1].repeat_interleave(N, 0)       # every candidate starts from its clip's frame 0
+            return {"video": _assemble(first, self.first_stage_decode(gen)), "tokens": gen, "token_logprobs": lp, "first": first,
+                    "behaviour_logprobs": st["policy_logprob"]}
         if lp is not None:
             scores, best = ops.clip_scores(lp, n_clips=Bc, n_cand=N)
             pscores = None

@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "policy_loss", "policy_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -636,6 +636,47 @@ def clip_scores(logprob: torch.Tensor, *, n_clips: int, n_cand: int = 1):
     best = torch.empty(n_clips, device=logprob.device, dtype=torch.int64) if n_cand > 1 else None
     _lib.check(l.mage_clip_scores(logprob.data_ptr(), n_clips, n_cand, logprob.numel() // (n_clips * n_cand), scores.data_ptr(), _p(best), s), l)
     return scores, best
+
+
+def _frames_ok(x: torch.Tensor) -> bool:
+    """[clips, T, C, H, W] fp32 with every clip's T*C*H*W values contiguous (the clips themselves may lie further apart)."""
+    if not (x.dtype == torch.float32 and x.dim() == 5 and x.numel() > 0):
+        return False
+    want = 1
+    for n, st in zip(reversed(x.shape[1:]), reversed(x.stride()[1:])):
+        if n != 1 and st != want:
+            return False
+        want *= n
+    return x.shape[0] == 1 or x.stride(0) >= want
+
+
+def video_metrics(video: torch.Tensor, target: torch.Tensor, *, tgt_div: int = 1, data_range: float = 2.0, mse: bool = True, psnr: bool = True,
+                  ssim: bool = True) -> dict:
+    """Per-frame metrics of video [clips, T, C, H, W] fp32 against target [>= ceil(clips / tgt_div), T, C, H, W] fp32, video clip r against
+    target clip r // tgt_div (mage_video_metrics).  Either side may be a view whose clips lie further apart than T*C*H*W (batch['images'][:, 1:]).
+    Returns the outputs asked for, fp32 [clips, T] each, under 'mse', 'psnr', 'ssim'."""
+    l, s = _dev(video)
+    assert _frames_ok(video) and _frames_ok(target) and target.device == video.device and target.shape[1:] == video.shape[1:]
+    clips, T, C, H, W = video.shape
+    assert tgt_div >= 1 and (clips - 1) // tgt_div < target.shape[0]                           # the last target clip addressed
+    out = {n: torch.empty(clips, T, device=video.device, dtype=torch.float32) for n, on in (("mse", mse), ("psnr", psnr), ("ssim", ssim)) if on}
+    _lib.check(l.mage_video_metrics(video.data_ptr(), max(video.stride(0), video[0].numel()), target.data_ptr(),
+                                    max(target.stride(0), target[0].numel()), clips, T, C, H, W, int(tgt_div), float(data_range),
+                                    _p(out.get("mse")), _p(out.get("psnr")), _p(out.get("ssim")), s), l)
+    return out
+
+
+def group_advantages(frame_reward: torch.Tensor, *, groups: int, n_cand: int, mode: int = 1, eps: float = 1e-6):
+    """(reward [groups, n_cand] fp32, advantage [groups * n_cand] fp32) of frame_reward [groups * n_cand, T] fp32: each candidate's mean over
+    its T frames, and it against its group's mean (mode 0) or mean and standard deviation (mode 1) (mage_group_advantages)."""
+    l, s = _dev(frame_reward)
+    assert frame_reward.dtype == torch.float32 and frame_reward.is_contiguous() and groups > 0 and n_cand > 0
+    assert frame_reward.numel() > 0 and frame_reward.numel() % (groups * n_cand) == 0
+    reward = torch.empty(groups, n_cand, device=frame_reward.device, dtype=torch.float32)
+    advantage = torch.empty(groups * n_cand, device=frame_reward.device, dtype=torch.float32)
+    _lib.check(l.mage_group_advantages(frame_reward.data_ptr(), groups, n_cand, frame_reward.numel() // (groups * n_cand), int(mode), float(eps),
+                                       reward.data_ptr(), advantage.data_ptr(), s), l)
+    return reward, advantage
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
