@@ -399,7 +399,9 @@ int mage_cross_entropy(const float* logits, const int64_t* target, int64_t rows,
  * mage_conv_out: channels-last [N, IH, IW, cin] (x_dtype) -> NCHW fp32 [N, cout<=4, OH, OW], y = tanh(.):
  *   transposed=1: ConvTranspose2d(dim, cout, 4, 2, 1) (vqvae_model.py:187-188), weight_t [4, 4, cout, cin]
  *   (= torch weight [cin, cout, ky, kx] permuted to ky, kx, cout, cin);
- *   transposed=0: Conv2d(dim, cout, 1) (:212-213), weight_t [cout, cin]. */
+ *   transposed=0: Conv2d(dim, cout, 1) (:212-213), weight_t [cout, cin].
+ * Both refuse (MAGE_EINVAL, nothing launched) a size that is not positive, a negative pad, and mage_conv_in a filter larger than the
+ * padded plane (no output pixel); so do mage_maxpool2 / mage_upsample2 and their backward twins for H, W or C <= 0. */
 int mage_conv_in(const float* x, const float* weight_t, const float* bias, const float* scale, const float* shift,
                  void* y, int32_t y_dtype, int32_t N, int32_t cin, int32_t H, int32_t W, int32_t cout,
                  int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t act, int32_t s2d, void* stream);

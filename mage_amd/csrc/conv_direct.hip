@@ -357,6 +357,8 @@ extern "C" int mage_conv_in(const float* x, const float* weight_t, const float* 
                             int32_t kw, int32_t stride, int32_t pad, int32_t act, int32_t s2d, void* stream) {
     MAGE_CHECK_ARG(x && weight_t && y, "mage_conv_in: null pointer");
     MAGE_CHECK_ARG(N > 0 && cin > 0 && cin <= 4 && cout % 4 == 0 && stride >= 1, "mage_conv_in: cin=%d cout=%d unsupported", cin, cout);
+    MAGE_CHECK_ARG(H > 0 && W > 0 && kh > 0 && kw > 0 && pad >= 0 && cout > 0 && kh <= H + 2 * pad && kw <= W + 2 * pad,
+                   "mage_conv_in: bad sizes H=%d W=%d kh=%d kw=%d pad=%d cout=%d (the filter must fit the padded plane)", H, W, kh, kw, pad, cout);
     MAGE_CHECK_ARG(!scale == !shift, "mage_conv_in: scale and shift must be given together");
     MAGE_CHECK_ARG(act == MAGE_ACT_NONE || act == MAGE_ACT_RELU, "mage_conv_in: act %d unsupported", act);
     const int OH = (H + 2 * pad - kh) / stride + 1, OW = (W + 2 * pad - kw) / stride + 1;
@@ -403,7 +405,8 @@ extern "C" int mage_conv_in(const float* x, const float* weight_t, const float* 
 extern "C" int mage_conv_out(const void* x, int32_t x_dtype, const float* weight_t, const float* bias, float* y, int32_t N,
                              int32_t IH, int32_t IW, int32_t cin, int32_t cout, int32_t transposed, void* stream) {
     MAGE_CHECK_ARG(x && weight_t && y, "mage_conv_out: null pointer");
-    MAGE_CHECK_ARG(N > 0 && cin % 4 == 0 && cout >= 1 && cout <= 4, "mage_conv_out: cin=%d cout=%d unsupported", cin, cout);
+    MAGE_CHECK_ARG(N > 0 && cin > 0 && cin % 4 == 0 && cout >= 1 && cout <= 4, "mage_conv_out: cin=%d cout=%d unsupported", cin, cout);
+    MAGE_CHECK_ARG(IH > 0 && IW > 0, "mage_conv_out: bad plane IH=%d IW=%d", IH, IW);
     const int OH = transposed ? IH * 2 : IH, OW = transposed ? IW * 2 : IW;
     const dim3 grid((unsigned)(((long)N * OH * OW + 3) / 4)), blk(256);
     hipStream_t s = (hipStream_t)stream;
@@ -458,7 +461,7 @@ extern "C" int mage_convt_fold_tanh(const float* taps, const float* bias, float*
 
 extern "C" int mage_maxpool2(const void* x, void* y, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t relu,
                              void* stream) {
-    MAGE_CHECK_ARG(x && y && N > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "mage_maxpool2: bad arguments");
+    MAGE_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "mage_maxpool2: bad arguments");
     const long items = (long)N * (H / 2) * (W / 2) * (C / 4);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MAGE_F32) hipLaunchKernelGGL((maxpool2_kernel<float>), grid1(items), dim3(256), 0, s, (const float*)x, (float*)y, N, H, W, C, relu);
@@ -469,7 +472,7 @@ extern "C" int mage_maxpool2(const void* x, void* y, int32_t dtype, int32_t N, i
 }
 
 extern "C" int mage_upsample2(const void* x, void* y, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
-    MAGE_CHECK_ARG(x && y && N > 0 && C % 4 == 0, "mage_upsample2: bad arguments");
+    MAGE_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "mage_upsample2: bad arguments");
     const long items = (long)N * (H * 2) * (W * 2) * (C / 4);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MAGE_F32) hipLaunchKernelGGL((upsample2_kernel<float>), grid1(items), dim3(256), 0, s, (const float*)x, (float*)y, N, H, W, C);

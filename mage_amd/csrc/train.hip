@@ -1667,7 +1667,7 @@ __global__ __launch_bounds__(256) void upsample2_bwd_kernel(const float* __restr
 }  // namespace
 
 extern "C" int mage_maxpool2_bwd(const float* x, const float* dy, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
-    MAGE_CHECK_ARG(x && dy && dx && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "mage_maxpool2_bwd: bad arguments");
+    MAGE_CHECK_ARG(x && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "mage_maxpool2_bwd: bad arguments");
     const long items = (long)N * (H / 2) * (W / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, N, H, W, C);
     MAGE_CHECK_LAUNCH("mage_maxpool2_bwd");
@@ -1675,7 +1675,7 @@ extern "C" int mage_maxpool2_bwd(const float* x, const float* dy, float* dx, int
 }
 
 extern "C" int mage_upsample2_bwd(const float* dy, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
-    MAGE_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && C % 4 == 0, "mage_upsample2_bwd: bad arguments");
+    MAGE_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "mage_upsample2_bwd: bad arguments");
     const long items = (long)N * H * W * (C / 4);
     hipLaunchKernelGGL(upsample2_bwd_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, H, W, C);
     MAGE_CHECK_LAUNCH("mage_upsample2_bwd");
