@@ -86,6 +86,63 @@ int mage_policy_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t l
                          int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature, float clip_lo,
                          float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream);
 
+/* mage_policy_loss with a penalty against a frozen reference policy (the per-token KL term of PPO / GRPO-style fine-tuning), and its
+ * gradient: no site in the reference.  Serves MAGE.policy_loss(reference_logprobs=, kl_coef=).
+ * Everything mage_policy_loss / mage_policy_loss_bwd state holds; in addition row i reads r = reference_logprob[i] (fp32: the token's
+ * log-probability under the reference policy, e.g. MAGE.token_policy_logprobs of a frozen copy).  With lp the row's logprob (unchanged, bit
+ * for bit mage_token_stats' policy_logprob) and d = r - lp formed as one fp32 subtraction, the forward call also writes
+ *   kl       (fp32)    kl_i = exp(d) - d - 1, the non-negative "k3" estimate of KL(policy || reference) at the drawn token,
+ * and row_loss is l_i(mage_policy_loss' rule) + kl_coef kl_i, the sum taken in fp64 together with the rule's fp64 terms and rounded once.
+ * The backward call uses g_i(mage_policy_loss_bwd's rule) + kl_coef (1 - exp(d)) in place of g_i (d kl / d logprob = 1 - exp(r - logprob);
+ * the two parts are added in fp64 and rounded once to fp32); the rest of dlogits -- the entropy term, the kept set read from cut -- is
+ * mage_policy_loss_bwd's formula.  A row whose gradient the clip switched off keeps its KL gradient.
+ * Accuracy: both factors are evaluated in fp64 from the fp32 value d, 1 - exp(d) as -expm1(d) (no cancellation), kl_i as expm1(d) - d for
+ * |d| >= 2^-8 (the subtraction costs at most 9 of fp64's 53 bits: relative error below 2^-42) and as the series
+ * d^2 (1/2 + d/6 + d^2/24 + d^3/120 + d^4/720) below it (first dropped term below 2^-51 of the sum): each is far inside one fp32 ulp for every
+ * d, down to |d| of 1e-12 and below, before its one rounding.  There is no clamp on d: a finite d large enough to overflow gives kl_i = +inf
+ * (and a gradient factor of -inf), as the arithmetic says.
+ * Exact cases: d == 0 (r has the bits of logprob) gives kl_i = 0 exactly, and a zero term is never added: that row's row_loss and dlogits
+ * row are bit for bit mage_policy_loss' and mage_policy_loss_bwd's for any kl_coef; kl_coef == 0 gives row_loss, logprob, entropy, cut and
+ * dlogits bit for bit theirs for any r (kl is still reported).
+ * Special rows: an outside row (logprob -inf) stays all zeros, kl_i = 0 included, and counts in the outside share only.  A row whose r is
+ * not finite (NaN, +-inf: e.g. -inf because the reference's filter could not draw the token) is an unanchored row: kl_i = 0, no KL gradient,
+ * otherwise treated by mage_policy_loss' rule.  A NaN logprob gives a NaN kl_i.
+ * summary[0..7): mage_policy_loss' five means (the loss mean now including the KL term), the mean of kl_i over `rows`, and the share of
+ * unanchored rows (inside rows whose r is not finite) -- the same two-stage fixed-order fp64 reduction through the same per-device buffer:
+ * two launches give the same bits, and calls of mage_policy_loss and mage_policy_loss_anchored on one device must be ordered.
+ * Arguments: the plain pair's rules; reference_logprob (and kl) non-null and 4-byte aligned, kl_coef finite and >= 0: MAGE_EINVAL
+ * otherwise, nothing launched.  The kernels are the plain pair's templates (one wave per row, one instance per filter combination) with the
+ * anchor compiled in: the plain entry points run the instances without it. */
+int mage_policy_loss_anchored(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                              int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature,
+                              int32_t top_k, float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, float* row_loss,
+                              float* logprob, float* entropy, uint32_t* cut, float* kl, float* summary, void* stream);
+int mage_policy_loss_anchored_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                  int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, const uint32_t* cut,
+                                  float temperature, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, const float* grad_out,
+                                  void* dlogits, int32_t dl_dtype, void* stream);
+
+/* Sum of squares of a flat fp32 buffer, and mage_adam with the gradient norm clipped: no site in the reference (it runs bare Adam).  Serve
+ * FlatAdam(max_grad_norm=) (mage_amd/optim.py).
+ * mage_sumsq: out[0] (fp64, device) = sum_i g[i]^2.  Every square is taken in fp64 (exact for fp32 values) and the sum is added in a fixed
+ * order -- one partial per workgroup over its contiguous part of g, then a second stage over the partials: two launches give the same bits,
+ * and the result does not depend on the alignment of g beyond the 4 bytes required (scalar loads only).  n > 0 is arbitrary (no n % 4 rule);
+ * g 4-byte and out 8-byte aligned: MAGE_EINVAL otherwise, nothing launched.  The partials pass through one per-device buffer of the
+ * library: calls of mage_sumsq on one device must be ordered (one stream, or events).
+ * mage_adam_clipped: mage_adam's arguments and update, with the gradient scaled by torch.nn.utils.clip_grad_norm_'s rule.  sumsq (device,
+ * fp64) holds the sum of squares of the whole (summed) gradient -- in a sharded step the all-reduced total of the shards' mage_sumsq.  Every
+ * thread derives the same scale from that one value:
+ *   norm = sqrt(*sumsq) * grad_scale  in fp64 (the norm of the averaged gradient);  coef = max_norm / (norm + 1e-6);
+ *   scale = grad_scale where coef >= 1, (float)(grad_scale * coef) otherwise,
+ * and the update is mage_adam's with `scale` for grad_scale (the same code): a step whose norm is within the limit leaves mage_adam's bits
+ * in p, m and v.  norm_out (device, fp32, may be null) receives (float)norm from one thread.  Nothing is read on the host.  A norm that is
+ * not finite propagates (NaN: the scale is NaN; +inf: the scale is 0 and 0 * inf = NaN where the gradient is infinite), as
+ * clip_grad_norm_(error_if_nonfinite=False) does; there is no skip-step guard.  max_norm finite and > 0, sumsq non-null and 8-byte aligned,
+ * otherwise mage_adam's rules: MAGE_EINVAL otherwise, nothing launched. */
+int mage_sumsq(const float* g, int64_t n, double* out, void* stream);
+int mage_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int32_t step,
+                      float grad_scale, const double* sumsq, float max_norm, float* norm_out, void* stream);
+
 /* Per-frame MSE, PSNR and SSIM between generated frames and their targets: no site in the reference (it reports no metric).  Serves
  * MAGE.video_metrics and the built-in rewards of MAGE.rollout (mage_amd/modules/mage_model.py).
  * video and target are fp32 [clips, T, C, H, W] with a frame's C*H*W values contiguous, frames of a clip T*C*H*W apart and clip r of video

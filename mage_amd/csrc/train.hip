@@ -678,11 +678,11 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, Y
 // ------------------------------------------------------------------------------------------------ Adam
 // torch.optim.Adam semantics (main_mage.py:121: betas (0.9, 0.98), eps 1e-6, no weight decay, no amsgrad):
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
-                                                   float bc1, float bc2_sqrt, float grad_scale) {
-    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
+// the four (or fewer, at the arena's tail) elements from index i on: the one statement of the update, shared by adam_kernel and
+// adam_clipped_kernel so that equal grad_scale values give equal bits
+__device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            long n, long i, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                            float grad_scale) {
     if (i + 4 <= n) {
         f32x4 pp = *(f32x4*)(p + i), gg = *(const f32x4*)(g + i), mm = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
 #pragma unroll
@@ -703,6 +703,73 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             p[j] -= (lr / bc1) * (m[j] / (sqrtf(v[j]) / bc2_sqrt + eps));
         }
     }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                                   float bc1, float bc2_sqrt, float grad_scale) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    adam_update(p, g, m, v, n, i, lr, b1, b2, eps, bc1, bc2_sqrt, grad_scale);
+}
+
+// mage_adam_clipped (include/mage_hip_ext.h): every thread derives the one scale from the one device value *sumsq -- the
+// clip_grad_norm_ rule on the averaged gradient -- and where the norm is within the limit the scale IS grad_scale, so the update is
+// adam_kernel's bit for bit.  A NaN norm fails the >= test and becomes the scale: it reaches every parameter, as clip_grad_norm_'s does.
+__global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                                           float bc1, float bc2_sqrt, float grad_scale, const double* __restrict__ sumsq,
+                                                           float max_norm, float* __restrict__ norm_out) {
+    const double norm = sqrt(sumsq[0]) * (double)grad_scale;
+    const double coef = (double)max_norm / (norm + 1e-6);
+    const float scale = coef >= 1.0 ? grad_scale : (float)((double)grad_scale * coef);
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = (float)norm;
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    adam_update(p, g, m, v, n, i, lr, b1, b2, eps, bc1, bc2_sqrt, scale);
+}
+
+// mage_sumsq, stage 1 of 2: workgroup b owns elements [b * chunk, (b + 1) * chunk) and leaves their sum of squares in g_sumsq_part[b].
+// Scalar loads only, indexed from g: nothing depends on the pointer's alignment.  A thread squares in fp64 (exact for fp32 values) and adds
+// its elements r0 + t, r0 + t + 256, ... into four accumulators in turn (they meet as ((a0 + a1) + a2) + a3), the lanes meet in an xor
+// butterfly, thread 0 adds the four waves in order: a fixed order.
+enum { SUMSQ_PARTS = 2048 };
+__device__ double g_sumsq_part[SUMSQ_PARTS];            // stage 1 -> stage 2, within one mage_sumsq call (stream order)
+__global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict__ g, long n, long chunk) {
+    __shared__ double red[4];
+    const long r0 = (long)blockIdx.x * chunk, r1 = r0 + chunk < n ? r0 + chunk : n;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    long i = r0 + threadIdx.x;
+    for (; i + 768 < r1; i += 1024) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double x = (double)g[i + e * 256];
+            a[e] += x * x;
+        }
+    }
+    for (int e = 0; i < r1; i += 256, ++e) {
+        const double x = (double)g[i];
+        a[e] += x * x;
+    }
+    double t = ((a[0] + a[1]) + a[2]) + a[3];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) g_sumsq_part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// stage 2: thread t adds partials t * 8 .. t * 8 + 7 in order; the same butterfly and wave order
+__global__ __launch_bounds__(256) void sumsq_final_kernel(double* __restrict__ out) {
+    __shared__ double red[4];
+    double t = 0.0;
+#pragma unroll
+    for (int e = 0; e < SUMSQ_PARTS / 256; ++e) t += g_sumsq_part[threadIdx.x * (SUMSQ_PARTS / 256) + e];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 
@@ -1395,6 +1462,31 @@ extern "C" int mage_adam(float* p, const float* g, float* m, float* v, int64_t n
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1,
                        beta2, eps, bc1, bc2_sqrt, grad_scale);
     MAGE_CHECK_LAUNCH("mage_adam");
+    return MAGE_OK;
+}
+
+extern "C" int mage_sumsq(const float* g, int64_t n, double* out, void* stream) {
+    MAGE_CHECK_ARG(g && out && n > 0, "mage_sumsq: null pointer or n=%ld <= 0", (long)n);
+    MAGE_CHECK_ARG((((uintptr_t)g) & 3) == 0 && (((uintptr_t)out) & 7) == 0, "mage_sumsq: g must be 4-byte and out 8-byte aligned");
+    hipLaunchKernelGGL(sumsq_part_kernel, dim3(SUMSQ_PARTS), dim3(256), 0, (hipStream_t)stream, g, (long)n,
+                       (long)((n + SUMSQ_PARTS - 1) / SUMSQ_PARTS));
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, out);
+    MAGE_CHECK_LAUNCH("mage_sumsq");
+    return MAGE_OK;
+}
+
+extern "C" int mage_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                 int32_t step, float grad_scale, const double* sumsq, float max_norm, float* norm_out, void* stream) {
+    MAGE_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "mage_adam_clipped: bad arguments");
+    MAGE_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "mage_adam_clipped: arenas must be 16-byte aligned");
+    MAGE_CHECK_ARG(sumsq && (((uintptr_t)sumsq) & 7) == 0 && (((uintptr_t)norm_out) & 3) == 0,
+                   "mage_adam_clipped: sumsq must be an 8-byte aligned pointer, norm_out null or 4-byte aligned");
+    MAGE_CHECK_ARG(__builtin_isfinite(max_norm) && max_norm > 0.f, "mage_adam_clipped: max_norm=%g must be finite and > 0", (double)max_norm);
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adam_clipped_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
+                       beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, sumsq, max_norm, norm_out);
+    MAGE_CHECK_LAUNCH("mage_adam_clipped");
     return MAGE_OK;
 }
 

@@ -867,6 +867,7 @@ class MAGE(nn.Module):
         self.last_token_entropy: Optional[torch.Tensor] = None           # entropy: fp32 [B, L-1, h, w], the full softmax at temperature 1 (nats)
         self.last_token_policy_entropy: Optional[torch.Tensor] = None    # entropy, sampling on: the filtered distribution's
         self.last_policy_token_logprobs: Optional[torch.Tensor] = None   # policy_loss: fp32 [B, L-1, h, w], the given tokens under the current policy
+        self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
         self._last_policy_out = None
 
     # ------------------------------------------------------------------ construction helpers
@@ -1004,7 +1005,8 @@ class MAGE(nn.Module):
             ops.check_device_errors(images.device)
         return scores.view(B)
 
-    def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0):
+    def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0, reference_logprobs=None,
+                    kl_coef: float = 0.0):
         """Policy-gradient loss of given tokens under the policy set_sampling currently describes (sampling off: temperature 1, no filter):
         (loss, info) of one teacher-forced pass over frame 0 of batch['images'] (plus batch['text'] and the optional batch['speed'], as
         autoregressive_generate reads them) followed by `tokens` (int64 [B, L-1, h, w], e.g. last_tokens), ending in mage_policy_loss
@@ -1017,6 +1019,12 @@ class MAGE(nn.Module):
         backward kernels, as forward's does: loss.backward(); optimizer.step() works.  Under torch.no_grad(): values only.
         info = {'loss', 'entropy', 'approx_kl' (mean of behaviour - logprob), 'clip_fraction', 'outside_fraction'} as floats;
         last_policy_token_logprobs keeps the per-token log-probabilities (fp32 [B, L-1, h, w]).
+        reference_logprobs fp32 [B, L-1, h, w] (the same tokens under a frozen reference policy: token_policy_logprobs of a copy of the
+        model taken before fine-tuning, or rollout(reference=)'s 'reference_logprobs') with kl_coef >= 0: every token's loss gains kl_coef
+        times the k3 estimate exp(d) - d - 1, d = reference - logprob, of its KL against the reference (mage_policy_loss_anchored); a token
+        whose reference value is not finite (the reference's filter could not draw it) is unanchored: no penalty.  info gains 'kl' (the
+        mean estimate) and 'unanchored_fraction', last_policy_token_kl keeps the per-token values.  Without a reference the call is the
+        plain one in every bit, and last_policy_token_kl is None.
         Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
         from . import mage_train
         L, R, K = self.frames_length, self.image_resolution, self.codebook_size
@@ -1051,27 +1059,56 @@ class MAGE(nn.Module):
             raise ValueError(f"policy_loss: clip lo={lo} must lie in [0, 1] and hi={hi} must be >= 0")
         if not math.isfinite(float(entropy_coef)):
             raise ValueError(f"policy_loss: entropy_coef must be finite, got {entropy_coef}")
+        ref = reference_logprobs
+        if ref is not None and not (torch.is_tensor(ref) and ref.dtype == F32 and tuple(ref.shape) == tshape):
+            raise ValueError(f"policy_loss: reference_logprobs must be fp32 {list(tshape)} or None")
+        if isinstance(kl_coef, bool) or not isinstance(kl_coef, (int, float)) or not (math.isfinite(kl_coef) and 0 <= kl_coef < 3.4e38):
+            raise ValueError(f"policy_loss: kl_coef must be finite and >= 0, got {kl_coef!r}")
+        if kl_coef > 0 and ref is None:
+            raise ValueError("policy_loss: kl_coef > 0 needs reference_logprobs (the penalty is against a reference policy)")
         for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("advantages", advantages),
-                        ("behaviour_logprobs", b)):
+                        ("behaviour_logprobs", b), ("reference_logprobs", ref)):
             if x is not None and not (x.is_cuda and x.device == images.device):
                 raise ValueError(f"policy_loss: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
         policy = dict(tokens=tokens.contiguous(), advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo,
                       clip_hi=hi, entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
+        if ref is not None:
+            policy.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
         with torch.cuda.device(images.device):
             if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
                 names = mage_train.trainable_names(self)
                 byname = dict(self.named_parameters())
                 loss = mage_train.MagePolicyLossFn.apply(self, batch, policy, names, *[byname[n] for n in names])
-                info, lp = self._last_policy_out
+                info, lp, kl = self._last_policy_out
                 self._last_policy_out = None
             else:
                 with torch.no_grad():
                     loss, tape = mage_train.train_forward(self, batch, policy)
-                info, lp = tape["parts"], tape["policy"]["logprob"]
+                info, lp, kl = tape["parts"], tape["policy"]["logprob"], tape["policy"]["kl"]
                 loss, tape = loss.clone(), None
             self.last_policy_token_logprobs = lp.view(tshape)
+            self.last_policy_token_kl = None if kl is None else kl.view(tshape)
             ops.check_device_errors(images.device)
         return loss, info
+
+    @torch.no_grad()
+    def token_policy_logprobs(self, batch, tokens) -> torch.Tensor:
+        """fp32 [B, L-1, h, w]: the log-probabilities of given tokens (int64 [B, L-1, h, w]) under the policy set_sampling currently
+        describes, by the teacher-forced pass policy_loss runs -- bit for bit last_policy_token_logprobs of a no-grad policy_loss on the
+        same inputs (-inf where the filter could not draw the token).  How a frozen copy of the model gives policy_loss its
+        reference_logprobs.  Values only; every last_* result is left as found."""
+        images = batch["images"] if isinstance(batch, dict) else None
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
+            raise ValueError("token_policy_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
+        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
+        try:
+            self.policy_loss(batch, tokens, torch.zeros(images.shape[0], device=images.device, dtype=F32))
+            return self.last_policy_token_logprobs
+        finally:
+            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
+                delattr(self, a)
+            for a, v in keep.items():
+                setattr(self, a, v)
 
     @torch.no_grad()
     def video_metrics(self, video, target, data_range: float = 2.0) -> dict:
@@ -1104,7 +1141,7 @@ class MAGE(nn.Module):
     _ROLLOUT_REWARDS = ("ssim", "psnr", "neg_mse")
 
     @torch.no_grad()
-    def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6) -> dict:
+    def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None) -> dict:
         """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
         under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
         rewarded on the device, and the rewards turned into group-relative advantages:
@@ -1120,6 +1157,9 @@ class MAGE(nn.Module):
         fp32 [B, N], 'advantages' fp32 [B*N], 'frame_metrics' {'mse', 'psnr', 'ssim'} fp32 [B*N, L-1] each (None for a callable reward),
         'seeds' int64 [B*N], 'batch': the input with every per-clip tensor repeated N times along dim 0, 'images' cut to frame 0 (all
         policy_loss reads)}; row b*N + c is candidate c of clip b throughout.
+        reference (another MAGE of the same configuration on the same GPU, e.g. a frozen copy taken before fine-tuning): the result gains
+        'reference_logprobs' = reference.token_policy_logprobs(out['batch'], out['tokens']) under THIS model's sampling settings (set on the
+        reference for the call; its own settings and last_* results are restored) -- policy_loss' reference_logprobs.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
         if not self.use_cids:
@@ -1145,6 +1185,14 @@ class MAGE(nn.Module):
         for name, x in batch.items():
             if torch.is_tensor(x) and name != "sample_seed" and not (x.is_cuda and x.device == images.device):
                 raise ValueError(f"rollout: batch['{name}'] must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        if reference is not None:
+            if not (isinstance(reference, MAGE) and reference.use_cids):
+                raise ValueError("rollout: reference must be a use_cids=True MAGE model (it scores tokens)")
+            for a in ("codebook_size", "frames_length", "image_resolution"):
+                if getattr(reference, a) != getattr(self, a):
+                    raise ValueError(f"rollout: the reference model's {a}={getattr(reference, a)} differs from this model's {getattr(self, a)}")
+            if next(reference.parameters()).device != images.device:
+                raise ValueError("rollout: the reference model must be on the same GPU as the batch")
         Bc = images.shape[0]
         keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
         settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
@@ -1171,6 +1219,13 @@ class MAGE(nn.Module):
                     fr = fr.contiguous()
                 out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
                 out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
+                if reference is not None:
+                    theirs = (getattr(reference, "sampling", None), reference.candidates)
+                    try:
+                        reference.sampling, reference.candidates = self.sampling, 1
+                        out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"])
+                    finally:
+                        reference.sampling, reference.candidates = theirs
                 ops.check_device_errors(images.device)
         finally:
             self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings

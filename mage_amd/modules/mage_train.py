@@ -577,7 +577,10 @@ def _text_backward(te, run32: _Run, tape, dout, grads, pre: str = "text_encoder"
 # ----------------------------------------------------------------------------------------------------------------- whole model
 def _policy_scalars(policy: dict) -> dict:
     """The scalar arguments mage_policy_loss and mage_policy_loss_bwd share."""
-    return {k: policy[k] for k in ("temperature", "clip_lo", "clip_hi", "entropy_coef")}
+    kw = {k: policy[k] for k in ("temperature", "clip_lo", "clip_hi", "entropy_coef")}
+    if policy.get("reference") is not None:              # the anchored entry points; without a reference the plain ones, called as before
+        kw.update(reference_logprob=policy["reference"], kl_coef=policy["kl_coef"])
+    return kw
 
 
 def train_forward(model, batch, policy: Optional[dict] = None):
@@ -586,7 +589,8 @@ def train_forward(model, batch, policy: Optional[dict] = None):
     policy (MAGE.policy_loss; use_cids models without the randomness branch): the pass runs over GIVEN tokens and ends in the policy-gradient
     loss instead of the cross-entropy -- frame 0 is still first_stage_encode(images[:, 0:1]), frames 1 .. L-1 are policy['tokens']
     (int64 [B, L-1, h, w]); policy['advantage'] (fp32, one per clip or per token), policy['behaviour'] (fp32 per token, or None) and the
-    scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h)."""
+    scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h); with
+    policy['reference'] (fp32 per token) and policy['kl_coef'] the pass ends in mage_policy_loss_anchored instead."""
     images = batch["images"]
     B = images.shape[0]
     R, L, Cc = model.image_resolution, model.frames_length, model.vision_width
@@ -656,7 +660,7 @@ def train_forward(model, batch, policy: Optional[dict] = None):
         res = ops.policy_loss(logits, target, policy["advantage"], policy["behaviour"], **_policy_scalars(policy), top_k=policy["top_k"],
                               top_p=policy["top_p"])
         recon = res["summary"][0]
-        policy = dict(policy, cut=res["cut"], logprob=res["logprob"], summary=res["summary"])
+        policy = dict(policy, cut=res["cut"], logprob=res["logprob"], summary=res["summary"], kl=res.get("kl"))
     elif model.use_cids:
         target = tok[:, 1:L].reshape(-1).contiguous()
         recon = ops.cross_entropy(logits, target)                                                            # :618
@@ -665,7 +669,8 @@ def train_forward(model, batch, policy: Optional[dict] = None):
         recon = ops.mse(logits, target, rows=B * (L - 1) * hw, cols=model.first_stage_model.embed_dim, lda=logits.shape[1], ldb=8)   # :620
         model.last_logits = logits
     if policy is not None:
-        parts = dict(zip(("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction"), policy["summary"].tolist()))
+        parts = dict(zip(("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction"),
+                         policy["summary"].tolist()))
         tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
                     logits=logits, target=target, speed=speed, B=B, rand=None, beta=0.0, alpha=0.0, parts=parts, policy=policy)
         return recon, tape
@@ -786,7 +791,8 @@ class MagePolicyLossFn(torch.autograd.Function):
     def forward(ctx, model, batch, policy, names, *params):
         with torch.no_grad():
             loss, tape = train_forward(model, batch, policy)
-        model._last_policy_out = (tape["parts"], tape["policy"]["logprob"])  # for MAGE.policy_loss: the summary and the per-token log-probabilities
+        # for MAGE.policy_loss: the summary, the per-token log-probabilities and (with a reference) KL estimates
+        model._last_policy_out = (tape["parts"], tape["policy"]["logprob"], tape["policy"]["kl"])
         ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
         ctx.devices = [p.device for p in params]
         return loss.clone()

@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT_RELU, ACT_TANH, BF16, BF16X3, F16, F16X3, F32, AttnDesc, GemmDesc
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
-           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
+           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
            "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
@@ -592,38 +592,69 @@ def _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div):
     return rows, K, logits.stride(0), adv_div
 
 
+def _policy_ref(reference_logprob, kl_coef, logits):
+    """The reference log-probabilities of the anchored pair: None (and then no kl_coef), or fp32 [rows] beside the logits."""
+    if reference_logprob is None:
+        if kl_coef != 0:
+            raise ValueError("policy_loss: kl_coef needs reference_logprob (the penalty is against a reference policy)")
+        return
+    assert reference_logprob.dtype == torch.float32 and reference_logprob.is_contiguous() and reference_logprob.numel() == logits.shape[0]
+    assert reference_logprob.device == logits.device
+
+
 def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor] = None, *,
                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, clip_lo: float = 0.2, clip_hi: float = 0.2,
-                entropy_coef: float = 0.0, adv_div: Optional[int] = None) -> dict:
+                entropy_coef: float = 0.0, adv_div: Optional[int] = None, reference_logprob: Optional[torch.Tensor] = None,
+                kl_coef: float = 0.0) -> dict:
     """mage_policy_loss over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows]; advantage fp32, row i using entry i // adv_div
     (default: rows / numel consecutive rows per entry); behaviour_logprob fp32 [rows] selects the clipped surrogate, None the reward-weighted likelihood.  Returns the per-row
     fp32 tensors 'row_loss', 'logprob', 'entropy', the uint32 thresholds 'cut' (kept as int32 storage: policy_loss_bwd's input) and
-    'summary' fp32 [5]: the means of the loss, the entropy, b - logprob, the clipped share and the outside share."""
+    'summary' fp32 [5]: the means of the loss, the entropy, b - logprob, the clipped share and the outside share.
+    reference_logprob fp32 [rows] (with kl_coef >= 0): mage_policy_loss_anchored -- the loss gains kl_coef times the k3 estimate of the KL
+    against the reference policy, the result the per-row 'kl', and 'summary' is fp32 [7]: the five, the mean KL and the unanchored share."""
+    _policy_ref(reference_logprob, kl_coef, logits)
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     mk = lambda n, dt: torch.empty(n, device=logits.device, dtype=dt)      # noqa: E731
     out = dict(row_loss=mk(rows, torch.float32), logprob=mk(rows, torch.float32), entropy=mk(rows, torch.float32), cut=mk(rows, torch.int32),
-               summary=mk(5, torch.float32))
-    _lib.check(l.mage_policy_loss(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
-                                  float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef),
-                                  out["row_loss"].data_ptr(), out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(),
-                                  out["summary"].data_ptr(), s), l)
+               summary=mk(5 if reference_logprob is None else 7, torch.float32))
+    if reference_logprob is None:
+        _lib.check(l.mage_policy_loss(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
+                                      float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef),
+                                      out["row_loss"].data_ptr(), out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(),
+                                      out["summary"].data_ptr(), s), l)
+        return out
+    out["kl"] = mk(rows, torch.float32)
+    _lib.check(l.mage_policy_loss_anchored(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                           _p(behaviour_logprob), reference_logprob.data_ptr(), float(temperature), int(top_k), float(top_p),
+                                           float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
+                                           out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), out["kl"].data_ptr(),
+                                           out["summary"].data_ptr(), s), l)
     return out
 
 
 def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor],
                     cut: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *, temperature: float = 1.0, clip_lo: float = 0.2,
-                    clip_hi: float = 0.2, entropy_coef: float = 0.0, adv_div: Optional[int] = None) -> torch.Tensor:
-    """mage_policy_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16 from policy_loss' inputs and its 'cut'; grad_out fp32 [1]."""
+                    clip_hi: float = 0.2, entropy_coef: float = 0.0, adv_div: Optional[int] = None,
+                    reference_logprob: Optional[torch.Tensor] = None, kl_coef: float = 0.0) -> torch.Tensor:
+    """mage_policy_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16 from policy_loss' inputs and its 'cut'; grad_out fp32 [1].  With
+    reference_logprob: mage_policy_loss_anchored_bwd."""
+    _policy_ref(reference_logprob, kl_coef, logits)
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.numel() == rows and cut.device == logits.device
     assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
     assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
     assert dlogits.device == logits.device
-    _lib.check(l.mage_policy_loss_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
-                                      cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef),
-                                      grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
+    if reference_logprob is None:
+        _lib.check(l.mage_policy_loss_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
+                                          cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef),
+                                          grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
+        return dlogits
+    _lib.check(l.mage_policy_loss_anchored_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                               _p(behaviour_logprob), reference_logprob.data_ptr(), cut.data_ptr(), float(temperature),
+                                               float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(),
+                                               dlogits.data_ptr(), code(dlogits), s), l)
     return dlogits
 
 
@@ -1118,6 +1149,29 @@ def adam(p, g, m, v, *, lr: float, beta1: float, beta2: float, eps: float, step:
         assert t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == p.numel()
     _lib.check(l.mage_adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1), float(beta2),
                            float(eps), int(step), float(grad_scale), s), l)
+    return p
+
+
+def sumsq(g: torch.Tensor) -> torch.Tensor:
+    """fp64 [1]: the sum of the squares of a flat fp32 tensor, exact squares added in a fixed order (mage_sumsq)."""
+    l, s = _dev(g)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() > 0
+    out = torch.empty(1, device=g.device, dtype=torch.float64)
+    _lib.check(l.mage_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), s), l)
+    return out
+
+
+def adam_clipped(p, g, m, v, *, lr: float, beta1: float, beta2: float, eps: float, step: int, grad_scale: float = 1.0, sumsq: torch.Tensor,
+                 max_norm: float, norm_out: Optional[torch.Tensor] = None):
+    """adam with the gradient scaled by clip_grad_norm_'s rule from the device value sumsq (fp64 [1]: the whole gradient's sum of squares);
+    norm_out (fp32 [1], optional) receives the norm of the averaged gradient before the clip (mage_adam_clipped)."""
+    l, s = _dev(p)
+    for t_ in (p, g, m, v):
+        assert t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == p.numel()
+    assert sumsq.dtype == torch.float64 and sumsq.numel() == 1 and sumsq.device == p.device
+    assert norm_out is None or (norm_out.dtype == torch.float32 and norm_out.numel() == 1 and norm_out.device == p.device)
+    _lib.check(l.mage_adam_clipped(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1), float(beta2),
+                                   float(eps), int(step), float(grad_scale), sumsq.data_ptr(), float(max_norm), _p(norm_out), s), l)
     return p
 
 

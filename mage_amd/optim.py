@@ -31,7 +31,7 @@ __all__ = ["FlatAdam"]
 
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.98), eps: float = 1e-6,
-                 process_group: Optional[dist.ProcessGroup] = None, shard: Optional[bool] = None):
+                 process_group: Optional[dist.ProcessGroup] = None, shard: Optional[bool] = None, max_grad_norm: Optional[float] = None):
         # The reference hands EVERY parameter to optim.Adam (main_mage.py:121: model.parameters(), the frozen first stage included -- its
         # parameters follow MAGE's three top-level nn.Parameters), so the indices of its checkpoint's 'state' and 'param_groups' count the
         # frozen ones too.  Keep that numbering: `all_params` is the caller's order, `index[i]` the position of trainable parameter i in it.
@@ -41,7 +41,10 @@ class FlatAdam(torch.optim.Optimizer):
         plist = [p for p in all_params if p.requires_grad]
         if not plist:
             raise ValueError("FlatAdam: no trainable parameters")
-        super().__init__(all_params, dict(lr=lr, betas=tuple(betas), eps=eps))
+        # max_grad_norm: clip the norm of the averaged gradient inside the step (torch.nn.utils.clip_grad_norm_'s rule, on the device);
+        # it lives in param_groups[0] beside lr, so a schedule can change it.  None: no clipping, the plain mage_adam step.
+        self._check_max_grad_norm(max_grad_norm)
+        super().__init__(all_params, dict(lr=lr, betas=tuple(betas), eps=eps, max_grad_norm=max_grad_norm))
         self.all_params = all_params
         self.index = [i for i, p in enumerate(all_params) if p.requires_grad]
         self.pg = process_group
@@ -75,6 +78,8 @@ class FlatAdam(torch.optim.Optimizer):
         self.v = torch.zeros(self.shard_n, device=dev, dtype=torch.float32)
         self.shard_g = torch.empty(self.shard_n, device=dev, dtype=torch.float32) if self.sharded else None
         self.steps = 0
+        # fp32 [1] on the device after every clipped step: the norm of the averaged gradient before the clip; never read on the host here
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self._consolidated = None                                # (steps, exp_avg, exp_avg_sq) gathered by consolidate_state_dict
         if self.world > 1:
             # DistributedDataParallel broadcasts rank 0's parameters when it wraps a model (main_mage.py:95); a bare model + FlatAdam
@@ -122,23 +127,54 @@ class FlatAdam(torch.optim.Optimizer):
             raise RuntimeError("FlatAdam runs on libmage_hip.so (mage_adam): the parameters must live on a ROCm GPU")
         ops.adam(p, g, m, v, lr=lr, beta1=b1, beta2=b2, eps=eps, step=step, grad_scale=grad_scale)
 
+    @staticmethod
+    def _check_max_grad_norm(c):
+        if c is not None and not (isinstance(c, (int, float)) and not isinstance(c, bool) and 0 < c < 3.4e38):
+            raise ValueError(f"FlatAdam: max_grad_norm must be None or a finite number > 0, got {c!r}")
+
+    def _sumsq(self, g):
+        """fp64 [1] on g's device: the sum of squares of a flat gradient (libmage_hip.so mage_sumsq).  No CPU path."""
+        if not g.is_cuda:
+            raise RuntimeError("FlatAdam runs on libmage_hip.so (mage_sumsq): the parameters must live on a ROCm GPU")
+        return ops.sumsq(g)
+
+    def _adam_clipped(self, p, g, m, v, lr, b1, b2, eps, step, grad_scale, sumsq, max_norm, norm_out):
+        """_adam with the gradient scaled by clip_grad_norm_'s rule from the device value sumsq (libmage_hip.so mage_adam_clipped)."""
+        if not p.is_cuda:
+            raise RuntimeError("FlatAdam runs on libmage_hip.so (mage_adam_clipped): the parameters must live on a ROCm GPU")
+        ops.adam_clipped(p, g, m, v, lr=lr, beta1=b1, beta2=b2, eps=eps, step=step, grad_scale=grad_scale, sumsq=sumsq, max_norm=max_norm,
+                         norm_out=norm_out)
+
+    def _update(self, p, g, m, v, all_reduce_sumsq: bool):
+        """The Adam launch over one flat shard: plain, or -- with param_groups[0]['max_grad_norm'] -- the shard's sum of squares (summed over
+        the ranks where each holds a different shard), then the clipped launch.  Everything stays on the device."""
+        g0 = self.param_groups[0]
+        lr, (b1, b2), eps, c = g0["lr"], g0["betas"], g0["eps"], g0.get("max_grad_norm")
+        if c is None:
+            return self._adam(p, g, m, v, lr, b1, b2, eps, self.steps, 1.0 / self.world)
+        self._check_max_grad_norm(c)
+        ss = self._sumsq(g)
+        if all_reduce_sumsq:
+            dist.all_reduce(ss, op=dist.ReduceOp.SUM, group=self.pg)
+        if self.last_grad_norm is None:
+            self.last_grad_norm = torch.zeros(1, device=p.device, dtype=torch.float32)
+        self._adam_clipped(p, g, m, v, lr, b1, b2, eps, self.steps, 1.0 / self.world, ss, float(c), self.last_grad_norm)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._collect_grads()
         self.steps += 1
-        g0 = self.param_groups[0]
-        lr, (b1, b2), eps = g0["lr"], g0["betas"], g0["eps"]
         if self.sharded:
             # gradient: summed over ranks, each rank keeps its shard (the mean's 1/W is folded into the Adam kernel)
             dist.reduce_scatter_tensor(self.shard_g, self.flat_g, op=dist.ReduceOp.SUM, group=self.pg)
             p_shard = self.flat_p[self.shard_off:self.shard_off + self.shard_n]
-            self._adam(p_shard, self.shard_g, self.m, self.v, lr, b1, b2, eps, self.steps, 1.0 / self.world)
+            self._update(p_shard, self.shard_g, self.m, self.v, all_reduce_sumsq=True)
             dist.all_gather_into_tensor(self.flat_p, p_shard.clone(), group=self.pg)
         else:
             if self.world > 1:                                   # replicated state: plain all-reduce of the arena
                 dist.all_reduce(self.flat_g, op=dist.ReduceOp.SUM, group=self.pg)
-            self._adam(self.flat_p, self.flat_g, self.m, self.v, lr, b1, b2, eps, self.steps, 1.0 / self.world)
+            self._update(self.flat_p, self.flat_g, self.m, self.v, all_reduce_sumsq=False)   # (the arena is the whole summed gradient already)
         _vq.bump_weights_epoch()                                 # the kernels' derived weight copies are stale now
         return loss
 
@@ -238,3 +274,4 @@ class FlatAdam(torch.optim.Optimizer):
         self.v.copy_(v[self.shard_off:self.shard_off + self.shard_n])
         for g, sg in zip(self.param_groups, groups):
             g.update({k: v_ for k, v_ in sg.items() if k not in ("params", "flat_adam_numbering")})
+            g["max_grad_norm"] = sg.get("max_grad_norm")         # a checkpoint without the key (torch.optim.Adam's, an older one): no clipping
