@@ -178,6 +178,32 @@ int mage_video_metrics(const float* video, int64_t video_clip_stride, const floa
 int mage_group_advantages(const float* frame_reward, int64_t groups, int32_t N, int32_t T, int32_t mode, float eps, float* reward,
                           float* advantage, void* stream);
 
+/* Seeded standard-normal noise of the randomness branch: the reference draws it with torch.randn (mage_model.py:661), unseeded and kept
+ * nowhere.  Serves batch['noise_seed'] of MAGE.autoregressive_generate and MAGE.rollout(noise='candidate') (mage_amd/modules/mage_model.py:
+ * _anchor_tail), whose recorded noise MAGE.policy_loss then conditions on.
+ * seeds is int64 [B] on the device; clip b gets C * hw values.  Two optional fp32 outputs, at least one given: nchw [B, C, hw] (the public
+ * video_noise layout, [B, C, h, w]) and rows [B * hw, C] (channel-last: what conv_d2's convolution reads).  The rule, for clip b, channel c,
+ * pixel p, in uint64 wrap-around arithmetic on hash32 (mage_amd/csrc/common.h):
+ *   e    = c * hw + p;   base = ((uint64)seeds[b] ^ 0x8000000000000000) * 0x9e3779b97f4a7c15;
+ *   m1   = hash32(base + 2e) >> 8 (24 bits),  u1 = (m1 + 0.5) 2^-24;      m2 = hash32(base + 2e + 1) >> 9 (23 bits);
+ *   z    = sqrt(-2 log(u1)) * cos(pi * (m2 + 0.5) 2^-22)                  (Box-Muller, one normal per element).
+ * log(u1) is taken as mage_sample_tokens takes its Gumbel logarithm -- logf of u1 below 1/2, log1pf of -(1 - u1) above, either argument
+ * exact in fp32 -- so u1 is never rounded; the angle (m2 + 0.5) 2^-22 in (0, 2) has 24 significant bits, is exact, and goes through cospif.
+ * z is finite by construction: u1 >= 2^-25 gives |z| <= sqrt(2 log 2^25) < 5.89, and the cosine is never exactly 0.
+ * A value depends on its clip's seed, its channel and its pixel only: not on B, the clip's place in the batch, which outputs are asked for,
+ * or the launch geometry.  Every value is computed once per launch and stored to both layouts: they hold the same bits.
+ * Domain separation from mage_sample_tokens: a rollout gives a candidate ONE seed s for both streams.  The sampler's counters are
+ * s * 0x9e3779b97f4a7c15 + t, t = pos * K + j < 2^63; flipping bit 63 of the seed before the multiply moves the base by exactly
+ * 2^63 * 0x9e3779b97f4a7c15 = 2^63 (mod 2^64: the multiplier is odd), so the noise counters are s * 0x9e3779b97f4a7c15 + 2^63 + t',
+ * t' < 2^31 -- the two sets are disjoint for every seed as long as the sampler's stream is shorter than 2^63, which its own argument rules
+ * guarantee.  (Under any affine scheme the noise of seed s is the sampler's stream of SOME other seed; here that seed is s ^ 2^63, never a
+ * neighbour s + c of a rollout.)
+ * B, C, hw > 0, at least one output, outputs 16-byte and seeds 8-byte aligned, C * hw <= 2^30 (the counters 2e + 1 stay below 2^31) and
+ * B * C * hw <= 2^38: MAGE_EINVAL otherwise, nothing launched.  hw and C need not be multiples of 4: a lane owns a tile of 4 channels x 4
+ * pixels and falls back from 16-byte to 4-byte stores where a quad crosses the end of its axis or is not 16-byte aligned.  No LDS, no
+ * atomics, plain vector-memory stores. */
+int mage_video_noise(const int64_t* seeds, int64_t B, int32_t C, int64_t hw, float* nchw, float* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,12 +281,13 @@ __device__ __forceinline__ unsigned sample_key(float s) {       // order-preserv
 __device__ __forceinline__ float sample_key_value(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-// g = -log(-log(u)) with u = (m + 0.5) 2^-24 never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
+// -log(u) of the 24-bit uniform u = (m + 0.5) 2^-24, never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
+__device__ __forceinline__ float sample_neglog_u(unsigned m) {
+    return m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f) : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
+}
+// g = -log(-log(u))
 __device__ __forceinline__ float sample_gumbel(unsigned long long ctr) {
-    const unsigned m = hash32(ctr) >> 8;
-    const float e = m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f)
-                                   : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
-    return -logf(e);
+    return -logf(sample_neglog_u(hash32(ctr) >> 8));
 }
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #pragma unroll
@@ -1223,6 +1224,91 @@ extern "C" int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, 
     else if (K <= 2048) sample_launch<32>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
     else sample_launch<64>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
     MAGE_CHECK_LAUNCH("mage_sample_tokens");
+    return MAGE_OK;
+}
+
+// ---- seeded standard-normal noise of the randomness branch (mage_video_noise; include/mage_hip_ext.h states the rule).  Element
+// e = channel * hw + pixel of a clip with seed s takes the two counters base + 2e and base + 2e + 1, base = (s ^ 2^63) * 0x9e3779b97f4a7c15
+// (uint64 wrap-around): the sampler's counters of the same seed start at s * 0x9e3779b97f4a7c15, exactly 2^63 away (the constant is odd), so
+// the two streams of one seed cannot meet while either is shorter than 2^63.  Box-Muller, one normal per element: the radius from the 24-bit
+// uniform of the first counter through sample_neglog_u (never rounded), the angle from the 23-bit one of the second through cospif of the
+// exactly representable (m2 + 0.5) 2^-22.
+// One lane owns a tile of 4 channels x 4 pixels and computes its 16 values ONCE: four 16-byte stores along the pixels into the NCHW tensor
+// and / or four along the channels into the channel-last rows, so the two layouts hold the same bits by construction.  Lanes run along the
+// channel quads first: the rows output is written in runs of 4 C bytes (whole rows), the NCHW output in runs of 64 bytes per channel.  A
+// quad that crosses the end of its axis, or whose address is not 16-byte aligned (hw or C no multiple of 4), is stored element by element.
+namespace {
+
+constexpr unsigned long long NOISE_SEPARATION = 0x8000000000000000ULL;
+
+__device__ __forceinline__ float video_noise_value(unsigned long long base, unsigned long long e) {
+    const unsigned long long ctr = base + 2ULL * e;
+    const float nl = sample_neglog_u(hash32(ctr) >> 8);                     // -log(u1), in (2^-25, 25 log 2]
+    const unsigned m2 = hash32(ctr + 1ULL) >> 9;
+    return __fmul_rn(sqrtf(2.0f * nl), cospif(((float)m2 + 0.5f) * 0x1p-22f));
+}
+
+__global__ __launch_bounds__(256) void video_noise_kernel(const int64_t* __restrict__ seeds, long tiles, int C, int hw, int CQ, int PQ,
+                                                          float* __restrict__ nchw, float* __restrict__ rows) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= tiles) return;
+    const int c0 = (int)(t % CQ) * 4;
+    const long r = t / CQ;
+    const int p0 = (int)(r % PQ) * 4;
+    const long b = r / PQ;
+    const unsigned long long base = ((unsigned long long)seeds[b] ^ NOISE_SEPARATION) * 0x9e3779b97f4a7c15ULL;
+    float v[4][4];                                                          // [channel][pixel] of the tile
+#pragma unroll
+    for (int ci = 0; ci < 4; ++ci)
+#pragma unroll
+        for (int pi = 0; pi < 4; ++pi)
+            v[ci][pi] = (c0 + ci < C && p0 + pi < hw) ? video_noise_value(base, (unsigned long long)(c0 + ci) * (unsigned)hw + (unsigned)(p0 + pi))
+                                                      : 0.f;
+    if (nchw) {
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            if (c0 + ci >= C) break;
+            const long i = (b * C + c0 + ci) * (long)hw + p0;
+            if (p0 + 3 < hw && (i & 3) == 0) {
+                store4(nchw + i, f32x4{v[ci][0], v[ci][1], v[ci][2], v[ci][3]});
+            } else {
+#pragma unroll
+                for (int pi = 0; pi < 4; ++pi)
+                    if (p0 + pi < hw) nchw[i + pi] = v[ci][pi];
+            }
+        }
+    }
+    if (rows) {
+#pragma unroll
+        for (int pi = 0; pi < 4; ++pi) {
+            if (p0 + pi >= hw) break;
+            const long i = (b * hw + p0 + pi) * (long)C + c0;
+            if (c0 + 3 < C && (i & 3) == 0) {
+                store4(rows + i, f32x4{v[0][pi], v[1][pi], v[2][pi], v[3][pi]});
+            } else {
+#pragma unroll
+                for (int ci = 0; ci < 4; ++ci)
+                    if (c0 + ci < C) rows[i + ci] = v[ci][pi];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int mage_video_noise(const int64_t* seeds, int64_t B, int32_t C, int64_t hw, float* nchw, float* rows, void* stream) {
+    MAGE_CHECK_ARG(seeds && (((uintptr_t)seeds) & 7) == 0, "mage_video_noise: seeds must be a non-null, 8-byte aligned int64 pointer");
+    MAGE_CHECK_ARG(B > 0 && C > 0 && hw > 0, "mage_video_noise: bad sizes B=%ld C=%d hw=%ld (all must be > 0)", (long)B, C, (long)hw);
+    MAGE_CHECK_ARG(nchw || rows, "mage_video_noise: no output (give the NCHW tensor, the channel-last rows, or both)");
+    MAGE_CHECK_ARG((((uintptr_t)nchw) & 15) == 0 && (((uintptr_t)rows) & 15) == 0, "mage_video_noise: outputs must be 16-byte aligned");
+    // a clip's counters are base + 2e + {0, 1} with e < C*hw <= 2^30 (the kernel's 32-bit tile coordinates cannot wrap, the counters stay
+    // below 2^31); the launch is one lane per 4 x 4 tile, at most 2^38 of them
+    MAGE_CHECK_ARG(hw <= (1LL << 30) && (int64_t)C * hw <= (1LL << 30) && B <= (1LL << 38) / ((int64_t)C * hw),
+                   "mage_video_noise: B=%ld C=%d hw=%ld is past the counter range (C*hw <= 2^30, B*C*hw <= 2^38)", (long)B, C, (long)hw);
+    const int CQ = (C + 3) / 4, PQ = (int)((hw + 3) / 4);
+    const long tiles = (long)B * CQ * PQ;
+    video_noise_kernel<<<dim3((unsigned)((tiles + 255) / 256)), 256, 0, (hipStream_t)stream>>>(seeds, tiles, C, (int)hw, CQ, PQ, nchw, rows);
+    MAGE_CHECK_LAUNCH("mage_video_noise");
     return MAGE_OK;
 }
 

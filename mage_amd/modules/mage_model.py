@@ -868,6 +868,7 @@ class MAGE(nn.Module):
         self.last_token_policy_entropy: Optional[torch.Tensor] = None    # entropy, sampling on: the filtered distribution's
         self.last_policy_token_logprobs: Optional[torch.Tensor] = None   # policy_loss: fp32 [B, L-1, h, w], the given tokens under the current policy
         self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
+        self.last_video_noise: Optional[torch.Tensor] = None             # randomness: fp32 [B, 64, h, w], the noise the last generation used
         self._last_policy_out = None
 
     # ------------------------------------------------------------------ construction helpers
@@ -1019,6 +1020,11 @@ class MAGE(nn.Module):
         backward kernels, as forward's does: loss.backward(); optimizer.step() works.  Under torch.no_grad(): values only.
         info = {'loss', 'entropy', 'approx_kl' (mean of behaviour - logprob), 'clip_fraction', 'outside_fraction'} as floats;
         last_policy_token_logprobs keeps the per-token log-probabilities (fp32 [B, L-1, h, w]).
+        randomness=True: the policy is pi(tokens | frame 0, caption, speed, z) with z the generation-time noise, a latent drawn from a fixed
+        N(0, 1) -- context, not a parameter: batch['video_noise'] (fp32 [B, 64, h, w]: last_video_noise of the generation that drew the
+        tokens, or rollout's out['batch']) is required, and the pass modulates the motion anchor with it as generation did (conv_d2, the
+        ADAIN convolutions, ADAIN; no Conv3d video prior, no reparameterisation, no KL of the prior: generation runs none of them, so their
+        parameters get zero gradients).
         reference_logprobs fp32 [B, L-1, h, w] (the same tokens under a frozen reference policy: token_policy_logprobs of a copy of the
         model taken before fine-tuning, or rollout(reference=)'s 'reference_logprobs') with kl_coef >= 0: every token's loss gains kl_coef
         times the k3 estimate exp(d) - d - 1, d = reference - logprob, of its KL against the reference (mage_policy_loss_anchored); a token
@@ -1030,8 +1036,10 @@ class MAGE(nn.Module):
         L, R, K = self.frames_length, self.image_resolution, self.codebook_size
         if not self.use_cids:
             raise ValueError("policy_loss: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
-        if self.randomness:
-            raise ValueError("policy_loss: randomness=True draws generation-time noise that has no backward here; not supported")
+        vn = batch.get("video_noise") if self.randomness else None
+        if self.randomness and vn is None:
+            raise ValueError("policy_loss: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
+                             "the noise the tokens were drawn under (last_video_noise of the generation, or rollout's out['batch'])")
         if self._dt() == torch.float16:
             raise ValueError("policy_loss: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
         t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
@@ -1042,6 +1050,8 @@ class MAGE(nn.Module):
             raise ValueError("policy_loss: batch['images'] must be [B, >= 1, C, H, W]")
         B = images.shape[0]
         tshape = (B, L - 1, R, R)
+        if vn is not None and not (torch.is_tensor(vn) and vn.dtype == F32 and tuple(vn.shape) == (B, 64, R, R)):
+            raise ValueError(f"policy_loss: batch['video_noise'] must be fp32 {[B, 64, R, R]} (randomness=True: the tokens' generation noise)")
         if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
             raise ValueError(f"policy_loss: tokens must be int64 {list(tshape)}")
         if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape)):
@@ -1067,7 +1077,7 @@ class MAGE(nn.Module):
         if kl_coef > 0 and ref is None:
             raise ValueError("policy_loss: kl_coef > 0 needs reference_logprobs (the penalty is against a reference policy)")
         for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("advantages", advantages),
-                        ("behaviour_logprobs", b), ("reference_logprobs", ref)):
+                        ("behaviour_logprobs", b), ("reference_logprobs", ref), ("batch['video_noise']", vn)):
             if x is not None and not (x.is_cuda and x.device == images.device):
                 raise ValueError(f"policy_loss: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
         policy = dict(tokens=tokens.contiguous(), advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo,
@@ -1141,7 +1151,8 @@ class MAGE(nn.Module):
     _ROLLOUT_REWARDS = ("ssim", "psnr", "neg_mse")
 
     @torch.no_grad()
-    def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None) -> dict:
+    def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None,
+                noise: str = "clip") -> dict:
         """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
         under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
         rewarded on the device, and the rewards turned into group-relative advantages:
@@ -1160,8 +1171,24 @@ class MAGE(nn.Module):
         reference (another MAGE of the same configuration on the same GPU, e.g. a frozen copy taken before fine-tuning): the result gains
         'reference_logprobs' = reference.token_policy_logprobs(out['batch'], out['tokens']) under THIS model's sampling settings (set on the
         reference for the call; its own settings and last_* results are restored) -- policy_loss' reference_logprobs.
+        noise (randomness=True models; the generation-time noise z is part of what the policy is conditioned on): 'clip' (the default) --
+        one draw per clip shared by its N candidates, from batch['video_noise'], batch['noise_seed'] or torch.randn as in
+        autoregressive_generate; 'candidate' -- candidate c of clip b draws its own noise with mage_video_noise under the seed that drives
+        its sampler, sample_seed[b] + c (the two streams of one seed are disjoint; the text and MA encoders still run once per clip, the
+        noise convolution, ADAIN and the speed term on the B*N rows), refused together with batch['video_noise'] and on a model without
+        the branch.  Either way the result carries 'video_noise' fp32 [B*N, 64, h, w], also as out['batch']['video_noise']: the
+        policy_loss call above -- and the reference's scoring -- condition on the noise the tokens were drawn under.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
+        if noise not in ("clip", "candidate"):
+            raise ValueError(f"rollout: noise must be 'clip' or 'candidate', got {noise!r}")
+        if noise == "candidate":
+            if not self.randomness:
+                raise ValueError("rollout: noise='candidate' needs the randomness branch; this model has none (randomness=False): there is "
+                                 "no generation-time noise to draw per candidate")
+            if batch.get("video_noise") is not None:
+                raise ValueError("rollout: noise='candidate' draws every candidate's noise from its seed; batch['video_noise'] holds one "
+                                 "tensor per clip and cannot describe N candidates -- drop it, or use noise='clip'")
         if not self.use_cids:
             raise ValueError("rollout: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
         if getattr(self, "sampling", None) is None:
@@ -1183,7 +1210,7 @@ class MAGE(nn.Module):
             raise ValueError(f"rollout: reward '{reward}' compares with the ground truth: batch['images'] must be fp32 [B, {L}, C, H, W] with "
                              "H, W >= 11")
         for name, x in batch.items():
-            if torch.is_tensor(x) and name != "sample_seed" and not (x.is_cuda and x.device == images.device):
+            if torch.is_tensor(x) and name not in ("sample_seed", "noise_seed") and not (x.is_cuda and x.device == images.device):
                 raise ValueError(f"rollout: batch['{name}'] must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
         if reference is not None:
             if not (isinstance(reference, MAGE) and reference.use_cids):
@@ -1198,14 +1225,18 @@ class MAGE(nn.Module):
         settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
         try:
             self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
-            b = self._sample_seeds(batch)
+            b = self._sample_seeds(self._noise_seeds(batch))
             with torch.cuda.device(images.device), weights_frozen():
-                out = self._generate_one(b, keep_all=True)
+                self.last_video_noise = None
+                out = self._generate_one(b, keep_all=True, candidate_noise=noise == "candidate")
                 seeds = (b["sample_seed"][:, None] + torch.arange(N, device=images.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
                 rep = {k: (v.repeat_interleave(N, 0) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == Bc else v) for k, v in batch.items()
-                       if k not in ("images", "sample_seed")}
+                       if k not in ("images", "sample_seed", "noise_seed")}
                 out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": seeds}
                 out["seeds"] = seeds
+                if self.randomness:                      # the noise every row was drawn under: what policy_loss conditions on
+                    vn = self.last_video_noise
+                    out["video_noise"] = out["batch"]["video_noise"] = vn if vn.shape[0] == Bc * N else vn.repeat_interleave(N, 0)
                 video = out["video"]
                 if builtin:
                     gen = video[:, 1:] if video.dtype == F32 else video[:, 1:].float()
@@ -1248,6 +1279,20 @@ class MAGE(nn.Module):
         seeds = seeds.to(images.device).contiguous()
         self.last_sample_seeds = seeds
         return {**batch, "sample_seed": seeds}
+
+    def _noise_seeds(self, batch) -> dict:
+        """The batch with its optional 'noise_seed' entry as int64 [B] on the images' device; without it on a model that has no randomness
+        branch (there it is ignored: the call, its graph key included, is the one without the entry)."""
+        if "noise_seed" not in batch:
+            return batch
+        if not self.randomness:
+            return {k: v for k, v in batch.items() if k != "noise_seed"}
+        images = batch["images"]
+        B = images.shape[0]
+        seeds = torch.as_tensor(batch["noise_seed"])
+        if seeds.dtype != torch.int64 or tuple(seeds.shape) != (B,):
+            raise ValueError(f"batch['noise_seed'] must be int64 [{B}], got {seeds.dtype} {tuple(seeds.shape)}")
+        return {**batch, "noise_seed": seeds.to(images.device).contiguous()}
 
     def _pick(self, logits, out, seeds: Optional[torch.Tensor], *, rows: int, K: int, pos_off: int, **kw) -> None:
         """Tokens of `rows` logits rows: the sampler with the clip seeds when sampling is on, argmax otherwise (argmax's row addressing)."""
@@ -1433,26 +1478,46 @@ class MAGE(nn.Module):
                        video_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Once-per-clip prologue, fp32 (mage_model.py:648-668 / 586-613): rows [B*hw, C].  video_rows [B*hw, 64] (forward with
         randomness: the reparameterised video prior, before conv_d2) replaces the sampled noise."""
-        d = self._derived.get(self._build)
+        return self._anchor_tail(self._anchor_head(tok0, batch, first), batch, noise, batch["text"].shape[0], video_rows=video_rows)
+
+    def _anchor_head(self, tok0: torch.Tensor, batch, first: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The part of the prologue that does not see the noise: text encoder and MA encoder over frame 0, rows [B*hw, C]."""
         B = batch["text"].shape[0]
-        R, Cc = self.image_resolution, self.vision_width
+        R = self.image_resolution
         if first is None:
             first = self._frame_features(tok0, F32)                                           # [B*hw, C]
         txt = self.text_encoder(batch["text"])                                                # [B, S, C]
         S = txt.shape[1]
-        ma = self.ma_encoder._run(first, txt.reshape(B * S, -1), B=B, nq=R * R, nk=S, seq_first=False)
+        return self.ma_encoder._run(first, txt.reshape(B * S, -1), B=B, nq=R * R, nk=S, seq_first=False)
+
+    def _anchor_tail(self, ma: torch.Tensor, batch, noise: Optional[torch.Tensor], B: int, video_rows: Optional[torch.Tensor] = None,
+                     noise_seed: Optional[torch.Tensor] = None, speed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The rest of it over B clips' rows of ma (rollout(noise='candidate'): B is clips x candidates): conv_d2 of the noise, ADAIN, the
+        speed term.  The noise is `noise` [B,64,h,w] when given, else mage_video_noise under noise_seed / batch['noise_seed'] (int64 [B]:
+        the rows come straight from the kernel, no permute copy), else torch.randn (mage_model.py:661); last_video_noise keeps it."""
+        d = self._derived.get(self._build)
+        R, Cc = self.image_resolution, self.vision_width
         if self.randomness:
             if video_rows is not None:                                                        # forward(): reparameterised prior
                 nz = video_rows
             else:
-                if noise is None:
-                    noise = torch.randn([B, 64, R, R], device=ma.device)                      # mage_model.py:661
-                nz = noise.float().permute(0, 2, 3, 1).reshape(B * R * R, 64).contiguous()
+                if noise_seed is None:
+                    noise_seed = batch.get("noise_seed")
+                if noise is None and noise_seed is not None:
+                    noise, nz = ops.video_noise(noise_seed, C=64, h=R, w=R)
+                else:
+                    if noise is None:
+                        noise = torch.randn([B, 64, R, R], device=ma.device)                  # mage_model.py:661
+                    noise = noise.float()
+                    nz = noise.permute(0, 2, 3, 1).reshape(B * R * R, 64).contiguous()
+                self.last_video_noise = noise
             y = VectorQuantizedVAE._conv(nz, d["conv_d2"], torch.empty(B * R * R, Cc, device=ma.device, dtype=F32), n_img=B,
                                          H=R, W=R, cin=64, cout=Cc, k=3)
             ma = self.adain._run(ma, y, B, R, R)
-        if "speed" in batch:
-            ops.add_scaled_rowvec(ma, batch["speed"].float().contiguous(), d["speed"], B=B, P=R * R, Cc=Cc)
+        if speed is None and "speed" in batch:
+            speed = batch["speed"]
+        if speed is not None:
+            ops.add_scaled_rowvec(ma, speed.float().contiguous(), d["speed"], B=B, P=R * R, Cc=Cc)
         return ma
 
     # ------------------------------------------------------------------ sampling (mage_model.py:641-693)
@@ -1471,6 +1536,8 @@ class MAGE(nn.Module):
         self.last_sample_seeds = None
         self._set_logprob_results([None] * len(self._LOGPROB_RESULTS))
         self._want_stats()                               # (refuses policy without sampling before anything runs)
+        self.last_video_noise = None
+        batch = self._noise_seeds(batch)
         if getattr(self, "sampling", None) is not None and self.use_cids:
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
@@ -1558,7 +1625,7 @@ class MAGE(nn.Module):
                 with torch.cuda.graph(g):
                     out = self._generate_eager(static)
                     toks, logits = self.last_tokens, self.last_logits
-                    lps = self._logprob_results()
+                    lps, vn = self._logprob_results(), self.last_video_noise
             except Exception:
                 if self.use_graph:                       # asked for explicitly: loud
                     raise
@@ -1569,7 +1636,7 @@ class MAGE(nn.Module):
                 if gc_was:
                     gc.enable()
                 recs = ops.PROFILE.capture_end(saved)
-            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "tok": toks, "logits": logits, "lps": lps, "recs": recs}
+            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "tok": toks, "logits": logits, "lps": lps, "vn": vn, "recs": recs}
         else:
             for k, v in batch.items():
                 ent["in"][k].copy_(v)
@@ -1583,6 +1650,7 @@ class MAGE(nn.Module):
         # last_logits across two generations must not find the first one overwritten by the second (0.5 MB per clip at cfg2)
         self.last_logits = None if ent["logits"] is None else ent["logits"].clone()
         self._set_logprob_results([None if t_ is None else t_.clone() for t_ in ent["lps"]])
+        self.last_video_noise = None if ent["vn"] is None else ent["vn"].clone()
         return ent["out"].clone()
 
     _LOGPROB_RESULTS = ("last_token_logprobs", "last_clip_logprob", "last_candidate_scores", "last_candidate_index",
@@ -1625,7 +1693,7 @@ class MAGE(nn.Module):
         main = torch.cuda.current_stream(batch["images"].device)
         if getattr(self, "_side_streams", None) is None or len(self._side_streams) != n:
             self._side_streams = [torch.cuda.Stream(device=batch["images"].device) for _ in range(n)]
-        outs, toks, lps = [None] * n, [None] * n, [None] * n
+        outs, toks, lps, vns = [None] * n, [None] * n, [None] * n, [None] * n
         for g, st in enumerate(self._side_streams):
             st.wait_stream(main)                                      # inputs were produced on the caller's stream
             with torch.cuda.stream(st):
@@ -1633,10 +1701,12 @@ class MAGE(nn.Module):
                 outs[g] = self._generate_one(sub)
                 toks[g] = self.last_tokens
                 lps[g] = self._logprob_results()
+                vns[g] = self.last_video_noise
         for st in self._side_streams:
             main.wait_stream(st)
-        for t_ in outs + toks + [t_ for l_ in lps for t_ in l_ if t_ is not None]:
+        for t_ in outs + toks + [t_ for l_ in lps for t_ in l_ if t_ is not None] + [t_ for t_ in vns if t_ is not None]:
             t_.record_stream(main)                                    # allocator plumbing: consumed on the caller's stream
+        self.last_video_noise = None if vns[0] is None else torch.cat(vns, 0)
         self.last_tokens, self.last_logits = torch.cat(toks, 0), None
         self._set_logprob_results([None if col[0] is None else torch.cat(col, 0) for col in zip(*lps)])
         return torch.cat(outs, 0)
@@ -1672,17 +1742,28 @@ class MAGE(nn.Module):
         return _assemble(images, video)
 
     @torch.no_grad()
-    def _generate_one(self, batch, keep_all: bool = False):
+    def _generate_one(self, batch, keep_all: bool = False, candidate_noise: bool = False):
         images = batch["images"]
         B = images.shape[0]
         R, L, K = self.image_resolution, self.frames_length, self.codebook_size
         hw, Lm1 = R * R, self.frames_length - 1
         dt = self._dt()
         tok0 = self.first_stage_encode(images[:, 0:1])[:, 0].reshape(B, hw)                   # :642
-        ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
         seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
         N, Bc = self._n_cand(), B
-        if N > 1:
+        if candidate_noise:
+            # rollout(noise='candidate'): the text and MA encoders run once per clip; every candidate then draws its own noise -- under the
+            # seed that also drives its sampler -- and conv_d2, ADAIN and the speed term run on the B * N rows
+            B = Bc * N
+            seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
+            ma = self._anchor_head(tok0, batch)
+            ma = ma.view(Bc, 1, hw, -1).expand(Bc, N, hw, ma.shape[-1]).reshape(B * hw, -1)
+            speed = batch["speed"].repeat_interleave(N, 0) if "speed" in batch else None
+            ma = self._anchor_tail(ma, {}, None, B, noise_seed=seeds, speed=speed)
+            tok0 = tok0[:, None, :].expand(Bc, N, hw).reshape(B, hw)
+        else:
+            ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
+        if N > 1 and not candidate_noise:
             # best of N: the once-per-clip prologue above ran once; from here every clip is N adjacent rows of a batch of B * N, candidate c
             # drawing with seed + c (int64 wrap-around), and only the winners are decoded
             B = Bc * N

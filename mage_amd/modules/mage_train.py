@@ -586,7 +586,8 @@ def _policy_scalars(policy: dict) -> dict:
 def train_forward(model, batch, policy: Optional[dict] = None):
     """Teacher-forced pass of MAGE.forward (mage_model.py:575-639) with the activations the backward pass needs.
     Returns (loss 0-dim fp32 tensor, tape).
-    policy (MAGE.policy_loss; use_cids models without the randomness branch): the pass runs over GIVEN tokens and ends in the policy-gradient
+    policy (MAGE.policy_loss; use_cids models; with the randomness branch batch['video_noise'] fp32 [B, 64, h, w] is the recorded
+    generation-time noise that modulates the motion anchor in place of the reparameterised video prior): the pass runs over GIVEN tokens and ends in the policy-gradient
     loss instead of the cross-entropy -- frame 0 is still first_stage_encode(images[:, 0:1]), frames 1 .. L-1 are policy['tokens']
     (int64 [B, L-1, h, w]); policy['advantage'] (fp32, one per clip or per token), policy['behaviour'] (fp32 per token, or None) and the
     scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h); with
@@ -646,8 +647,14 @@ def train_forward(model, batch, policy: Optional[dict] = None):
     t_rand = None
     if model.randomness:                                                     # :601-609: ADAIN modulation by the reparameterised video prior
         from . import mage_train_prior
-        ma, t_rand = mage_train_prior.rand_forward(model, batch, tok, ma, B, lat_rows=None if model.use_cids else lat_all.view(-1, 8),
-                                                   L=0 if model.use_cids else lat_all.shape[1])
+        if policy is not None:
+            # the policy is conditioned on the noise its tokens were generated under (batch['video_noise'], recorded by the generation):
+            # generation's modulation -- conv_d2, the ADAIN convolutions, ADAIN -- without the Conv3d prior, which generation never runs
+            nz = batch["video_noise"].permute(0, 2, 3, 1).reshape(B * hw, 64).contiguous()
+            ma, t_rand = mage_train_prior.modulate_forward(model, nz, ma, B)
+        else:
+            ma, t_rand = mage_train_prior.rand_forward(model, batch, tok, ma, B, lat_rows=None if model.use_cids else lat_all.view(-1, 8),
+                                                       L=0 if model.use_cids else lat_all.shape[1])
     speed = None
     if "speed" in batch:
         speed = batch["speed"].float().contiguous()
@@ -672,7 +679,7 @@ def train_forward(model, batch, policy: Optional[dict] = None):
         parts = dict(zip(("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction"),
                          policy["summary"].tolist()))
         tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
-                    logits=logits, target=target, speed=speed, B=B, rand=None, beta=0.0, alpha=0.0, parts=parts, policy=policy)
+                    logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=0.0, alpha=0.0, parts=parts, policy=policy)
         return recon, tape
     loss, parts = recon, {"prediction": recon.item()}
     beta = alpha = 0.0
@@ -732,8 +739,11 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
         grads["speed_embedding"] = gs
     if tape["rand"] is not None:
         from . import mage_train_prior
-        kl_coef = (gout * (tape["beta"] / B)).contiguous()
-        dma = mage_train_prior.rand_backward(model, tape["rand"], dma, kl_coef, grads, acc)
+        if pol is not None:                                                  # the noise is a recorded constant: the ADAIN half, no dz
+            dma, _ = mage_train_prior.modulate_backward(model, tape["rand"], dma, grads, want_dz=False)
+        else:
+            kl_coef = (gout * (tape["beta"] / B)).contiguous()
+            dma = mage_train_prior.rand_backward(model, tape["rand"], dma, kl_coef, grads, acc)
         tape["rand"] = None
     dfirst, dtxt = _ma_backward(model.ma_encoder, run32, tape["ma"], dma, grads)
     _text_backward(model.text_encoder, run32, tape["text"], dtxt, grads)

@@ -28,7 +28,7 @@ from .vqvae_model import VectorQuantizedVAE
 F32 = torch.float32
 _conv = VectorQuantizedVAE._conv
 
-__all__ = ["rand_forward", "rand_backward"]
+__all__ = ["rand_forward", "rand_backward", "modulate_forward", "modulate_backward"]
 
 
 def _flip(d: Dict[str, torch.Tensor], key: str, cin: int, cout: int, dt=F32) -> torch.Tensor:
@@ -101,15 +101,26 @@ def rand_forward(model, batch, tok, ma, B: int, lat_rows=None, L: int = 0):
     eps = eps.to(dev).float().permute(0, 2, 3, 1).reshape(B * hw, 64).contiguous()
     kl_sum = torch.empty(B, device=dev, dtype=F32)
     z = ops.reparam_kl(mu.view(B, -1), logvar.view(B, -1), eps.view(B, -1), torch.empty_like(mu).view(B, -1), kl_sum).view(B * hw, 64)
+    out, tape = modulate_forward(model, z, ma, B)
+    tape.update(blocks=blocks, prior=prior, mu=mu, logvar=logvar, eps=eps, kl_sum=kl_sum, tok=tok, lat_rows=lat_rows,
+                L=L if tok is None else tok.shape[1])
+    return out, tape
+
+
+def modulate_forward(model, z, ma, B: int):
+    """The branch from z onwards: z [B*hw, 64] fp32 channel-last rows (rand_forward: the reparameterised video prior; MAGE.policy_loss: the
+    recorded generation-time noise), ma [B*hw, C] fp32 -> (ADAIN2D(ma, conv_d2(z)), tape of z, y, g0, gam, b0, ma, B)."""
+    d = model._derived.get(model._build)
+    da = model.adain._derived.get(model.adain._build)
+    R, Cc = model.image_resolution, model.vision_width
+    hw, dev = R * R, ma.device
     y = _conv(z, d["conv_d2"], torch.empty(B * hw, Cc, device=dev, dtype=F32), n_img=B, H=R, W=R, cin=64, cout=Cc, k=3)
     g0 = _conv(y, da["mu0.w"], torch.empty(B * hw, Cc, device=dev, dtype=F32), n_img=B, H=R, W=R, cin=Cc, cout=Cc, k=3, bias=da["mu0.b"])
     gam = _conv(g0, da["mu1.w"], torch.empty_like(g0), n_img=B, H=R, W=R, cin=Cc, cout=Cc, k=3, bias=da["mu1.b"])
     b0 = _conv(y, da["var0.w"], torch.empty_like(g0), n_img=B, H=R, W=R, cin=Cc, cout=Cc, k=3, bias=da["var0.b"])
     bet = _conv(b0, da["var1.w"], torch.empty_like(g0), n_img=B, H=R, W=R, cin=Cc, cout=Cc, k=3, bias=da["var1.b"])
     out = ops.adain(ma, gam, bet, torch.empty_like(ma), B=B, P=hw, Cc=Cc, eps=model.adain.norm.eps)
-    tape = dict(blocks=blocks, prior=prior, mu=mu, logvar=logvar, eps=eps, z=z, y=y, g0=g0, gam=gam, b0=b0, ma=ma, kl_sum=kl_sum, tok=tok,
-                lat_rows=lat_rows, L=L if tok is None else tok.shape[1], B=B)
-    return out, tape
+    return out, dict(z=z, y=y, g0=g0, gam=gam, b0=b0, ma=ma, B=B)
 
 
 # ----------------------------------------------------------------------------------------------------------------- backward
@@ -177,23 +188,9 @@ def rand_backward(model, tape, dout_ma, kl_coef: torch.Tensor, grads: Dict[str, 
     """dout_ma = d loss / d (ADAIN output) [B*hw, C]; kl_coef = 1-element device tensor (d loss / d kl) / B.  Fills the gradients of
     conv3d.*, conv_mu2 / conv_var2, conv_d2, adain.*; adds the video prior's share to acc['emb'] (MAGE+: acc['emb_lin.*']); returns d loss / d (MA encoder output)."""
     d = model._derived.get(model._build)
-    da = model.adain._derived.get(model.adain._build)
     R, Cc, B = model.image_resolution, model.vision_width, tape["B"]
     hw, dev = R * R, dout_ma.device
-    dma, dgam = ops.adain_bwd(tape["ma"], tape["gam"], dout_ma, B=B, P=hw, Cc=Cc, eps=model.adain.norm.eps)
-    dbet = dout_ma
-    geo = dict(B=B, R=R, cin=Cc, cout=Cc, want_bias=True)
-    gw, gb, dg0 = _conv2d_bwd(da, "mu1.w", dgam, tape["g0"], **geo)
-    grads["adain.conv_mu.1.weight"], grads["adain.conv_mu.1.bias"] = gw, gb
-    gw, gb, dy = _conv2d_bwd(da, "mu0.w", dg0, tape["y"], **geo)
-    grads["adain.conv_mu.0.weight"], grads["adain.conv_mu.0.bias"] = gw, gb
-    gw, gb, db0 = _conv2d_bwd(da, "var1.w", dbet, tape["b0"], **geo)
-    grads["adain.conv_var.1.weight"], grads["adain.conv_var.1.bias"] = gw, gb
-    gw, gb, dy = _conv2d_bwd(da, "var0.w", db0, tape["y"], dx_acc=dy, **geo)
-    grads["adain.conv_var.0.weight"], grads["adain.conv_var.0.bias"] = gw, gb
-    del dgam, dg0, db0
-    gw, _, dz = _conv2d_bwd(d, "conv_d2", dy, tape["z"], B=B, R=R, cin=64, cout=Cc, want_bias=False)
-    grads["conv_d2.weight"] = gw
+    dma, dz = modulate_backward(model, tape, dout_ma, grads)
     dmu, dlv = ops.reparam_kl_bwd(tape["mu"], tape["logvar"], tape["eps"], dz, kl_coef)
     Cp = tape["prior"].shape[1]
     gw, gb, dprior = _conv2d_bwd(d, "mu2.w", dmu, tape["prior"], B=B, R=R, cin=Cp, cout=64, want_bias=True)
@@ -213,3 +210,27 @@ def rand_backward(model, tape, dout_ma, kl_coef: torch.Tensor, grads: Dict[str, 
         acc["emb_lin.w"] = dW if acc.get("emb_lin.w") is None else acc["emb_lin.w"] + dW
         acc["emb_lin.b"] = db if acc.get("emb_lin.b") is None else acc["emb_lin.b"] + db
     return dma
+
+
+def modulate_backward(model, tape, dout_ma, grads: Dict[str, torch.Tensor], want_dz: bool = True):
+    """Backward of modulate_forward: fills the gradients of adain.* and conv_d2.weight; returns (d loss / d (MA encoder output), d loss / d z).
+    want_dz False (MAGE.policy_loss: z is recorded noise, a constant): the input-gradient convolution of conv_d2 is not run, dz is None."""
+    d = model._derived.get(model._build)
+    da = model.adain._derived.get(model.adain._build)
+    R, Cc, B = model.image_resolution, model.vision_width, tape["B"]
+    hw = R * R
+    dma, dgam = ops.adain_bwd(tape["ma"], tape["gam"], dout_ma, B=B, P=hw, Cc=Cc, eps=model.adain.norm.eps)
+    dbet = dout_ma
+    geo = dict(B=B, R=R, cin=Cc, cout=Cc, want_bias=True)
+    gw, gb, dg0 = _conv2d_bwd(da, "mu1.w", dgam, tape["g0"], **geo)
+    grads["adain.conv_mu.1.weight"], grads["adain.conv_mu.1.bias"] = gw, gb
+    gw, gb, dy = _conv2d_bwd(da, "mu0.w", dg0, tape["y"], **geo)
+    grads["adain.conv_mu.0.weight"], grads["adain.conv_mu.0.bias"] = gw, gb
+    gw, gb, db0 = _conv2d_bwd(da, "var1.w", dbet, tape["b0"], **geo)
+    grads["adain.conv_var.1.weight"], grads["adain.conv_var.1.bias"] = gw, gb
+    gw, gb, dy = _conv2d_bwd(da, "var0.w", db0, tape["y"], dx_acc=dy, **geo)
+    grads["adain.conv_var.0.weight"], grads["adain.conv_var.0.bias"] = gw, gb
+    del dgam, dg0, db0
+    gw, _, dz = _conv2d_bwd(d, "conv_d2", dy, tape["z"], B=B, R=R, cin=64, cout=Cc, want_bias=False, want_dx=want_dz)
+    grads["conv_d2.weight"] = gw
+    return dma, dz

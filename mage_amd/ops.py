@@ -535,6 +535,18 @@ def sample_tokens(logits: torch.Tensor, out: torch.Tensor, seeds: torch.Tensor, 
     return out
 
 
+def video_noise(seeds: torch.Tensor, *, C: int, h: int, w: int, nchw: bool = True, rows: bool = True):
+    """(noise fp32 [B, C, h, w] or None, the same values as channel-last rows fp32 [B*h*w, C] or None) of int64 seeds [B] on the GPU: clip b's
+    standard-normal noise under seeds[b] (mage_video_noise: one launch, both layouts bit-equal)."""
+    l, s = _dev(seeds)
+    assert seeds.dtype == torch.int64 and seeds.dim() == 1 and seeds.is_contiguous() and (nchw or rows)
+    B = seeds.shape[0]
+    a = torch.empty(B, C, h, w, device=seeds.device, dtype=torch.float32) if nchw else None
+    r = torch.empty(B * h * w, C, device=seeds.device, dtype=torch.float32) if rows else None
+    _lib.check(l.mage_video_noise(seeds.data_ptr(), B, C, h * w, _p(a), _p(r), s), l)
+    return a, r
+
+
 def token_logprob(logits: torch.Tensor, tokens: torch.Tensor, logprob: torch.Tensor, *, rows: int, K: int, ld: Optional[int] = None,
                   group: Optional[int] = None, in_group_stride: Optional[int] = None, in_off: int = 0,
                   tok_group_stride: Optional[int] = None, tok_off: int = 0) -> torch.Tensor:
