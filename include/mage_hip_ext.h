@@ -204,6 +204,25 @@ int mage_group_advantages(const float* frame_reward, int64_t groups, int32_t N, 
  * atomics, plain vector-memory stores. */
 int mage_video_noise(const int64_t* seeds, int64_t B, int32_t C, int64_t hw, float* nchw, float* rows, void* stream);
 
+/* Classifier-free guidance of the token logits: no site in the reference (it decodes one caption's logits).  Serves MAGE.set_guidance
+ * (mage_amd/modules/mage_model.py: _generate_one runs the decoder over [clips under the caption | the same clips under the negative caption]
+ * and combines the two logit rows of every position, in place on the caption's half, before the token is picked).
+ * Row i of cond, uncond and out is K fp32 values at mage_argmax's input address, ((i / group) * in_group_stride + i % group + in_off) * ld, in
+ * each buffer; row i uses s = scale[i / scale_div] (fp32, device; scale_div = rows per clip: one value per clip, as mage_policy_loss'
+ * adv_div).  The rule, per element, in fp32:
+ *   w = s - 1 (one subtraction per row);   d = c - u;   z = c where w == 0 or d == 0,   z = fma(w, d, c) otherwise (one rounding).
+ * So z = c + (s - 1)(c - u), the usual u + s (c - u), written so that two cases are exact by construction: scale 1 returns cond's bits, and
+ * uncond equal to cond returns cond's bits for every finite scale, the sign of a zero included (0 * w + (-0) would be +0: hence the selects).
+ * Special values: NaN propagates -- a NaN in c, u or s gives NaN (the comparisons are false, the fma runs); inf - inf in d is NaN; an
+ * infinite s with d == 0 still returns c.  A row's bits depend on its own two rows and its scale only, not on `rows` or the row's place in
+ * the launch.  No reduction, no LDS, no atomics; 16-byte loads, plain 16-byte vector-memory stores; columns K .. ld of out are not written.
+ * out may be cond itself, exactly (every lane reads the quads it writes, and no others, before it writes them); otherwise out must not
+ * overlap either input.
+ * K % 4 == 0, K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0, ld >= K, cond / uncond / out non-null and 16-byte aligned, scale non-null and 4-byte
+ * aligned, rows, group, scale_div > 0, in_group_stride and in_off >= 0: MAGE_EINVAL otherwise, nothing launched.  Row bases are 64-bit. */
+int mage_guide_logits(const float* cond, const float* uncond, float* out, int64_t rows, int32_t K, int64_t ld, int64_t group,
+                      int64_t in_group_stride, int64_t in_off, const float* scale, int64_t scale_div, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

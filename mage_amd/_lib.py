@@ -137,6 +137,7 @@ EXT_SIGNATURES = {
     "mage_video_metrics": (C.c_int, [vp, i64, vp, i64, i64, i32, i32, i32, i32, i64, f32, vp, vp, vp, vp]),
     "mage_group_advantages": (C.c_int, [vp, i64, i32, i32, i32, f32, vp, vp, vp]),
     "mage_video_noise": (C.c_int, [vp, i64, i32, i64, vp, vp, vp]),
+    "mage_guide_logits": (C.c_int, [vp, vp, vp, i64, i32, i64, i64, i64, i64, vp, i64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1384,6 +1384,70 @@ extern "C" int mage_token_stats(const float* logits, int64_t rows, int32_t K, in
     return MAGE_OK;
 }
 
+// ---- classifier-free guidance of the logits (mage_guide_logits; include/mage_hip_ext.h states the rule): z = c + (s - 1)(c - u) per element,
+// one explicit fma behind two selects that make scale 1 and u == c return c's bits.  Pure streaming, 12 bytes per element: no reduction, no
+// LDS, no atomics.  A workgroup owns RB whole rows (RB * K/4 quads, about 1024: four per lane); consecutive lanes take consecutive quads, so a
+// wave-instruction moves 1 KiB of one row (or of adjacent rows), and a lane issues all of its up to eight 16-byte loads before the first
+// store: ~32 KiB in flight per workgroup.  A lane reads the quads it writes and no other, before it writes them: out may be cond itself.
+namespace {
+
+constexpr int GUIDE_QUADS = 4;                                              // quads per lane
+
+__global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, const float* uncond, float* out, long rows, int KQ, long ld, long group,
+                                                           long in_stride, long in_off, const float* __restrict__ scale, long scale_div, int RB) {
+    const long row0 = (long)blockIdx.x * RB;
+    const long left = rows - row0;
+    const int n = (int)(left < RB ? left : RB) * KQ;                        // this workgroup's quads
+    long at[GUIDE_QUADS];
+    float w[GUIDE_QUADS];
+    f32x4 c[GUIDE_QUADS], u[GUIDE_QUADS];
+#pragma unroll
+    for (int j = 0; j < GUIDE_QUADS; ++j) {
+        const int idx = (int)threadIdx.x + j * 256;
+        if (idx < n) {
+            const int r = idx / KQ;
+            const long row = row0 + r;
+            at[j] = ((row / group) * in_stride + row % group + in_off) * ld + 4 * (idx - r * KQ);
+            w[j] = __fsub_rn(scale[row / scale_div], 1.0f);
+            c[j] = load4(cond + at[j]);
+            u[j] = load4(uncond + at[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < GUIDE_QUADS; ++j) {
+        if ((int)threadIdx.x + j * 256 < n) {
+            f32x4 z;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = __fsub_rn(c[j][e], u[j][e]);
+                z[e] = (w[j] == 0.f || d == 0.f) ? c[j][e] : __fmaf_rn(w[j], d, c[j][e]);
+            }
+            store4(out + at[j], z);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int mage_guide_logits(const float* cond, const float* uncond, float* out, int64_t rows, int32_t K, int64_t ld, int64_t group,
+                                 int64_t in_group_stride, int64_t in_off, const float* scale, int64_t scale_div, void* stream) {
+    MAGE_CHECK_ARG(cond && uncond && out && scale, "mage_guide_logits: null pointer");
+    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
+                   in_off >= 0 && scale_div > 0,
+                   "mage_guide_logits: bad sizes rows=%ld K=%d ld=%ld group=%ld scale_div=%ld (K %% 4 == 0, K <= %d, ld %% 4 == 0, ld >= K)",
+                   (long)rows, K, (long)ld, (long)group, (long)scale_div, MAGE_SAMPLE_MAX_K);
+    MAGE_CHECK_ARG(((((uintptr_t)cond) | ((uintptr_t)uncond) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)scale) & 3) == 0,
+                   "mage_guide_logits: cond, uncond and out must be 16-byte aligned, scale 4-byte aligned");
+    const int KQ = K / 4;
+    const int RB = KQ >= 256 * GUIDE_QUADS ? 1 : 256 * GUIDE_QUADS / KQ;    // whole rows per workgroup, RB * KQ <= 1024 quads
+    const int64_t blocks = (rows + RB - 1) / RB;
+    MAGE_CHECK_ARG(blocks <= 0x7fffffffLL, "mage_guide_logits: rows=%ld is more than one launch covers", (long)rows);
+    guide_logits_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(cond, uncond, out, (long)rows, KQ, (long)ld, (long)group,
+                                                                                (long)in_group_stride, (long)in_off, scale, (long)scale_div, RB);
+    MAGE_CHECK_LAUNCH("mage_guide_logits");
+    return MAGE_OK;
+}
+
 extern "C" int mage_clip_scores(const float* logprob, int64_t n_clips, int32_t n_cand, int64_t per_clip, float* scores, int64_t* best,
                                 void* stream) {
     MAGE_CHECK_ARG(logprob && scores, "mage_clip_scores: null pointer");

@@ -870,6 +870,10 @@ class MAGE(nn.Module):
         self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
         self.last_video_noise: Optional[torch.Tensor] = None             # randomness: fp32 [B, 64, h, w], the noise the last generation used
         self._last_policy_out = None
+        self.guidance: Optional[float] = None                            # set_guidance: the classifier-free guidance scale; None: off
+        self.last_guidance_scale: Optional[torch.Tensor] = None          # guidance on: fp32 [B], the per-clip scales the last generation used
+        self.caption_dropout = 0.0     # forward in training mode: the probability that a clip's caption is replaced by the null caption
+        self.last_caption_drop: Optional[torch.Tensor] = None            # bool [B]: the clips whose caption the last forward dropped
 
     # ------------------------------------------------------------------ construction helpers
     def instantiate_first_stage(self, config):
@@ -922,6 +926,72 @@ class MAGE(nn.Module):
         self.sampling, self.candidates = (t, k, p), int(candidates)
         return self
 
+    def set_guidance(self, scale: Optional[float] = None) -> "MAGE":
+        """Classifier-free guidance of autoregressive_generate: how strongly the caption steers the video.  scale None (the default): off,
+        every call is the unguided one.  Otherwise a float that is finite in fp32; any finite value is legal -- 1 is "no guidance, at twice
+        the cost", values above 1 push towards the caption, values below 1 (negative ones too) away from it.
+        The caption reaches the decoder only through the motion anchor, so a guided call is the same decoder over 2 B clips -- the B clips
+        under batch['text'], then the same clips under the negative caption, both halves fed the same tokens -- and every position's two
+        logit rows are combined before its token is picked: z = c + (scale - 1)(c - u) (mage_guide_logits, include/mage_hip_ext.h: scale 1,
+        and a negative caption equal to the caption, return the unguided logits bit for bit).  Everything downstream sees the guided logits:
+        argmax or the sampler, best-of-N (set_sampling(candidates=N)), graph replay, both AR modes, last_logits, and set_logprobs'
+        results -- last_token_logprobs is the softmax of the GUIDED logits at temperature 1, last_token_policy_logprobs the sampler's
+        filtered view of the same guided logits.  Every result has B clips.
+        batch['guidance_scale'] (fp32 [B], optional) overrides the float per clip: a tensor, so a captured graph replays under new scales;
+        last_guidance_scale keeps what the call used.  batch['negative_text'] (int64, the shape of batch['text'], optional) is the caption
+        steered away from; absent, it is mage_amd.utils.glue.null_caption(text, padding_idx) -- [CLS] [SEP] and padding -- which
+        caption_dropout teaches a model fine-tuned here.  Both keys are ignored while guidance is off.  On a randomness=True model clip b's
+        negative half uses clip b's noise and speed.
+        While guidance is on, score, policy_loss, token_policy_logprobs and rollout are refused: a guided behaviour policy against an
+        unguided learner is a different estimator."""
+        if scale is None:
+            self.guidance = None
+            return self
+        if not self.use_cids:
+            raise ValueError("set_guidance: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+            raise ValueError(f"set_guidance: scale must be a float or None, got {scale!r}")
+        s = float(scale)
+        if not (math.isfinite(s) and abs(s) < 3.4028236e38 and math.isfinite(ctypes.c_float(s).value)):
+            raise ValueError(f"set_guidance: scale must be finite (in fp32), got {scale}")
+        self.guidance = s
+        return self
+
+    def _guided(self) -> bool:
+        return self.use_cids and getattr(self, "guidance", None) is not None
+
+    def _refuse_guided(self, who: str) -> None:
+        if self._guided():
+            raise ValueError(f"{who}: classifier-free guidance is on (set_guidance): it shapes generation only -- a guided behaviour policy "
+                             "against an unguided learner is a different estimator; switch it off with set_guidance(None) first")
+
+    def _guidance_inputs(self, batch) -> dict:
+        """Guidance on: the batch with 'guidance_scale' as fp32 [B] (the float of set_guidance where the batch gives none; kept as
+        last_guidance_scale) and 'negative_text' as int64 in the shape of 'text' (the null caption when absent: index operations on the
+        device, no host synchronisation) on the images' device.  Guidance off: the batch without the two keys."""
+        if not self._guided():
+            return {k: v for k, v in batch.items() if k not in ("guidance_scale", "negative_text")} if (
+                "guidance_scale" in batch or "negative_text" in batch) else batch
+        images, text = batch["images"], batch["text"]
+        B = images.shape[0]
+        gs = batch.get("guidance_scale")
+        if gs is None:
+            gs = torch.full((B,), self.guidance, dtype=F32)
+        gs = torch.as_tensor(gs)
+        if gs.dtype != F32 or tuple(gs.shape) != (B,):
+            raise ValueError(f"batch['guidance_scale'] must be fp32 [{B}], got {gs.dtype} {tuple(gs.shape)}")
+        gs = gs.to(images.device).contiguous()
+        neg = batch.get("negative_text")
+        if neg is None:
+            from ..utils.glue import null_caption
+            neg = null_caption(text.to(torch.int64), int(getattr(self.text_encoder, "padding_idx", 0)))
+        neg = torch.as_tensor(neg)
+        if neg.dtype != torch.int64 or tuple(neg.shape) != tuple(text.shape):
+            raise ValueError(f"batch['negative_text'] must be int64 {list(text.shape)} (the shape of batch['text']: the motion-anchor "
+                             f"cross-attention is unmasked, so the padded length is part of the result), got {neg.dtype} {list(neg.shape)}")
+        self.last_guidance_scale = gs
+        return {**batch, "guidance_scale": gs, "negative_text": neg.to(images.device).contiguous()}
+
     def set_logprobs(self, on: bool = True, *, policy: bool = False, entropy: bool = False) -> "MAGE":
         """on: autoregressive_generate leaves last_token_logprobs (fp32 [B, L-1, h, w]: the log-probability of each generated token under the
         logits it was picked from -- the model's full softmax at temperature 1, not the filtered set of set_sampling) and last_clip_logprob
@@ -933,6 +1003,8 @@ class MAGE(nn.Module):
         [B, N] (the winner is still picked by the model log-probability).
         entropy (needs on; works with greedy decoding): last_token_entropy (fp32 [B, L-1, h, w], nats: the full softmax at temperature 1) and,
         with sampling on, last_token_policy_entropy (the kept set's).  score honours both flags for the batch's own tokens.
+        With set_guidance on, "the logits it was picked from" are the guided logits: last_token_logprobs is their softmax at temperature
+        1, last_token_policy_logprobs the sampler's filtered view of the same guided logits, and the entropies are theirs too.
         set_logprobs(False) clears all three switches."""
         if (policy or entropy) and not on:
             raise ValueError("set_logprobs: policy / entropy need on=True")
@@ -982,6 +1054,7 @@ class MAGE(nn.Module):
         does not compute is None afterwards, last_candidate_policy_scores included (score has no candidates)."""
         if not self.use_cids:
             raise ValueError("score: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        self._refuse_guided("score")
         images = batch["images"]
         _need_gpu(images, "MAGE.score")
         self._want_stats()                                # (refuses policy without sampling before anything runs)
@@ -1036,6 +1109,7 @@ class MAGE(nn.Module):
         L, R, K = self.frames_length, self.image_resolution, self.codebook_size
         if not self.use_cids:
             raise ValueError("policy_loss: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        self._refuse_guided("policy_loss")
         vn = batch.get("video_noise") if self.randomness else None
         if self.randomness and vn is None:
             raise ValueError("policy_loss: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
@@ -1107,6 +1181,7 @@ class MAGE(nn.Module):
         describes, by the teacher-forced pass policy_loss runs -- bit for bit last_policy_token_logprobs of a no-grad policy_loss on the
         same inputs (-inf where the filter could not draw the token).  How a frozen copy of the model gives policy_loss its
         reference_logprobs.  Values only; every last_* result is left as found."""
+        self._refuse_guided("token_policy_logprobs")
         images = batch["images"] if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("token_policy_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
@@ -1180,6 +1255,7 @@ class MAGE(nn.Module):
         policy_loss call above -- and the reference's scoring -- condition on the noise the tokens were drawn under.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
+        self._refuse_guided("rollout")
         if noise not in ("clip", "candidate"):
             raise ValueError(f"rollout: noise must be 'clip' or 'candidate', got {noise!r}")
         if noise == "candidate":
@@ -1540,6 +1616,8 @@ class MAGE(nn.Module):
         batch = self._noise_seeds(batch)
         if getattr(self, "sampling", None) is not None and self.use_cids:
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
+        self.last_guidance_scale = None
+        batch = self._guidance_inputs(batch)             # (likewise: the scales and the negative caption are inputs of a captured graph)
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
         with torch.cuda.device(images.device), weights_frozen():
             ug = self._graph_auto(batch) if self.use_graph is None else bool(self.use_graph)
@@ -1557,9 +1635,10 @@ class MAGE(nn.Module):
     def _graph_auto(self, batch) -> bool:
         """use_graph = None: replay from a captured graph where the call is launch-bound -- up to 4 clips per call (the reference samples
         ONE, main_mage.py:205: ~870 launches of 3-15 µs; 13.7 ms eager vs 7.6 ms replayed per 16-frame clip), the VQ-token path only (an
-        external latent first stage is not ours to capture), and not while per-launch profiling is on."""
+        external latent first stage is not ours to capture), and not while per-launch profiling is on.  A guided call decodes 2 B clips."""
         images = batch["images"]
-        return (self.use_cids and images.shape[0] * self.image_resolution ** 2 <= 1024 and not ops.PROFILE.enabled
+        clips = images.shape[0] * (2 if self._guided() else 1)
+        return (self.use_cids and clips * self.image_resolution ** 2 <= 1024 and not ops.PROFILE.enabled
                 and all(torch.is_tensor(v) for v in batch.values()) and config.get().auto_graph)
 
     def _graph_fingerprint(self):
@@ -1569,7 +1648,8 @@ class MAGE(nn.Module):
                 getattr(self.ma_encoder, "split_kind", 0), getattr(self.text_encoder, "split_kind", 0),
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
                 config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None),
-                self._want_logprobs(), self._n_cand(), bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False)))
+                self._want_logprobs(), self._n_cand(), bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False)),
+                self._guided())                          # (on / off selects the launches; the scales themselves are a batch tensor)
 
     def _generate_eager(self, batch):
         if not self.use_cids:
@@ -1751,7 +1831,22 @@ class MAGE(nn.Module):
         tok0 = self.first_stage_encode(images[:, 0:1])[:, 0].reshape(B, hw)                   # :642
         seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
         N, Bc = self._n_cand(), B
-        if candidate_noise:
+        gs = batch.get("guidance_scale") if self._guided() else None                          # None: no guidance
+        if gs is not None:
+            # classifier-free guidance: the prologue runs once over 2 B captions -- [the clips under their caption | the same clips under the
+            # negative caption], clip b's second copy with clip b's frame 0, noise and speed -- and from here the batch is [cond | uncond]
+            assert not candidate_noise and not keep_all                                       # (rollout is refused while guidance is on)
+            two = lambda t_: torch.cat([t_, t_], 0)      # noqa: E731
+            tok0 = two(tok0)
+            noise, nseed = batch.get("video_noise"), batch.get("noise_seed")
+            if self.randomness and noise is None and nseed is None:
+                noise = torch.randn([Bc, 64, R, R], device=images.device)                     # mage_model.py:661, one draw per clip
+            ma = self._anchor_head(tok0, {"text": torch.cat([batch["text"].to(torch.int64), batch["negative_text"]], 0)})
+            ma = self._anchor_tail(ma, {}, None if noise is None else two(noise), 2 * Bc, noise_seed=None if nseed is None else two(nseed),
+                                   speed=two(batch["speed"]) if "speed" in batch else None)
+            if self.last_video_noise is not None:
+                self.last_video_noise = self.last_video_noise[:Bc]
+        elif candidate_noise:
             # rollout(noise='candidate'): the text and MA encoders run once per clip; every candidate then draws its own noise -- under the
             # seed that also drives its sampler -- and conv_d2, ADAIN and the speed term run on the B * N rows
             B = Bc * N
@@ -1767,23 +1862,29 @@ class MAGE(nn.Module):
             # best of N: the once-per-clip prologue above ran once; from here every clip is N adjacent rows of a batch of B * N, candidate c
             # drawing with seed + c (int64 wrap-around), and only the winners are decoded
             B = Bc * N
-            tok0 = tok0[:, None, :].expand(Bc, N, hw).reshape(B, hw)
-            ma = ma.view(Bc, 1, hw, -1).expand(Bc, N, hw, ma.shape[-1]).reshape(B * hw, -1)
+            Bp = tok0.shape[0]                                                                # Bc, or 2 Bc under guidance: each half expands alike
+            tok0 = tok0[:, None, :].expand(Bp, N, hw).reshape(Bp * N, hw)
+            ma = ma.view(Bp, 1, hw, -1).expand(Bp, N, hw, ma.shape[-1]).reshape(Bp * N * hw, -1)
             seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
         ma_dt = _to_dt(ma, dt)
         gen = torch.empty(B, Lm1, R, R, device=images.device, dtype=torch.int64)
         want_lp = self._want_logprobs()
+        # B: the clips (x candidates) whose tokens are picked; Bd: the decoder's batch -- under guidance 2 B, rows B .. 2 B the uncond half,
+        # which is fed the tokens of the cond half.  Every pick / logprob / stats launch below addresses the first B clips only.
+        Bd = B if gs is None else 2 * B
         if self.ar_mode == "incremental":
             # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
-            st = self.generate_model._inc_begin(B, R, R)
+            st = self.generate_model._inc_begin(Bd, R, R)
             prev = tok0.contiguous()
             lp_t = torch.empty(Lm1, B, hw, device=images.device, dtype=F32) if want_lp else None
             st_t = self._stats_alloc((Lm1, B, hw), images.device)
-            gen_t = torch.empty(Lm1, B, hw, device=images.device, dtype=torch.int64)         # frame-major: a frame's tokens are contiguous,
+            gen_t = torch.empty(Lm1, Bd, hw, device=images.device, dtype=torch.int64)        # frame-major: a frame's tokens are contiguous,
             for i in range(Lm1):                                                              # the argmax writes them where the next step reads them
                 feats = self._frame_source(prev, dt)                                          # newest frame only
                 step_logits = self.generate_model._inc_step(st, ma_dt if i == 0 else None, feats)
                 prev = gen_t[i]
+                if gs is not None:                        # in place on the cond half's rows: one value per clip covers its N candidates
+                    ops.guide_logits(step_logits, step_logits[B * hw:], gs, rows=B * hw, K=K, scale_div=N * hw)
                 if seeds is None:
                     ops.argmax(step_logits, prev, rows=B * hw, K=K)
                 else:                                                                         # clip = row // hw, position i*hw + pixel
@@ -1792,6 +1893,10 @@ class MAGE(nn.Module):
                     ops.token_logprob(step_logits, prev, lp_t[i], rows=B * hw, K=K)
                 if st_t is not None:
                     self._stats(step_logits, prev, st_t, lambda b: b[i], rows=B * hw, K=K)
+                if gs is not None and i != Lm1 - 1:
+                    prev[B:].copy_(prev[:B])              # the uncond half conditions on the same tokens (one small int64 copy per frame)
+            if gs is not None:
+                gen_t = gen_t[:, :B]
             gen = gen_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else gen_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # index plumbing, once
             clip_major = lambda t_: t_.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # noqa: E731
             lp = clip_major(lp_t) if want_lp else None
@@ -1806,9 +1911,17 @@ class MAGE(nn.Module):
         for i in range(Lm1):                                                                  # :673-684
             feats = self._frame_source(cur, dt)
             ev = ops.PROFILE.begin() if ops.PROFILE.wants("decoder_step") else None          # bench.py: the transformer step on its own
-            logits = self.generate_model._run(ma_dt, feats, B=B, hh=R, ww=R)                  # [B*(L-1)*hw, K]
+            logits = self.generate_model._run(ma_dt, feats, B=Bd, hh=R, ww=R)                 # [Bd*(L-1)*hw, K]
             if ev is not None:
                 ops.PROFILE.end("decoder_step", ev, 0.0)
+            if gs is not None:
+                # in place on the cond half.  Frame i's rows (argmax's regrouped addressing) are all the pick needs; the last iteration
+                # guides every frame, so that the greedy final argmax and last_logits see guided logits throughout
+                unc = logits[B * Lm1 * hw:]
+                if i != Lm1 - 1:
+                    ops.guide_logits(logits, unc, gs, rows=B * hw, K=K, scale_div=N * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw)
+                else:
+                    ops.guide_logits(logits, unc, gs, rows=B * Lm1 * hw, K=K, scale_div=N * Lm1 * hw)
             if i != Lm1 - 1:                                                                  # argmax of frame i -> slot i+1
                 self._pick(logits, cur, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw,
                            out_group_stride=Lm1 * hw, out_off=(i + 1) * hw)
@@ -1816,6 +1929,8 @@ class MAGE(nn.Module):
                     ops.token_logprob(logits, cur.view(-1)[hw:], lp.view(-1), in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
                 if st is not None and seeds is not None:
                     self._stats(logits, cur.view(-1)[hw:], st, flat, in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
+                if gs is not None:
+                    cur[B:, i + 1].copy_(cur[:B, i + 1])  # the picked slot goes to both halves
         if seeds is None:
             ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                   # :687
             if want_lp:
@@ -1824,14 +1939,14 @@ class MAGE(nn.Module):
                 self._stats(logits, gen, st, flat, rows=B * Lm1 * hw, K=K)
         else:
             # sampled: frames 0..L-3 are the tokens the loop conditioned on (slots 1..L-2); only the last frame is drawn from these logits
-            gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:, 1:])
+            gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:B, 1:])
             self._pick(logits, gen, seeds, rows=B * hw, K=K, pos_off=(Lm1 - 1) * hw, group=hw, in_group_stride=Lm1 * hw,
                        in_off=(Lm1 - 1) * hw, out_group_stride=Lm1 * hw, out_off=(Lm1 - 1) * hw)
             if want_lp:
                 ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
             if st is not None:
                 self._stats(logits, gen, st, flat, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-        return self._finish(images, gen, logits.view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all)
+        return self._finish(images, gen, logits[:B * Lm1 * hw].view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all)
 
     def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None, keep_all: bool = False):
         """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
@@ -2034,6 +2149,29 @@ class MAGE(nn.Module):
             ops.check_device_errors(batch["images"].device)
         return loss, {f"{prefix}/{k}": v for k, v in self._last_train_parts.items()}
 
+    def _drop_captions(self, batch) -> dict:
+        """Caption dropout at the top of forward (see there): the batch with the dropped rows of 'text' replaced by their null caption (one
+        torch.where on the text's device), and without its 'caption_drop' entry."""
+        self.last_caption_drop = None
+        p = getattr(self, "caption_dropout", 0.0)
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError(f"caption_dropout must be a float in [0, 1], got {p!r}")
+        drop = batch.get("caption_drop")
+        if drop is None and not (self.training and p > 0):
+            return batch
+        text = batch["text"]
+        B = text.shape[0]
+        if drop is None:
+            drop = torch.rand(B) < p                     # torch's default CPU generator, as the dropout seeds and the sample seeds
+        drop = torch.as_tensor(drop)
+        if drop.dtype != torch.bool or tuple(drop.shape) != (B,):
+            raise ValueError(f"batch['caption_drop'] must be bool [{B}], got {drop.dtype} {tuple(drop.shape)}")
+        from ..utils.glue import null_caption
+        drop = drop.to(text.device)
+        self.last_caption_drop = drop
+        text = torch.where(drop[:, None], null_caption(text, int(getattr(self.text_encoder, "padding_idx", 0))), text)
+        return {**{k: v for k, v in batch.items() if k != "caption_drop"}, "text": text}
+
     def forward(self, batch, test_flag=False):
         """(loss, loss_dict) of the teacher-forced pass (mage_model.py:575-639), incl. the randomness=True terms (KL of the
         reparameterised video prior, the PID-controlled or fixed beta, the speed-embedding l2).  batch['reparam_noise']
@@ -2041,7 +2179,13 @@ class MAGE(nn.Module):
         (batch['video_noise'] injects it) while the KL term still comes from mu / logvar (:604).  Under ``torch.no_grad()``: values only.  In grad mode (any
         parameter requiring grad): the returned loss carries an autograd node backed by the HIP backward kernels
         (modules/mage_train.py, mage_train_prior.py: every config family -- MNIST, CATER with the randomness branch, MAGE+), so
-        ``loss.backward(); optimizer.step()`` works."""
+        ``loss.backward(); optimizer.step()`` works.
+        Caption dropout (what teaches the model the null caption classifier-free guidance steers away from, set_guidance): with
+        ``self.caption_dropout = p`` in (0, 1] and the model in training mode, each clip's caption is replaced, with probability p, by
+        mage_amd.utils.glue.null_caption of itself before anything else runs -- the mask comes from torch's default CPU generator;
+        batch['caption_drop'] (bool [B], optional) replaces the draw and applies in either mode.  last_caption_drop keeps the mask (None when
+        nothing was dropped or drawn).  p = 0 (the default) and no mask: the call is the one it was."""
+        batch = self._drop_captions(batch)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if test_flag and self.randomness:
                 raise NotImplementedError("forward(test_flag=True) is an evaluation switch (mage_model.py:604): call it under torch.no_grad()")

@@ -587,6 +587,25 @@ def token_stats(logits: torch.Tensor, tokens: Optional[torch.Tensor], *, rows: i
                                   _p(policy_entropy), _p(kept), _p(entropy), s), l)
 
 
+def guide_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None, *, rows: int, K: int,
+                 scale_div: int, ld: Optional[int] = None, group: Optional[int] = None, in_group_stride: Optional[int] = None,
+                 in_off: int = 0) -> torch.Tensor:
+    """Classifier-free guidance, z = c + (scale - 1)(c - u) (mage_guide_logits): argmax's input addressing in all three buffers, each
+    addressed from its first element; row i uses scale[i // scale_div].  out None: in place on cond."""
+    l, s = _dev(cond)
+    out = cond if out is None else out
+    assert cond.dtype == uncond.dtype == out.dtype == scale.dtype == torch.float32 and scale.is_contiguous()
+    assert uncond.device == cond.device and out.device == cond.device and scale.device == cond.device
+    ld = K if ld is None else ld
+    group = rows if group is None else group
+    in_group_stride = group if in_group_stride is None else in_group_stride
+    end = (((rows - 1) // group) * in_group_stride + (rows - 1) % group + in_off) * ld + K       # one past the last element addressed
+    assert in_off >= 0 and end <= min(cond.numel(), uncond.numel(), out.numel()) and scale.numel() >= (rows - 1) // scale_div + 1
+    _lib.check(l.mage_guide_logits(cond.data_ptr(), uncond.data_ptr(), out.data_ptr(), rows, K, ld, group, in_group_stride, in_off,
+                                   scale.data_ptr(), scale_div, s), l)
+    return out
+
+
 def _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div):
     """The asserts policy_loss and policy_loss_bwd share; returns (rows, K, ld, adv_div).  adv_div None: advantage's entries share the rows
     out equally (one per row, or one per clip)."""

@@ -23,7 +23,7 @@ import torch
 from . import synth
 
 __all__ = ["MNIST_VOCAB", "CATER_V1_VOCAB", "CATER_V2_VOCAB", "encode_caption", "decode_caption", "sample_indices", "sample_clip", "collate",
-           "SyntheticMovingMnist", "make_checkpoint", "save_checkpoint", "load_checkpoint_into", "save_gifs"]
+           "null_caption", "SyntheticMovingMnist", "make_checkpoint", "save_checkpoint", "load_checkpoint_into", "save_gifs"]
 
 # word tables (data, dataload.py:199-203, 300-312): ids are part of the checkpoint contract (text_encoder.token_embedding rows)
 _MNIST_WORDS = ["[PAD]", "[CLS]", "[SEP]", "0", "1", "2", "3", "4", "5", "6", "7", "8", "9", "the", "digit", "and", "is", "are",
@@ -70,6 +70,20 @@ def collate(items: List[Dict[str, torch.Tensor]], padding_idx: int = 0) -> Dict[
     """dataload.py:263-271: images stacked, captions right-padded with padding_idx, speeds stacked."""
     text = torch.nn.utils.rnn.pad_sequence([d["text"] for d in items], batch_first=True, padding_value=padding_idx)
     return {"images": torch.stack([d["images"] for d in items], 0), "text": text, "speed": torch.stack([d["speed"] for d in items], 0)}
+
+
+def null_caption(text: torch.Tensor, padding_idx: int = 0) -> torch.Tensor:
+    """The caption that says nothing, in the shape of `text` (int64 [B, S]): column 0 of each row ([CLS]), then the row's last non-padding
+    token ([SEP]), then padding_idx.  A row with fewer than two non-padding tokens is returned as is.  What classifier-free guidance steers
+    away from when no negative caption is given (MAGE.set_guidance), and what caption dropout trains (MAGE.caption_dropout); the padded
+    length is kept because the motion-anchor cross-attention is unmasked.  Index operations on text's device: nothing is read on the host."""
+    if text.dim() != 2:
+        raise ValueError(f"null_caption: text must be [B, S], got {list(text.shape)}")
+    keep = text != padding_idx
+    pos = torch.arange(text.shape[1], device=text.device)[None, :]
+    last = text.gather(1, (pos * keep).amax(1, keepdim=True))                # the last non-padding token (column 0 for an all-padding row)
+    null = torch.where(pos == 0, text[:, :1], torch.where(pos == 1, last, torch.full_like(text, padding_idx)))
+    return torch.where(keep.sum(1, keepdim=True) >= 2, null, text)
 
 
 _MOTIONS = ["up then down", "left then right", "down then up", "right then left"]        # data/mnist_caption_single.py:30
