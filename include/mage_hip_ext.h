@@ -223,6 +223,59 @@ int mage_video_noise(const int64_t* seeds, int64_t B, int32_t C, int64_t hw, flo
 int mage_guide_logits(const float* cond, const float* uncond, float* out, int64_t rows, int32_t K, int64_t ld, int64_t group,
                       int64_t in_group_stride, int64_t in_off, const float* scale, int64_t scale_div, void* stream);
 
+/* Preference loss over ranked pairs of clips (DPO / IPO), its pair stage: no site in the reference (its only objective is the mean
+ * cross-entropy).  Serves MAGE.preference_loss (mage_amd/modules/mage_train.py: train_forward with preference=, after mage_token_logprob and
+ * mage_clip_scores have reduced the logits to one log-likelihood per clip).
+ * clip_logprob s and reference_logprob r are fp32 [clips] (a clip's summed token log-probabilities under the model and under the frozen
+ * reference); pairs is int64 [n_pairs, 2] on the device, pair p = (w, l): the chosen row and the rejected row.  Everything is computed in
+ * fp64 from the fp32 inputs (beta and label_smoothing eps widened from their fp32 values), each output rounded to fp32 once:
+ *   a = s_w - r_w;   b = s_l - r_l;   u = a - b;   h = beta u;
+ *   mode 0 (DPO):  l_p = -(1 - eps) logsig(h) - eps logsig(-h),  logsig(x) = min(x, 0) - log1p(exp(-|x|))   (never overflows; the eps term
+ *                  is not formed at all when eps == 0, so a saturated pair is 0 and not 0 * inf);
+ *                  g_p = dl/du = -beta [(1 - eps) sig(-h) - eps sig(h)],  sig(|h|) = 1 / (1 + e), sig(-|h|) = e / (1 + e), e = exp(-|h|);
+ *   mode 1 (IPO):  l_p = (u - 1 / (2 beta))^2,  g_p = 2 (u - 1 / (2 beta));  label_smoothing must be 0.
+ * Outputs: pair_loss [n_pairs] = l_p;  pair_margin [n_pairs] = h;
+ *   clip_coef [clips]: clip_coef[c] = (sum_{p: w_p = c} g_p - sum_{p: l_p = c} g_p) / n_pairs, the derivative of the mean loss with respect to
+ *   clip_logprob[c] (what mage_token_logprob_bwd takes as its weights): the terms are added in fp64 in increasing p, whichever side names c.
+ *   A pair with w == l contributes nothing (its u is exactly 0: no preference); a clip in no pair gets +0.
+ *   summary [5]: five means over the pairs -- l, the share of pairs with u > 0 (the accuracy), beta a (the chosen reward), beta b (the
+ *   rejected reward), h (the margin) -- each a fixed-order fp64 sum (a workgroup's 256 pairs meet in an xor butterfly and its four waves in
+ *   order; the workgroups' sums meet the same way), divided by n_pairs and rounded once.
+ * The launch geometry is a function of clips and n_pairs alone and every sum has a fixed order: two launches give the same bits.  There are
+ * no floating-point atomics.  A non-finite input propagates as the arithmetic says (inf - inf is NaN); nothing is checked on the host.  An
+ * index outside [0, clips) is recorded for mage_check_device_errors and clamped, as mage_token_logprob's out-of-range token is.
+ * Two launches: one thread per pair writes pair_loss, pair_margin, (w, l, g_p) and its workgroup's partial sums into per-device buffers of the
+ * library (calls of mage_preference_loss on one device must be ordered: one stream, or events); then one thread per clip, 256 clips per
+ * workgroup, walks all pairs, staged through LDS 256 at a time (16 bytes each): a wave looks at 64 staged pairs at once, one per lane,
+ * ballots the ones that name one of ITS 64 clips and adds only those, in order.  The walk is n_pairs / 64 steps per wave plus one step per
+ * pair naming one of the wave's clips; a clip's own terms are one dependent fp64 add each, whatever the kernel does.
+ * Limits: clips and n_pairs in [1, 65536] (the per-device pair buffer holds 65536 entries); beta finite and > 0 (and 1 / (2 beta) finite);
+ * label_smoothing in [0, 0.5), 0 in mode 1; mode 0 or 1; every pointer non-null and aligned to its element size (4 bytes, pairs 8):
+ * MAGE_EINVAL otherwise, nothing launched. */
+int mage_preference_loss(const float* clip_logprob, const float* reference_logprob, int64_t clips, const int64_t* pairs, int64_t n_pairs,
+                         float beta, float label_smoothing, int32_t mode, float* pair_loss, float* pair_margin, float* clip_coef,
+                         float* summary, void* stream);
+
+/* Gradient of sum_i weight[i / weight_div] * logprob_i with respect to the logits, logprob_i being mage_token_logprob's value for row i (the
+ * log-softmax of the row at temperature 1, no filter, gathered at tokens[i]): no site in the reference.  Serves the backward pass of
+ * MAGE.preference_loss (mage_amd/modules/mage_train.py: train_backward), with mage_preference_loss' clip_coef as the weights and
+ * weight_div = rows per clip.
+ * Row i is the K fp32 logits z at logits + i*ld with its token t = tokens[i] (int64).  With c_i = grad_out[0] * weight[i / weight_div] (one
+ * fp32 product) and p the softmax of the row in mage_cross_entropy_bwd's arithmetic (fp32: m = max_j z_j, w_j = expf(z_j - m), p_j = w_j *
+ * (1 / sum_j w_j), the sum in a fixed order: a lane adds its own terms in register order, the lanes meet in an xor butterfly),
+ *   dlogits_ij = c_i (1[j = t] - p_ij),
+ * written contiguous ([rows, K]) as dl_dtype MAGE_F32 or MAGE_BF16.  A row with c_i == 0 is written as +0 throughout WITHOUT reading its
+ * logits (most clips of a large rollout are in no pair; a NaN in such a row does not show).  A -inf logit gives p = 0 and so a zero at its
+ * column; a token outside [0, K) gets no one-hot (mage_token_logprob, which runs before, records it); a NaN logit, or a row whose maximum is
+ * not finite, makes the row NaN as it makes logprob_i NaN.  A row's bits depend on the row, its token and c_i alone.
+ * One wave per row, the row in registers in the sampler's layout (4 .. 64 values per lane by K, code k = chunk*256 + lane*4 + e): every logit
+ * is read once with a 16-byte load, and every output is written once with a 16-byte store -- for bf16 two neighbouring lanes exchange
+ * their packed quads so that each stores eight consecutive values (K % 8 == 0; other K: 8-byte stores).
+ * mage_token_stats' size rules: rows > 0, K % 4 == 0, 0 < K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0, ld >= K, logits and dlogits 16-byte aligned;
+ * weight_div > 0; tokens 8-byte, weight and grad_out 4-byte aligned; every pointer non-null: MAGE_EINVAL otherwise, nothing launched. */
+int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
+                           int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

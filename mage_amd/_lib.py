@@ -138,6 +138,8 @@ EXT_SIGNATURES = {
     "mage_group_advantages": (C.c_int, [vp, i64, i32, i32, i32, f32, vp, vp, vp]),
     "mage_video_noise": (C.c_int, [vp, i64, i32, i64, vp, vp, vp]),
     "mage_guide_logits": (C.c_int, [vp, vp, vp, i64, i32, i64, i64, i64, i64, vp, i64, vp]),
+    "mage_preference_loss": (C.c_int, [vp, vp, i64, vp, i64, f32, f32, i32, vp, vp, vp, vp, vp]),
+    "mage_token_logprob_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

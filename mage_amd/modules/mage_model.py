@@ -870,6 +870,12 @@ class MAGE(nn.Module):
         self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
         self.last_video_noise: Optional[torch.Tensor] = None             # randomness: fp32 [B, 64, h, w], the noise the last generation used
         self._last_policy_out = None
+        self.last_preference_clip_logprobs: Optional[torch.Tensor] = None    # preference_loss: fp32 [B], the clips' log-likelihoods under the model
+        self.last_preference_clip_coef: Optional[torch.Tensor] = None        # fp32 [B]: d(loss) / d(clip log-likelihood)
+        self.last_preference_pair_loss: Optional[torch.Tensor] = None        # fp32 [P]
+        self.last_preference_pair_margin: Optional[torch.Tensor] = None      # fp32 [P]: beta * ((s_w - r_w) - (s_l - r_l))
+        self.last_preference_token_logprobs: Optional[torch.Tensor] = None   # fp32 [B, L-1, h, w]: the given tokens at temperature 1, no filter
+        self._last_preference_out = None
         self.guidance: Optional[float] = None                            # set_guidance: the classifier-free guidance scale; None: off
         self.last_guidance_scale: Optional[torch.Tensor] = None          # guidance on: fp32 [B], the per-clip scales the last generation used
         self.caption_dropout = 0.0     # forward in training mode: the probability that a clip's caption is replaced by the null caption
@@ -1195,6 +1201,116 @@ class MAGE(nn.Module):
             for a, v in keep.items():
                 setattr(self, a, v)
 
+    _PREFERENCE_LOSSES = {"sigmoid": 0, "ipo": 1}
+
+    def preference_loss(self, batch, tokens, pairs, reference_logprobs, *, beta: float = 0.1, label_smoothing: float = 0.0,
+                        loss: str = "sigmoid"):
+        """Preference loss (DPO; loss='ipo': IPO) over ranked pairs of clips: (loss, info) of policy_loss' teacher-forced pass over frame 0
+        of batch['images'] (plus batch['text'], the optional batch['speed'], and batch['video_noise'] on a randomness=True model) followed
+        by `tokens` (int64 [B, L-1, h, w]), ending in mage_token_logprob, mage_clip_scores and mage_preference_loss (include/mage_hip_ext.h
+        states the rule).  pairs: int64 [P, 2] rows of the batch, (chosen, rejected) -- e.g. rollout(pairs='best_worst')'s, human labels
+        or a stored dataset; a pair (i, i) is no preference and has no gradient.  reference_logprobs: fp32 [B], the same clips'
+        log-likelihoods under a frozen reference model: ref.clip_logprobs(batch, tokens), or rollout(reference=, pairs=)'s
+        'reference_clip_logprobs'.  With s the clips' log-likelihoods under this model, r the reference's and u = (s_w - r_w) - (s_l - r_l)
+        for a pair (w, l), the loss is the mean over the pairs of -(1 - eps) logsig(beta u) - eps logsig(-beta u) (eps = label_smoothing in
+        [0, 0.5)), or of (u - 1 / (2 beta))^2 with loss='ipo' (label_smoothing must be 0).
+        The log-likelihoods are the model's own -- the full softmax at temperature 1 with no filter, what score reports -- whatever
+        set_sampling says: a preference is about the model, and a filtered policy would turn one undrawable token into a -inf sequence.
+        In grad mode the loss carries one autograd node over the trainable parameters, as policy_loss' does: its backward pass starts from
+        mage_token_logprob_bwd with one coefficient per clip (clips in no pair cost a zero fill).  Under torch.no_grad(): values only.
+        info = {'loss', 'accuracy' (the share of pairs with u > 0), 'chosen_reward' (mean beta (s_w - r_w)), 'rejected_reward', 'margin'
+        (mean beta u)} as floats; last_preference_clip_logprobs (fp32 [B]), last_preference_clip_coef (fp32 [B]: d loss / d s),
+        last_preference_pair_loss, last_preference_pair_margin (fp32 [P]) and last_preference_token_logprobs (fp32 [B, L-1, h, w]) keep the
+        rest.  Dropout follows self.training, as in forward: compare with a reference in eval()."""
+        return self._preference("preference_loss", batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss)
+
+    def _preference(self, who, batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss):
+        """preference_loss under the name `who` (clip_logprobs runs it too); every refusal comes before the first launch."""
+        from . import mage_train
+        L, R = self.frames_length, self.image_resolution
+        if not self.use_cids:
+            raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        self._refuse_guided(who)
+        if not isinstance(batch, dict):
+            raise ValueError(f"{who}: batch must be a dict with 'images' and 'text'")
+        vn = batch.get("video_noise") if self.randomness else None
+        if self.randomness and vn is None:
+            raise ValueError(f"{who}: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
+                             "the noise the tokens were drawn under (last_video_noise of the generation, or rollout's out['batch'])")
+        if self._dt() == torch.float16:
+            raise ValueError(f"{who}: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
+        images = batch.get("images")
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1 and images.shape[1] >= 1):
+            raise ValueError(f"{who}: batch['images'] must be [B, >= 1, C, H, W]")
+        B = images.shape[0]
+        tshape = (B, L - 1, R, R)
+        if vn is not None and not (torch.is_tensor(vn) and vn.dtype == F32 and tuple(vn.shape) == (B, 64, R, R)):
+            raise ValueError(f"{who}: batch['video_noise'] must be fp32 {[B, 64, R, R]} (randomness=True: the tokens' generation noise)")
+        if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
+            raise ValueError(f"{who}: tokens must be int64 {list(tshape)}")
+        if not (torch.is_tensor(pairs) and pairs.dtype == torch.int64 and pairs.dim() == 2 and pairs.shape[1] == 2
+                and 1 <= pairs.shape[0] <= 65536):
+            raise ValueError(f"{who}: pairs must be int64 [P, 2] (chosen row, rejected row) with 1 <= P <= 65536")
+        if B > 65536:
+            raise ValueError(f"{who}: at most 65536 clips per call, got {B}")
+        ref = reference_logprobs
+        if not (torch.is_tensor(ref) and ref.dtype == F32 and tuple(ref.shape) == (B,)):
+            raise ValueError(f"{who}: reference_logprobs must be fp32 [{B}] (clip_logprobs of the reference model)")
+        if loss not in self._PREFERENCE_LOSSES:
+            raise ValueError(f"{who}: loss must be one of {list(self._PREFERENCE_LOSSES)}, got {loss!r}")
+        ok_num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)      # noqa: E731
+        if not (ok_num(beta) and 1e-45 <= beta < 3.4e38):              # (a positive fp32 value)
+            raise ValueError(f"{who}: beta must be finite and > 0, got {beta!r}")
+        if not (ok_num(label_smoothing) and 0 <= label_smoothing < 0.5):
+            raise ValueError(f"{who}: label_smoothing must lie in [0, 0.5), got {label_smoothing!r}")
+        if loss == "ipo" and label_smoothing != 0:
+            raise ValueError(f"{who}: label_smoothing is the sigmoid loss's; loss='ipo' takes 0, got {label_smoothing!r}")
+        for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("pairs", pairs),
+                        ("reference_logprobs", ref), ("batch['video_noise']", vn)):
+            if x is not None and not (x.is_cuda and x.device == images.device):
+                raise ValueError(f"{who}: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        pref = dict(tokens=tokens.contiguous(), pairs=pairs.contiguous(), reference=ref.contiguous(), beta=float(beta),
+                    label_smoothing=float(label_smoothing), mode=self._PREFERENCE_LOSSES[loss])
+        with torch.cuda.device(images.device):
+            if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+                names = mage_train.trainable_names(self)
+                byname = dict(self.named_parameters())
+                val = mage_train.MagePreferenceLossFn.apply(self, batch, pref, names, *[byname[n] for n in names])
+                info, res = self._last_preference_out
+                self._last_preference_out = None
+            else:
+                with torch.no_grad():
+                    val, tape = mage_train.train_forward(self, batch, preference=pref)
+                info, res = tape["parts"], tape["preference"]
+                val, tape = val.clone(), None
+            self.last_preference_clip_logprobs = res["clip_logprob"]
+            self.last_preference_clip_coef = res["clip_coef"]
+            self.last_preference_pair_loss = res["pair_loss"]
+            self.last_preference_pair_margin = res["pair_margin"]
+            self.last_preference_token_logprobs = res["logprob"].view(tshape)
+            ops.check_device_errors(images.device)
+        return val, info
+
+    @torch.no_grad()
+    def clip_logprobs(self, batch, tokens) -> torch.Tensor:
+        """fp32 [B]: the teacher-forced log-likelihood of given tokens (int64 [B, L-1, h, w]) after frame 0 of batch['images'], under the
+        model's own distribution -- the full softmax at temperature 1 with no filter, the one score reports, whatever set_sampling says --
+        by the pass preference_loss runs: bit for bit its last_preference_clip_logprobs on the same inputs.  How a frozen copy of the model
+        gives preference_loss its reference_logprobs.  Values only; every last_* result is left as found."""
+        images = batch.get("images") if isinstance(batch, dict) else None
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
+            raise ValueError("clip_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
+        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
+        try:
+            self._preference("clip_logprobs", batch, tokens, torch.zeros(1, 2, device=images.device, dtype=torch.int64),   # (0, 0): no preference
+                             torch.zeros(images.shape[0], device=images.device, dtype=F32), 1.0, 0.0, "sigmoid")
+            return self.last_preference_clip_logprobs
+        finally:
+            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
+                delattr(self, a)
+            for a, v in keep.items():
+                setattr(self, a, v)
+
     @torch.no_grad()
     def video_metrics(self, video, target, data_range: float = 2.0) -> dict:
         """Per-frame quality of `video` against `target`, both fp32 [B, T, C, H, W] on the model's GPU: {'mse', 'psnr', 'ssim'}, fp32 [B, T]
@@ -1227,7 +1343,7 @@ class MAGE(nn.Module):
 
     @torch.no_grad()
     def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None,
-                noise: str = "clip") -> dict:
+                noise: str = "clip", pairs: Optional[str] = None) -> dict:
         """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
         under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
         rewarded on the device, and the rewards turned into group-relative advantages:
@@ -1253,6 +1369,13 @@ class MAGE(nn.Module):
         noise convolution, ADAIN and the speed term on the B*N rows), refused together with batch['video_noise'] and on a model without
         the branch.  Either way the result carries 'video_noise' fp32 [B*N, 64, h, w], also as out['batch']['video_noise']: the
         policy_loss call above -- and the reference's scoring -- condition on the noise the tokens were drawn under.
+        pairs='best_worst': the result gains 'pairs' int64 [B, 2], rows into the B*N candidates -- every clip's highest-reward candidate as
+        the chosen one and its lowest-reward candidate as the rejected one, built on the device; a clip whose candidates all earned the
+        same reward gives (i, i), which preference_loss treats as no preference (zero gradient).  With reference as well the result also
+        gains 'reference_clip_logprobs' = reference.clip_logprobs(out['batch'], out['tokens']) (fp32 [B*N]), so that
+            out = m.rollout(batch, 8, reference=ref, pairs='best_worst')
+            loss, info = m.preference_loss(out['batch'], out['tokens'], out['pairs'], out['reference_clip_logprobs'])
+        runs as written.  Without pairs the call is the one it was, launch for launch.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
         self._refuse_guided("rollout")
@@ -1265,6 +1388,8 @@ class MAGE(nn.Module):
             if batch.get("video_noise") is not None:
                 raise ValueError("rollout: noise='candidate' draws every candidate's noise from its seed; batch['video_noise'] holds one "
                                  "tensor per clip and cannot describe N candidates -- drop it, or use noise='clip'")
+        if pairs not in (None, "best_worst"):
+            raise ValueError(f"rollout: pairs must be 'best_worst' or None, got {pairs!r}")
         if not self.use_cids:
             raise ValueError("rollout: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
         if getattr(self, "sampling", None) is None:
@@ -1333,6 +1458,14 @@ class MAGE(nn.Module):
                         out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"])
                     finally:
                         reference.sampling, reference.candidates = theirs
+                if pairs is not None:
+                    rw = out["rewards"].view(Bc, N)
+                    hi, lo = rw.argmax(1), rw.argmin(1)
+                    lo = torch.where(rw.amax(1) == rw.amin(1), hi, lo)           # all rewards equal: (i, i), no preference
+                    base = torch.arange(Bc, device=images.device, dtype=torch.int64) * N
+                    out["pairs"] = torch.stack([base + hi, base + lo], 1).contiguous()
+                    if reference is not None:
+                        out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"])
                 ops.check_device_errors(images.device)
         finally:
             self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings

@@ -583,7 +583,7 @@ def _policy_scalars(policy: dict) -> dict:
     return kw
 
 
-def train_forward(model, batch, policy: Optional[dict] = None):
+def train_forward(model, batch, policy: Optional[dict] = None, preference: Optional[dict] = None):
     """Teacher-forced pass of MAGE.forward (mage_model.py:575-639) with the activations the backward pass needs.
     Returns (loss 0-dim fp32 tensor, tape).
     policy (MAGE.policy_loss; use_cids models; with the randomness branch batch['video_noise'] fp32 [B, 64, h, w] is the recorded
@@ -591,7 +591,12 @@ def train_forward(model, batch, policy: Optional[dict] = None):
     loss instead of the cross-entropy -- frame 0 is still first_stage_encode(images[:, 0:1]), frames 1 .. L-1 are policy['tokens']
     (int64 [B, L-1, h, w]); policy['advantage'] (fp32, one per clip or per token), policy['behaviour'] (fp32 per token, or None) and the
     scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h); with
-    policy['reference'] (fp32 per token) and policy['kl_coef'] the pass ends in mage_policy_loss_anchored instead."""
+    policy['reference'] (fp32 per token) and policy['kl_coef'] the pass ends in mage_policy_loss_anchored instead.
+    preference (MAGE.preference_loss; instead of policy): the same pass over frame 0 plus preference['tokens'] (and batch['video_noise'] with
+    the randomness branch), ending in mage_token_logprob (temperature 1, no filter: the model's own distribution), mage_clip_scores (one
+    log-likelihood per clip) and mage_preference_loss over preference['pairs'] (int64 [P, 2]) and preference['reference'] (fp32 [B]) with
+    the scalars beta, label_smoothing and mode (include/mage_hip_ext.h)."""
+    given = policy if policy is not None else preference                      # the branch that scores GIVEN tokens, either way
     images = batch["images"]
     B = images.shape[0]
     R, L, Cc = model.image_resolution, model.frames_length, model.vision_width
@@ -610,10 +615,10 @@ def train_forward(model, batch, policy: Optional[dict] = None):
     dev = images.device
     tok = tok_in = tok0 = lat_all = lat_in = lat0 = None
     if model.use_cids:
-        if policy is None:
+        if given is None:
             tok = model.first_stage_encode(images).reshape(B, -1, hw)                 # frozen first stage: no gradient
         else:
-            tok = torch.cat([model.first_stage_encode(images[:, 0:1]).reshape(B, 1, hw), policy["tokens"].reshape(B, L - 1, hw)], 1)
+            tok = torch.cat([model.first_stage_encode(images[:, 0:1]).reshape(B, 1, hw), given["tokens"].reshape(B, L - 1, hw)], 1)
         tok_in = tok[:, :L - 1].contiguous()
         tok0 = tok[:, 0].contiguous()
         # frame features for the decoder (compute dtype) and, as the inference prologue does, frame 0's in fp32 for the MA encoder
@@ -647,7 +652,7 @@ def train_forward(model, batch, policy: Optional[dict] = None):
     t_rand = None
     if model.randomness:                                                     # :601-609: ADAIN modulation by the reparameterised video prior
         from . import mage_train_prior
-        if policy is not None:
+        if given is not None:
             # the policy is conditioned on the noise its tokens were generated under (batch['video_noise'], recorded by the generation):
             # generation's modulation -- conv_d2, the ADAIN convolutions, ADAIN -- without the Conv3d prior, which generation never runs
             nz = batch["video_noise"].permute(0, 2, 3, 1).reshape(B * hw, 64).contiguous()
@@ -668,6 +673,19 @@ def train_forward(model, batch, policy: Optional[dict] = None):
                               top_p=policy["top_p"])
         recon = res["summary"][0]
         policy = dict(policy, cut=res["cut"], logprob=res["logprob"], summary=res["summary"], kl=res.get("kl"))
+    elif preference is not None:
+        target = tok[:, 1:L].reshape(-1).contiguous()
+        lp = ops.token_logprob(logits, target, torch.empty(target.shape, device=dev, dtype=F32), rows=target.numel(), K=logits.shape[1],
+                               ld=logits.stride(0))
+        clip_lp = ops.clip_scores(lp, n_clips=B)[0].view(B)
+        res = ops.preference_loss(clip_lp, preference["reference"], preference["pairs"], beta=preference["beta"],
+                                  label_smoothing=preference["label_smoothing"], mode=preference["mode"])
+        recon = res["summary"][0]
+        preference = dict(preference, logprob=lp, clip_logprob=clip_lp, **res)
+        parts = dict(zip(("loss", "accuracy", "chosen_reward", "rejected_reward", "margin"), res["summary"].tolist()))
+        tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
+                    logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=0.0, alpha=0.0, parts=parts, preference=preference)
+        return recon, tape
     elif model.use_cids:
         target = tok[:, 1:L].reshape(-1).contiguous()
         recon = ops.cross_entropy(logits, target)                                                            # :618
@@ -713,8 +731,11 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
     dev = tape["logits"].device
     grads: Dict[str, torch.Tensor] = {}
     gout = grad_out.detach().to(device=dev, dtype=F32).reshape(1).contiguous()
-    pol = tape.get("policy")
-    if pol is not None:
+    pol, pref = tape.get("policy"), tape.get("preference")
+    if pref is not None:                                                     # one coefficient per clip: d(mean pair loss) / d(clip log-likelihood)
+        dlogits = ops.token_logprob_bwd(tape["logits"], tape["target"], pref["clip_coef"], gout,
+                                        torch.empty(tape["logits"].shape, device=dev, dtype=dt))
+    elif pol is not None:
         dlogits = ops.policy_loss_bwd(tape["logits"], tape["target"], pol["advantage"], pol["behaviour"], pol["cut"], gout,
                                       torch.empty(tape["logits"].shape, device=dev, dtype=dt), **_policy_scalars(pol))
     elif model.use_cids:
@@ -739,7 +760,7 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
         grads["speed_embedding"] = gs
     if tape["rand"] is not None:
         from . import mage_train_prior
-        if pol is not None:                                                  # the noise is a recorded constant: the ADAIN half, no dz
+        if pol is not None or pref is not None:                              # the noise is a recorded constant: the ADAIN half, no dz
             dma, _ = mage_train_prior.modulate_backward(model, tape["rand"], dma, grads, want_dz=False)
         else:
             kl_coef = (gout * (tape["beta"] / B)).contiguous()
@@ -803,6 +824,24 @@ class MagePolicyLossFn(torch.autograd.Function):
             loss, tape = train_forward(model, batch, policy)
         # for MAGE.policy_loss: the summary, the per-token log-probabilities and (with a reference) KL estimates
         model._last_policy_out = (tape["parts"], tape["policy"]["logprob"], tape["policy"]["kl"])
+        ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
+        ctx.devices = [p.device for p in params]
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (None, *MageLossFn.backward(ctx, grad_out))
+
+
+class MagePreferenceLossFn(torch.autograd.Function):
+    """loss = MagePreferenceLossFn.apply(model, batch, preference, names, *params): MageLossFn's node over train_forward(model, batch,
+    preference=preference); train_backward starts from mage_token_logprob_bwd with the pair stage's clip_coef."""
+
+    @staticmethod
+    def forward(ctx, model, batch, preference, names, *params):
+        with torch.no_grad():
+            loss, tape = train_forward(model, batch, preference=preference)
+        model._last_preference_out = (tape["parts"], tape["preference"])     # for MAGE.preference_loss: the summary and the per-pair results
         ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
         ctx.devices = [p.device for p in params]
         return loss.clone()

@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -686,6 +686,49 @@ def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch
                                                _p(behaviour_logprob), reference_logprob.data_ptr(), cut.data_ptr(), float(temperature),
                                                float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(),
                                                dlogits.data_ptr(), code(dlogits), s), l)
+    return dlogits
+
+
+def preference_loss(clip_logprob: torch.Tensor, reference_logprob: torch.Tensor, pairs: torch.Tensor, *, beta: float = 0.1,
+                    label_smoothing: float = 0.0, mode: int = 0) -> dict:
+    """mage_preference_loss: the pair stage of DPO (mode 0) / IPO (mode 1) over clip_logprob and reference_logprob fp32 [clips] and pairs
+    int64 [n_pairs, 2] (chosen row, rejected row).  Returns fp32 'pair_loss' and 'pair_margin' [n_pairs], 'clip_coef' [clips] (the derivative
+    of the mean loss with respect to clip_logprob: token_logprob_bwd's weights) and 'summary' [5]: the means of the loss, the accuracy, the
+    chosen reward, the rejected reward and the margin."""
+    l, s = _dev(clip_logprob)
+    clips = clip_logprob.numel()
+    for x in (clip_logprob, reference_logprob):
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == clips and x.device == clip_logprob.device
+    assert pairs.dtype == torch.int64 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous()
+    assert pairs.device == clip_logprob.device
+    P = pairs.shape[0]
+    mk = lambda n: torch.empty(n, device=clip_logprob.device, dtype=torch.float32)      # noqa: E731
+    out = dict(pair_loss=mk(P), pair_margin=mk(P), clip_coef=mk(clips), summary=mk(5))
+    _lib.check(l.mage_preference_loss(clip_logprob.data_ptr(), reference_logprob.data_ptr(), clips, pairs.data_ptr(), P, float(beta),
+                                      float(label_smoothing), int(mode), out["pair_loss"].data_ptr(), out["pair_margin"].data_ptr(),
+                                      out["clip_coef"].data_ptr(), out["summary"].data_ptr(), s), l)
+    return out
+
+
+def token_logprob_bwd(logits: torch.Tensor, tokens: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *,
+                      weight_div: Optional[int] = None) -> torch.Tensor:
+    """mage_token_logprob_bwd: dlogits [rows, K] contiguous fp32 or bf16, the gradient of sum_i weight[i // weight_div] * token_logprob_i
+    times grad_out (fp32 [1]) over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows].  weight_div None: weight's entries share
+    the rows out equally (one per row, or one per clip).  Rows of weight 0 are written as zeros without being read."""
+    l, s = _dev(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows, K = logits.shape
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() == rows and tokens.device == logits.device
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.device == logits.device
+    if weight_div is None:
+        assert weight.numel() > 0 and rows % weight.numel() == 0, "one weight per row, or per equal group of consecutive rows"
+        weight_div = rows // weight.numel()
+    assert weight_div > 0 and (rows - 1) // weight_div < weight.numel()      # the largest index addressed
+    assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
+    assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
+    assert dlogits.device == logits.device
+    _lib.check(l.mage_token_logprob_bwd(logits.data_ptr(), rows, K, logits.stride(0), tokens.data_ptr(), weight.data_ptr(), weight_div,
+                                        grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
     return dlogits
 
 
