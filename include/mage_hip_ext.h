@@ -43,7 +43,7 @@ int mage_token_stats(const float* logits, int64_t rows, int32_t K, int64_t ld, i
                      float* policy_logprob, float* policy_entropy, int32_t* kept, float* entropy, void* stream);
 
 /* Policy-gradient loss over given tokens, and its gradient with respect to the logits: no site in the reference (its only objective is the
- * mean cross-entropy).  Serves MAGE.policy_loss (mage_amd/modules/mage_train.py: train_forward / train_backward with a policy).
+ * mean cross-entropy).  Serves MAGE.policy_loss (mage_amd/modules/mage_train.py: train_forward / train_backward with a PolicyHead).
  * Row i is the K fp32 logits z at logits + i*ld with its token t = tokens[i] (int64), its advantage A = advantage[i / adv_div] (fp32;
  * adv_div = 1: one per row, adv_div = rows per clip: one per clip) and, when behaviour_logprob is given, b = behaviour_logprob[i] (fp32:
  * the log-probability under which the token was drawn).  The policy is mage_sample_tokens' under (temperature, top_k, top_p): with
@@ -224,7 +224,7 @@ int mage_guide_logits(const float* cond, const float* uncond, float* out, int64_
                       int64_t in_group_stride, int64_t in_off, const float* scale, int64_t scale_div, void* stream);
 
 /* Preference loss over ranked pairs of clips (DPO / IPO), its pair stage: no site in the reference (its only objective is the mean
- * cross-entropy).  Serves MAGE.preference_loss (mage_amd/modules/mage_train.py: train_forward with preference=, after mage_token_logprob and
+ * cross-entropy).  Serves MAGE.preference_loss (mage_amd/modules/mage_train.py: train_forward with a PreferenceHead, after mage_token_logprob and
  * mage_clip_scores have reduced the logits to one log-likelihood per clip).
  * clip_logprob s and reference_logprob r are fp32 [clips] (a clip's summed token log-probabilities under the model and under the frozen
  * reference); pairs is int64 [n_pairs, 2] on the device, pair p = (w, l): the chosen row and the rejected row.  Everything is computed in

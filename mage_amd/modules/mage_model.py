@@ -16,6 +16,7 @@ products per K slab, fp32 accumulation -- include/mage_hip.h): fp32-class logits
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import gc
 import math
@@ -869,13 +870,12 @@ class MAGE(nn.Module):
         self.last_policy_token_logprobs: Optional[torch.Tensor] = None   # policy_loss: fp32 [B, L-1, h, w], the given tokens under the current policy
         self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
         self.last_video_noise: Optional[torch.Tensor] = None             # randomness: fp32 [B, 64, h, w], the noise the last generation used
-        self._last_policy_out = None
         self.last_preference_clip_logprobs: Optional[torch.Tensor] = None    # preference_loss: fp32 [B], the clips' log-likelihoods under the model
         self.last_preference_clip_coef: Optional[torch.Tensor] = None        # fp32 [B]: d(loss) / d(clip log-likelihood)
         self.last_preference_pair_loss: Optional[torch.Tensor] = None        # fp32 [P]
         self.last_preference_pair_margin: Optional[torch.Tensor] = None      # fp32 [P]: beta * ((s_w - r_w) - (s_l - r_l))
         self.last_preference_token_logprobs: Optional[torch.Tensor] = None   # fp32 [B, L-1, h, w]: the given tokens at temperature 1, no filter
-        self._last_preference_out = None
+        self._last_head_out = None                                       # mage_train.MageLossFn -> _run_head: (loss dict, what the head saved)
         self.guidance: Optional[float] = None                            # set_guidance: the classifier-free guidance scale; None: off
         self.last_guidance_scale: Optional[torch.Tensor] = None          # guidance on: fp32 [B], the per-clip scales the last generation used
         self.caption_dropout = 0.0     # forward in training mode: the probability that a clip's caption is replaced by the null caption
@@ -1112,28 +1112,10 @@ class MAGE(nn.Module):
         plain one in every bit, and last_policy_token_kl is None.
         Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
         from . import mage_train
-        L, R, K = self.frames_length, self.image_resolution, self.codebook_size
-        if not self.use_cids:
-            raise ValueError("policy_loss: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
-        self._refuse_guided("policy_loss")
-        vn = batch.get("video_noise") if self.randomness else None
-        if self.randomness and vn is None:
-            raise ValueError("policy_loss: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
-                             "the noise the tokens were drawn under (last_video_noise of the generation, or rollout's out['batch'])")
-        if self._dt() == torch.float16:
-            raise ValueError("policy_loss: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
+        images, B, tshape, vn = self._given_tokens_inputs("policy_loss", batch, tokens)
         t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
         if k == 1:
             raise ValueError("policy_loss: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient")
-        images = batch["images"]
-        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[1] >= 1):
-            raise ValueError("policy_loss: batch['images'] must be [B, >= 1, C, H, W]")
-        B = images.shape[0]
-        tshape = (B, L - 1, R, R)
-        if vn is not None and not (torch.is_tensor(vn) and vn.dtype == F32 and tuple(vn.shape) == (B, 64, R, R)):
-            raise ValueError(f"policy_loss: batch['video_noise'] must be fp32 {[B, 64, R, R]} (randomness=True: the tokens' generation noise)")
-        if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
-            raise ValueError(f"policy_loss: tokens must be int64 {list(tshape)}")
         if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape)):
             raise ValueError(f"policy_loss: advantages must be fp32 [{B}] or {list(tshape)}")
         b = behaviour_logprobs
@@ -1156,30 +1138,78 @@ class MAGE(nn.Module):
             raise ValueError(f"policy_loss: kl_coef must be finite and >= 0, got {kl_coef!r}")
         if kl_coef > 0 and ref is None:
             raise ValueError("policy_loss: kl_coef > 0 needs reference_logprobs (the penalty is against a reference policy)")
-        for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("advantages", advantages),
-                        ("behaviour_logprobs", b), ("reference_logprobs", ref), ("batch['video_noise']", vn)):
-            if x is not None and not (x.is_cuda and x.device == images.device):
-                raise ValueError(f"policy_loss: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
-        policy = dict(tokens=tokens.contiguous(), advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo,
-                      clip_hi=hi, entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
+        self._refuse_off_gpu("policy_loss", batch, images, tokens, vn, (("advantages", advantages), ("behaviour_logprobs", b),
+                                                                       ("reference_logprobs", ref)))
+        args = dict(advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo, clip_hi=hi,
+                    entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
         if ref is not None:
-            policy.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
+            args.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
         with torch.cuda.device(images.device):
-            if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
-                names = mage_train.trainable_names(self)
-                byname = dict(self.named_parameters())
-                loss = mage_train.MagePolicyLossFn.apply(self, batch, policy, names, *[byname[n] for n in names])
-                info, lp, kl = self._last_policy_out
-                self._last_policy_out = None
-            else:
-                with torch.no_grad():
-                    loss, tape = mage_train.train_forward(self, batch, policy)
-                info, lp, kl = tape["parts"], tape["policy"]["logprob"], tape["policy"]["kl"]
-                loss, tape = loss.clone(), None
-            self.last_policy_token_logprobs = lp.view(tshape)
-            self.last_policy_token_kl = None if kl is None else kl.view(tshape)
+            loss, (info, res) = self._run_head(batch, mage_train.PolicyHead(tokens.contiguous(), **args))
+            self.last_policy_token_logprobs = res["logprob"].view(tshape)
+            self.last_policy_token_kl = None if res.get("kl") is None else res["kl"].view(tshape)
             ops.check_device_errors(images.device)
         return loss, info
+
+    def _given_tokens_inputs(self, who, batch, tokens):
+        """The refusals every pass over given tokens shares (policy_loss and preference_loss, under the name `who`), all before the first
+        launch.  Returns (images, B, the tokens' shape (B, L-1, h, w), batch['video_noise'] on a randomness=True model or None)."""
+        L, R = self.frames_length, self.image_resolution
+        if not self.use_cids:
+            raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        self._refuse_guided(who)
+        if not isinstance(batch, dict):
+            raise ValueError(f"{who}: batch must be a dict with 'images' and 'text'")
+        vn = batch.get("video_noise") if self.randomness else None
+        if self.randomness and vn is None:
+            raise ValueError(f"{who}: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
+                             "the noise the tokens were drawn under (last_video_noise of the generation, or rollout's out['batch'])")
+        if self._dt() == torch.float16:
+            raise ValueError(f"{who}: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
+        images = batch.get("images")
+        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1 and images.shape[1] >= 1):
+            raise ValueError(f"{who}: batch['images'] must be [B, >= 1, C, H, W]")
+        B = images.shape[0]
+        tshape = (B, L - 1, R, R)
+        if vn is not None and not (torch.is_tensor(vn) and vn.dtype == F32 and tuple(vn.shape) == (B, 64, R, R)):
+            raise ValueError(f"{who}: batch['video_noise'] must be fp32 {[B, 64, R, R]} (randomness=True: the tokens' generation noise)")
+        if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
+            raise ValueError(f"{who}: tokens must be int64 {list(tshape)}")
+        return images, B, tshape, vn
+
+    @staticmethod
+    def _refuse_off_gpu(who, batch, images, tokens, vn, own):
+        """The last refusal of a pass over given tokens: the batch's tensors, the tokens and the method's `own` (name, tensor) arguments."""
+        for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), *own, ("batch['video_noise']", vn)):
+            if x is not None and not (x.is_cuda and x.device == images.device):
+                raise ValueError(f"{who}: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+
+    def _run_head(self, batch, head):
+        """One mage_train pass ending in `head` (None: forward's own): (loss, (loss dict, what the head saved)).  In grad mode (any parameter
+        requiring grad) the loss carries the autograd node over the trainable parameters; under torch.no_grad(): values only."""
+        from . import mage_train
+        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+            names = mage_train.trainable_names(self)
+            byname = dict(self.named_parameters())
+            loss = mage_train.MageLossFn.apply(self, batch, head, names, *[byname[n] for n in names])
+            out, self._last_head_out = self._last_head_out, None
+            return loss, out
+        with torch.no_grad():
+            loss, tape = mage_train.train_forward(self, batch, head)
+        return loss.clone(), (tape["parts"], tape["saved"])
+
+    @contextlib.contextmanager
+    def _last_results_kept(self):
+        """Every last_* result is left as found: what the block adds is removed, what it overwrites is put back."""
+        last = lambda: {a: v for a, v in vars(self).items() if a.startswith("last_")}      # noqa: E731
+        keep = last()
+        try:
+            yield
+        finally:
+            for a in last().keys() - keep.keys():
+                delattr(self, a)
+            for a, v in keep.items():
+                setattr(self, a, v)
 
     @torch.no_grad()
     def token_policy_logprobs(self, batch, tokens) -> torch.Tensor:
@@ -1191,15 +1221,9 @@ class MAGE(nn.Module):
         images = batch["images"] if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("token_policy_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
-        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
-        try:
+        with self._last_results_kept():
             self.policy_loss(batch, tokens, torch.zeros(images.shape[0], device=images.device, dtype=F32))
             return self.last_policy_token_logprobs
-        finally:
-            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
-                delattr(self, a)
-            for a, v in keep.items():
-                setattr(self, a, v)
 
     _PREFERENCE_LOSSES = {"sigmoid": 0, "ipo": 1}
 
@@ -1227,27 +1251,7 @@ class MAGE(nn.Module):
     def _preference(self, who, batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss):
         """preference_loss under the name `who` (clip_logprobs runs it too); every refusal comes before the first launch."""
         from . import mage_train
-        L, R = self.frames_length, self.image_resolution
-        if not self.use_cids:
-            raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
-        self._refuse_guided(who)
-        if not isinstance(batch, dict):
-            raise ValueError(f"{who}: batch must be a dict with 'images' and 'text'")
-        vn = batch.get("video_noise") if self.randomness else None
-        if self.randomness and vn is None:
-            raise ValueError(f"{who}: randomness=True conditions the policy on the generation-time noise: batch['video_noise'] must hold "
-                             "the noise the tokens were drawn under (last_video_noise of the generation, or rollout's out['batch'])")
-        if self._dt() == torch.float16:
-            raise ValueError(f"{who}: precision 'f16' is a generation mode: train with set_precision('bf16') or 'fp32'")
-        images = batch.get("images")
-        if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1 and images.shape[1] >= 1):
-            raise ValueError(f"{who}: batch['images'] must be [B, >= 1, C, H, W]")
-        B = images.shape[0]
-        tshape = (B, L - 1, R, R)
-        if vn is not None and not (torch.is_tensor(vn) and vn.dtype == F32 and tuple(vn.shape) == (B, 64, R, R)):
-            raise ValueError(f"{who}: batch['video_noise'] must be fp32 {[B, 64, R, R]} (randomness=True: the tokens' generation noise)")
-        if not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tuple(tokens.shape) == tshape):
-            raise ValueError(f"{who}: tokens must be int64 {list(tshape)}")
+        images, B, tshape, vn = self._given_tokens_inputs(who, batch, tokens)
         if not (torch.is_tensor(pairs) and pairs.dtype == torch.int64 and pairs.dim() == 2 and pairs.shape[1] == 2
                 and 1 <= pairs.shape[0] <= 65536):
             raise ValueError(f"{who}: pairs must be int64 [P, 2] (chosen row, rejected row) with 1 <= P <= 65536")
@@ -1265,24 +1269,11 @@ class MAGE(nn.Module):
             raise ValueError(f"{who}: label_smoothing must lie in [0, 0.5), got {label_smoothing!r}")
         if loss == "ipo" and label_smoothing != 0:
             raise ValueError(f"{who}: label_smoothing is the sigmoid loss's; loss='ipo' takes 0, got {label_smoothing!r}")
-        for name, x in (("batch['images']", images), ("batch['text']", batch["text"]), ("tokens", tokens), ("pairs", pairs),
-                        ("reference_logprobs", ref), ("batch['video_noise']", vn)):
-            if x is not None and not (x.is_cuda and x.device == images.device):
-                raise ValueError(f"{who}: {name} must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
-        pref = dict(tokens=tokens.contiguous(), pairs=pairs.contiguous(), reference=ref.contiguous(), beta=float(beta),
-                    label_smoothing=float(label_smoothing), mode=self._PREFERENCE_LOSSES[loss])
+        self._refuse_off_gpu(who, batch, images, tokens, vn, (("pairs", pairs), ("reference_logprobs", ref)))
+        head = mage_train.PreferenceHead(tokens.contiguous(), pairs=pairs.contiguous(), reference=ref.contiguous(), beta=float(beta),
+                                         label_smoothing=float(label_smoothing), mode=self._PREFERENCE_LOSSES[loss])
         with torch.cuda.device(images.device):
-            if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
-                names = mage_train.trainable_names(self)
-                byname = dict(self.named_parameters())
-                val = mage_train.MagePreferenceLossFn.apply(self, batch, pref, names, *[byname[n] for n in names])
-                info, res = self._last_preference_out
-                self._last_preference_out = None
-            else:
-                with torch.no_grad():
-                    val, tape = mage_train.train_forward(self, batch, preference=pref)
-                info, res = tape["parts"], tape["preference"]
-                val, tape = val.clone(), None
+            val, (info, res) = self._run_head(batch, head)
             self.last_preference_clip_logprobs = res["clip_logprob"]
             self.last_preference_clip_coef = res["clip_coef"]
             self.last_preference_pair_loss = res["pair_loss"]
@@ -1300,16 +1291,10 @@ class MAGE(nn.Module):
         images = batch.get("images") if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("clip_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
-        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
-        try:
+        with self._last_results_kept():
             self._preference("clip_logprobs", batch, tokens, torch.zeros(1, 2, device=images.device, dtype=torch.int64),   # (0, 0): no preference
                              torch.zeros(images.shape[0], device=images.device, dtype=F32), 1.0, 0.0, "sigmoid")
             return self.last_preference_clip_logprobs
-        finally:
-            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
-                delattr(self, a)
-            for a, v in keep.items():
-                setattr(self, a, v)
 
     @torch.no_grad()
     def video_metrics(self, video, target, data_range: float = 2.0) -> dict:
@@ -1422,57 +1407,53 @@ class MAGE(nn.Module):
             if next(reference.parameters()).device != images.device:
                 raise ValueError("rollout: the reference model must be on the same GPU as the batch")
         Bc = images.shape[0]
-        keep = {a: v for a, v in vars(self).items() if a.startswith("last_")}
         settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
-        try:
-            self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
-            b = self._sample_seeds(self._noise_seeds(batch))
-            with torch.cuda.device(images.device), weights_frozen():
-                self.last_video_noise = None
-                out = self._generate_one(b, keep_all=True, candidate_noise=noise == "candidate")
-                seeds = (b["sample_seed"][:, None] + torch.arange(N, device=images.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
-                rep = {k: (v.repeat_interleave(N, 0) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == Bc else v) for k, v in batch.items()
-                       if k not in ("images", "sample_seed", "noise_seed")}
-                out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": seeds}
-                out["seeds"] = seeds
-                if self.randomness:                      # the noise every row was drawn under: what policy_loss conditions on
-                    vn = self.last_video_noise
-                    out["video_noise"] = out["batch"]["video_noise"] = vn if vn.shape[0] == Bc * N else vn.repeat_interleave(N, 0)
-                video = out["video"]
-                if builtin:
-                    gen = video[:, 1:] if video.dtype == F32 else video[:, 1:].float()
-                    fm = out["frame_metrics"] = ops.video_metrics(gen, images[:, 1:L], tgt_div=N, data_range=2.0)
-                    fr = fm[reward] if reward != "neg_mse" else -fm["mse"]
-                else:
-                    out["frame_metrics"] = None
-                    fr = reward(video, out["batch"])
-                    if not (torch.is_tensor(fr) and fr.dtype == F32 and tuple(fr.shape) == (Bc * N,) and fr.device == images.device):
-                        raise ValueError(f"rollout: the reward callable must return fp32 [{Bc * N}] on the model's GPU")
-                    fr = fr.contiguous()
-                out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
-                out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
-                if reference is not None:
-                    theirs = (getattr(reference, "sampling", None), reference.candidates)
-                    try:
-                        reference.sampling, reference.candidates = self.sampling, 1
-                        out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"])
-                    finally:
-                        reference.sampling, reference.candidates = theirs
-                if pairs is not None:
-                    rw = out["rewards"].view(Bc, N)
-                    hi, lo = rw.argmax(1), rw.argmin(1)
-                    lo = torch.where(rw.amax(1) == rw.amin(1), hi, lo)           # all rewards equal: (i, i), no preference
-                    base = torch.arange(Bc, device=images.device, dtype=torch.int64) * N
-                    out["pairs"] = torch.stack([base + hi, base + lo], 1).contiguous()
+        with self._last_results_kept():
+            try:
+                self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
+                b = self._sample_seeds(self._noise_seeds(batch))
+                with torch.cuda.device(images.device), weights_frozen():
+                    self.last_video_noise = None
+                    out = self._generate_one(b, keep_all=True, candidate_noise=noise == "candidate")
+                    seeds = (b["sample_seed"][:, None] + torch.arange(N, device=images.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
+                    rep = {k: (v.repeat_interleave(N, 0) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == Bc else v) for k, v in batch.items()
+                           if k not in ("images", "sample_seed", "noise_seed")}
+                    out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": seeds}
+                    out["seeds"] = seeds
+                    if self.randomness:                      # the noise every row was drawn under: what policy_loss conditions on
+                        vn = self.last_video_noise
+                        out["video_noise"] = out["batch"]["video_noise"] = vn if vn.shape[0] == Bc * N else vn.repeat_interleave(N, 0)
+                    video = out["video"]
+                    if builtin:
+                        gen = video[:, 1:] if video.dtype == F32 else video[:, 1:].float()
+                        fm = out["frame_metrics"] = ops.video_metrics(gen, images[:, 1:L], tgt_div=N, data_range=2.0)
+                        fr = fm[reward] if reward != "neg_mse" else -fm["mse"]
+                    else:
+                        out["frame_metrics"] = None
+                        fr = reward(video, out["batch"])
+                        if not (torch.is_tensor(fr) and fr.dtype == F32 and tuple(fr.shape) == (Bc * N,) and fr.device == images.device):
+                            raise ValueError(f"rollout: the reward callable must return fp32 [{Bc * N}] on the model's GPU")
+                        fr = fr.contiguous()
+                    out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
+                    out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
                     if reference is not None:
-                        out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"])
-                ops.check_device_errors(images.device)
-        finally:
-            self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings
-            for a in [a for a in vars(self) if a.startswith("last_") and a not in keep]:
-                delattr(self, a)
-            for a, v in keep.items():
-                setattr(self, a, v)
+                        theirs = (getattr(reference, "sampling", None), reference.candidates)
+                        try:
+                            reference.sampling, reference.candidates = self.sampling, 1
+                            out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"])
+                        finally:
+                            reference.sampling, reference.candidates = theirs
+                    if pairs is not None:
+                        rw = out["rewards"].view(Bc, N)
+                        hi, lo = rw.argmax(1), rw.argmin(1)
+                        lo = torch.where(rw.amax(1) == rw.amin(1), hi, lo)           # all rewards equal: (i, i), no preference
+                        base = torch.arange(Bc, device=images.device, dtype=torch.int64) * N
+                        out["pairs"] = torch.stack([base + hi, base + lo], 1).contiguous()
+                        if reference is not None:
+                            out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"])
+                    ops.check_device_errors(images.device)
+            finally:
+                self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings
         return out
 
     def _sample_seeds(self, batch) -> dict:
@@ -2271,16 +2252,13 @@ class MAGE(nn.Module):
 
     def _forward_with_graph(self, batch):
         """Grad mode (the training loop, main_mage.py:150-153): the same pass as one autograd node whose inputs are the trainable
-        parameters (mage_train.MageLossFn), so that ``loss.backward()`` fills every ``.grad`` from the HIP backward kernels."""
-        from . import mage_train
+        parameters (mage_train.MageLossFn, through _run_head), so that ``loss.backward()`` fills every ``.grad`` from the HIP backward kernels."""
         _need_gpu(batch["images"], "MAGE.forward")
         with torch.cuda.device(batch["images"].device):
-            names = mage_train.trainable_names(self)
-            byname = dict(self.named_parameters())
-            loss = mage_train.MageLossFn.apply(self, batch, names, *[byname[n] for n in names])
+            loss, (parts, _) = self._run_head(batch, None)
             prefix = "train" if self.training else "val"
             ops.check_device_errors(batch["images"].device)
-        return loss, {f"{prefix}/{k}": v for k, v in self._last_train_parts.items()}
+        return loss, {f"{prefix}/{k}": v for k, v in parts.items()}
 
     def _drop_captions(self, batch) -> dict:
         """Caption dropout at the top of forward (see there): the batch with the dropped rows of 'text' replaced by their null caption (one

@@ -583,20 +583,94 @@ def _policy_scalars(policy: dict) -> dict:
     return kw
 
 
-def train_forward(model, batch, policy: Optional[dict] = None, preference: Optional[dict] = None):
+# Loss heads: what train_forward ends in and train_backward starts from.  A head has `tokens` (None: the pass runs over the batch's own video;
+# int64 [B, L-1, h, w]: over frame 0 plus these GIVEN tokens), forward(model, logits, target, B) -> (loss, parts, saved) and
+# backward(logits, target, saved, gout, dt) -> d loss / d logits in dt.  parts is the loss dict the MAGE method reports, saved whatever backward
+# and the method need besides; both travel back to the method as model._last_head_out = (parts, saved).
+def _dlogits(logits, dt):
+    return torch.empty(logits.shape, device=logits.device, dtype=dt)
+
+
+class CrossEntropyHead:
+    """forward on a use_cids model (mage_model.py:618)."""
+    tokens = None
+
+    def forward(self, model, logits, target, B):
+        loss = ops.cross_entropy(logits, target)
+        return loss, {"prediction": loss.item()}, None
+
+    def backward(self, logits, target, saved, gout, dt):
+        return ops.cross_entropy_bwd(logits, target, gout, _dlogits(logits, dt))
+
+
+class MseHead:
+    """forward on a MAGE+ model (mage_model.py:620): `logits` are the predicted latents, kept as model.last_logits."""
+    tokens = None
+
+    def forward(self, model, logits, target, B):
+        E = model.first_stage_model.embed_dim
+        loss = ops.mse(logits, target, rows=logits.shape[0], cols=E, lda=logits.shape[1], ldb=8)
+        model.last_logits = logits
+        return loss, {"prediction": loss.item()}, E
+
+    def backward(self, logits, target, saved, gout, dt):
+        g = ops.mse_bwd(logits, target, gout, rows=logits.shape[0], cols=saved, lda=logits.shape[1], ldb=8)
+        return g if dt == F32 else ops.cast(g, _dlogits(g, dt))
+
+
+class PolicyHead:
+    """MAGE.policy_loss: mage_policy_loss over the given tokens, or mage_policy_loss_anchored when args holds a 'reference' (_policy_scalars'
+    rule).  args: advantage (fp32, one per clip or per token), behaviour (fp32 per token, or None) and the scalars temperature, top_k, top_p,
+    clip_lo, clip_hi, entropy_coef [, reference (fp32 per token), kl_coef] of include/mage_hip_ext.h.  saved: the kernel's results
+    (cut, logprob, summary [, kl])."""
+    PARTS = ("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction")
+
+    def __init__(self, tokens, **args):
+        self.tokens, self.args = tokens, args
+
+    def forward(self, model, logits, target, B):
+        a = self.args
+        res = ops.policy_loss(logits, target, a["advantage"], a["behaviour"], **_policy_scalars(a), top_k=a["top_k"], top_p=a["top_p"])
+        return res["summary"][0], dict(zip(self.PARTS, res["summary"].tolist())), res
+
+    def backward(self, logits, target, saved, gout, dt):
+        a = self.args
+        return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **_policy_scalars(a))
+
+
+class PreferenceHead:
+    """MAGE.preference_loss: mage_token_logprob (temperature 1, no filter: the model's own distribution), mage_clip_scores (one log-likelihood
+    per clip) and mage_preference_loss over args' pairs (int64 [P, 2]) and reference (fp32 [B]) with the scalars beta, label_smoothing and mode
+    (include/mage_hip_ext.h); backward is mage_token_logprob_bwd with the pair stage's one coefficient per clip.  saved: the pair stage's
+    results plus logprob and clip_logprob."""
+    PARTS = ("loss", "accuracy", "chosen_reward", "rejected_reward", "margin")
+
+    def __init__(self, tokens, **args):
+        self.tokens, self.args = tokens, args
+
+    def forward(self, model, logits, target, B):
+        a = self.args
+        lp = ops.token_logprob(logits, target, torch.empty(target.shape, device=logits.device, dtype=F32), rows=target.numel(), K=logits.shape[1],
+                               ld=logits.stride(0))
+        clip_lp = ops.clip_scores(lp, n_clips=B)[0].view(B)
+        res = ops.preference_loss(clip_lp, a["reference"], a["pairs"], beta=a["beta"], label_smoothing=a["label_smoothing"], mode=a["mode"])
+        return res["summary"][0], dict(zip(self.PARTS, res["summary"].tolist())), dict(res, logprob=lp, clip_logprob=clip_lp)
+
+    def backward(self, logits, target, saved, gout, dt):
+        return ops.token_logprob_bwd(logits, target, saved["clip_coef"], gout, _dlogits(logits, dt))
+
+
+def train_forward(model, batch, head=None):
     """Teacher-forced pass of MAGE.forward (mage_model.py:575-639) with the activations the backward pass needs.
     Returns (loss 0-dim fp32 tensor, tape).
-    policy (MAGE.policy_loss; use_cids models; with the randomness branch batch['video_noise'] fp32 [B, 64, h, w] is the recorded
-    generation-time noise that modulates the motion anchor in place of the reparameterised video prior): the pass runs over GIVEN tokens and ends in the policy-gradient
-    loss instead of the cross-entropy -- frame 0 is still first_stage_encode(images[:, 0:1]), frames 1 .. L-1 are policy['tokens']
-    (int64 [B, L-1, h, w]); policy['advantage'] (fp32, one per clip or per token), policy['behaviour'] (fp32 per token, or None) and the
-    scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef are mage_policy_loss' arguments (include/mage_hip_ext.h); with
-    policy['reference'] (fp32 per token) and policy['kl_coef'] the pass ends in mage_policy_loss_anchored instead.
-    preference (MAGE.preference_loss; instead of policy): the same pass over frame 0 plus preference['tokens'] (and batch['video_noise'] with
-    the randomness branch), ending in mage_token_logprob (temperature 1, no filter: the model's own distribution), mage_clip_scores (one
-    log-likelihood per clip) and mage_preference_loss over preference['pairs'] (int64 [P, 2]) and preference['reference'] (fp32 [B]) with
-    the scalars beta, label_smoothing and mode (include/mage_hip_ext.h)."""
-    given = policy if policy is not None else preference                      # the branch that scores GIVEN tokens, either way
+    head: the loss head the pass ends in (above); None: the model's own, CrossEntropyHead or MseHead.  With head.tokens None the pass runs over
+    the batch's own video and the loss gains forward's randomness terms (the prior's KL under beta, the PID, the speed l2 under alpha).  With
+    given tokens (use_cids models) frame 0 is still first_stage_encode(images[:, 0:1]) and frames 1 .. L-1 are head.tokens; the loss is the
+    head's alone (beta = alpha = 0), and with the randomness branch batch['video_noise'] (fp32 [B, 64, h, w], the recorded generation-time
+    noise) modulates the motion anchor in place of the reparameterised video prior."""
+    if head is None:
+        head = CrossEntropyHead() if model.use_cids else MseHead()
+    given = head.tokens is not None
     images = batch["images"]
     B = images.shape[0]
     R, L, Cc = model.image_resolution, model.frames_length, model.vision_width
@@ -615,10 +689,10 @@ def train_forward(model, batch, policy: Optional[dict] = None, preference: Optio
     dev = images.device
     tok = tok_in = tok0 = lat_all = lat_in = lat0 = None
     if model.use_cids:
-        if given is None:
-            tok = model.first_stage_encode(images).reshape(B, -1, hw)                 # frozen first stage: no gradient
+        if given:
+            tok = torch.cat([model.first_stage_encode(images[:, 0:1]).reshape(B, 1, hw), head.tokens.reshape(B, L - 1, hw)], 1)
         else:
-            tok = torch.cat([model.first_stage_encode(images[:, 0:1]).reshape(B, 1, hw), given["tokens"].reshape(B, L - 1, hw)], 1)
+            tok = model.first_stage_encode(images).reshape(B, -1, hw)                 # frozen first stage: no gradient
         tok_in = tok[:, :L - 1].contiguous()
         tok0 = tok[:, 0].contiguous()
         # frame features for the decoder (compute dtype) and, as the inference prologue does, frame 0's in fp32 for the MA encoder
@@ -652,7 +726,7 @@ def train_forward(model, batch, policy: Optional[dict] = None, preference: Optio
     t_rand = None
     if model.randomness:                                                     # :601-609: ADAIN modulation by the reparameterised video prior
         from . import mage_train_prior
-        if given is not None:
+        if given:
             # the policy is conditioned on the noise its tokens were generated under (batch['video_noise'], recorded by the generation):
             # generation's modulation -- conv_d2, the ADAIN convolutions, ADAIN -- without the Conv3d prior, which generation never runs
             nz = batch["video_noise"].permute(0, 2, 3, 1).reshape(B * hw, 64).contiguous()
@@ -667,57 +741,30 @@ def train_forward(model, batch, policy: Optional[dict] = None, preference: Optio
         ops.add_scaled_rowvec(ma, speed, d["speed"], B=B, P=hw, Cc=Cc)
     ma_dt = ma if dt == F32 else ma.to(dt)
     logits, t_dec = _dec_forward(model.generate_model, run, ma_dt, feats, B, R, R)
-    if policy is not None:
+    if model.use_cids:
         target = tok[:, 1:L].reshape(-1).contiguous()
-        res = ops.policy_loss(logits, target, policy["advantage"], policy["behaviour"], **_policy_scalars(policy), top_k=policy["top_k"],
-                              top_p=policy["top_p"])
-        recon = res["summary"][0]
-        policy = dict(policy, cut=res["cut"], logprob=res["logprob"], summary=res["summary"], kl=res.get("kl"))
-    elif preference is not None:
-        target = tok[:, 1:L].reshape(-1).contiguous()
-        lp = ops.token_logprob(logits, target, torch.empty(target.shape, device=dev, dtype=F32), rows=target.numel(), K=logits.shape[1],
-                               ld=logits.stride(0))
-        clip_lp = ops.clip_scores(lp, n_clips=B)[0].view(B)
-        res = ops.preference_loss(clip_lp, preference["reference"], preference["pairs"], beta=preference["beta"],
-                                  label_smoothing=preference["label_smoothing"], mode=preference["mode"])
-        recon = res["summary"][0]
-        preference = dict(preference, logprob=lp, clip_logprob=clip_lp, **res)
-        parts = dict(zip(("loss", "accuracy", "chosen_reward", "rejected_reward", "margin"), res["summary"].tolist()))
-        tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
-                    logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=0.0, alpha=0.0, parts=parts, preference=preference)
-        return recon, tape
-    elif model.use_cids:
-        target = tok[:, 1:L].reshape(-1).contiguous()
-        recon = ops.cross_entropy(logits, target)                                                            # :618
     else:
         target = lat_all[:, 1:L].contiguous().view(-1, 8)
-        recon = ops.mse(logits, target, rows=B * (L - 1) * hw, cols=model.first_stage_model.embed_dim, lda=logits.shape[1], ldb=8)   # :620
-        model.last_logits = logits
-    if policy is not None:
-        parts = dict(zip(("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction"),
-                         policy["summary"].tolist()))
-        tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=None, lat0=None, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
-                    logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=0.0, alpha=0.0, parts=parts, policy=policy)
-        return recon, tape
-    loss, parts = recon, {"prediction": recon.item()}
-    beta = alpha = 0.0
-    if model.randomness:                                                     # :622-632 ([B]-element reductions and scalars)
-        kl = -0.5 * t_rand["kl_sum"].mean()
-        parts["kl_loss"] = kl.item()
-        if model.auto_beta:
-            model.beta, _ = model.PID.pid(model.KL_loss, parts["kl_loss"])
-            parts["beta"] = model.beta
-            beta = float(model.beta)
-            loss = recon + beta * kl
-        else:
-            if speed is None:
-                raise KeyError("MAGE.forward with randomness=True and auto_beta=False needs batch['speed'] (mage_model.py:631)")
-            beta, alpha = float(model.beta), float(model.alpha)
-            l2 = (speed ** 2).mean() * (d["speed"] ** 2).sum()
-            loss = recon + beta * kl + alpha * l2
-    parts["final_loss"] = loss.item()
+    recon, parts, saved = head.forward(model, logits, target, B)
+    loss, beta, alpha = recon, 0.0, 0.0
+    if not given:                                                            # forward's own terms; a given-tokens head's loss is final
+        if model.randomness:                                                 # :622-632 ([B]-element reductions and scalars)
+            kl = -0.5 * t_rand["kl_sum"].mean()
+            parts["kl_loss"] = kl.item()
+            if model.auto_beta:
+                model.beta, _ = model.PID.pid(model.KL_loss, parts["kl_loss"])
+                parts["beta"] = model.beta
+                beta = float(model.beta)
+                loss = recon + beta * kl
+            else:
+                if speed is None:
+                    raise KeyError("MAGE.forward with randomness=True and auto_beta=False needs batch['speed'] (mage_model.py:631)")
+                beta, alpha = float(model.beta), float(model.alpha)
+                l2 = (speed ** 2).mean() * (d["speed"] ** 2).sum()
+                loss = recon + beta * kl + alpha * l2
+        parts["final_loss"] = loss.item()
     tape = dict(run=run, run32=run32, tok_in=tok_in, tok0=tok0, lat_in=lat_in, lat0=lat0, emb=emb, emb0=emb0, text=t_text, ma=t_ma, dec=t_dec,
-                logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=beta, alpha=alpha, parts=parts)
+                logits=logits, target=target, speed=speed, B=B, rand=t_rand, beta=beta, alpha=alpha, parts=parts, head=head, saved=saved)
     return loss, tape
 
 
@@ -731,19 +778,8 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
     dev = tape["logits"].device
     grads: Dict[str, torch.Tensor] = {}
     gout = grad_out.detach().to(device=dev, dtype=F32).reshape(1).contiguous()
-    pol, pref = tape.get("policy"), tape.get("preference")
-    if pref is not None:                                                     # one coefficient per clip: d(mean pair loss) / d(clip log-likelihood)
-        dlogits = ops.token_logprob_bwd(tape["logits"], tape["target"], pref["clip_coef"], gout,
-                                        torch.empty(tape["logits"].shape, device=dev, dtype=dt))
-    elif pol is not None:
-        dlogits = ops.policy_loss_bwd(tape["logits"], tape["target"], pol["advantage"], pol["behaviour"], pol["cut"], gout,
-                                      torch.empty(tape["logits"].shape, device=dev, dtype=dt), **_policy_scalars(pol))
-    elif model.use_cids:
-        dlogits = ops.cross_entropy_bwd(tape["logits"], tape["target"], gout, torch.empty(tape["logits"].shape, device=dev, dtype=dt))
-    else:
-        pred = tape["logits"]
-        dlogits = _to_dt(run, ops.mse_bwd(pred, tape["target"], gout, rows=pred.shape[0], cols=model.first_stage_model.embed_dim,
-                                          lda=pred.shape[1], ldb=8))
+    head = tape["head"]
+    dlogits = head.backward(tape["logits"], tape["target"], tape["saved"], gout, dt)
     tape["logits"] = None
     dfeats, dma = _dec_backward(model.generate_model, run, tape["dec"], dlogits, grads)
     del dlogits
@@ -760,7 +796,7 @@ def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tenso
         grads["speed_embedding"] = gs
     if tape["rand"] is not None:
         from . import mage_train_prior
-        if pol is not None or pref is not None:                              # the noise is a recorded constant: the ADAIN half, no dz
+        if head.tokens is not None:                                          # given tokens: the noise is a recorded constant: the ADAIN half, no dz
             dma, _ = mage_train_prior.modulate_backward(model, tape["rand"], dma, grads, want_dz=False)
         else:
             kl_coef = (gout * (tape["beta"] / B)).contiguous()
@@ -790,13 +826,15 @@ def trainable_names(model):
 
 
 class MageLossFn(torch.autograd.Function):
-    """loss = MageLossFn.apply(model, batch, names, *params): autograd sees one node whose inputs are the trainable parameters."""
+    """loss = MageLossFn.apply(model, batch, head, names, *params): autograd sees one node whose inputs are the trainable parameters.
+    head: train_forward's.  What the MAGE method reads back -- the loss dict (the reference's loss_dict values, without the prefix) and what the
+    head saved -- is left in model._last_head_out for it to take and clear."""
 
     @staticmethod
-    def forward(ctx, model, batch, names, *params):
+    def forward(ctx, model, batch, head, names, *params):
         with torch.no_grad():
-            loss, tape = train_forward(model, batch)
-        model._last_train_parts = tape["parts"]                              # the reference's loss_dict values (without the prefix)
+            loss, tape = train_forward(model, batch, head)
+        model._last_head_out = (tape["parts"], tape["saved"])
         ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
         ctx.devices = [p.device for p in params]
         return loss.clone()
@@ -812,40 +850,4 @@ class MageLossFn(torch.autograd.Function):
         for n, shp, dev in zip(ctx.names, ctx.shapes, ctx.devices):
             g = grads.get(n)
             out.append(g.reshape(shp) if g is not None else torch.zeros(shp, device=dev, dtype=F32))     # ln_q / ln_kv: unused -> 0
-        return (None, None, None, *out)
-
-
-class MagePolicyLossFn(torch.autograd.Function):
-    """loss = MagePolicyLossFn.apply(model, batch, policy, names, *params): MageLossFn's node over train_forward(model, batch, policy)."""
-
-    @staticmethod
-    def forward(ctx, model, batch, policy, names, *params):
-        with torch.no_grad():
-            loss, tape = train_forward(model, batch, policy)
-        # for MAGE.policy_loss: the summary, the per-token log-probabilities and (with a reference) KL estimates
-        model._last_policy_out = (tape["parts"], tape["policy"]["logprob"], tape["policy"]["kl"])
-        ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
-        ctx.devices = [p.device for p in params]
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        return (None, *MageLossFn.backward(ctx, grad_out))
-
-
-class MagePreferenceLossFn(torch.autograd.Function):
-    """loss = MagePreferenceLossFn.apply(model, batch, preference, names, *params): MageLossFn's node over train_forward(model, batch,
-    preference=preference); train_backward starts from mage_token_logprob_bwd with the pair stage's clip_coef."""
-
-    @staticmethod
-    def forward(ctx, model, batch, preference, names, *params):
-        with torch.no_grad():
-            loss, tape = train_forward(model, batch, preference=preference)
-        model._last_preference_out = (tape["parts"], tape["preference"])     # for MAGE.preference_loss: the summary and the per-pair results
-        ctx.model, ctx.tape, ctx.names, ctx.shapes = model, tape, names, [p.shape for p in params]
-        ctx.devices = [p.device for p in params]
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        return (None, *MageLossFn.backward(ctx, grad_out))
+        return (None, None, None, None, *out)

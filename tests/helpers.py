@@ -173,6 +173,24 @@ def within(entry, name, got, ref, bound):
                           f"(ref {float(ref.expand_as(err).flatten()[w]):.9e}, got {float(got.flatten()[w]):.9e})")
 
 
+def count_lib_calls(monkeypatch, lib=None):
+    """Every C-ABI entry point of `lib` (default: the library of GPU 0) appends its name to the returned list when called; monkeypatch.undo()
+    ends the counting."""
+    from mage_amd import _lib
+    lib = _lib.lib(0) if lib is None else lib
+    calls = []
+
+    def counted(name, fn):
+        def f(*a):
+            calls.append(name)
+            return fn(*a)
+        return f
+    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
+        if name not in ("mage_last_error", "mage_abi_version"):
+            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    return calls
+
+
 def refused(call, *outs):
     with pytest.raises(ValueError):
         call()

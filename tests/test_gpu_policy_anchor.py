@@ -9,11 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from mage_amd import _lib
 from mage_amd.optim import FlatAdam
 from mage_amd.utils import synth
 from oracle import mage_oracle as O
-from tests.helpers import build_mage, cpu_sd
+from tests.helpers import build_mage, count_lib_calls, cpu_sd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -236,17 +235,7 @@ def test_refusals_launch_nothing(small, monkeypatch):
     longer = build_mage(synth.mnist_model_config(frames_length=L + 1, **SMALL), 5, DEV)
     on_cpu = build_mage(synth.mnist_model_config(frames_length=L, **SMALL), 5)
     m.set_sampling(0.9)
-    lib = _lib.lib(0)
-    calls = []
-
-    def counted(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    calls = count_lib_calls(monkeypatch)
 
     def refused(match, fn, *a, **kw):
         with pytest.raises(ValueError, match=match):

@@ -6,11 +6,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from mage_amd import _lib
 from mage_amd.optim import FlatAdam
 from mage_amd.utils import synth
 from oracle import mage_oracle as O
-from tests.helpers import build_mage, cpu_sd
+from tests.helpers import build_mage, count_lib_calls, cpu_sd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -232,17 +231,7 @@ def test_refusals_launch_nothing_and_leave_forward_alone(small, monkeypatch):
     assert torch.equal(loss0, loss1) and g0.keys() == g1.keys() and all(torch.equal(g0[n], g1[n]) for n in g0)       # no state leaks
     m.zero_grad(set_to_none=True)
 
-    lib = _lib.lib(0)
-    calls = []
-
-    def counted(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    calls = count_lib_calls(monkeypatch)
 
     def refused(match, *a, **kw):
         with pytest.raises(ValueError, match=match):
@@ -273,5 +262,7 @@ def test_refusals_launch_nothing_and_leave_forward_alone(small, monkeypatch):
     refused("GPU", b, tokens, adv.cpu())
     refused("GPU", b, tokens, adv, blp.cpu())
     refused("GPU", {k: v.cpu() for k, v in b.items()}, tokens, adv)
+    refused("batch must be a dict", [b], tokens, adv)
+    refused("images", {**b, "images": b["images"][:0]}, tokens[:0], adv[:0])
     monkeypatch.undo()
     _reset(m)

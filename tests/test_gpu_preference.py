@@ -18,7 +18,7 @@ from mage_amd.optim import FlatAdam
 from mage_amd.utils import synth
 from oracle import mage_oracle as O
 from tests import preference_ref as R
-from tests.helpers import build_mage, cpu_sd, within
+from tests.helpers import build_mage, count_lib_calls, cpu_sd, within
 from tests.test_gpu_policy_train import GRAD_TOL, SMALL, dev_batch, rel
 
 pytestmark = pytest.mark.gpu
@@ -215,21 +215,6 @@ def test_bf16_mode_reaches_the_bf16_instance(small, monkeypatch):
     assert len(grads) >= 90 and all(bool(torch.isfinite(g).all()) for g in grads) and any(g.abs().max().item() > 0 for g in grads)
 
 
-def _counting(monkeypatch):
-    lib = _lib.lib(0)
-    calls = []
-
-    def counted(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
-    return calls
-
-
 def test_rollout_hands_over_pairs(small, monkeypatch):
     m, ref = small["m"], small["ref"]
     N = 3
@@ -256,7 +241,7 @@ def test_rollout_hands_over_pairs(small, monkeypatch):
     assert len(grads) >= 90 and all(g.abs().max().item() == 0.0 for g in grads)
     m.zero_grad(set_to_none=True)
     # pairs add no launch, and without pairs no new entry point is reached
-    calls = _counting(monkeypatch)
+    calls = count_lib_calls(monkeypatch)
     plain = m.rollout(batch, N)
     n_plain = collections.Counter(calls)
     calls.clear()
@@ -268,10 +253,48 @@ def test_rollout_hands_over_pairs(small, monkeypatch):
     _reset(m)
 
 
+def test_preference_loss_runs_policy_loss_pass(small, monkeypatch):
+    """'preference_loss runs policy_loss' pass', by the call counter: for the same batch and tokens the ordered C-ABI entry points policy_loss
+    reaches before its first mage_policy_loss* call are the ones preference_loss reaches before its first mage_token_logprob call, in grad
+    mode and under no_grad; and in backward the entry points after the head's own *_bwd kernel are the same list too."""
+    m, b, tok, pairs, ref_lp = small["m"], small["b"], small["tok"], small["pairs"], small["ref_lp"]
+    _reset(m)
+    adv = torch.ones(B, device=DEV)
+    runs = {"policy_loss": (lambda: m.policy_loss(b, tok, adv)[0], "mage_policy_loss", "mage_policy_loss_bwd"),
+            "preference_loss": (lambda: m.preference_loss(b, tok, pairs, ref_lp)[0], "mage_token_logprob", "mage_token_logprob_bwd")}
+    for run, _, _ in runs.values():
+        run().backward()                                                         # derived caches built
+    calls = count_lib_calls(monkeypatch)
+
+    def before(prefix):
+        return calls[:next(i for i, c in enumerate(calls) if c.startswith(prefix))]
+    seen = {}
+    for name, (run, head, head_bwd) in runs.items():
+        del calls[:]
+        with torch.no_grad():
+            run()
+        no_grad = before(head)
+        del calls[:]
+        loss = run()
+        grad = before(head)
+        del calls[:]
+        loss.backward()
+        first = next(i for i, c in enumerate(calls) if c.endswith("_bwd"))
+        assert calls[first] == head_bwd, calls[:first + 1]
+        seen[name] = (no_grad, grad, calls[first + 1:])
+        print(f"{name}: {len(no_grad)} entry points before the head under no_grad, {len(grad)} in grad mode, {len(seen[name][2])} after {head_bwd}")
+    monkeypatch.undo()
+    _reset(m)
+    pol, pref = seen["policy_loss"], seen["preference_loss"]
+    assert min(map(len, pol)) >= 20 and "mage_attention" in pol[0] and "mage_attention_bwd" in pol[2]
+    for what, x, y in zip(("no_grad forward", "grad-mode forward", "backward"), pol, pref):
+        assert x == y, (what, [(i, p, q) for i, (p, q) in enumerate(zip(x, y)) if p != q][:5], len(x), len(y))
+
+
 def test_refusals_launch_nothing(small, monkeypatch):
     m, b, tok, pairs, ref_lp = small["m"], small["b"], small["tok"], small["pairs"], small["ref_lp"]
     _reset(m)
-    calls = _counting(monkeypatch)
+    calls = count_lib_calls(monkeypatch)
 
     def refused(match, *a, **kw):
         with pytest.raises(ValueError, match=match):

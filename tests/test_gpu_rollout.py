@@ -5,10 +5,10 @@ import numpy as np
 import pytest
 import torch
 
-from mage_amd import _lib, ops
+from mage_amd import ops
 from mage_amd.utils import synth
 from tests import video_metrics_ref as R
-from tests.helpers import build_mage
+from tests.helpers import build_mage, count_lib_calls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -188,17 +188,7 @@ def test_a_callable_reward_reaches_the_advantages(small, rolled):
 def test_refusals_launch_nothing(small, monkeypatch):
     m, batch = small
     _reset(m)
-    lib = _lib.lib(0)
-    calls = []
-
-    def counted(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    calls = count_lib_calls(monkeypatch)
 
     def refused(match, *a, **kw):
         before = _settings(m)

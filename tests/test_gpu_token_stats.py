@@ -23,10 +23,10 @@ import numpy as np
 import pytest
 import torch
 
-from mage_amd import _lib, ops
+from mage_amd import ops
 from mage_amd.utils import synth
 from tests import token_stats_ref as R
-from tests.helpers import build_mage
+from tests.helpers import build_mage, count_lib_calls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -481,17 +481,7 @@ def test_off_is_off_and_on_is_counted(small, monkeypatch):
     mage_token_logprob / mage_clip_scores.  Flags on: exactly one mage_token_stats behind every mage_token_logprob, one more
     mage_clip_scores for policy."""
     m, batch = small
-    lib = _lib.lib(0)
-    calls = []
-
-    def counted(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, counted(name, getattr(lib, name)))
+    calls = count_lib_calls(monkeypatch)
     ours = ("mage_token_logprob", "mage_clip_scores", "mage_token_stats")
     Lm1 = SMALL["frames_length"] - 1
 

@@ -12,7 +12,7 @@ from scipy import ndimage
 from mage_amd import _lib
 from mage_amd.utils import synth
 from tests import video_metrics_ref as R
-from tests.helpers import build_mage
+from tests.helpers import build_mage, count_lib_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float("nan"), float("inf")
@@ -144,18 +144,7 @@ def test_group_advantages_refuses_bad_arguments(bad):
 # ---------------------------------------------------------------- Python refusals on a CPU model
 @pytest.fixture()
 def counted(monkeypatch):
-    lib = _lib.load()
-    calls = []
-
-    def wrap(name, fn):
-        def f(*a):
-            calls.append(name)
-            return fn(*a)
-        return f
-    for name in {**_lib.SIGNATURES, **_lib.EXT_SIGNATURES}:
-        if name not in ("mage_last_error", "mage_abi_version"):
-            monkeypatch.setattr(lib, name, wrap(name, getattr(lib, name)))
-    return calls
+    return count_lib_calls(monkeypatch, _lib.load())
 
 
 def test_rollout_and_video_metrics_refuse_on_a_cpu_model(counted):
