@@ -80,6 +80,8 @@ __device__ __forceinline__ void mage_raise(int* word, int code, long value, int 
 int mage_gemm_cu_count();                  // CUs of the current device rounded down to a multiple of 8 (256 if unknown): the GEMM schedulers' grid
 // Set by mage_gemm_kernel_name for the duration of one mage_gemm call: the launch that call selects stores its kernel here instead of running.
 extern thread_local const void** mage_gemm_plan;
+// the rocprofv3-style name of a kernel by its address (gemm.hip), for the *_kernel_name entry points
+int mage_kernel_symbol_name(const void* kernel, char* buf, int32_t len, const char* who);
 // Sets the kernel's dynamic-LDS limit once per device, launches it, checks the launch.  The flags are per DEVICE (a process may drive several
 // GPUs, e.g. nn.DataParallel, main_mage.py:106); setting one twice from two threads is harmless.
 template <auto KERNEL, typename Args>

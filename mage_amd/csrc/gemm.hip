@@ -118,17 +118,8 @@ extern "C" int mage_gemm(const mage_gemm_desc* d_in, void* stream) {
 
 thread_local const void** mage_gemm_plan = nullptr;
 
-// The kernel mage_gemm would launch for `desc`, by its symbol: mage_gemm itself runs with mage_gemm_plan set, so every argument check, default
-// and selection rule is the dispatch's own and nothing is enqueued.  The name comes from the runtime (hipGetFuncBySymbol + hipKernelNameRef:
-// no stream involved, so also safe while a graph is being captured), demangled, normalised as the kernel statistics of rocprofv3 are read
-// (tools/kernel_stats_summary.py: no "void ", no "(anonymous namespace)::", no parameter list) and cached per kernel.
-extern "C" int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int32_t len) {
-    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_kernel_name: no buffer");
-    const void* kernel = nullptr;
-    mage_gemm_plan = &kernel;
-    const int r = mage_gemm(desc, nullptr);
-    mage_gemm_plan = nullptr;
-    if (r != MAGE_OK) return r;
+// kernel address -> the name rocprofv3's kernel statistics give it (demangled, no "void ", no "(anonymous namespace)::", no parameter list), cached
+int mage_kernel_symbol_name(const void* kernel, char* buf, int32_t len, const char* who) {
     static std::mutex mu;
     static std::unordered_map<const void*, std::string> names;
     std::string name;
@@ -139,7 +130,7 @@ extern "C" int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int3
             hipFunction_t f = nullptr;
             const char* raw = hipGetFuncBySymbol(&f, kernel) == hipSuccess ? hipKernelNameRef(f) : nullptr;
             if (!raw) {
-                mage_set_error("mage_gemm_kernel_name: the runtime has no name for the selected kernel");
+                mage_set_error("%s: the runtime has no name for the selected kernel", who);
                 return MAGE_EHIP;
             }
             std::string n = raw;
@@ -155,7 +146,21 @@ extern "C" int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int3
         }
         name = it->second;
     }
-    MAGE_CHECK_ARG((int32_t)name.size() < len, "mage_gemm_kernel_name: %d bytes are too few for '%s'", (int)len, name.c_str());
+    MAGE_CHECK_ARG((int32_t)name.size() < len, "%s: %d bytes are too few for '%s'", who, (int)len, name.c_str());
     memcpy(buf, name.c_str(), name.size() + 1);
     return MAGE_OK;
+}
+
+// The kernel mage_gemm would launch for `desc`, by its symbol: mage_gemm itself runs with mage_gemm_plan set, so every argument check, default
+// and selection rule is the dispatch's own and nothing is enqueued.  The name comes from the runtime (hipGetFuncBySymbol + hipKernelNameRef:
+// no stream involved, so also safe while a graph is being captured), demangled, normalised as the kernel statistics of rocprofv3 are read
+// (tools/kernel_stats_summary.py: no "void ", no "(anonymous namespace)::", no parameter list) and cached per kernel.
+extern "C" int mage_gemm_kernel_name(const mage_gemm_desc* desc, char* buf, int32_t len) {
+    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_kernel_name: no buffer");
+    const void* kernel = nullptr;
+    mage_gemm_plan = &kernel;
+    const int r = mage_gemm(desc, nullptr);
+    mage_gemm_plan = nullptr;
+    if (r != MAGE_OK) return r;
+    return mage_kernel_symbol_name(kernel, buf, len, "mage_gemm_kernel_name");
 }

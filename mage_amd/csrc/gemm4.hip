@@ -43,6 +43,7 @@
 
 #include "gemm_shared.h"
 #include "gemm4_regs.h"
+#include "attn_mfma.h"
 
 namespace {
 
@@ -59,6 +60,12 @@ struct Gemm4Args {
     int M, N, K, lda, ldw, ldy, ldr, ldy2, y_dtype, a_off, y_off;
     int ntiles_n, ntiles;
     int stagger_groups, stagger_sleeps;
+    // the fused H / W axial attention pair (QF != 0, see gemm4_body): P scratch [M][heads][16] fp32, 1 = H axis | 2 = W axis, softmax scale,
+    // the regrouping of the output rows (out_w rows at a time, y_img_stride apart)
+    float* attn_p;
+    int attn_axis;
+    float attn_scale;
+    int out_w, y_img_stride;
 };
 
 #ifndef MAGE4_ABL
@@ -98,9 +105,54 @@ __device__ __forceinline__ void g4_mfma32(const u32x4& w, const u32x4& x) {
     else asm volatile("v_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(w), "v"(x), "i"(16 * B), "i"(16 * B + 15));
 }
 #endif
-template <int ACT, int EK, int LN, bool RB, bool HF = false>
-__global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
+// QF (the fused H / W axial attention of the decoder, 16 x 16 frames, head width 32, LayerNorm-consuming in_proj; mage_gemm_attn_fused): the pair
+// QKV GEMM -> attention_mfma_kernel as TWO launches of gemm4_attn_kernel, q and k never stored.  A 256-row tile is one frame; the loader fetches its
+// rows so that every 16-row m-fragment is one axial sequence (W axis: rows as they lie; H axis: tile row R = w*16 + h reads frame row
+// h*16 + w), the LayerNorm statistics and the output rows follow the same map.
+//   QF = 1, N = 2C, the in_proj rows of q and k packed per head as 64 columns [q_h | k_h], the 32 columns of each in the order that makes a
+//     lane's two packed accumulator blocks the 8 consecutive head dims the S MFMA wants (column nt*16 + g*4 + e = dim g*8 + nt*4 + e): the
+//     epilogue finishes the LayerNorm, adds the bias and rounds as epilogue_lean does (the values qkv held), then per m-fragment and head
+//     S^T = K Q^T by ONE 16x16x32 MFMA on those registers, scale and softmax in attention_mfma_kernel's order, and p = exp(s - max) leaves as
+//     fp32: P[m][head][16] (row m in TILE order: private to the pair).
+//   QF = 2, N = C, the v rows of in_proj, MFMA roles swapped (A operand = the activation rows, as gemm4h_kernel: the same products in the same
+//     k order): an accumulator block then holds V^T the way the P V MFMA takes it (lane = head dim, register = key).  Same epilogue
+//     arithmetic per element, then den, P = hi + lo, O^T = V^T P_hi^T + V^T P_lo^T, the lane swap, 1 / den and the 16-byte row stores of
+//     attention_mfma_kernel: the same bits in `ao`.
+// The epilogue MFMAs of the fused attention pair (QF): attention_mfma_kernel's instructions (attn_mfma_qk / attn_mfma_pv in attn_mfma.h) on the
+// same operands, but as inline asm on VGPRs: given the builtins, hipcc puts their results into the accumulator registers it believes free
+// (a[0:3] -- live accumulators of the tile).  Wait states inside the strings: a just-written operand (1), the result before any reader (16);
+// an accumulate chain needs none.
+typedef unsigned g4_u32x2 __attribute__((ext_vector_type(2)));
+template <bool HF>
+__device__ __forceinline__ f32x4 g4_epi_qk(const u32x4& k, const u32x4& q) {
+    f32x4 d;
+    if constexpr (HF) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0\n\ts_nop 15" : "=&v"(d) : "v"(k), "v"(q));
+    else asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, 0\n\ts_nop 15" : "=&v"(d) : "v"(k), "v"(q));
+    return d;
+}
+// o0 = vt0 x p_hi + vt0 x p_lo, o1 = vt1 x p_hi + vt1 x p_lo (each: the hi product into C = 0, then the lo product accumulated)
+#define G4_EPI_PV(OP)                                                                                                                               \
+    asm volatile("s_nop 1\n\t" OP " %0, %2, %4, 0\n\t" OP " %1, %3, %4, 0\n\t" OP " %0, %2, %5, %0\n\t" OP " %1, %3, %5, %1\n\ts_nop 15"           \
+                 : "=&v"(o0), "=&v"(o1)                                                                                                             \
+                 : "v"(__builtin_bit_cast(g4_u32x2, vt0)), "v"(__builtin_bit_cast(g4_u32x2, vt1)), "v"(__builtin_bit_cast(g4_u32x2, phi)),          \
+                   "v"(__builtin_bit_cast(g4_u32x2, plo)))
+template <bool HF>
+__device__ __forceinline__ void g4_epi_pv(const ashort4& vt0, const ashort4& vt1, const ashort4& phi, const ashort4& plo, f32x4& o0, f32x4& o1) {
+    if constexpr (HF) G4_EPI_PV("v_mfma_f32_16x16x16_f16");
+    else G4_EPI_PV("v_mfma_f32_16x16x16_bf16");
+}
+
+// one MFMA of the K loop: A operand = the W fragment, B operand = the activation fragment; SWAP (QF = 2): the roles swapped (transposed block)
+template <bool SWAP, int I, bool ZERO, bool CLOB, bool HF>
+__device__ __forceinline__ void g4_mm(const u32x4& w, const u32x4& x) {
+    if constexpr (SWAP) g4_mfma<I, ZERO, CLOB, HF>(x, w);
+    else g4_mfma<I, ZERO, CLOB, HF>(w, x);
+}
+// (the body of both kernels below: gemm4_kernel = QF 0, gemm4_attn_kernel = the fused pair's launches)
+template <int ACT, int EK, int LN, bool RB, bool HF, int QF>
+__device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     static_assert(EK != EK_GENERAL, "lean epilogue kinds");
+    static_assert(QF == 0 || (LN == LN_CONSUME && ACT == MAGE_ACT_NONE), "fused attention pair: the LayerNorm-consuming in_proj");
     static_assert(!HF || (LN != LN_DUAL && LN != LN_GELUBWD), "f16 form: the generation path's epilogues");
     typedef std::conditional_t<HF, f16_t, unsigned short> H16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -128,14 +180,16 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
     // vmcnt wait in front of each slab's barrier.
     const int lr = lane >> 3, lp = lane & 7;
     unsigned voffA[8], voffW[8];
+    // QF: tile row R (0..255) -> row of the frame (H axis: sequences run down the columns of the 16 x 16 frame)
+    [[maybe_unused]] auto frame_row = [&](int R) { return g.attn_axis == 1 ? ((R & 15) << 4) + (R >> 4) : R; };
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int r = u * 8 + lr;
         const int ch = lp ^ ((r >> 1) & 7);
-        voffA[u] = (unsigned)(r * g.lda * 2 + ch * 16 + 8192 - u * 1024);
+        voffA[u] = (unsigned)((QF ? frame_row(wave * 64 + r) : r) * g.lda * 2 + ch * 16 + 8192 - u * 1024);
         voffW[u] = (unsigned)(r * g.ldw * 2 + ch * 16 + 8192 - u * 1024);
     }
-    auto a_base = [&](int tile) { return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + wave * 64) + g.a_off) * g.lda * 2 - 4096; };
+    auto a_base = [&](int tile) { return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + (QF ? 0 : wave * 64)) + g.a_off) * g.lda * 2 - 4096; };
     auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * 256 + wave * 64) * g.ldw * 2 - 4096; };
     // two cursors: A pieces run 2 slabs ahead of the compute cursor, W pieces 1; at a tile's end they jump to the next tile's bases
     const char* a_src = a_base(c_tile);
@@ -221,6 +275,20 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
         f32x4 biasm[2][4];
         [[maybe_unused]] float ln_mean[8], ln_rstd[8];
         [[maybe_unused]] f32x4 lns[2][4];
+        // QF = 2: the probabilities of one epilogue step (column half h = 2 heads, row half mh = 4 sequences) as the QF = 1 launch left them:
+        // lane (l15, grp) reads p of query l15, keys 4 grp .. 4 grp + 3 -- 16 bytes per lane, 1 KiB contiguous per (sequence, head).  Requested one step ahead: step 0's in the
+        // last quarter of the last slab, a later step's sequence mt as soon as the step before has consumed its own (ahead of that sequence's row stores, which a
+        // load issued behind them would wait for).
+        [[maybe_unused]] f32x4 pl[4][2];
+        // (the lane's coordinates, opaque once per tile: the per-lane 64-bit addresses of P and of the output rows built from them are then
+        // recomputed where they are used instead of living in registers across the K loop, which this instantiation does not have)
+        [[maybe_unused]] int ql15 = l15, qgrp = grp;
+        if constexpr (QF != 0) asm volatile("" : "+v"(ql15), "+v"(qgrp));
+        [[maybe_unused]] auto qf_p_request = [&](int mt, int h, int mh) __attribute__((always_inline)) {
+            const float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4 + mt) * (g.N >> 5) + (n0 >> 5) + h * 2) * 256 + (qgrp * 16 + ql15) * 4;
+#pragma unroll
+            for (int hd = 0; hd < 2; ++hd) pl[mt][hd] = *(const f32x4*)(pp + hd * 256);
+        };
         // One slab.  j = its index in the tile (runtime; only the cursors' tile jumps depend on it), S = its stage.
         // LDS-DMA issue points: W(j+1) in Q0 and A(j+2) in Q3, one instruction per four MFMAs.  A tile's FIRST slab issues no W: the
         // previous tile's LAST slab sent W of this tile's slab 1 together with its A in Q3, BEFORE the epilogue's stores -- memory
@@ -233,7 +301,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             // ---- Q0: (t0, rows 0-63) from wf[0], xf[0]
             g4_for<32>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mfma<((nt >> 2) * 8 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[0][m]);
+                g4_mm<QF == 2, ((nt >> 2) * 8 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[0][m]);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(MAGE4_ABL & 4) && i < 4) {
                     rd_x1(1, S, 0, 4 + i);
@@ -256,7 +324,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             // ---- Q1: (t0, rows 64-127) from wf[0], xf[1]
             g4_for<32>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mfma<((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[1][m]);
+                g4_mm<QF == 2, ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[1][m]);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(MAGE4_ABL & 4) && i < 12) {
                     if constexpr (i < 4) rd_x1(0, S, 1, i);
@@ -268,6 +336,11 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             if constexpr (LAST) {                      // the epilogue's vectors, late: their registers are free during the K loop
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {          // column half 0 (half 1: requested in the epilogue, under half 0's arithmetic)
+                    if constexpr (QF == 2) {           // transposed blocks: this lane's column of block b is b*16 + l15
+                        biasm[0][0][b] = g.bias[n0 + b * 16 + l15];
+                        lns[0][0][b] = g.ln_colsum[n0 + b * 16 + l15];
+                        continue;
+                    }
                     const int n = n0 + b * 16 + grp * 4;
                     biasm[0][b] = *(const f32x4*)(g.bias + n);                         // bias != null (host)
                     if constexpr (LN == LN_CONSUME) lns[0][b] = *(const f32x4*)(g.ln_colsum + n);
@@ -275,7 +348,8 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
                 if constexpr (LN == LN_CONSUME) {
 #pragma unroll
                     for (int a = 0; a < 8; ++a) {
-                        const float2 st = *(const float2*)(g.ln_stats + 2 * (long)(m0 + a * 16 + l15));
+                        const long row = QF ? (long)tm * 256 + frame_row(wm * 128 + a * 16 + ql15) : (long)(m0 + a * 16 + l15);
+                        const float2 st = *(const float2*)(g.ln_stats + 2 * row);
                         ln_mean[a] = st.x;
                         ln_rstd[a] = st.y;
                     }
@@ -284,7 +358,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             }
             g4_for<32>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mfma<((nt >> 2) * 8 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[0][m]);
+                g4_mm<QF == 2, ((nt >> 2) * 8 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[0][m]);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(MAGE4_ABL & 4) && i < 4) {
                     rd_x1(1, S, 1, 4 + i);
@@ -295,6 +369,13 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             // the previous tile's epilogue traffic (4 or 8 vector loads and >= 32 stores per wave), which may stay in flight (the count waited
             // for is four below that traffic: a margin against any reordering of the epilogue's last stores)
             if constexpr (MAGE4_ABL & 16) __builtin_amdgcn_s_waitcnt(0xC07F);
+            // QF: only the instructions whose place behind the pieces the source fixes are counted -- the stores, which follow the accumulator
+            // reads (asm statements), not the epilogue's loads, which hipcc is free to issue earlier: QF 1: the 16 stores of P, four below
+            // = vmcnt(12) (with the 8 vector loads 24 lie behind the pieces); QF 2: the 32 row stores = vmcnt(32), the largest count the
+            // encoding below keeps simple (8 + 24 loads as well: 64 behind the pieces).  A too-low count only waits for some store
+            // acknowledgements; tightening them is unmeasured.
+            else if constexpr (FIRST && QF == 1) __builtin_amdgcn_s_waitcnt(0x007C);
+            else if constexpr (FIRST && QF == 2) __builtin_amdgcn_s_waitcnt(0x8070);
             else if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(LN == LN_CONSUME ? 0x8074 : 0x8070);       // vmcnt(36 | 32) lgkmcnt(0): four below the count
             else __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
             ring_barrier();
@@ -302,7 +383,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
             // ---- Q3: (t1, rows 64-127) from wf[1], xf[1]; next slab's first fragments into wf[0], xf[0]
             g4_for<32>([&](auto i_) {
                 constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mfma<((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[1][m]);
+                g4_mm<QF == 2, ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[1][m]);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(MAGE4_ABL & 4) && i < 12 && !LAST) {     // (a tile's last slab: after the epilogue, whose registers these would occupy)
                     if constexpr (i < 4) rd_x1(0, S ^ 1, 0, i);
@@ -320,6 +401,10 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
                     if constexpr ((i & 1) == 1 && i < 16) g4_dma<(i >> 1)>(voffA[i >> 1], a_src);
                     if constexpr ((i & 1) == 1 && i > 16) g4_dma<((i - 16) >> 1)>(voffW[(i - 16) >> 1], w_src);
                     if constexpr (i == 0 || i == 16 || (i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (QF == 2 && LAST && (i & 7) == 6) {         // the first epilogue step's probabilities (the slab's other fragment registers are free)
+                    qf_p_request(i >> 3, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             });
             if constexpr (!(MAGE4_ABL & 8)) a_src = (j == nk - 3) ? a_next : a_src + 128;
@@ -400,6 +485,11 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
         char* win = smem + G4_RING + wave * 4096;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
+            if constexpr (QF == 2) {
+                biasm[1][0][b] = g.bias[n0 + 64 + b * 16 + l15];
+                lns[1][0][b] = g.ln_colsum[n0 + 64 + b * 16 + l15];
+                continue;
+            }
             const int n = n0 + 64 + b * 16 + grp * 4;
             biasm[1][b] = *(const f32x4*)(g.bias + n);
             if constexpr (LN == LN_CONSUME) lns[1][b] = *(const f32x4*)(g.ln_colsum + n);
@@ -407,6 +497,109 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
         // gemm.hip's epilogue_lean, 64 x 64 outputs = 64 accumulator registers at a time.  (A software-pipelined rewrite -- 64 rows of staging
         // writes, then their reads under the next 64 rows' arithmetic -- was built and measured 5 % SLOWER per launch: the epilogue is not
         // waiting for its LDS round trips, it is issue-bound on the vector ALU at the clock the K loop's power draw leaves: 1.5 GHz.)
+        if constexpr (QF != 0) {
+            g4_for<4>([&](auto c_) {
+                constexpr int c = decltype(c_)::value, h = c >> 1, mh = c & 1;
+                __builtin_amdgcn_sched_barrier(0);
+                f32x4 t[4][4];
+                g4_for<16>([&](auto q_) {
+                    constexpr int q = decltype(q_)::value;
+                    t[q >> 2][q & 3] = g4_acc_read<(h * 8 + mh * 4 + (q >> 2)) * 4 + (q & 3), q == 0>();
+                });
+                if constexpr (QF == 1) {
+                    // N = 2C: 64 packed columns per head; P[frame][sequence][head][lane][4]: one store instruction = 1 KiB contiguous
+                    float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4) * (g.N >> 6) + (n0 >> 6) + h) * 256 + (qgrp * 16 + ql15) * 4;
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt) {
+                        uint2 pk[4];
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) {
+                            const f32x4 v = (t[mt][nt] - lns[h][nt] * ln_mean[mh * 4 + mt]) * ln_rstd[mh * 4 + mt] + biasm[h][nt];      // epilogue_lean's LN_CONSUME
+                            pk[nt] = uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])};
+                        }
+                        // attention_mfma_kernel, one key block, every key visible: S^T = K Q^T, scale, max, exp
+                        f32x4 st = g4_epi_qk<HF>(u32x4{pk[2].x, pk[2].y, pk[3].x, pk[3].y}, u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y});
+                        // (no contraction: there the scaled scores pass a select before the maximum is taken off, so the product is rounded --
+                        // s * scale - max as ONE fma would give exp(> 0) at the maximum itself)
+                        f32x4 p;
+                        {
+#pragma clang fp contract(off)
+                            float mx = -INFINITY;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                st[e] = st[e] * g.attn_scale;
+                                mx = fmaxf(mx, st[e]);
+                            }
+                            mx = fmaxf(mx, __shfl_xor(mx, 16));
+                            mx = fmaxf(mx, __shfl_xor(mx, 32));
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) p[e] = expf(st[e] - mx);
+                        }
+                        *(f32x4*)(pp + (long)mt * (g.N >> 6) * 256) = p;
+                    }
+                } else {
+                    const long shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
+                    // the two heads' 16 rows x 64 B through the wave's staging window (epilogue_lean's swizzle; a wave's DS operations execute in order):
+                    // stored as 2 x (8 rows x 128 B) instead of 2 x (16 rows x 64 B)
+                    const int srow = (qgrp * 16 + ql15) >> 3, scc = ql15 & 7;
+                    H16* op = (H16*)g.Y + n0 + h * 64 + scc * 8;
+                    const int wchunk = (qgrp & 1) * 2 + (qgrp >> 1);
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt) {
+                        f32x4 mean4, rstd4;            // the statistics of this lane's four rows of the transposed blocks: 4 grp + e
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            mean4[e] = __shfl(ln_mean[mh * 4 + mt], 4 * grp + e);
+                            rstd4[e] = __shfl(ln_rstd[mh * 4 + mt], 4 * grp + e);
+                        }
+#pragma unroll
+                        for (int hd = 0; hd < 2; ++hd) {
+                            const f32x4 p = pl[mt][hd];
+                            float den = 0.f;
+                            ashort4 phi, plo;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                den += p[e];
+                                short ph, pw;
+                                attn_p_split<H16>(p[e], ph, pw);
+                                phi[e] = ph;
+                                plo[e] = pw;
+                            }
+                            den += __shfl_xor(den, 16);
+                            den += __shfl_xor(den, 32);
+                            if constexpr (c < 3) {
+                                if (hd == 1) qf_p_request(mt, (c + 1) >> 1, (c + 1) & 1);
+                            }
+                            f32x4 o[2];
+                            ashort4 vt[2];
+#pragma unroll
+                            for (int b = 0; b < 2; ++b) {
+                                const int nt = hd * 2 + b;
+                                const f32x4 v = (t[mt][nt] - mean4 * lns[h][0][nt]) * rstd4 + biasm[h][0][nt];
+                                vt[b] = __builtin_bit_cast(ashort4, uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])});
+                            }
+                            g4_epi_pv<HF>(vt[0], vt[1], phi, plo, o[0], o[1]);
+                            const float inv = 1.0f / den;
+                            f32x4 v0, v1;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[0][e]), __float_as_uint(o[1][e]), false, false);
+                                v0[e] = __uint_as_float(sw[0]) * inv;
+                                v1[e] = __uint_as_float(sw[1]) * inv;
+                            }
+                            *(u32x4*)(win + ql15 * 128 + (((hd * 4 + wchunk) ^ ((ql15 >> 1) & 7)) << 4)) =
+                                u32x4{pack16x2<H16>(v0[0], v0[1]), pack16x2<H16>(v0[2], v0[3]), pack16x2<H16>(v1[0], v1[1]), pack16x2<H16>(v1[2], v1[3])};
+                        }
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const int r = srow + 8 * i;
+                            const long yrow = (long)tm * 256 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
+                            *(u32x4*)(op + yrow * g.ldy) = *(const u32x4*)(win + r * 128 + ((scc ^ ((r >> 1) & 7)) << 4));
+                        }
+                    }
+                }
+            });
+        } else {
         mage_gemm_desc e = {};
         e.M = 0x7fffffff;
         e.N = LN == LN_PRODUCE ? g.N : 0x7fffffff;
@@ -447,6 +640,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
                 else epilogue_lean<ACT, H16, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);
             }
         });
+        }
 #endif
         G4_STAMP(it, 2);
         // the next tile's first fragments (its slab 0 has been in stage 0 since the last slab's barrier)
@@ -466,8 +660,23 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
 }
 
 template <int ACT, int EK, int LN, bool RB, bool HF = false>
-int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
+__global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
+    gemm4_body<ACT, EK, LN, RB, HF, 0>(g);
+}
+// QF = 1: the Q K launch, 2: the V launch of the fused H / W axial attention pair (see gemm4_body)
+template <bool HF, int QF>
+__global__ __launch_bounds__(256) void gemm4_attn_kernel(const Gemm4Args g) {
+    gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, QF>(g);
+}
+
+template <int ACT, int EK, int LN, bool RB, bool HF = false, int QF = 0>
+int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, float* attn_p = nullptr, int attn_axis = 0, float attn_scale = 0.f) {
     Gemm4Args a;
+    a.attn_p = attn_p;
+    a.attn_axis = attn_axis;
+    a.attn_scale = attn_scale;
+    a.out_w = d->out_w;
+    a.y_img_stride = d->y_img_stride;
     a.A = d->A;
     a.W = d->W;
     a.Y = d->Y;
@@ -501,7 +710,9 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu) {
         a.stagger_groups = st_groups;
         a.stagger_sleeps = (int)(period * st_percent / 100 / st_groups / 1024);
     }
-    const int r = mage_gemm_launch<gemm4_kernel<ACT, EK, LN, RB, HF>>(grid, 256, G4_LDS, s, a);
+    int r;
+    if constexpr (QF != 0) r = mage_gemm_launch<gemm4_attn_kernel<HF, QF>>(grid, 256, G4_LDS, s, a);
+    else r = mage_gemm_launch<gemm4_kernel<ACT, EK, LN, RB, HF>>(grid, 256, G4_LDS, s, a);
     return r < 0 ? r : 1;
 }
 
@@ -786,6 +997,54 @@ int mage_gemm4_try(const mage_gemm_desc* d, hipStream_t s) {
     }
     if (d->act == MAGE_ACT_NONE) return launch4<MAGE_ACT_NONE, EK_BIAS, LN_NONE, false>(d, s, n_cu);
     return launch4<MAGE_ACT_QUICKGELU, EK_BIAS, LN_NONE, false>(d, s, n_cu);
+}
+
+// The fused H / W axial attention pair (include/mage_hip_ext.h): phase 1 = the Q K launch (N = 2C, P out), phase 2 = the V launch (N = C, ao out)
+extern "C" int mage_gemm_attn_fused(const mage_gemm_desc* d, int32_t phase, int32_t axis, float scale, float* p, void* stream) {
+    MAGE_CHECK_ARG(d != nullptr, "mage_gemm_attn_fused: null descriptor");
+    MAGE_CHECK_ARG(phase == 1 || phase == 2, "mage_gemm_attn_fused: phase %d (1 = the Q K launch, 2 = the V launch)", (int)phase);
+    MAGE_CHECK_ARG(axis == 1 || axis == 2, "mage_gemm_attn_fused: axis %d (1 = H, 2 = W of 16 x 16 frames)", (int)axis);
+    MAGE_CHECK_ARG(d->dtype == MAGE_BF16 || d->dtype == MAGE_F16, "mage_gemm_attn_fused: bf16 or f16 operands");
+    MAGE_CHECK_ARG(d->A && d->W && p && d->bias && d->ln_stats && d->ln_colsum && (phase == 1 || d->Y),
+                   "mage_gemm_attn_fused: A, W, bias, ln_stats, ln_colsum, the P scratch%s must be given", phase == 2 ? " and Y" : "");
+    MAGE_CHECK_ARG(d->M > 0 && d->M % 256 == 0 && d->N % 256 == 0 && d->K % 128 == 0 && d->K >= 256 && d->K <= 1024,
+                   "mage_gemm_attn_fused: M=%d, N=%d multiples of 256 (whole 16 x 16 frames), K=%d a multiple of 128 in [256, 1024]", d->M, d->N, d->K);
+    MAGE_CHECK_ARG(d->taps_h * d->taps_w == 1 && d->stride == 1 && !d->dy0 && !d->dx0 && d->in_h == 1 && d->out_h == 1 && d->in_w == d->out_w && !d->a_half &&
+                       d->y_mul_x == 1 && (d->out_w >= d->M || (d->out_w % 256 == 0 && d->a_img_stride == d->out_w)) && d->a_off % 256 == 0 && d->a_off >= 0,
+                   "mage_gemm_attn_fused: plain rows in (a_off a multiple of 256), output rows regrouped whole frames at a time");
+    MAGE_CHECK_ARG(!d->scale && !d->shift && !d->rowadd && !d->residual && !d->post_relu && !d->res_half && !d->y2 && !d->ln_part && !d->head_w && !d->a_relu &&
+                       d->n_split <= 1 && d->act == MAGE_ACT_NONE,
+                   "mage_gemm_attn_fused: the LayerNorm-consuming bias epilogue only");
+    MAGE_CHECK_ARG(phase == 1 || (d->y_dtype == d->dtype && d->ldy % 8 == 0 && d->ldy >= d->N && (((uintptr_t)d->Y) & 15) == 0 && d->y_off >= 0),
+                   "mage_gemm_attn_fused: the V launch writes 16-bit rows of the operands' type, ldy a multiple of 8, Y 16-byte aligned");
+    const int ldw = d->ldw ? d->ldw : d->K;
+    MAGE_CHECK_ARG(ldw == d->K && d->lda % 8 == 0 && d->lda >= d->K, "mage_gemm_attn_fused: W packed [N][K], lda a multiple of 8");
+    MAGE_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->bias | (uintptr_t)d->ln_colsum | (uintptr_t)p) & 15) == 0 && (((uintptr_t)d->ln_stats) & 7) == 0,
+                   "mage_gemm_attn_fused: operands must be 16-byte aligned");
+    MAGE_CHECK_ARG(((long)d->M + d->a_off) * d->lda * 2 + 16384 < (1L << 32) && (long)d->N * ldw * 2 + 16384 < (1L << 32),
+                   "mage_gemm_attn_fused: operands beyond the kernel's 32-bit lane offsets");
+    hipStream_t s = (hipStream_t)stream;
+    const int n_cu = mage_gemm_cu_count();
+    int r;
+    if (d->dtype == MAGE_F16)
+        r = phase == 1 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 1>(d, s, n_cu, p, axis, scale)
+                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 2>(d, s, n_cu, p, axis, scale);
+    else
+        r = phase == 1 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 1>(d, s, n_cu, p, axis, scale)
+                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 2>(d, s, n_cu, p, axis, scale);
+    return r < 0 ? r : MAGE_OK;
+}
+
+// The kernel mage_gemm_attn_fused launches for this descriptor and phase, named as mage_gemm_kernel_name names mage_gemm's
+extern "C" int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* d, int32_t phase, int32_t axis, char* buf, int32_t len) {
+    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_attn_fused_kernel_name: no buffer");
+    float dummy_p[4] __attribute__((aligned(16)));
+    const void* kernel = nullptr;
+    mage_gemm_plan = &kernel;
+    const int r = mage_gemm_attn_fused(d, phase, axis, 1.f, dummy_p, nullptr);
+    mage_gemm_plan = nullptr;
+    if (r != MAGE_OK) return r;
+    return mage_kernel_symbol_name(kernel, buf, len, "mage_gemm_attn_fused_kernel_name");
 }
 
 // mage_gemm_tn on the one-wave-per-SIMD schedule: 1 = launched, 0 = not eligible (gemm_tn.hip then runs its 8-wave kernel)

@@ -422,6 +422,7 @@ class FlatAxialDecoder(nn.Module):
         self.compute_dtype = F32
         self.split_kind = 0                    # ops.BF16X3 / ops.F16X3: the fast parity modes (compute_dtype stays fp32)
         self.stream_bf16 = True                # bf16 mode: x stays in bf16 between the blocks (_stream_bf16)
+        self.qk_fuse_tiles = 4                 # H / W attention inside the in_proj GEMM from this many V-launch tiles per CU on (_qk_fuse)
         self._derived = _Derived(self)
 
     def initialize_parameters(self):
@@ -469,6 +470,8 @@ class FlatAxialDecoder(nn.Module):
                 d[f"b{i}.{lin}.lns"] = wq.float().sum(dim=1).contiguous()
                 # c_n = sum_k W_nk beta_k + b_n in fp64 (a row-wise reduction: derived-cache bookkeeping, no BLAS call)
                 d[f"b{i}.{lin}.lnc"] = ((w.double() * bt.double()[None, :]).sum(1) + d[f"b{i}.{lin}.b"].double()).float().contiguous()
+            if i % 3 and self.model_channels % 64 == 0:         # H / W blocks: in_proj as the fused attention pair takes it (_qk_fuse)
+                self._qk_fuse_pack(d, f"b{i}", d[f"b{i}.in_proj.lnw"], d[f"b{i}.in_proj.lns"], "")
         return d
 
     def _fold(self, dt, B: int, hw: int) -> bool:
@@ -508,6 +511,38 @@ class FlatAxialDecoder(nn.Module):
             wq = (d[f"{p}.{lin}.f32"] * d[f"{p}.{ln}.w"][None, :]).to(F16)
             d[kw_], d[ks_] = wq, wq.float().sum(dim=1).contiguous()
         return d[kw_], d[ks_]
+
+    def _qk_fuse(self, xb, M: int, hh: int, ww: int, stats_rows: bool, cache) -> bool:
+        """The H / W blocks of a pass run their attention inside the in_proj GEMM (ops.gemm_attn_fused): the 16-bit LayerNorm-fold path with
+        (mean, rstd) rows, 16 x 16 frames (a 256-row GEMM tile is one frame), head width 32, and at least qk_fuse_tiles = four tiles per CU in the V launch
+        (the one-wave-per-SIMD kernel's own rule: the full loop; the incremental step and small batches keep the QKV GEMM + attention pair --
+        both write the same bits; the pair has only been timed at the cfg2 full-loop size, where that threshold is not measured against
+        a lower one).  use_cids=False keeps the old pair.  config qk_fuse = False (MAGE_NO_QK_FUSE=1) turns it off."""
+        Cc = self.model_channels
+        if not (stats_rows and cache is None and hh == 16 and ww == 16 and self.use_cids and config.get().qk_fuse):
+            return False
+        if Cc % 256 or not 256 <= Cc <= 1024 or M % 256 or (M + 8) * Cc * 2 >= 2 ** 32:
+            return False
+        return (M // 256) * (Cc // 256) >= getattr(self, "qk_fuse_tiles", 4) * torch.cuda.get_device_properties(xb.device).multi_processor_count
+
+    def _qk_fuse_w(self, d, p, dt):
+        """Block p's LayerNorm-folded in_proj operands (_ln_fold_w) as the fused pair takes them: the q and k rows packed per head
+        (ops.qk_pack_rows) with their colsum and bias in the same order, and the v rows.  bf16: from _build; f16: on first use."""
+        sfx = ".f16" if dt == F16 else ""
+        if f"{p}.in_proj.qk.w{sfx}" not in d:
+            lnw, lns = self._ln_fold_w(d, p, "in_proj", dt)
+            self._qk_fuse_pack(d, p, lnw, lns, sfx)
+        q = f"{p}.in_proj."
+        return dict(wqk=d[q + "qk.w" + sfx], sqk=d[q + "qk.s" + sfx], cqk=d[q + "qk.c"],
+                    wv=d[q + "v.w" + sfx], sv=d[q + "v.s" + sfx], cv=d[q + "v.c"])          # (the fp32 biases serve both types)
+
+    def _qk_fuse_pack(self, d, p, lnw, lns, sfx: str) -> None:
+        Cc = self.model_channels
+        idx = ops.qk_pack_rows(Cc, lnw.device)
+        lnc = d[f"{p}.in_proj.lnc"]
+        d[f"{p}.in_proj.qk.w{sfx}"], d[f"{p}.in_proj.qk.s{sfx}"] = lnw[idx].contiguous(), lns[idx].contiguous()
+        d[f"{p}.in_proj.v.w{sfx}"], d[f"{p}.in_proj.v.s{sfx}"] = lnw[2 * Cc:].contiguous(), lns[2 * Cc:].contiguous()
+        d[f"{p}.in_proj.qk.c"], d[f"{p}.in_proj.v.c"] = lnc[idx].contiguous(), lnc[2 * Cc:].contiguous()       # (fp32: one copy serves both types)
 
     def _stats_inline(self, xb, M: int) -> bool:
         """One clip per call: every Linear that follows a LayerNorm (N = C .. 4C) runs on the few-rows kernel, which reduces the
@@ -643,12 +678,21 @@ class FlatAxialDecoder(nn.Module):
         ao = torch.empty(M, Cc, device=dev, dtype=dt)
         hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
         geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
+        fuse = self._qk_fuse(xb, M, hh, ww, fold and not inl, cache)
+        pscr = torch.empty(M, Cc // 32, 16, device=dev, dtype=F32) if fuse else None      # the fused pair's probabilities
         for i in range(self.layers):
             p = f"b{i}"
             ln1 = ln if i else ln0
             if ln1 is None:
                 ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5)
-            if i % 3 == 0 and cache is not None:
+            if fuse and i % 3:
+                # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): a Q K launch that leaves the softmax
+                # numerators, a V launch that finishes P V -- the same bits in ao as the QKV GEMM + ops.attention below, q and k never stored
+                f = self._qk_fuse_w(d, p, dt)
+                kw = dict(axis=i % 3, M=M, K=Cc, lda=Cc, ln_stats=stats)
+                ops.gemm_attn_fused(xb, f["wqk"], None, pscr, phase=1, N=2 * Cc, bias=f["cqk"], ln_colsum=f["sqk"], **kw)
+                ops.gemm_attn_fused(xb, f["wv"], ao, pscr, phase=2, N=Cc, ldy=Cc, bias=f["cv"], ln_colsum=f["sv"], **kw)
+            elif i % 3 == 0 and cache is not None:
                 # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
                 # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)
                 if p0 == 0:
@@ -659,7 +703,8 @@ class FlatAxialDecoder(nn.Module):
             else:
                 q = kv = qkv
                 self._ln_linear(d, p, "in_proj", xn, xb, ln1, qkv, M=M, N=3 * Cc)
-            ops.attention(q, kv[:, Cc:], kv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, **geo[i % 3])
+            if not (fuse and i % 3):
+                ops.attention(q, kv[:, Cc:], kv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, **geo[i % 3])
             _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, **res)
             if fold and not inl:
                 ops.ln_stats(part, Cc, 1e-5, stats)
