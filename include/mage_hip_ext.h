@@ -293,6 +293,24 @@ int mage_gemm_attn_fused(const mage_gemm_desc* desc, int32_t phase, int32_t axis
 /* The symbol of the kernel mage_gemm_attn_fused(desc, phase, axis, ...) launches, named as mage_gemm_kernel_name names mage_gemm's. */
 int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* desc, int32_t phase, int32_t axis, char* buf, int32_t len);
 
+/* Given tokens over picked ones: no site in the reference (it generates every token after frame 0).  Serves MAGE.set_context and
+ * batch['known_tokens'] (mage_amd/modules/mage_model.py: _generate_one, after each frame's pick and its log-probability / statistics
+ * launches).
+ * Row i in [0, rows) has c = i / group, j = i % group and uses index t = c*tok_group_stride + j + tok_off of tokens (int64) and of every
+ * result buffer -- mage_token_logprob's token addressing, so a frame is forced where the pick kernels wrote it in either AR mode -- and
+ * k = known[(c / known_clip_div)*known_group_stride + j + known_off] (int64; known_clip_div = N: a clip's N candidates share one row).
+ *   k < 0   the slot is free: nothing at index t is written, in any buffer;
+ *   k >= 0  tokens[t] = k, and each of the five result buffers that is non-null gets, at t, its value under a policy that takes the given
+ *           token with certainty: logprob, policy_logprob, entropy, policy_entropy (fp32) 0, kept (int32) 1.  So clip totals
+ *           (mage_clip_scores) are sums over the free tokens, and an importance ratio at a forced slot is 1.
+ * k >= K is recorded for mage_check_device_errors and clamped to K - 1, as mage_token_logprob's out-of-range token is.
+ * One thread per row, plain vector-memory stores, no LDS, no atomics; two rows that map to one index t must carry the same k.
+ * tokens and known non-null, rows >= 0, group > 0, known_clip_div > 0, strides and offsets >= 0, K > 0: MAGE_EINVAL otherwise, nothing
+ * launched.  rows == 0 is a no-op. */
+int mage_apply_known_tokens(int64_t* tokens, int64_t rows, int64_t group, int64_t tok_group_stride, int64_t tok_off, const int64_t* known,
+                            int64_t known_group_stride, int64_t known_off, int64_t known_clip_div, int32_t K, float* logprob,
+                            float* policy_logprob, float* entropy, float* policy_entropy, int32_t* kept, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

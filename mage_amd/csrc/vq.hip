@@ -1448,6 +1448,58 @@ extern "C" int mage_guide_logits(const float* cond, const float* uncond, float* 
     return MAGE_OK;
 }
 
+// ---- given tokens over picked ones (mage_apply_known_tokens; include/mage_hip_ext.h states the rule).  One thread per row: it reads its
+// `known` value and, where that is >= 0, stores it and the certain policy's results (log-probabilities 0, entropies 0, kept 1) at the row's
+// token index.  A free row stores nothing.  8 bytes read and at most 28 written per row: launch-bound at a frame's size.  No LDS, no atomics.
+namespace {
+
+__global__ __launch_bounds__(256) void apply_known_kernel(int64_t* __restrict__ tokens, long rows, long group, long tok_stride, long tok_off,
+                                                          const int64_t* __restrict__ known, long known_stride, long known_off, long known_div,
+                                                          int K, float* __restrict__ logprob, float* __restrict__ policy_logprob,
+                                                          float* __restrict__ entropy, float* __restrict__ policy_entropy,
+                                                          int32_t* __restrict__ kept, int* __restrict__ err) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    const long c = i / group, j = i - c * group;
+    long k = known[(c / known_div) * known_stride + j + known_off];
+    if (k < 0) return;
+    if (k >= K) {                                       // reported by mage_check_device_errors, as mage_token_logprob's bad token is
+        mage_raise(err, MAGE_DEVERR_TOKEN_ID, k, K);
+        k = K - 1;
+    }
+    const long t = c * tok_stride + j + tok_off;
+    tokens[t] = k;
+    if (logprob) logprob[t] = 0.f;
+    if (policy_logprob) policy_logprob[t] = 0.f;
+    if (entropy) entropy[t] = 0.f;
+    if (policy_entropy) policy_entropy[t] = 0.f;
+    if (kept) kept[t] = 1;
+}
+
+}  // namespace
+
+extern "C" int mage_apply_known_tokens(int64_t* tokens, int64_t rows, int64_t group, int64_t tok_group_stride, int64_t tok_off,
+                                       const int64_t* known, int64_t known_group_stride, int64_t known_off, int64_t known_clip_div, int32_t K,
+                                       float* logprob, float* policy_logprob, float* entropy, float* policy_entropy, int32_t* kept,
+                                       void* stream) {
+    MAGE_CHECK_ARG(tokens && known, "mage_apply_known_tokens: null pointer");
+    MAGE_CHECK_ARG(rows >= 0 && group > 0 && known_clip_div > 0 && tok_group_stride >= 0 && tok_off >= 0 && known_group_stride >= 0 &&
+                   known_off >= 0 && K > 0,
+                   "mage_apply_known_tokens: bad sizes rows=%ld group=%ld known_clip_div=%ld K=%d (strides and offsets >= 0)", (long)rows,
+                   (long)group, (long)known_clip_div, K);
+    if (rows == 0) return MAGE_OK;
+    const int64_t blocks = (rows + 255) / 256;
+    MAGE_CHECK_ARG(blocks <= 0x7fffffffLL, "mage_apply_known_tokens: rows=%ld is more than one launch covers", (long)rows);
+    int* err = mage_error_word();
+    MAGE_CHECK_ARG(err != nullptr, "mage_apply_known_tokens: mage_init() has not been called");
+    apply_known_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(tokens, (long)rows, (long)group, (long)tok_group_stride,
+                                                                               (long)tok_off, known, (long)known_group_stride, (long)known_off,
+                                                                               (long)known_clip_div, K, logprob, policy_logprob, entropy,
+                                                                               policy_entropy, kept, err);
+    MAGE_CHECK_LAUNCH("mage_apply_known_tokens");
+    return MAGE_OK;
+}
+
 extern "C" int mage_clip_scores(const float* logprob, int64_t n_clips, int32_t n_cand, int64_t per_clip, float* scores, int64_t* best,
                                 void* stream) {
     MAGE_CHECK_ARG(logprob && scores, "mage_clip_scores: null pointer");

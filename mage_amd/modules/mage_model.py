@@ -573,15 +573,16 @@ class FlatAxialDecoder(nn.Module):
         return {"B": B, "hh": hh, "ww": ww, "kv": {}, "p": 0}
 
     @torch.no_grad()
-    def _inc_step(self, st: dict, motion: Optional[torch.Tensor], imgs: torch.Tensor) -> torch.Tensor:
+    def _inc_step(self, st: dict, motion: Optional[torch.Tensor], imgs: torch.Tensor, nf: int = 1) -> torch.Tensor:
         """Append position(s): the first call takes the motion anchor (slot 0) and frame 0's features (slot 1); later calls
-        take the features of the newest frame only.  Returns the logits of the last appended slot, [B*hw, K] fp32."""
+        take the features of the newest frame only.  nf > 1 (MAGE.set_context's prefill): imgs holds nf given frames per clip, appended as
+        one window.  Returns the logits of the last appended slot, [B*hw, K] fp32: the head runs on that slot only."""
         p0 = st["p"]
-        P = 2 if motion is not None else 1                                  # new positions p0 .. p0+P-1
+        P = nf + 1 if motion is not None else nf                            # new positions p0 .. p0+P-1
         # (the MAGE+ head's GroupNorm spans all frames of a clip: only the full loop is valid there)
-        assert self.use_cids and (p0 == 0) == (motion is not None) and p0 + P <= self.frames_length
+        assert self.use_cids and nf >= 1 and (p0 == 0) == (motion is not None) and p0 + P <= self.frames_length
         run = self._pass_split if self._split_on() else self._pass
-        logits = run(motion, imgs, B=st["B"], hh=st["hh"], ww=st["ww"], p0=p0, P=P, nf=1, cache=st["kv"])
+        logits = run(motion, imgs, B=st["B"], hh=st["hh"], ww=st["ww"], p0=p0, P=P, nf=nf, nh=1, cache=st["kv"])
         st["p"] = p0 + P
         return logits
 
@@ -642,8 +643,10 @@ class FlatAxialDecoder(nn.Module):
             return self._lin_s(xa, d, "out", logits, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
         return _linear(xa, d, "out", logits, dt, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
 
-    def _pass(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict]) -> torch.Tensor:
-        """fp32 / bf16 / f16: one window (see above) through the stack.  cache (incremental loop): block -> its [B, L, hw, q|k|v] rows."""
+    def _pass(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict],
+              nh: Optional[int] = None) -> torch.Tensor:
+        """fp32 / bf16 / f16: one window (see above) through the stack.  cache (incremental loop): block -> its [B, L, hw, q|k|v] rows.
+        nf frames are embedded into the window's last nf slots; the head runs on the last nh of them (None: all nf)."""
         d = self._derived.get(self._build)
         dt, Cc, L = self.compute_dtype, self.model_channels, self.frames_length
         dev = (imgs.tokens if isinstance(imgs, FrameTokens) else imgs).device
@@ -724,7 +727,7 @@ class FlatAxialDecoder(nn.Module):
                 else:
                     xa = torch.empty(M, Cc, device=dev, dtype=F32) if sb else x
                 _linear(hdn, d, p + ".c_proj", xa, dt, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
-        return self._head(d, xa, B=B, hw=hw, P=P, nf=nf)
+        return self._head(d, xa, B=B, hw=hw, P=P, nf=nf if nh is None else nh)
 
     # ------------------------------------------------------------------ the fast parity modes ('f16x3' / 'bf16x3')
     # The stack of _pass with fp32 everywhere EXCEPT the operands of the Linear layers: those are split-precision
@@ -763,7 +766,8 @@ class FlatAxialDecoder(nn.Module):
         return ops.gemm(a, w, y, M=M, N=N, K=K, lda=kw.pop("lda", 2 * K), ldy=kw.pop("ldy", 2 * N if y_split else N), bias=b,
                         split_kind=sk, y_split=y_split, **kw)
 
-    def _pass_split(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict]) -> torch.Tensor:
+    def _pass_split(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict],
+                    nh: Optional[int] = None) -> torch.Tensor:
         """f16x3 / bf16x3: one window through the stack.  cache (incremental loop): block -> its [B, L, hw, K|V] rows, fp32 or (when the
         attention reads split operands) split rows; q of the new positions stays packed in qkv."""
         d = self._derived.get(self._build)
@@ -803,7 +807,7 @@ class FlatAxialDecoder(nn.Module):
                 self._lin_s(hdn, d, p + ".c_proj", xn, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y_split=True)
             else:
                 self._lin_s(hdn, d, p + ".c_proj", x, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
-        return self._head(d, xn if self.use_cids else x, B=B, hw=hw, P=P, nf=nf, split=True)
+        return self._head(d, xn if self.use_cids else x, B=B, hw=hw, P=P, nf=nf if nh is None else nh, split=True)
 
     def forward(self, motion: torch.Tensor, imgs: torch.Tensor) -> torch.Tensor:
         """motion [B,H,W,Cc], imgs [B,L-1,H,W,Ci] -> logits [B,L-1,H,W,out] fp32."""
@@ -923,6 +927,9 @@ class MAGE(nn.Module):
         self._last_head_out = None                                       # mage_train.MageLossFn -> _run_head: (loss dict, what the head saved)
         self.guidance: Optional[float] = None                            # set_guidance: the classifier-free guidance scale; None: off
         self.last_guidance_scale: Optional[torch.Tensor] = None          # guidance on: fp32 [B], the per-clip scales the last generation used
+        self.context_frames = 1        # set_context: frames 0 .. k-1 of batch['images'] are given; 1: only frame 0 (off)
+        self.context_prefill = True    # incremental mode: the given frames enter as ONE window; False: one position at a time, no pick
+        self.last_known_mask: Optional[torch.Tensor] = None              # bool [B, L-1, h, w]: the slots the last generation was given
         self.caption_dropout = 0.0     # forward in training mode: the probability that a clip's caption is replaced by the null caption
         self.last_caption_drop: Optional[torch.Tensor] = None            # bool [B]: the clips whose caption the last forward dropped
 
@@ -1043,6 +1050,69 @@ class MAGE(nn.Module):
         self.last_guidance_scale = gs
         return {**batch, "guidance_scale": gs, "negative_text": neg.to(images.device).contiguous()}
 
+    def set_context(self, frames: int = 1) -> "MAGE":
+        """Continue a clip: frames 0 .. k-1 of batch['images'] are given (1 <= k <= frames_length - 1; 1, the default: only frame 0, off)
+        and autoregressive_generate produces frames k .. L-1.  All B * k given frames go through the VQ encoder in one call (or come as
+        batch['context_tokens'], int64 [B, k, h, w], which replaces the encode); the returned video holds images[:, :k] verbatim, as frame 0
+        is held, and only the generated frames are decoded.
+        Together with batch['known_tokens'] (int64 [B, L-1, h, w]: slot i is frame i + 1, any negative value means "free") this is one
+        mechanism -- some token slots are given, the rest are picked, later frames condition on both: after every frame's pick one
+        mage_apply_known_tokens launch (include/mage_hip_ext.h) stores the given tokens over the picked ones.  Given frames 1 .. k-1 are slots
+        0 .. k-2 and win over known_tokens there.  A given slot reports log-probability 0, entropy 0 and a kept set of 1 in set_logprobs'
+        results (a policy that takes the token with certainty), so clip totals and the best-of-N choice are over the free tokens; last_logits
+        (full loop) still holds the model's own prediction everywhere.  last_known_mask (bool [B, L-1, h, w]) tells which slots were given.
+        Free slots keep their sampler counters: a clip with nothing given is the unconstrained clip bit for bit.
+        Incremental mode takes the anchor and the k given frames as one window (no decoder step and no pick before frame k).
+        While k > 1, or for a batch that carries known_tokens, score, policy_loss, token_policy_logprobs, clip_logprobs, preference_loss and
+        rollout are refused: their loss heads have no per-token mask yet."""
+        if isinstance(frames, bool) or not isinstance(frames, int):
+            raise ValueError(f"set_context: frames must be an integer, got {frames!r}")
+        if not 1 <= frames <= self.frames_length - 1:
+            raise ValueError(f"set_context: frames must be in [1, {self.frames_length - 1}] (frames_length - 1), got {frames}")
+        if frames > 1 and not self.use_cids:
+            raise ValueError("set_context: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to hold")
+        self.context_frames = frames
+        return self
+
+    def _ctx(self) -> int:
+        return int(getattr(self, "context_frames", 1)) if self.use_cids else 1
+
+    def _refuse_known(self, who: str, batch=None) -> None:
+        if self._ctx() > 1 or (isinstance(batch, dict) and ("known_tokens" in batch or "context_tokens" in batch)):
+            raise ValueError(f"{who}: given frames or tokens (set_context, batch['known_tokens'] / ['context_tokens']) shape generation only -- "
+                             "the loss heads have no per-token mask; call set_context(1) and drop the keys first")
+
+    def _known_inputs(self, batch) -> dict:
+        """The batch with its optional 'context_tokens' (int64 [B, k, h, w]) and 'known_tokens' (int64 [B, L-1, h, w]) checked and on the
+        images' device; last_known_mask is set from them (None on a call with neither set_context(k > 1) nor known_tokens)."""
+        self.last_known_mask = None
+        ctx, known = batch.get("context_tokens"), batch.get("known_tokens")
+        if not self.use_cids:
+            if ctx is not None or known is not None:
+                raise ValueError("batch['context_tokens'] / ['known_tokens']: a use_cids=False (MAGE+) model regresses continuous latents; "
+                                 "it has no tokens to hold")
+            return batch
+        k = self._ctx()
+        if ctx is None and known is None and k == 1:
+            return batch
+        images = batch["images"]
+        B, R, Lm1 = images.shape[0], self.image_resolution, self.frames_length - 1
+        if images.shape[1] < k:
+            raise ValueError(f"set_context({k}): batch['images'] holds {images.shape[1]} frames")
+        out = dict(batch)
+        for key, t_, shape in (("context_tokens", ctx, (B, k, R, R)), ("known_tokens", known, (B, Lm1, R, R))):
+            if t_ is None:
+                continue
+            t_ = torch.as_tensor(t_)
+            if t_.dtype != torch.int64 or tuple(t_.shape) != shape:
+                raise ValueError(f"batch['{key}'] must be int64 {list(shape)}, got {t_.dtype} {list(t_.shape)}")
+            out[key] = t_.to(images.device).contiguous()
+        if known is not None or k > 1:
+            mask = out["known_tokens"] >= 0 if known is not None else torch.zeros(B, Lm1, R, R, device=images.device, dtype=torch.bool)
+            mask[:, :k - 1] = True
+            self.last_known_mask = mask
+        return out
+
     def set_logprobs(self, on: bool = True, *, policy: bool = False, entropy: bool = False) -> "MAGE":
         """on: autoregressive_generate leaves last_token_logprobs (fp32 [B, L-1, h, w]: the log-probability of each generated token under the
         logits it was picked from -- the model's full softmax at temperature 1, not the filtered set of set_sampling) and last_clip_logprob
@@ -1106,6 +1176,7 @@ class MAGE(nn.Module):
         if not self.use_cids:
             raise ValueError("score: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
         self._refuse_guided("score")
+        self._refuse_known("score", batch)
         images = batch["images"]
         _need_gpu(images, "MAGE.score")
         self._want_stats()                                # (refuses policy without sampling before anything runs)
@@ -1203,6 +1274,7 @@ class MAGE(nn.Module):
         if not self.use_cids:
             raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
         self._refuse_guided(who)
+        self._refuse_known(who, batch)
         if not isinstance(batch, dict):
             raise ValueError(f"{who}: batch must be a dict with 'images' and 'text'")
         vn = batch.get("video_noise") if self.randomness else None
@@ -1263,6 +1335,7 @@ class MAGE(nn.Module):
         same inputs (-inf where the filter could not draw the token).  How a frozen copy of the model gives policy_loss its
         reference_logprobs.  Values only; every last_* result is left as found."""
         self._refuse_guided("token_policy_logprobs")
+        self._refuse_known("token_policy_logprobs", batch)
         images = batch["images"] if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("token_policy_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
@@ -1409,6 +1482,7 @@ class MAGE(nn.Module):
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
         self._refuse_guided("rollout")
+        self._refuse_known("rollout", batch)
         if noise not in ("clip", "candidate"):
             raise ValueError(f"rollout: noise must be 'clip' or 'candidate', got {noise!r}")
         if noise == "candidate":
@@ -1762,6 +1836,9 @@ class MAGE(nn.Module):
         'video_noise' [B,64,h,w] optional (injects the randomness-branch noise instead of torch.randn), 'sample_seed' int64 [B] optional
         (one seed per clip when set_sampling is on; drawn from torch's default CPU generator when absent, kept as last_sample_seeds)}
         -> [B,L,C,H,W].
+        set_context(k): frames 0 .. k-1 of 'images' are read and given ('context_tokens' int64 [B,k,h,w] optional: their tokens, in place
+        of the encode); 'known_tokens' int64 [B,L-1,h,w] optional: slot i is frame i+1, negative = free, anything else is held
+        (set_context's docstring; last_known_mask tells which slots were given).
 
         With ``self.streams = n > 1`` the clips are processed as n independent groups on n HIP streams: clips never
         interact, so the results are bit-identical, and the HBM-bound kernels of one group (LayerNorm, attention, casts)
@@ -1777,6 +1854,7 @@ class MAGE(nn.Module):
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         self.last_guidance_scale = None
         batch = self._guidance_inputs(batch)             # (likewise: the scales and the negative caption are inputs of a captured graph)
+        batch = self._known_inputs(batch)                # (likewise the given tokens; refuses a wrong dtype or shape before anything runs)
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
         with torch.cuda.device(images.device), weights_frozen():
             ug = self._graph_auto(batch) if self.use_graph is None else bool(self.use_graph)
@@ -1791,6 +1869,82 @@ class MAGE(nn.Module):
             ops.check_device_errors(images.device)        # e.g. a caption id >= vocab_size: the reference raises IndexError
         return out
 
+    @torch.no_grad()
+    def generate_long(self, batch, frames: int, overlap: int = 1, texts=None):
+        """A video of `frames` >= frames_length frames as a chain of windows -> [B, frames, C, H, W].  Window 0 is
+        autoregressive_generate(batch) as it stands (set_context included); window w >= 1 takes the tokens of the last `overlap` frames of
+        window w-1 (1 <= overlap <= L-1) as its batch['context_tokens'] -- the hand-over stays on the device: no pixel decode or encode, no
+        host decision -- so its frame 0, the motion anchor's input, is the oldest of them, and it adds L - overlap new frames.  The last
+        window's surplus frames are dropped.
+        texts: a sequence of one caption tensor [B, S] per window (default: batch['text'] for every window).  Window w samples with
+        sample_seed + 1_000_003 * w (int64 wrap-around) and, where batch['noise_seed'] is given, draws its noise under noise_seed + w.
+        Only new tokens are decoded.  last_tokens and every per-token last_* result are [B, frames-1, h, w], each frame's entry from the
+        window that generated it; the per-clip totals are mage_clip_scores of those; last_video_noise is stacked per window
+        [windows, B, 64, h, w]; last_logits is None.  candidates > 1, batch['known_tokens'] and a use_cids=False model are refused."""
+        L = self.frames_length
+        if not self.use_cids:
+            raise ValueError("generate_long: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to hand over")
+        if self._n_cand() > 1:
+            raise ValueError("generate_long: candidates > 1 is refused (a winner per window would be a host-side choice of what to hand over)")
+        if "known_tokens" in batch:
+            raise ValueError("generate_long: batch['known_tokens'] is refused (its slots are one window's)")
+        for name, v, lo, hi in (("frames", frames, L, None), ("overlap", overlap, 1, L - 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"generate_long: {name} must be an integer in [{lo}, {'...' if hi is None else hi}], got {v!r}")
+        step = L - overlap
+        n_win = 1 + -(-(frames - L) // step)
+        if texts is not None and len(texts) != n_win:
+            raise ValueError(f"generate_long: texts must hold one caption tensor per window ({n_win}), got {len(texts)}")
+        images = batch["images"]
+        _need_gpu(images, "MAGE.generate_long")
+        base = dict(batch)
+        if getattr(self, "sampling", None) is not None:
+            base = self._sample_seeds(base)              # drawn once when absent: every window derives its seeds from these
+        seeds0, nseed0 = base.get("sample_seed"), base.get("noise_seed")
+        k0 = self.context_frames
+        videos, toks, masks, noises = [], [], [], []
+        per_tok = {a: [] for a in ("last_token_logprobs",) + tuple(attr for _, attr in self._STATS_RESULTS)}
+        try:
+            for w in range(n_win):
+                b = dict(base)
+                if texts is not None:
+                    b["text"] = texts[w]
+                if w:
+                    if seeds0 is not None:
+                        b["sample_seed"] = seeds0 + 1_000_003 * w                              # (int64 tensors wrap around)
+                    if nseed0 is not None:
+                        b["noise_seed"] = torch.as_tensor(nseed0) + w
+                    b["images"] = videos[-1][:, L - overlap:]                                # only its first `overlap` frames are read
+                    b["context_tokens"] = self.last_tokens[:, L - 1 - overlap:].contiguous()  # slot i is frame i + 1
+                    self.context_frames = overlap
+                out = self.autoregressive_generate(b)
+                new = slice(0, None) if w == 0 else slice(overlap - 1, None)                  # the slots this window generated
+                videos.append(out)
+                toks.append(self.last_tokens[:, new])
+                masks.append(self.last_known_mask[:, new] if w == 0 and self.last_known_mask is not None else None)
+                noises.append(self.last_video_noise)
+                for a, col in per_tok.items():
+                    t_ = getattr(self, a, None)
+                    col.append(None if t_ is None else t_[:, new])
+        finally:
+            self.context_frames = k0
+        B = images.shape[0]
+        cat = lambda col: None if col[0] is None else torch.cat(col, 1)[:, :frames - 1].contiguous()      # noqa: E731
+        self.last_tokens, self.last_logits = cat(toks), None
+        for a, col in per_tok.items():
+            setattr(self, a, cat(col))
+        self.last_known_mask = None
+        if masks[0] is not None:
+            self.last_known_mask = torch.zeros(self.last_tokens.shape, device=images.device, dtype=torch.bool)
+            self.last_known_mask[:, :L - 1] = masks[0]
+        self.last_video_noise = None if noises[0] is None else torch.stack(noises, 0)
+        self.last_sample_seeds = seeds0                   # window 0's: the seeds that reproduce the whole chain
+        if self.last_token_logprobs is not None:
+            self.last_clip_logprob = ops.clip_scores(self.last_token_logprobs, n_clips=B)[0].view(B)
+        if self.last_token_policy_logprobs is not None:
+            self.last_clip_policy_logprob = ops.clip_scores(self.last_token_policy_logprobs, n_clips=B)[0].view(B)
+        return torch.cat([videos[0]] + [v[:, overlap:] for v in videos[1:]], 1)[:, :frames].contiguous()
+
     def _graph_auto(self, batch) -> bool:
         """use_graph = None: replay from a captured graph where the call is launch-bound -- up to 4 clips per call (the reference samples
         ONE, main_mage.py:205: ~870 launches of 3-15 µs; 13.7 ms eager vs 7.6 ms replayed per 16-frame clip), the VQ-token path only (an
@@ -1800,7 +1954,7 @@ class MAGE(nn.Module):
         return (self.use_cids and clips * self.image_resolution ** 2 <= 1024 and not ops.PROFILE.enabled
                 and all(torch.is_tensor(v) for v in batch.values()) and config.get().auto_graph)
 
-    def _graph_fingerprint(self):
+    def _graph_fingerprint(self, batch=None):
         """Everything besides shapes, precision, AR mode and weights that selects kernels: a captured graph replays only under the same."""
         fs = self.first_stage_model
         return (int(getattr(self, "streams", 1)), bool(getattr(self, "frame_table", True)), self.generate_model._stream_bf16(), bool(getattr(self.ma_encoder, "mage_plus", False)),
@@ -1808,7 +1962,9 @@ class MAGE(nn.Module):
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
                 config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None),
                 self._want_logprobs(), self._n_cand(), bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False)),
-                self._guided())                          # (on / off selects the launches; the scales themselves are a batch tensor)
+                self._guided(),                          # (on / off selects the launches; the scales themselves are a batch tensor)
+                self._ctx(), bool(getattr(self, "context_prefill", True)),       # (likewise: the given tokens are batch tensors)
+                batch is not None and "known_tokens" in batch, batch is not None and "context_tokens" in batch)
 
     def _generate_eager(self, batch):
         if not self.use_cids:
@@ -1837,7 +1993,7 @@ class MAGE(nn.Module):
         if prof != "off" and not ops.graph_events_supported(batch["images"].device):
             return self._generate_eager(batch)              # per-launch events wanted, but they cannot be captured here
         key = (tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(batch.items())), self.precision, self.ar_mode, gens, prof,
-               str(batch["images"].device), self._graph_fingerprint())
+               str(batch["images"].device), self._graph_fingerprint(batch))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs = {k: v for k, v in self._graphs.items() if k[3] == gens}       # graphs of replaced weights are dead
@@ -1987,7 +2143,18 @@ class MAGE(nn.Module):
         R, L, K = self.image_resolution, self.frames_length, self.codebook_size
         hw, Lm1 = R * R, self.frames_length - 1
         dt = self._dt()
-        tok0 = self.first_stage_encode(images[:, 0:1])[:, 0].reshape(B, hw)                   # :642
+        # k given frames (set_context; 1: frame 0 alone): one encode of all B * k, or batch['context_tokens'] in its place
+        k = self._ctx()
+        ctx = batch.get("context_tokens")
+        ctx = (self.first_stage_encode(images[:, 0:k]) if ctx is None else ctx).reshape(B, k, hw)      # :642
+        tok0 = ctx[:, 0].contiguous()
+        # kn [B, (L-1) * hw]: the given token of every slot, negative where the slot is free (None: nothing given) -- batch['known_tokens']
+        # with the given frames 1 .. k-1 merged into slots 0 .. k-2 on the device
+        kn = batch.get("known_tokens")
+        if kn is not None or k > 1:
+            assert not keep_all                                                               # (rollout is refused with either)
+            kn = torch.full((B, Lm1, hw), -1, device=images.device, dtype=torch.int64) if kn is None else kn.reshape(B, Lm1, hw).clone()
+            kn[:, :k - 1] = ctx[:, 1:]
         seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
         N, Bc = self._n_cand(), B
         gs = batch.get("guidance_scale") if self._guided() else None                          # None: no guidance
@@ -1996,7 +2163,7 @@ class MAGE(nn.Module):
             # negative caption], clip b's second copy with clip b's frame 0, noise and speed -- and from here the batch is [cond | uncond]
             assert not candidate_noise and not keep_all                                       # (rollout is refused while guidance is on)
             two = lambda t_: torch.cat([t_, t_], 0)      # noqa: E731
-            tok0 = two(tok0)
+            tok0, ctx = two(tok0), two(ctx)
             noise, nseed = batch.get("video_noise"), batch.get("noise_seed")
             if self.randomness and noise is None and nseed is None:
                 noise = torch.randn([Bc, 64, R, R], device=images.device)                     # mage_model.py:661, one draw per clip
@@ -2023,6 +2190,7 @@ class MAGE(nn.Module):
             B = Bc * N
             Bp = tok0.shape[0]                                                                # Bc, or 2 Bc under guidance: each half expands alike
             tok0 = tok0[:, None, :].expand(Bp, N, hw).reshape(Bp * N, hw)
+            ctx = ctx[:, None].expand(Bp, N, k, hw).reshape(Bp * N, k, hw)
             ma = ma.view(Bp, 1, hw, -1).expand(Bp, N, hw, ma.shape[-1]).reshape(Bp * N * hw, -1)
             seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
         ma_dt = _to_dt(ma, dt)
@@ -2031,16 +2199,29 @@ class MAGE(nn.Module):
         # B: the clips (x candidates) whose tokens are picked; Bd: the decoder's batch -- under guidance 2 B, rows B .. 2 B the uncond half,
         # which is fed the tokens of the cond half.  Every pick / logprob / stats launch below addresses the first B clips only.
         Bd = B if gs is None else 2 * B
+        # one launch per frame stores the given tokens over the picked ones (and the certain policy's 0 / 0 / 1 over their results): the
+        # first B clips, a clip's N candidates sharing its row of kn; `a` is token_logprob's token addressing of the slot
+        force = lambda tokens, res, rows, **a: ops.apply_known_tokens(      # noqa: E731
+            tokens, kn, rows=rows, K=K, known_group_stride=Lm1 * hw, known_clip_div=N, **res, **a)
+        res_of = lambda lp_, st_, sel: {**({} if lp_ is None else {"logprob": sel(lp_)}),      # noqa: E731
+                                        **({} if st_ is None else {n: None if b is None else sel(b) for n, b in st_.items()})}
         if self.ar_mode == "incremental":
             # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
             st = self.generate_model._inc_begin(Bd, R, R)
-            prev = tok0.contiguous()
+            prev = tok0.contiguous() if k == 1 else ctx.contiguous()                          # [Bd, k, hw]: the given frames
             lp_t = torch.empty(Lm1, B, hw, device=images.device, dtype=F32) if want_lp else None
             st_t = self._stats_alloc((Lm1, B, hw), images.device)
             gen_t = torch.empty(Lm1, Bd, hw, device=images.device, dtype=torch.int64)        # frame-major: a frame's tokens are contiguous,
-            for i in range(Lm1):                                                              # the argmax writes them where the next step reads them
-                feats = self._frame_source(prev, dt)                                          # newest frame only
-                step_logits = self.generate_model._inc_step(st, ma_dt if i == 0 else None, feats)
+            for i in range(k - 1):                        # the given frames' own slots: nothing is decoded or picked for them
+                force(gen_t[i], res_of(lp_t, st_t, lambda b: b[i]), B * hw, group=hw, known_off=i * hw)
+            for i in range(k - 1, Lm1):                                                       # the argmax writes them where the next step reads them
+                if i > k - 1 or k == 1 or getattr(self, "context_prefill", True):
+                    # newest frame only; the first step takes the anchor and all k given frames as one window, the head on its last slot
+                    feats = self._frame_source(prev, dt)
+                    step_logits = self.generate_model._inc_step(st, ma_dt if i == k - 1 else None, feats, nf=k if i == k - 1 else 1)
+                else:                                     # context_prefill off: the given frames one position at a time, no pick
+                    for j in range(k):
+                        step_logits = self.generate_model._inc_step(st, ma_dt if j == 0 else None, self._frame_source(prev[:, j].contiguous(), dt))
                 prev = gen_t[i]
                 if gs is not None:                        # in place on the cond half's rows: one value per clip covers its N candidates
                     ops.guide_logits(step_logits, step_logits[B * hw:], gs, rows=B * hw, K=K, scale_div=N * hw)
@@ -2052,6 +2233,8 @@ class MAGE(nn.Module):
                     ops.token_logprob(step_logits, prev, lp_t[i], rows=B * hw, K=K)
                 if st_t is not None:
                     self._stats(step_logits, prev, st_t, lambda b: b[i], rows=B * hw, K=K)
+                if kn is not None:
+                    force(prev, res_of(lp_t, st_t, lambda b: b[i]), B * hw, group=hw, known_off=i * hw)
                 if gs is not None and i != Lm1 - 1:
                     prev[B:].copy_(prev[:B])              # the uncond half conditions on the same tokens (one small int64 copy per frame)
             if gs is not None:
@@ -2060,14 +2243,16 @@ class MAGE(nn.Module):
             clip_major = lambda t_: t_.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # noqa: E731
             lp = clip_major(lp_t) if want_lp else None
             st = None if st_t is None else {n: None if b is None else clip_major(b) for n, b in st_t.items()}
-            return self._finish(images, gen, None, lp, Bc, N, st, keep_all)
+            return self._finish(images, gen, None, lp, Bc, N, st, keep_all, k)
         cur = tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                                 # :670 future slots hold frame 0
+        if k > 1:
+            cur[:, 1:k] = ctx[:, 1:]                                                          # slots 1 .. k-1: the given frames
         logits = None
         lp = torch.empty(B, Lm1, R, R, device=images.device, dtype=F32) if want_lp else None
         st = self._stats_alloc((B, Lm1, R, R), images.device)
         flat = lambda b: b.view(-1)      # noqa: E731
         frame = dict(rows=B * hw, K=K, group=hw, in_group_stride=Lm1 * hw)                  # frame i of every clip: (in_ / tok_) off = i * hw
-        for i in range(Lm1):                                                                  # :673-684
+        for i in range(k - 1, Lm1):                                                           # :673-684
             feats = self._frame_source(cur, dt)
             ev = ops.PROFILE.begin() if ops.PROFILE.wants("decoder_step") else None          # bench.py: the transformer step on its own
             logits = self.generate_model._run(ma_dt, feats, B=Bd, hh=R, ww=R)                 # [Bd*(L-1)*hw, K]
@@ -2088,6 +2273,9 @@ class MAGE(nn.Module):
                     ops.token_logprob(logits, cur.view(-1)[hw:], lp.view(-1), in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
                 if st is not None and seeds is not None:
                     self._stats(logits, cur.view(-1)[hw:], st, flat, in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
+                if kn is not None:                        # (slot i+1 of cur is index i*hw of the flat view one frame on, as for the two above)
+                    force(cur.view(-1)[hw:], res_of(lp, st, flat) if seeds is not None else {}, B * hw, group=hw,
+                          tok_group_stride=Lm1 * hw, tok_off=i * hw, known_off=i * hw)
                 if gs is not None:
                     cur[B:, i + 1].copy_(cur[:B, i + 1])  # the picked slot goes to both halves
         if seeds is None:
@@ -2105,9 +2293,11 @@ class MAGE(nn.Module):
                 ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
             if st is not None:
                 self._stats(logits, gen, st, flat, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-        return self._finish(images, gen, logits[:B * Lm1 * hw].view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all)
+        if kn is not None:                                # every slot at once: the final pick's tokens and results, the given frames' slots
+            force(gen, res_of(lp, st, flat), B * Lm1 * hw, group=Lm1 * hw)
+        return self._finish(images, gen, logits[:B * Lm1 * hw].view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all, k)
 
-    def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None, keep_all: bool = False):
+    def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None, keep_all: bool = False, k: int = 1):
         """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
         of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691).  st: the
         mage_token_stats buffers of set_logprobs(policy=, entropy=), [B * N, L-1, h, w] each (None: off); the winner's rows are kept.
@@ -2142,6 +2332,9 @@ class MAGE(nn.Module):
                 for name, attr in self._STATS_RESULTS:
                     setattr(self, attr, st[name])
         self.last_tokens, self.last_logits = gen, logits
+        if k > 1:                                         # the k given frames verbatim, then the generated ones: only those are decoded
+            video = self.first_stage_decode(gen[:, k - 1:])
+            return torch.cat([images[:, :k].to(video.dtype), video], 1)
         video = self.first_stage_decode(gen)
         return _assemble(images, video)
 

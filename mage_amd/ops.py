@@ -657,6 +657,36 @@ def guide_logits(cond: torch.Tensor, uncond: torch.Tensor, scale: torch.Tensor, 
     return out
 
 
+def apply_known_tokens(tokens: torch.Tensor, known: torch.Tensor, *, rows: int, K: int, group: Optional[int] = None,
+                       tok_group_stride: Optional[int] = None, tok_off: int = 0, known_group_stride: Optional[int] = None, known_off: int = 0,
+                       known_clip_div: int = 1, logprob: Optional[torch.Tensor] = None, policy_logprob: Optional[torch.Tensor] = None,
+                       entropy: Optional[torch.Tensor] = None, policy_entropy: Optional[torch.Tensor] = None,
+                       kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Given tokens over picked ones (mage_apply_known_tokens): row i reads known[((i // group) // known_clip_div) * known_group_stride +
+    i % group + known_off]; a value >= 0 is stored at token_logprob's index (i // group) * tok_group_stride + i % group + tok_off of tokens, and
+    that index of every result given gets the certain policy's value (log-probabilities and entropies 0, kept 1).  A negative value leaves the
+    slot as it is.  Every buffer is addressed from its first element."""
+    l, s = _dev(tokens)
+    assert tokens.dtype == torch.int64 and known.dtype == torch.int64 and known.device == tokens.device
+    group = max(rows, 1) if group is None else group
+    tok_group_stride = group if tok_group_stride is None else tok_group_stride
+    known_group_stride = group if known_group_stride is None else known_group_stride
+    if rows > 0:
+        c, j = (rows - 1) // group, (rows - 1) % group
+        full = group - 1 if c > 0 else j                                                      # a full group before a partial last one
+        last = max(c * tok_group_stride + j, (c - 1) * tok_group_stride + full) + tok_off     # the largest index addressed
+        assert tok_off >= 0 and known_off >= 0 and last < tokens.numel()
+        kc, kp = c // known_clip_div, (c - 1) // known_clip_div
+        assert max(kc * known_group_stride + j, kp * known_group_stride + full) + known_off < known.numel()
+        for o, dt in ((logprob, torch.float32), (policy_logprob, torch.float32), (entropy, torch.float32), (policy_entropy, torch.float32),
+                      (kept, torch.int32)):
+            assert o is None or (o.dtype == dt and o.device == tokens.device and last < o.numel())
+    _lib.check(l.mage_apply_known_tokens(tokens.data_ptr(), rows, group, tok_group_stride, tok_off, known.data_ptr(), known_group_stride,
+                                         known_off, known_clip_div, K, _p(logprob), _p(policy_logprob), _p(entropy), _p(policy_entropy),
+                                         _p(kept), s), l)
+    return tokens
+
+
 def _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div):
     """The asserts policy_loss and policy_loss_bwd share; returns (rows, K, ld, adv_div).  adv_div None: advantage's entries share the rows
     out equally (one per row, or one per clip)."""
