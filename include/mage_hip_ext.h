@@ -311,6 +311,45 @@ int mage_apply_known_tokens(int64_t* tokens, int64_t rows, int64_t group, int64_
                             int64_t known_group_stride, int64_t known_off, int64_t known_clip_div, int32_t K, float* logprob,
                             float* policy_logprob, float* entropy, float* policy_entropy, int32_t* kept, void* stream);
 
+/* mage_policy_loss / mage_policy_loss_anchored over the rows that were drawn, leaving out the rows that were given: no site in the reference.
+ * Serves MAGE.policy_loss(given=) (mage_amd/modules/mage_train.py: PolicyHead with a 'given' argument) for tokens of a rollout that
+ * continued given frames or filled in around given tokens (MAGE.rollout(context=, known_tokens=)).
+ * The arguments are mage_policy_loss_anchored's plus given (uint8 [rows], one byte per row, non-zero: the row's token was given, not drawn; a
+ * torch.bool tensor as it is) and norm (fp32 [1], device).  reference_logprob and kl may both be null: the plain rule of mage_policy_loss
+ * (kl_coef must then be 0); both non-null: the anchored rule.
+ *   A free row (given[i] == 0) is computed by the operations of the unmasked kernels (the same kernel instances, behind one wave-uniform
+ *   branch): cut, logprob, entropy, kl and row_loss carry, bit for bit, what mage_policy_loss / mage_policy_loss_anchored write for that row.
+ *   A given row is never read: not its logits (a NaN there does not show), not its advantage, behaviour or reference value; its token is not
+ *   range-checked.  The forward call writes cut = 0 and logprob = entropy = kl = row_loss = +0; the backward call writes its dlogits row as +0
+ *   with the stores the free rows use (fp32: 16 bytes, bf16: 8 bytes per lane).
+ * summary[0..7) are the anchored call's seven means (under the plain rule the sixth and seventh are 0) taken OVER THE FREE ROWS, sum / n_free:
+ * the same two-stage fixed-order fp64 reduction through the same per-device buffer -- a thread adds its free rows in ascending order -- so
+ * the ordering rule between calls holds, and with nothing given the seven carry the unmasked call's bits.  summary[7] is the share of given
+ * rows over `rows`.  The forward call also writes norm[0] = 1.0f / (float)n_free, the expression the unmasked backward call forms for
+ * 1.0f / (float)rows; the backward call reads norm[0] in its place (dlogits of a free row = the unmasked rule with n_free for rows: its bits
+ * depend on the row and on norm[0] alone).  Nothing is read on the host.
+ * n_free == 0: norm[0] = 0, the seven means are +0, summary[7] = 1, dlogits is all zeros; no NaN anywhere.
+ * The plain pair's argument rules; given non-null, norm non-null and 4-byte aligned, reference_logprob and kl both null or both non-null
+ * (the backward call: reference_logprob alone decides), kl_coef == 0 without a reference: MAGE_EINVAL otherwise, nothing launched. */
+int mage_policy_loss_masked(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                            int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature, int32_t top_k,
+                            float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, float* row_loss, float* logprob,
+                            float* entropy, uint32_t* cut, float* kl, float* summary, float* norm, const uint8_t* given, void* stream);
+int mage_policy_loss_masked_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, const uint32_t* cut,
+                                float temperature, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, const float* grad_out,
+                                const float* norm, void* dlogits, int32_t dl_dtype, const uint8_t* given, void* stream);
+
+/* mage_token_logprob_bwd with given rows left out: no site in the reference.  Serves the backward pass of MAGE.preference_loss(given=).
+ * mage_token_logprob_bwd's arguments plus given (uint8 [rows], as mage_policy_loss_masked's).  A given row is a row of c_i == 0: +0
+ * throughout, its logits not read (a NaN there does not show); every other row carries mage_token_logprob_bwd's bits (one kernel template,
+ * the mask behind a wave-uniform branch).  The forward side needs no kernel of its own: one mage_apply_known_tokens launch after
+ * mage_token_logprob writes the given slots' 0, and mage_clip_scores then sums the free tokens.
+ * mage_token_logprob_bwd's rules; given non-null: MAGE_EINVAL otherwise, nothing launched. */
+int mage_token_logprob_bwd_masked(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
+                                  int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, const uint8_t* given,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

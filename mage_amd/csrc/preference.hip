@@ -178,12 +178,15 @@ __device__ __forceinline__ void logprob_bwd_store(OT* __restrict__ o, int lane, 
 template <int NV, typename OT>
 __global__ __launch_bounds__(256) void token_logprob_bwd_kernel(const float* __restrict__ logits, long rows, int K, long ld,
                                                                 const int64_t* __restrict__ tokens, const float* __restrict__ weight,
-                                                                long weight_div, const float* __restrict__ gout, OT* __restrict__ dl, bool wide) {
+                                                                long weight_div, const float* __restrict__ gout, OT* __restrict__ dl, bool wide,
+                                                                const uint8_t* __restrict__ given) {
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= rows) return;
     const int lane = threadIdx.x & 63;
     OT* o = dl + i * (long)K;
-    const float ci = __fmul_rn(gout[0], weight[i / weight_div]);
+    // (mage_token_logprob_bwd_masked: a given row is a row of c_i == 0; a null mask, the unmasked entry point, has none)
+    const bool gv = given && __builtin_amdgcn_readfirstlane((int)given[i]) != 0;
+    const float ci = gv ? 0.f : __fmul_rn(gout[0], weight[i / weight_div]);
     float d[NV];
     if (ci == 0.f) {                                    // (wave-uniform)
 #pragma unroll
@@ -253,22 +256,24 @@ extern "C" int mage_preference_loss(const float* clip_logprob, const float* refe
     return MAGE_OK;
 }
 
-extern "C" int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
-                                      int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream) {
-    MAGE_CHECK_ARG(logits && tokens && weight && grad_out && dlogits, "mage_token_logprob_bwd: null pointer");
+// mage_token_logprob_bwd (given null) and mage_token_logprob_bwd_masked behind one set of argument rules
+static int token_logprob_backward(const char* who, const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
+                                  const float* weight, int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype,
+                                  const uint8_t* given, void* stream) {
+    MAGE_CHECK_ARG(logits && tokens && weight && grad_out && dlogits, "%s: null pointer", who);
     MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && weight_div > 0 &&
                    (((uintptr_t)logits) & 15) == 0 && (((uintptr_t)dlogits) & 15) == 0,
-                   "mage_token_logprob_bwd: bad sizes rows=%ld K=%d ld=%ld weight_div=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)",
+                   "%s: bad sizes rows=%ld K=%d ld=%ld weight_div=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", who,
                    (long)rows, K, (long)ld, (long)weight_div, MAGE_SAMPLE_MAX_K);
     MAGE_CHECK_ARG((((uintptr_t)tokens) & 7) == 0 && ((((uintptr_t)weight) | ((uintptr_t)grad_out)) & 3) == 0,
-                   "mage_token_logprob_bwd: tokens must be 8-byte, weight and grad_out 4-byte aligned");
-    MAGE_CHECK_ARG(dl_dtype == MAGE_F32 || dl_dtype == MAGE_BF16, "mage_token_logprob_bwd: bad dtype %d", dl_dtype);
+                   "%s: tokens must be 8-byte, weight and grad_out 4-byte aligned", who);
+    MAGE_CHECK_ARG(dl_dtype == MAGE_F32 || dl_dtype == MAGE_BF16, "%s: bad dtype %d", who, dl_dtype);
     const dim3 grid((unsigned)((rows + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
     const bool wide = K % 8 == 0;
 #define MAGE_LPB(NV, OT)                                                                                                                \
     hipLaunchKernelGGL((token_logprob_bwd_kernel<NV, OT>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, tokens, weight,   \
-                       (long)weight_div, grad_out, (OT*)dlogits, wide)
+                       (long)weight_div, grad_out, (OT*)dlogits, wide, given)
 #define MAGE_LPB_NV(NV)                                  \
     do {                                                 \
         if (dl_dtype == MAGE_F32) MAGE_LPB(NV, float);   \
@@ -281,6 +286,20 @@ extern "C" int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t
     else MAGE_LPB_NV(64);
 #undef MAGE_LPB_NV
 #undef MAGE_LPB
-    MAGE_CHECK_LAUNCH("mage_token_logprob_bwd");
+    MAGE_CHECK_LAUNCH(who);
     return MAGE_OK;
+}
+
+extern "C" int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
+                                      int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream) {
+    return token_logprob_backward("mage_token_logprob_bwd", logits, rows, K, ld, tokens, weight, weight_div, grad_out, dlogits, dl_dtype, nullptr,
+                                  stream);
+}
+
+extern "C" int mage_token_logprob_bwd_masked(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
+                                             int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, const uint8_t* given,
+                                             void* stream) {
+    MAGE_CHECK_ARG(given != nullptr, "mage_token_logprob_bwd_masked: given must not be null (mage_token_logprob_bwd takes no mask)");
+    return token_logprob_backward("mage_token_logprob_bwd_masked", logits, rows, K, ld, tokens, weight, weight_div, grad_out, dlogits, dl_dtype,
+                                  given, stream);
 }

@@ -704,6 +704,12 @@ __device__ __forceinline__ long policy_token(const int64_t* __restrict__ tokens,
     return tg;
 }
 
+// mage_policy_loss_masked's per-row byte, one scalar value per wave (the row index is the wave's); a null mask (the unmasked entry points) has
+// no given row
+__device__ __forceinline__ bool policy_row_given(const uint8_t* __restrict__ given, long i) {
+    return given && __builtin_amdgcn_readfirstlane((int)given[i]) != 0;
+}
+
 template <int NV, bool TOPK, bool TOPP, bool ANCH>
 __global__ __launch_bounds__(256) void policy_loss_kernel(const float* __restrict__ logits, long rows, int K, long ld,
                                                           const int64_t* __restrict__ tokens, const float* __restrict__ adv, long adv_div,
@@ -711,10 +717,21 @@ __global__ __launch_bounds__(256) void policy_loss_kernel(const float* __restric
                                                           float cmax, float ent_coef, float* __restrict__ row_loss,
                                                           float* __restrict__ logprob, float* __restrict__ entropy,
                                                           unsigned* __restrict__ cut, int* __restrict__ err,
-                                                          const float* __restrict__ ref, float kl_coef, float* __restrict__ kl) {
+                                                          const float* __restrict__ ref, float kl_coef, float* __restrict__ kl,
+                                                          const uint8_t* __restrict__ given) {
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= rows) return;
     const int lane = threadIdx.x & 63;
+    if (policy_row_given(given, i)) {                   // (wave-uniform) mage_policy_loss_masked: nothing of the row is read
+        if (lane == 0) {
+            cut[i] = 0u;
+            logprob[i] = 0.f;
+            entropy[i] = 0.f;
+            row_loss[i] = 0.f;
+            if (kl) kl[i] = 0.f;
+        }
+        return;
+    }
     const float* p = logits + i * ld;
     float s[NV], w[NV];
     unsigned key[NV];
@@ -754,17 +771,26 @@ __global__ __launch_bounds__(256) void policy_loss_kernel(const float* __restric
 // entropies, b - logprob, the rows whose gradient the clip switched off, the outside rows (an outside row counts in the last one only) and,
 // for the anchored call (W = 7), the KL estimates and the unanchored rows (a reference log-probability that is not finite).
 // A thread adds its rows in ascending order, the lanes meet in an xor butterfly, thread 0 adds the four waves in order: a fixed order.
-enum { POLICY_PARTS = 256, POLICY_MEANS = 7 };
-__device__ double g_policy_part[POLICY_PARTS * POLICY_MEANS];      // stage 1 -> stage 2, within one mage_policy_loss* call (stream order)
+// The masked call (W = 8) adds the free rows only, in the same order, and counts the given ones in an eighth sum; its kl and ref may be null
+// (the plain rule: sums 5 and 6 stay 0).
+enum { POLICY_PARTS = 256, POLICY_MEANS = 7, POLICY_MASKED = 8 };
+__device__ double g_policy_part[POLICY_PARTS * POLICY_MASKED];     // stage 1 -> stage 2, within one mage_policy_loss* call (stream order)
 template <int W>
 __global__ __launch_bounds__(256) void policy_part_kernel(const float* __restrict__ row_loss, const float* __restrict__ logprob,
                                                           const float* __restrict__ entropy, const float* __restrict__ adv, long adv_div,
                                                           const float* __restrict__ blp, float cmin, float cmax, long rows, long chunk,
-                                                          const float* __restrict__ kl, const float* __restrict__ ref) {
+                                                          const float* __restrict__ kl, const float* __restrict__ ref,
+                                                          const uint8_t* __restrict__ given) {
     __shared__ double red[4][W];
     const long r0 = (long)blockIdx.x * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
     double a[W] = {};
     for (long i = r0 + threadIdx.x; i < r1; i += 256) {
+        if constexpr (W == POLICY_MASKED) {
+            if (given[i]) {
+                a[7] += 1.0;
+                continue;
+            }
+        }
         const float lp = logprob[i];
         if (lp == -INFINITY) {
             a[4] += 1.0;
@@ -777,9 +803,11 @@ __global__ __launch_bounds__(256) void policy_part_kernel(const float* __restric
             a[2] += (double)b - (double)lp;
             a[3] += policy_term(lp, 0.f, adv[i / adv_div], true, b, cmin, cmax, 0.f).off ? 1.0 : 0.0;
         }
-        if constexpr (W == 7) {
-            a[5] += (double)kl[i];
-            a[6] += __builtin_isfinite(ref[i]) ? 0.0 : 1.0;
+        if constexpr (W >= POLICY_MEANS) {
+            if (W == POLICY_MEANS || ref) {
+                a[5] += (double)kl[i];
+                a[6] += __builtin_isfinite(ref[i]) ? 0.0 : 1.0;
+            }
         }
     }
 #pragma unroll
@@ -813,6 +841,34 @@ __global__ __launch_bounds__(256) void policy_summary_kernel(float* __restrict__
     }
 }
 
+// stage 2 of the masked call: the same sums; the eighth one is the number of given rows (exact in fp64), so n_free = rows - given.  The seven
+// means are multiplied by 1 / n_free (the unmasked call's 1.0 / rows when nothing is given; 0 when everything is), summary[7] is the given
+// share, and norm[0] = 1.0f / (float)n_free is left for the backward call: the value the unmasked one forms on the host for its `rows`.
+__global__ __launch_bounds__(256) void policy_summary_masked_kernel(float* __restrict__ summary, float* __restrict__ norm, long rows) {
+    constexpr int W = POLICY_MASKED;
+    __shared__ double red[4][W];
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+        double v = g_policy_part[threadIdx.x * W + q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < W) {
+        const int q = threadIdx.x;
+        const double ng = ((red[0][7] + red[1][7]) + red[2][7]) + red[3][7];
+        const long n_free = rows - (long)ng;
+        if (q < POLICY_MEANS) {
+            const double inv = n_free > 0 ? 1.0 / (double)n_free : 0.0;
+            summary[q] = (float)((((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) * inv);
+        } else {
+            summary[7] = (float)(ng / (double)rows);
+            norm[0] = n_free > 0 ? __fdiv_rn(1.0f, (float)n_free) : 0.f;
+        }
+    }
+}
+
 // dlogits_ij = scale * [ g_i (1[j = t] - p_j) + ent_coef p_j (log p_j + H_i) ] for j in N, 0 outside N and in outside rows; scale =
 // grad_out[0] / rows * inv_t, p_j = w_j / Z, log p_j + H_i = (s_j - smax) - (sum_N w (s - smax)) / Z; a p_j = 0 term is 0.  Z, H, logprob are
 // recomputed with the forward kernel's operations (policy_sums), so g_i is decided by the forward pass's rho.
@@ -822,12 +878,22 @@ __global__ __launch_bounds__(256) void policy_loss_bwd_kernel(const float* __res
                                                               const float* __restrict__ blp, const unsigned* __restrict__ cut, float inv_t,
                                                               float cmin, float cmax, float ent_coef, const float* __restrict__ gout,
                                                               float inv_rows, OT* __restrict__ dl, const float* __restrict__ ref,
-                                                              float kl_coef) {
+                                                              float kl_coef, const uint8_t* __restrict__ given,
+                                                              const float* __restrict__ norm) {
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= rows) return;
     const int lane = threadIdx.x & 63;
     const float* p = logits + i * ld;
     OT* o = dl + i * (long)K;
+    if (policy_row_given(given, i)) {                                   // (wave-uniform) a zero row by the free rows' stores, nothing read
+#pragma unroll
+        for (int c = 0; c < NV / 4; ++c) {
+            const int k = c * 256 + lane * 4;
+            if (k < K) store4(o + k, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+        return;
+    }
+    if (norm) inv_rows = norm[0];                                       // the masked call: 1 / n_free, left by its forward call
     const unsigned lo = cut[i];
     float s[NV], w[NV];
     unsigned key[NV];
@@ -1551,10 +1617,10 @@ template <int NV, bool ANCH>
 static void policy_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, const int64_t* tokens,
                           const float* adv, long adv_div, const float* blp, float inv_t, int top_k, float top_p, float cmin, float cmax,
                           float ent_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, int* err, const float* ref,
-                          float kl_coef, float* kl) {
+                          float kl_coef, float* kl, const uint8_t* given) {
 #define MAGE_POLICY(TK, TP)                                                                                                                  \
     hipLaunchKernelGGL((policy_loss_kernel<NV, TK, TP, ANCH>), grid, dim3(256), 0, s, logits, rows, K, ld, tokens, adv, adv_div, blp, inv_t, \
-                       top_k, top_p, cmin, cmax, ent_coef, row_loss, logprob, entropy, cut, err, ref, kl_coef, kl)
+                       top_k, top_p, cmin, cmax, ent_coef, row_loss, logprob, entropy, cut, err, ref, kl_coef, kl, given)
     if (topk && topp) MAGE_POLICY(true, true);
     else if (topk) MAGE_POLICY(true, false);
     else if (topp) MAGE_POLICY(false, true);
@@ -1562,12 +1628,14 @@ static void policy_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const 
 #undef MAGE_POLICY
 }
 
-// mage_policy_loss (ANCH false: reference_logprob, kl_coef and kl unused) and mage_policy_loss_anchored behind their own argument rules
+// mage_policy_loss (ANCH false: reference_logprob, kl_coef and kl unused) and mage_policy_loss_anchored behind their own argument rules;
+// given non-null: mage_policy_loss_masked in either form (the masked reduction, norm written)
 template <bool ANCH>
 static int policy_forward(const char* who, const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
                           int64_t adv_div, const float* behaviour_logprob, float temperature, int32_t top_k, float top_p, float clip_lo,
                           float clip_hi, float entropy_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* summary,
-                          const float* reference_logprob, float kl_coef, float* kl, void* stream) {
+                          const float* reference_logprob, float kl_coef, float* kl, void* stream, const uint8_t* given = nullptr,
+                          float* norm = nullptr) {
     MAGE_CHECK_ARG(logits && tokens && advantage && row_loss && logprob && entropy && cut && summary, "%s: null pointer", who);
     const float inv_t = (float)(1.0 / (double)temperature);
     if (int rc = policy_check(who, logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
@@ -1585,7 +1653,8 @@ static int policy_forward(const char* who, const float* logits, int64_t rows, in
     hipStream_t s = (hipStream_t)stream;
 #define MAGE_POLICY_NV(NV)                                                                                                                   \
     policy_launch<NV, ANCH>(topk, topp, grid, s, logits, (long)rows, K, (long)ld, tokens, advantage, (long)adv_div, behaviour_logprob, inv_t, \
-                            top_k, top_p, cmin, cmax, entropy_coef, row_loss, logprob, entropy, cut, err, reference_logprob, kl_coef, kl)
+                            top_k, top_p, cmin, cmax, entropy_coef, row_loss, logprob, entropy, cut, err, reference_logprob, kl_coef, kl, \
+                            given)
     if (K <= 256) MAGE_POLICY_NV(4);
     else if (K <= 512) MAGE_POLICY_NV(8);
     else if (K <= 1024) MAGE_POLICY_NV(16);
@@ -1593,9 +1662,16 @@ static int policy_forward(const char* who, const float* logits, int64_t rows, in
     else MAGE_POLICY_NV(64);
 #undef MAGE_POLICY_NV
     constexpr int W = ANCH ? POLICY_MEANS : 5;
-    hipLaunchKernelGGL(policy_part_kernel<W>, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage, (long)adv_div,
-                       behaviour_logprob, cmin, cmax, (long)rows, (long)((rows + POLICY_PARTS - 1) / POLICY_PARTS), kl, reference_logprob);
-    hipLaunchKernelGGL(policy_summary_kernel<W>, dim3(1), dim3(POLICY_PARTS), 0, s, summary, 1.0 / (double)rows);
+    const long chunk = (long)((rows + POLICY_PARTS - 1) / POLICY_PARTS);
+    if (given) {
+        hipLaunchKernelGGL(policy_part_kernel<POLICY_MASKED>, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage,
+                           (long)adv_div, behaviour_logprob, cmin, cmax, (long)rows, chunk, kl, reference_logprob, given);
+        hipLaunchKernelGGL(policy_summary_masked_kernel, dim3(1), dim3(POLICY_PARTS), 0, s, summary, norm, (long)rows);
+    } else {
+        hipLaunchKernelGGL(policy_part_kernel<W>, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage, (long)adv_div,
+                           behaviour_logprob, cmin, cmax, (long)rows, chunk, kl, reference_logprob, given);
+        hipLaunchKernelGGL(policy_summary_kernel<W>, dim3(1), dim3(POLICY_PARTS), 0, s, summary, 1.0 / (double)rows);
+    }
     MAGE_CHECK_LAUNCH(who);
     return MAGE_OK;
 }
@@ -1604,7 +1680,8 @@ template <bool ANCH>
 static int policy_backward(const char* who, const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
                            const float* advantage, int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature,
                            float clip_lo, float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype,
-                           const float* reference_logprob, float kl_coef, void* stream) {
+                           const float* reference_logprob, float kl_coef, void* stream, const uint8_t* given = nullptr,
+                           const float* norm = nullptr) {
     MAGE_CHECK_ARG(logits && tokens && advantage && cut && grad_out && dlogits, "%s: null pointer", who);
     const float inv_t = (float)(1.0 / (double)temperature);
     if (int rc = policy_check(who, logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
@@ -1618,7 +1695,7 @@ static int policy_backward(const char* who, const float* logits, int64_t rows, i
 #define MAGE_POLICY_BWD(NV, OT)                                                                                                            \
     hipLaunchKernelGGL((policy_loss_bwd_kernel<NV, OT, ANCH>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, tokens, advantage, \
                        (long)adv_div, behaviour_logprob, cut, inv_t, cmin, cmax, entropy_coef, grad_out, 1.0f / (float)rows, (OT*)dlogits, \
-                       reference_logprob, kl_coef)
+                       reference_logprob, kl_coef, given, norm)
 #define MAGE_POLICY_BWD_NV(NV)                                  \
     do {                                                        \
         if (dl_dtype == MAGE_F32) MAGE_POLICY_BWD(NV, float);   \
@@ -1667,4 +1744,42 @@ extern "C" int mage_policy_loss_anchored_bwd(const float* logits, int64_t rows, 
                                              int32_t dl_dtype, void* stream) {
     return policy_backward<true>("mage_policy_loss_anchored_bwd", logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut,
                                  temperature, clip_lo, clip_hi, entropy_coef, grad_out, dlogits, dl_dtype, reference_logprob, kl_coef, stream);
+}
+
+// the mask and the normaliser of the masked pair, and its one rule about the anchor: reference_logprob and kl come together or not at all
+static int policy_masked_check(const char* who, const uint8_t* given, const float* norm, bool has_ref, bool has_kl, float kl_coef) {
+    MAGE_CHECK_ARG(given != nullptr, "%s: given must not be null (the unmasked entry points take no mask)", who);
+    MAGE_CHECK_ARG(norm && (((uintptr_t)norm) & 3) == 0, "%s: norm must be a 4-byte aligned pointer", who);
+    MAGE_CHECK_ARG(has_ref == has_kl, "%s: reference_logprob and kl are given together (the anchored rule) or both null (the plain rule)", who);
+    MAGE_CHECK_ARG(has_ref || kl_coef == 0.f, "%s: kl_coef=%g needs reference_logprob", who, (double)kl_coef);
+    return MAGE_OK;
+}
+
+extern "C" int mage_policy_loss_masked(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                       int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature,
+                                       int32_t top_k, float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef,
+                                       float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* kl, float* summary, float* norm,
+                                       const uint8_t* given, void* stream) {
+    const char* who = "mage_policy_loss_masked";
+    if (int rc = policy_masked_check(who, given, norm, reference_logprob != nullptr, kl != nullptr, kl_coef)) return rc;
+    if (reference_logprob)
+        return policy_forward<true>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k, top_p, clip_lo,
+                                    clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, reference_logprob, kl_coef, kl, stream, given,
+                                    norm);
+    return policy_forward<false>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k, top_p, clip_lo,
+                                 clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, nullptr, 0.f, nullptr, stream, given, norm);
+}
+
+extern "C" int mage_policy_loss_masked_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
+                                           const float* advantage, int64_t adv_div, const float* behaviour_logprob,
+                                           const float* reference_logprob, const uint32_t* cut, float temperature, float clip_lo, float clip_hi,
+                                           float entropy_coef, float kl_coef, const float* grad_out, const float* norm, void* dlogits,
+                                           int32_t dl_dtype, const uint8_t* given, void* stream) {
+    const char* who = "mage_policy_loss_masked_bwd";
+    if (int rc = policy_masked_check(who, given, norm, reference_logprob != nullptr, reference_logprob != nullptr, kl_coef)) return rc;
+    if (reference_logprob)
+        return policy_backward<true>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut, temperature, clip_lo, clip_hi,
+                                     entropy_coef, grad_out, dlogits, dl_dtype, reference_logprob, kl_coef, stream, given, norm);
+    return policy_backward<false>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut, temperature, clip_lo, clip_hi,
+                                  entropy_coef, grad_out, dlogits, dl_dtype, nullptr, 0.f, stream, given, norm);
 }

@@ -1064,7 +1064,8 @@ class MAGE(nn.Module):
         Free slots keep their sampler counters: a clip with nothing given is the unconstrained clip bit for bit.
         Incremental mode takes the anchor and the k given frames as one window (no decoder step and no pick before frame k).
         While k > 1, or for a batch that carries known_tokens, score, policy_loss, token_policy_logprobs, clip_logprobs, preference_loss and
-        rollout are refused: their loss heads have no per-token mask yet."""
+        rollout are refused: the setting and the batch keys shape generation.  Fine-tuning on continued clips is explicit instead --
+        rollout(context=, known_tokens=) draws them and the loss methods take the mask of the given slots as given=."""
         if isinstance(frames, bool) or not isinstance(frames, int):
             raise ValueError(f"set_context: frames must be an integer, got {frames!r}")
         if not 1 <= frames <= self.frames_length - 1:
@@ -1080,7 +1081,21 @@ class MAGE(nn.Module):
     def _refuse_known(self, who: str, batch=None) -> None:
         if self._ctx() > 1 or (isinstance(batch, dict) and ("known_tokens" in batch or "context_tokens" in batch)):
             raise ValueError(f"{who}: given frames or tokens (set_context, batch['known_tokens'] / ['context_tokens']) shape generation only -- "
-                             "the loss heads have no per-token mask; call set_context(1) and drop the keys first")
+                             "call set_context(1) and drop the keys first; the loss methods take the given slots explicitly, as given= "
+                             "(rollout: as context= and known_tokens=)")
+
+    def _given_mask(self, who: str, given, tshape, device=None):
+        """given= of the loss methods: None, or bool [B, L-1, h, w] on the model's GPU (slot i is frame i + 1: last_known_mask's layout,
+        rollout's out['given']), contiguous.  Refused before any launch otherwise."""
+        if given is None:
+            return None
+        if not self.use_cids:
+            raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to hold (given=)")
+        if not (torch.is_tensor(given) and given.dtype == torch.bool and tuple(given.shape) == tuple(tshape)):
+            raise ValueError(f"{who}: given must be bool {list(tshape)} (True: the slot's token was given, not drawn)")
+        if not (given.is_cuda and (device is None or given.device == device)):
+            raise ValueError(f"{who}: given must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        return given.contiguous()
 
     def _known_inputs(self, batch) -> dict:
         """The batch with its optional 'context_tokens' (int64 [B, k, h, w]) and 'known_tokens' (int64 [B, L-1, h, w]) checked and on the
@@ -1168,17 +1183,22 @@ class MAGE(nn.Module):
                       ("policy_entropy", "last_token_policy_entropy"))
 
     @torch.no_grad()
-    def score(self, batch) -> torch.Tensor:
+    def score(self, batch, given=None) -> torch.Tensor:
         """Teacher-forced log-likelihood of the batch's own video under its caption: fp32 [B], the sum over frames 1 .. L-1 of the
         log-probabilities of the frames' VQ tokens given the frames before them (last_token_logprobs [B, L-1, h, w] keeps the terms).
         With set_logprobs(policy=, entropy=) it leaves their results for the batch's own tokens too; every result of theirs that this call
-        does not compute is None afterwards, last_candidate_policy_scores included (score has no candidates)."""
+        does not compute is None afterwards, last_candidate_policy_scores included (score has no candidates).
+        given (bool [B, L-1, h, w], slot i is frame i + 1): the slots whose tokens were given, not drawn -- one mage_apply_known_tokens launch
+        writes what generation reports there (log-probabilities and entropies 0, kept 1) before the clip totals, so the score of a continued
+        clip is the sum over its free tokens: the generation's last_clip_logprob, by the same mechanism on both sides."""
         if not self.use_cids:
             raise ValueError("score: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
         self._refuse_guided("score")
         self._refuse_known("score", batch)
         images = batch["images"]
         _need_gpu(images, "MAGE.score")
+        given = self._given_mask("score", given, (images.shape[0], self.frames_length - 1, self.image_resolution, self.image_resolution),
+                                 images.device)
         self._want_stats()                                # (refuses policy without sampling before anything runs)
         with torch.cuda.device(images.device), weights_frozen():
             tok, logits = self.teacher_forced_logits(batch)
@@ -1186,7 +1206,8 @@ class MAGE(nn.Module):
             tgt = tok[:, 1:L].contiguous()
             lp = torch.empty(tgt.shape, device=images.device, dtype=F32)
             ops.token_logprob(logits, tgt, lp, rows=tgt.numel(), K=K)
-            scores, _ = ops.clip_scores(lp, n_clips=B)
+            if given is None:
+                scores, _ = ops.clip_scores(lp, n_clips=B)
             self.last_token_logprobs = lp
             st = self._stats_alloc(tgt.shape, images.device)   # the batch's own tokens under the current sampler: -inf where it could never draw one
             for _, attr in self._STATS_RESULTS:
@@ -1196,13 +1217,16 @@ class MAGE(nn.Module):
                 self._stats(logits, tgt, st, lambda b: b, rows=tgt.numel(), K=K)
                 for name, attr in self._STATS_RESULTS:
                     setattr(self, attr, st[name])
-                if st["policy_logprob"] is not None:
-                    self.last_clip_policy_logprob = ops.clip_scores(st["policy_logprob"], n_clips=B)[0].view(B)
+            if given is not None:                         # the given slots' results, then the totals over the free tokens
+                ops.apply_known_tokens(tgt, torch.where(given, tgt, -1), rows=tgt.numel(), K=K, logprob=lp, **(st or {}))
+                scores, _ = ops.clip_scores(lp, n_clips=B)
+            if st is not None and st["policy_logprob"] is not None:
+                self.last_clip_policy_logprob = ops.clip_scores(st["policy_logprob"], n_clips=B)[0].view(B)
             ops.check_device_errors(images.device)
         return scores.view(B)
 
     def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0, reference_logprobs=None,
-                    kl_coef: float = 0.0):
+                    kl_coef: float = 0.0, given=None):
         """Policy-gradient loss of given tokens under the policy set_sampling currently describes (sampling off: temperature 1, no filter):
         (loss, info) of one teacher-forced pass over frame 0 of batch['images'] (plus batch['text'] and the optional batch['speed'], as
         autoregressive_generate reads them) followed by `tokens` (int64 [B, L-1, h, w], e.g. last_tokens), ending in mage_policy_loss
@@ -1226,6 +1250,12 @@ class MAGE(nn.Module):
         whose reference value is not finite (the reference's filter could not draw it) is unanchored: no penalty.  info gains 'kl' (the
         mean estimate) and 'unanchored_fraction', last_policy_token_kl keeps the per-token values.  Without a reference the call is the
         plain one in every bit, and last_policy_token_kl is None.
+        given bool [B, L-1, h, w] (slot i is frame i + 1; rollout(context=, known_tokens=)'s out['given'], or last_known_mask of a
+        generation): the slots whose tokens were given, not drawn (mage_policy_loss_masked).  A given slot is not scored -- no ratio, no KL
+        term, no gradient, its logits are not even read -- every mean in info is over the free tokens, info gains 'given_fraction', and
+        last_policy_token_logprobs / last_policy_token_kl hold 0 there.  With advantages 1, sampling off and entropy_coef 0 this is the
+        cross-entropy over the free tokens only: the supervised loss for continuation fine-tuning.  Without given the call is the unmasked
+        one in every launch.
         Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
         from . import mage_train
         images, B, tshape, vn = self._given_tokens_inputs("policy_loss", batch, tokens)
@@ -1254,12 +1284,15 @@ class MAGE(nn.Module):
             raise ValueError(f"policy_loss: kl_coef must be finite and >= 0, got {kl_coef!r}")
         if kl_coef > 0 and ref is None:
             raise ValueError("policy_loss: kl_coef > 0 needs reference_logprobs (the penalty is against a reference policy)")
+        given = self._given_mask("policy_loss", given, tshape)
         self._refuse_off_gpu("policy_loss", batch, images, tokens, vn, (("advantages", advantages), ("behaviour_logprobs", b),
-                                                                       ("reference_logprobs", ref)))
+                                                                       ("reference_logprobs", ref), ("given", given)))
         args = dict(advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo, clip_hi=hi,
                     entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
         if ref is not None:
             args.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
+        if given is not None:
+            args.update(given=given.reshape(-1))
         with torch.cuda.device(images.device):
             loss, (info, res) = self._run_head(batch, mage_train.PolicyHead(tokens.contiguous(), **args))
             self.last_policy_token_logprobs = res["logprob"].view(tshape)
@@ -1329,24 +1362,24 @@ class MAGE(nn.Module):
                 setattr(self, a, v)
 
     @torch.no_grad()
-    def token_policy_logprobs(self, batch, tokens) -> torch.Tensor:
+    def token_policy_logprobs(self, batch, tokens, given=None) -> torch.Tensor:
         """fp32 [B, L-1, h, w]: the log-probabilities of given tokens (int64 [B, L-1, h, w]) under the policy set_sampling currently
         describes, by the teacher-forced pass policy_loss runs -- bit for bit last_policy_token_logprobs of a no-grad policy_loss on the
         same inputs (-inf where the filter could not draw the token).  How a frozen copy of the model gives policy_loss its
-        reference_logprobs.  Values only; every last_* result is left as found."""
+        reference_logprobs.  given: policy_loss' (0 at the given slots).  Values only; every last_* result is left as found."""
         self._refuse_guided("token_policy_logprobs")
         self._refuse_known("token_policy_logprobs", batch)
         images = batch["images"] if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("token_policy_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
         with self._last_results_kept():
-            self.policy_loss(batch, tokens, torch.zeros(images.shape[0], device=images.device, dtype=F32))
+            self.policy_loss(batch, tokens, torch.zeros(images.shape[0], device=images.device, dtype=F32), given=given)
             return self.last_policy_token_logprobs
 
     _PREFERENCE_LOSSES = {"sigmoid": 0, "ipo": 1}
 
     def preference_loss(self, batch, tokens, pairs, reference_logprobs, *, beta: float = 0.1, label_smoothing: float = 0.0,
-                        loss: str = "sigmoid"):
+                        loss: str = "sigmoid", given=None):
         """Preference loss (DPO; loss='ipo': IPO) over ranked pairs of clips: (loss, info) of policy_loss' teacher-forced pass over frame 0
         of batch['images'] (plus batch['text'], the optional batch['speed'], and batch['video_noise'] on a randomness=True model) followed
         by `tokens` (int64 [B, L-1, h, w]), ending in mage_token_logprob, mage_clip_scores and mage_preference_loss (include/mage_hip_ext.h
@@ -1363,10 +1396,13 @@ class MAGE(nn.Module):
         info = {'loss', 'accuracy' (the share of pairs with u > 0), 'chosen_reward' (mean beta (s_w - r_w)), 'rejected_reward', 'margin'
         (mean beta u)} as floats; last_preference_clip_logprobs (fp32 [B]), last_preference_clip_coef (fp32 [B]: d loss / d s),
         last_preference_pair_loss, last_preference_pair_margin (fp32 [P]) and last_preference_token_logprobs (fp32 [B, L-1, h, w]) keep the
-        rest.  Dropout follows self.training, as in forward: compare with a reference in eval()."""
-        return self._preference("preference_loss", batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss)
+        rest.  Dropout follows self.training, as in forward: compare with a reference in eval().
+        given bool [B, L-1, h, w] (policy_loss'): the given slots count 0 in every clip's log-likelihood (one mage_apply_known_tokens launch
+        before the totals: what generation and score(given=) report) and get no gradient (mage_token_logprob_bwd_masked); the reference's
+        log-likelihoods should leave them out alike (clip_logprobs(given=)).  info gains 'given_fraction'."""
+        return self._preference("preference_loss", batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss, given)
 
-    def _preference(self, who, batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss):
+    def _preference(self, who, batch, tokens, pairs, reference_logprobs, beta, label_smoothing, loss, given=None):
         """preference_loss under the name `who` (clip_logprobs runs it too); every refusal comes before the first launch."""
         from . import mage_train
         images, B, tshape, vn = self._given_tokens_inputs(who, batch, tokens)
@@ -1387,11 +1423,15 @@ class MAGE(nn.Module):
             raise ValueError(f"{who}: label_smoothing must lie in [0, 0.5), got {label_smoothing!r}")
         if loss == "ipo" and label_smoothing != 0:
             raise ValueError(f"{who}: label_smoothing is the sigmoid loss's; loss='ipo' takes 0, got {label_smoothing!r}")
-        self._refuse_off_gpu(who, batch, images, tokens, vn, (("pairs", pairs), ("reference_logprobs", ref)))
+        given = self._given_mask(who, given, tshape)
+        self._refuse_off_gpu(who, batch, images, tokens, vn, (("pairs", pairs), ("reference_logprobs", ref), ("given", given)))
         head = mage_train.PreferenceHead(tokens.contiguous(), pairs=pairs.contiguous(), reference=ref.contiguous(), beta=float(beta),
-                                         label_smoothing=float(label_smoothing), mode=self._PREFERENCE_LOSSES[loss])
+                                         label_smoothing=float(label_smoothing), mode=self._PREFERENCE_LOSSES[loss],
+                                         **({} if given is None else {"given": given.reshape(-1)}))
         with torch.cuda.device(images.device):
             val, (info, res) = self._run_head(batch, head)
+            if given is not None:
+                info = dict(info, given_fraction=int(given.sum().item()) / given.numel())
             self.last_preference_clip_logprobs = res["clip_logprob"]
             self.last_preference_clip_coef = res["clip_coef"]
             self.last_preference_pair_loss = res["pair_loss"]
@@ -1401,17 +1441,18 @@ class MAGE(nn.Module):
         return val, info
 
     @torch.no_grad()
-    def clip_logprobs(self, batch, tokens) -> torch.Tensor:
+    def clip_logprobs(self, batch, tokens, given=None) -> torch.Tensor:
         """fp32 [B]: the teacher-forced log-likelihood of given tokens (int64 [B, L-1, h, w]) after frame 0 of batch['images'], under the
         model's own distribution -- the full softmax at temperature 1 with no filter, the one score reports, whatever set_sampling says --
         by the pass preference_loss runs: bit for bit its last_preference_clip_logprobs on the same inputs.  How a frozen copy of the model
-        gives preference_loss its reference_logprobs.  Values only; every last_* result is left as found."""
+        gives preference_loss its reference_logprobs.  given: preference_loss' (the totals are over the free slots).  Values only; every
+        last_* result is left as found."""
         images = batch.get("images") if isinstance(batch, dict) else None
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1):
             raise ValueError("clip_logprobs: batch['images'] must be [B, >= 1, C, H, W]")
         with self._last_results_kept():
             self._preference("clip_logprobs", batch, tokens, torch.zeros(1, 2, device=images.device, dtype=torch.int64),   # (0, 0): no preference
-                             torch.zeros(images.shape[0], device=images.device, dtype=F32), 1.0, 0.0, "sigmoid")
+                             torch.zeros(images.shape[0], device=images.device, dtype=F32), 1.0, 0.0, "sigmoid", given)
             return self.last_preference_clip_logprobs
 
     @torch.no_grad()
@@ -1446,7 +1487,7 @@ class MAGE(nn.Module):
 
     @torch.no_grad()
     def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None,
-                noise: str = "clip", pairs: Optional[str] = None) -> dict:
+                noise: str = "clip", pairs: Optional[str] = None, context: int = 1, known_tokens=None) -> dict:
         """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
         under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
         rewarded on the device, and the rewards turned into group-relative advantages:
@@ -1479,6 +1520,17 @@ class MAGE(nn.Module):
             out = m.rollout(batch, 8, reference=ref, pairs='best_worst')
             loss, info = m.preference_loss(out['batch'], out['tokens'], out['pairs'], out['reference_clip_logprobs'])
         runs as written.  Without pairs the call is the one it was, launch for launch.
+        context=k (set_context's range; 1: off) and known_tokens (int64 [B, L-1, h, w], negative: free; batch['known_tokens']' layout):
+        every candidate continues frames 0 .. k-1 of batch['images'] and holds the given tokens, by generation's own mechanism (the model's
+        set_context setting is put back afterwards, as the sampler settings are).  The result gains 'given' (bool [B*N, L-1, h, w]: the slots
+        that were given, policy_loss' given=; None without either argument); 'tokens' hold the given tokens there and
+        'behaviour_logprobs' / 'token_logprobs' 0; out['batch'] carries neither key, so that
+            out = m.rollout(batch, 8, context=4, reference=ref)
+            loss, info = m.policy_loss(out['batch'], out['tokens'], out['advantages'], out['behaviour_logprobs'],
+                                       reference_logprobs=out['reference_logprobs'], kl_coef=0.1, given=out['given'])
+        runs as written; the reference's scores leave the given slots out alike.  Under context=k the video holds the k given frames
+        verbatim and the built-in rewards average over the generated frames k .. L-1 alone ('frame_metrics' is [B*N, L-k]: the given frames
+        would add a constant); with known_tokens alone all L-1 frames count.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
         self._refuse_guided("rollout")
@@ -1510,6 +1562,17 @@ class MAGE(nn.Module):
         images = batch["images"]
         if not (torch.is_tensor(images) and images.dim() == 5 and images.shape[0] >= 1 and images.shape[1] >= 1):
             raise ValueError("rollout: batch['images'] must be [B, >= 1, C, H, W]")
+        if isinstance(context, bool) or not isinstance(context, int) or not 1 <= context <= L - 1:
+            raise ValueError(f"rollout: context must be an integer in [1, {L - 1}] (frames_length - 1), got {context!r}")
+        if images.shape[1] < context:
+            raise ValueError(f"rollout: context={context} continues that many frames; batch['images'] holds {images.shape[1]}")
+        if known_tokens is not None:
+            kshape = (images.shape[0], L - 1, self.image_resolution, self.image_resolution)
+            if not (torch.is_tensor(known_tokens) and known_tokens.dtype == torch.int64 and tuple(known_tokens.shape) == kshape):
+                raise ValueError(f"rollout: known_tokens must be int64 {list(kshape)} (negative: free)")
+            if not (known_tokens.is_cuda and known_tokens.device == images.device):
+                raise ValueError("rollout: known_tokens must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        masked = context > 1 or known_tokens is not None
         builtin = not callable(reward)
         if builtin and not (images.shape[1] >= L and images.dtype == F32 and min(images.shape[-2:]) >= 11):
             raise ValueError(f"rollout: reward '{reward}' compares with the ground truth: batch['images'] must be fp32 [B, {L}, C, H, W] with "
@@ -1527,10 +1590,14 @@ class MAGE(nn.Module):
                 raise ValueError("rollout: the reference model must be on the same GPU as the batch")
         Bc = images.shape[0]
         settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
+        ctx_setting = getattr(self, "context_frames", 1)
         with self._last_results_kept():
             try:
                 self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
                 b = self._sample_seeds(self._noise_seeds(batch))
+                if masked:                                # generation's own path: the setting and the batch key, for this call
+                    self.context_frames = context
+                    b = self._known_inputs(b if known_tokens is None else {**b, "known_tokens": known_tokens})
                 with torch.cuda.device(images.device), weights_frozen():
                     self.last_video_noise = None
                     out = self._generate_one(b, keep_all=True, candidate_noise=noise == "candidate")
@@ -1543,9 +1610,10 @@ class MAGE(nn.Module):
                         vn = self.last_video_noise
                         out["video_noise"] = out["batch"]["video_noise"] = vn if vn.shape[0] == Bc * N else vn.repeat_interleave(N, 0)
                     video = out["video"]
-                    if builtin:
-                        gen = video[:, 1:] if video.dtype == F32 else video[:, 1:].float()
-                        fm = out["frame_metrics"] = ops.video_metrics(gen, images[:, 1:L], tgt_div=N, data_range=2.0)
+                    out["given"] = self.last_known_mask.repeat_interleave(N, 0) if masked else None
+                    if builtin:                              # the generated frames: context .. L-1 (the given ones came back verbatim)
+                        gen = video[:, context:] if video.dtype == F32 else video[:, context:].float()
+                        fm = out["frame_metrics"] = ops.video_metrics(gen, images[:, context:L], tgt_div=N, data_range=2.0)
                         fr = fm[reward] if reward != "neg_mse" else -fm["mse"]
                     else:
                         out["frame_metrics"] = None
@@ -1555,11 +1623,12 @@ class MAGE(nn.Module):
                         fr = fr.contiguous()
                     out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
                     out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
+                    giv = {"given": out["given"]} if masked else {}
                     if reference is not None:
                         theirs = (getattr(reference, "sampling", None), reference.candidates)
                         try:
                             reference.sampling, reference.candidates = self.sampling, 1
-                            out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"])
+                            out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"], **giv)
                         finally:
                             reference.sampling, reference.candidates = theirs
                     if pairs is not None:
@@ -1569,10 +1638,11 @@ class MAGE(nn.Module):
                         base = torch.arange(Bc, device=images.device, dtype=torch.int64) * N
                         out["pairs"] = torch.stack([base + hi, base + lo], 1).contiguous()
                         if reference is not None:
-                            out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"])
+                            out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"], **giv)
                     ops.check_device_errors(images.device)
             finally:
                 self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings
+                self.context_frames = ctx_setting
         return out
 
     def _sample_seeds(self, batch) -> dict:
@@ -2152,7 +2222,6 @@ class MAGE(nn.Module):
         # with the given frames 1 .. k-1 merged into slots 0 .. k-2 on the device
         kn = batch.get("known_tokens")
         if kn is not None or k > 1:
-            assert not keep_all                                                               # (rollout is refused with either)
             kn = torch.full((B, Lm1, hw), -1, device=images.device, dtype=torch.int64) if kn is None else kn.reshape(B, Lm1, hw).clone()
             kn[:, :k - 1] = ctx[:, 1:]
         seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
@@ -2182,6 +2251,7 @@ class MAGE(nn.Module):
             speed = batch["speed"].repeat_interleave(N, 0) if "speed" in batch else None
             ma = self._anchor_tail(ma, {}, None, B, noise_seed=seeds, speed=speed)
             tok0 = tok0[:, None, :].expand(Bc, N, hw).reshape(B, hw)
+            ctx = ctx[:, None].expand(Bc, N, k, hw).reshape(B, k, hw)
         else:
             ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
         if N > 1 and not candidate_noise:
@@ -2305,8 +2375,12 @@ class MAGE(nn.Module):
         log-probabilities as a dict, and no result attribute is written."""
         if keep_all:
             first = images[:, 0:1] if N == 1 else images[:, 0:1].repeat_interleave(N, 0)       # every candidate starts from its clip's frame 0
-            return {"video": _assemble(first, self.first_stage_decode(gen)), "tokens": gen, "token_logprobs": lp, "first": first,
-                    "behaviour_logprobs": st["policy_logprob"]}
+            if k > 1:                                     # rollout(context=k): the k given frames verbatim, only the generated ones decoded
+                dec = self.first_stage_decode(gen[:, k - 1:])
+                video = torch.cat([images[:, :k].repeat_interleave(N, 0).to(dec.dtype), dec], 1)
+            else:
+                video = _assemble(first, self.first_stage_decode(gen))
+            return {"video": video, "tokens": gen, "token_logprobs": lp, "first": first, "behaviour_logprobs": st["policy_logprob"]}
         if lp is not None:
             scores, best = ops.clip_scores(lp, n_clips=Bc, n_cand=N)
             pscores = None

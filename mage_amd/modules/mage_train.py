@@ -580,6 +580,8 @@ def _policy_scalars(policy: dict) -> dict:
     kw = {k: policy[k] for k in ("temperature", "clip_lo", "clip_hi", "entropy_coef")}
     if policy.get("reference") is not None:              # the anchored entry points; without a reference the plain ones, called as before
         kw.update(reference_logprob=policy["reference"], kl_coef=policy["kl_coef"])
+    if policy.get("given") is not None:                  # the masked entry points, in either form
+        kw.update(given=policy["given"])
     return kw
 
 
@@ -622,7 +624,8 @@ class PolicyHead:
     """MAGE.policy_loss: mage_policy_loss over the given tokens, or mage_policy_loss_anchored when args holds a 'reference' (_policy_scalars'
     rule).  args: advantage (fp32, one per clip or per token), behaviour (fp32 per token, or None) and the scalars temperature, top_k, top_p,
     clip_lo, clip_hi, entropy_coef [, reference (fp32 per token), kl_coef] of include/mage_hip_ext.h.  saved: the kernel's results
-    (cut, logprob, summary [, kl])."""
+    (cut, logprob, summary [, kl]).  With a 'given' (bool per token: the token was given, not drawn) it is mage_policy_loss_masked: the means
+    are over the free tokens, parts gains 'given_fraction' and saved 'norm'."""
     PARTS = ("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction")
 
     def __init__(self, tokens, **args):
@@ -631,18 +634,26 @@ class PolicyHead:
     def forward(self, model, logits, target, B):
         a = self.args
         res = ops.policy_loss(logits, target, a["advantage"], a["behaviour"], **_policy_scalars(a), top_k=a["top_k"], top_p=a["top_p"])
-        return res["summary"][0], dict(zip(self.PARTS, res["summary"].tolist())), res
+        summary = res["summary"].tolist()
+        parts = dict(zip(self.PARTS, summary))
+        if a.get("given") is not None:                   # summary [8]: the unmasked call's keys (5, or 7 with a reference) and the share
+            parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary), given_fraction=summary[7])
+        return res["summary"][0], parts, res
 
     def backward(self, logits, target, saved, gout, dt):
         a = self.args
-        return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **_policy_scalars(a))
+        kw = _policy_scalars(a)
+        if a.get("given") is not None:
+            kw.update(norm=saved["norm"])
+        return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **kw)
 
 
 class PreferenceHead:
     """MAGE.preference_loss: mage_token_logprob (temperature 1, no filter: the model's own distribution), mage_clip_scores (one log-likelihood
     per clip) and mage_preference_loss over args' pairs (int64 [P, 2]) and reference (fp32 [B]) with the scalars beta, label_smoothing and mode
     (include/mage_hip_ext.h); backward is mage_token_logprob_bwd with the pair stage's one coefficient per clip.  saved: the pair stage's
-    results plus logprob and clip_logprob."""
+    results plus logprob and clip_logprob.  With a 'given' (bool per token) one mage_apply_known_tokens launch writes the given slots'
+    log-probability 0 before the clip totals -- what generation reports there -- and backward is mage_token_logprob_bwd_masked."""
     PARTS = ("loss", "accuracy", "chosen_reward", "rejected_reward", "margin")
 
     def __init__(self, tokens, **args):
@@ -652,12 +663,15 @@ class PreferenceHead:
         a = self.args
         lp = ops.token_logprob(logits, target, torch.empty(target.shape, device=logits.device, dtype=F32), rows=target.numel(), K=logits.shape[1],
                                ld=logits.stride(0))
+        if a.get("given") is not None:
+            ops.apply_known_tokens(target, torch.where(a["given"].view(target.shape), target, -1), rows=target.numel(), K=logits.shape[1],
+                                   logprob=lp)
         clip_lp = ops.clip_scores(lp, n_clips=B)[0].view(B)
         res = ops.preference_loss(clip_lp, a["reference"], a["pairs"], beta=a["beta"], label_smoothing=a["label_smoothing"], mode=a["mode"])
         return res["summary"][0], dict(zip(self.PARTS, res["summary"].tolist())), dict(res, logprob=lp, clip_logprob=clip_lp)
 
     def backward(self, logits, target, saved, gout, dt):
-        return ops.token_logprob_bwd(logits, target, saved["clip_coef"], gout, _dlogits(logits, dt))
+        return ops.token_logprob_bwd(logits, target, saved["clip_coef"], gout, _dlogits(logits, dt), given=self.args.get("given"))
 
 
 def train_forward(model, batch, head=None):

@@ -714,22 +714,43 @@ def _policy_ref(reference_logprob, kl_coef, logits):
     assert reference_logprob.device == logits.device
 
 
+def _given_rows(given, logits):
+    """The per-row mask of the masked entry points: None, or bool / uint8 [rows] (any shape, contiguous) beside the logits."""
+    if given is not None:
+        assert given.dtype in (torch.bool, torch.uint8) and given.is_contiguous() and given.numel() == logits.shape[0]
+        assert given.device == logits.device
+
+
 def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor] = None, *,
                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, clip_lo: float = 0.2, clip_hi: float = 0.2,
                 entropy_coef: float = 0.0, adv_div: Optional[int] = None, reference_logprob: Optional[torch.Tensor] = None,
-                kl_coef: float = 0.0) -> dict:
+                kl_coef: float = 0.0, given: Optional[torch.Tensor] = None) -> dict:
     """mage_policy_loss over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows]; advantage fp32, row i using entry i // adv_div
     (default: rows / numel consecutive rows per entry); behaviour_logprob fp32 [rows] selects the clipped surrogate, None the reward-weighted likelihood.  Returns the per-row
     fp32 tensors 'row_loss', 'logprob', 'entropy', the uint32 thresholds 'cut' (kept as int32 storage: policy_loss_bwd's input) and
     'summary' fp32 [5]: the means of the loss, the entropy, b - logprob, the clipped share and the outside share.
     reference_logprob fp32 [rows] (with kl_coef >= 0): mage_policy_loss_anchored -- the loss gains kl_coef times the k3 estimate of the KL
-    against the reference policy, the result the per-row 'kl', and 'summary' is fp32 [7]: the five, the mean KL and the unanchored share."""
+    against the reference policy, the result the per-row 'kl', and 'summary' is fp32 [7]: the five, the mean KL and the unanchored share.
+    given bool [rows] (True: the row's token was given, not drawn): mage_policy_loss_masked in either form -- a given row is not read and
+    gets zeros, 'summary' is fp32 [8]: the seven means over the free rows (the last two 0 without a reference) and the given share, and the
+    result gains 'norm' fp32 [1] = 1 / the number of free rows, policy_loss_bwd's input."""
     _policy_ref(reference_logprob, kl_coef, logits)
+    _given_rows(given, logits)
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     mk = lambda n, dt: torch.empty(n, device=logits.device, dtype=dt)      # noqa: E731
     out = dict(row_loss=mk(rows, torch.float32), logprob=mk(rows, torch.float32), entropy=mk(rows, torch.float32), cut=mk(rows, torch.int32),
-               summary=mk(5 if reference_logprob is None else 7, torch.float32))
+               summary=mk(8 if given is not None else 5 if reference_logprob is None else 7, torch.float32))
+    if given is not None:
+        out["norm"] = mk(1, torch.float32)
+        if reference_logprob is not None:
+            out["kl"] = mk(rows, torch.float32)
+        _lib.check(l.mage_policy_loss_masked(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                             _p(behaviour_logprob), _p(reference_logprob), float(temperature), int(top_k), float(top_p),
+                                             float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
+                                             out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), _p(out.get("kl")),
+                                             out["summary"].data_ptr(), out["norm"].data_ptr(), given.data_ptr(), s), l)
+        return out
     if reference_logprob is None:
         _lib.check(l.mage_policy_loss(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
                                       float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef),
@@ -748,16 +769,26 @@ def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Ten
 def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor],
                     cut: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *, temperature: float = 1.0, clip_lo: float = 0.2,
                     clip_hi: float = 0.2, entropy_coef: float = 0.0, adv_div: Optional[int] = None,
-                    reference_logprob: Optional[torch.Tensor] = None, kl_coef: float = 0.0) -> torch.Tensor:
+                    reference_logprob: Optional[torch.Tensor] = None, kl_coef: float = 0.0, given: Optional[torch.Tensor] = None,
+                    norm: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mage_policy_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16 from policy_loss' inputs and its 'cut'; grad_out fp32 [1].  With
-    reference_logprob: mage_policy_loss_anchored_bwd."""
+    reference_logprob: mage_policy_loss_anchored_bwd.  With given (and the masked policy_loss' 'norm'): mage_policy_loss_masked_bwd."""
     _policy_ref(reference_logprob, kl_coef, logits)
+    _given_rows(given, logits)
+    assert (given is None) == (norm is None), "given and norm come together (the masked forward call writes norm)"
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.numel() == rows and cut.device == logits.device
     assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
     assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
     assert dlogits.device == logits.device
+    if given is not None:
+        assert norm.dtype == torch.float32 and norm.numel() == 1 and norm.device == logits.device
+        _lib.check(l.mage_policy_loss_masked_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                                 _p(behaviour_logprob), _p(reference_logprob), cut.data_ptr(), float(temperature), float(clip_lo),
+                                                 float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(), norm.data_ptr(),
+                                                 dlogits.data_ptr(), code(dlogits), given.data_ptr(), s), l)
+        return dlogits
     if reference_logprob is None:
         _lib.check(l.mage_policy_loss_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
                                           cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef),
@@ -792,10 +823,12 @@ def preference_loss(clip_logprob: torch.Tensor, reference_logprob: torch.Tensor,
 
 
 def token_logprob_bwd(logits: torch.Tensor, tokens: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *,
-                      weight_div: Optional[int] = None) -> torch.Tensor:
+                      weight_div: Optional[int] = None, given: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mage_token_logprob_bwd: dlogits [rows, K] contiguous fp32 or bf16, the gradient of sum_i weight[i // weight_div] * token_logprob_i
     times grad_out (fp32 [1]) over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows].  weight_div None: weight's entries share
-    the rows out equally (one per row, or one per clip).  Rows of weight 0 are written as zeros without being read."""
+    the rows out equally (one per row, or one per clip).  Rows of weight 0 are written as zeros without being read.  given bool [rows]:
+    mage_token_logprob_bwd_masked -- a given row is a row of weight 0."""
+    _given_rows(given, logits)
     l, s = _dev(logits)
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     rows, K = logits.shape
@@ -808,6 +841,10 @@ def token_logprob_bwd(logits: torch.Tensor, tokens: torch.Tensor, weight: torch.
     assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
     assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
     assert dlogits.device == logits.device
+    if given is not None:
+        _lib.check(l.mage_token_logprob_bwd_masked(logits.data_ptr(), rows, K, logits.stride(0), tokens.data_ptr(), weight.data_ptr(), weight_div,
+                                                   grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), given.data_ptr(), s), l)
+        return dlogits
     _lib.check(l.mage_token_logprob_bwd(logits.data_ptr(), rows, K, logits.stride(0), tokens.data_ptr(), weight.data_ptr(), weight_div,
                                         grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
     return dlogits
