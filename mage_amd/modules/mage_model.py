@@ -846,6 +846,65 @@ def disabled_train(self, mode=True):
     return self
 
 
+class _Generation:
+    """What is fixed for one MAGE._generate_one call, and the per-frame step both AR loops share.  B = Bc * N: the clips (x candidates)
+    whose tokens are picked; Bd: the decoder's batch -- under guidance 2 B, rows B .. 2 B the uncond half, fed the tokens of the cond half.
+    Every pick / logprob / stats / known-token launch addresses the first B clips only, in the ops functions' own terms: a group is one
+    clip's frame (hw rows), in_group_stride / in_off find its logits rows, tok_group_stride / tok_off its token slot, and `sel` takes the
+    launch's view of a result buffer, indexed like the tokens."""
+
+    def __init__(self, model: "MAGE", images, Bc: int, N: int, k: int, tok0, ctx, ma, seeds, gs, kn, lp, st):
+        self.model, self.images, self.Bc, self.N, self.k = model, images, Bc, N, k            # k: the given frames (set_context)
+        self.tok0, self.ctx, self.ma = tok0, ctx, ma     # int64 [Bd, hw] frame 0, [Bd, k, hw] the given frames; the anchor's rows [Bd * hw, C]
+        self.seeds, self.gs, self.kn = seeds, gs, kn     # int64 [B] (None: greedy); fp32 [Bc] (None: no guidance); int64 [Bc, (L-1) * hw] (None)
+        self.B = Bc * N
+        self.Bd = self.B * (1 if gs is None else 2)
+        self.hw, self.Lm1, self.K = model.image_resolution ** 2, model.frames_length - 1, model.codebook_size
+        self.lp, self.st = lp, st                        # the result buffers (None: off): fp32 token log-probabilities, _stats_alloc's dict
+
+    def guide(self, logits, frames: int = 1, **at) -> None:
+        """Guidance on: `frames` frames of the first B clips, in place on the cond half's rows of the decoder's [cond | uncond] logits; one
+        scale per clip covers its N candidates.  at: group / in_group_stride / in_off."""
+        if self.gs is not None:
+            ops.guide_logits(logits, logits[logits.shape[0] // 2:], self.gs, rows=self.B * frames * self.hw, K=self.K,
+                             scale_div=self.N * frames * self.hw, **at)
+
+    def pick(self, logits, tokens, sel, *, rows: int, pos_off: int = 0, scored: bool = True, tok_group_stride=None, tok_off: int = 0, **inp) -> None:
+        """Tokens of `rows` logits rows (inp: group / in_group_stride / in_off) into their slots -- the sampler under the candidates' seeds,
+        or argmax -- then (scored) the log-probabilities and statistics of the tokens just picked, under the logits they came from."""
+        out = dict(rows=rows, K=self.K, out_group_stride=tok_group_stride, out_off=tok_off, **inp)
+        if self.seeds is None:
+            ops.argmax(logits, tokens, **out)
+        else:
+            t, k, p = self.model.sampling
+            ops.sample_tokens(logits, tokens, self.seeds, temperature=t, top_k=k, top_p=p, pos_off=pos_off, **out)
+        at = dict(rows=rows, K=self.K, tok_group_stride=tok_group_stride, tok_off=tok_off, **inp)
+        if scored and self.lp is not None:
+            ops.token_logprob(logits, tokens, sel(self.lp), **at)
+        if scored and self.st is not None:
+            self.model._stats(logits, tokens, self.st, sel, **at)
+
+    def hold(self, tokens, sel, rows: int, **at) -> None:
+        """Tokens given: one launch stores them over the picked ones, and the certain policy's 0 / 0 / 1 over their results (sel None: the
+        tokens alone); a clip's N candidates share its row of kn.  at: group / tok_group_stride / tok_off / known_off."""
+        if self.kn is not None:
+            res = {} if sel is None else {n: sel(b) for n, b in (("logprob", self.lp), *(self.st or {}).items()) if b is not None}
+            ops.apply_known_tokens(tokens, self.kn, rows=rows, K=self.K, known_group_stride=self.Lm1 * self.hw, known_clip_div=self.N, **res, **at)
+
+    def frame(self, i: int, logits, tokens, sel, *, in_group_stride: int, in_off: int = 0, tok_group_stride: int, tok_off: int = 0,
+              slot=None, scored: bool = True) -> None:
+        """Frame i of every clip: guide its logits, pick its tokens (position i * hw + pixel of the clip's sampler stream), score them
+        (scored False: the results are filled later), store the given tokens over them, and copy the slot ([Bd, hw]; None: nothing reads
+        it) to the uncond half, which conditions on the same tokens (one small int64 copy per frame)."""
+        hw, rows = self.hw, self.B * self.hw
+        self.guide(logits, group=hw, in_group_stride=in_group_stride, in_off=in_off)
+        self.pick(logits, tokens, sel, rows=rows, pos_off=i * hw, scored=scored, group=hw, in_group_stride=in_group_stride, in_off=in_off,
+                  tok_group_stride=tok_group_stride, tok_off=tok_off)
+        self.hold(tokens, sel if scored else None, rows, group=hw, tok_group_stride=tok_group_stride, tok_off=tok_off, known_off=i * hw)
+        if self.gs is not None and slot is not None:
+            slot[self.B:].copy_(slot[:self.B])
+
+
 class MAGE(nn.Module):
     def __init__(self, first_stage_config, text_encoder_config, ma_config, generate_decoder_config, codebook_size: int,
                  frames_length: int, image_resolution: int, vision_width: int, dropout: float = 0.1, use_cids=False,
@@ -900,6 +959,7 @@ class MAGE(nn.Module):
         self._graphs: dict = {}
         self._derived = _Derived(self)
         self.last_tokens: Optional[torch.Tensor] = None
+        self.last_logits: Optional[torch.Tensor] = None           # full AR mode: fp32 [B, L-1, h, w, K], the last iteration's logits
         self.sampling: Optional[Tuple[float, int, float]] = None   # (temperature, top_k, top_p) of set_sampling; None: greedy (the reference)
         self.last_sample_seeds: Optional[torch.Tensor] = None     # the per-clip seeds of the last sampled call
         self.logprobs = False          # set_logprobs: autoregressive_generate also leaves the log-probabilities of the tokens it generated
@@ -1016,7 +1076,7 @@ class MAGE(nn.Module):
         return self
 
     def _guided(self) -> bool:
-        return self.use_cids and getattr(self, "guidance", None) is not None
+        return self.use_cids and self.guidance is not None
 
     def _refuse_guided(self, who: str) -> None:
         if self._guided():
@@ -1076,7 +1136,7 @@ class MAGE(nn.Module):
         return self
 
     def _ctx(self) -> int:
-        return int(getattr(self, "context_frames", 1)) if self.use_cids else 1
+        return int(self.context_frames) if self.use_cids else 1
 
     def _refuse_known(self, who: str, batch=None) -> None:
         if self._ctx() > 1 or (isinstance(batch, dict) and ("known_tokens" in batch or "context_tokens" in batch)):
@@ -1150,17 +1210,17 @@ class MAGE(nn.Module):
         return self
 
     def _n_cand(self) -> int:
-        return int(getattr(self, "candidates", 1)) if getattr(self, "sampling", None) is not None and self.use_cids else 1
+        return int(self.candidates) if self.sampling is not None and self.use_cids else 1
 
     def _want_logprobs(self) -> bool:
-        return self.use_cids and (bool(getattr(self, "logprobs", False)) or self._n_cand() > 1)
+        return self.use_cids and (bool(self.logprobs) or self._n_cand() > 1)
 
     def _want_stats(self) -> Tuple[bool, bool]:
         """(policy, entropy) of set_logprobs; policy without a sampler to describe is refused here, where a generation or score starts."""
-        if not (self.use_cids and getattr(self, "logprobs", False)):
+        if not (self.use_cids and self.logprobs):
             return False, False
-        pol, ent = bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False))
-        if pol and getattr(self, "sampling", None) is None:
+        pol, ent = bool(self.logprob_policy), bool(self.logprob_entropy)
+        if pol and self.sampling is None:
             raise ValueError("set_logprobs(policy=True) reports the sampler's distribution: switch sampling on with set_sampling first")
         return pol, ent
 
@@ -1169,14 +1229,14 @@ class MAGE(nn.Module):
         pol, ent = self._want_stats()
         if not (pol or ent):
             return None
-        sampled = getattr(self, "sampling", None) is not None
+        sampled = self.sampling is not None
         mk = lambda want, dt: torch.empty(shape, device=device, dtype=dt) if want else None      # noqa: E731
         return {"policy_logprob": mk(pol, F32), "kept": mk(pol, torch.int32), "entropy": mk(ent, F32), "policy_entropy": mk(ent and sampled, F32)}
 
     def _stats(self, logits, tokens, bufs: dict, sel, **kw) -> None:
         """One mage_token_stats launch beside a mage_token_logprob one (same addressing kw), under the current sampler (greedy: the plain
         softmax); sel picks the launch's view of each buffer."""
-        t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
+        t, k, p = self.sampling or (1.0, 0, 1.0)
         ops.token_stats(logits, tokens, temperature=t, top_k=k, top_p=p, **{n: None if b is None else sel(b) for n, b in bufs.items()}, **kw)
 
     _STATS_RESULTS = (("policy_logprob", "last_token_policy_logprobs"), ("kept", "last_token_kept"), ("entropy", "last_token_entropy"),
@@ -1259,7 +1319,7 @@ class MAGE(nn.Module):
         Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
         from . import mage_train
         images, B, tshape, vn = self._given_tokens_inputs("policy_loss", batch, tokens)
-        t, k, p = getattr(self, "sampling", None) or (1.0, 0, 1.0)
+        t, k, p = self.sampling or (1.0, 0, 1.0)
         if k == 1:
             raise ValueError("policy_loss: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient")
         if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape)):
@@ -1548,7 +1608,7 @@ class MAGE(nn.Module):
             raise ValueError(f"rollout: pairs must be 'best_worst' or None, got {pairs!r}")
         if not self.use_cids:
             raise ValueError("rollout: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
-        if getattr(self, "sampling", None) is None:
+        if self.sampling is None:
             raise ValueError("rollout: candidates are drawn by the sampler: switch sampling on with set_sampling first")
         if isinstance(candidates, bool) or not isinstance(candidates, int) or candidates < 2:
             raise ValueError(f"rollout: candidates must be an integer >= 2 (a group of one has no relative advantage), got {candidates!r}")
@@ -1589,8 +1649,7 @@ class MAGE(nn.Module):
             if next(reference.parameters()).device != images.device:
                 raise ValueError("rollout: the reference model must be on the same GPU as the batch")
         Bc = images.shape[0]
-        settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy)
-        ctx_setting = getattr(self, "context_frames", 1)
+        settings = (self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy, self.context_frames)
         with self._last_results_kept():
             try:
                 self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = N, True, True, False
@@ -1601,11 +1660,9 @@ class MAGE(nn.Module):
                 with torch.cuda.device(images.device), weights_frozen():
                     self.last_video_noise = None
                     out = self._generate_one(b, keep_all=True, candidate_noise=noise == "candidate")
-                    seeds = (b["sample_seed"][:, None] + torch.arange(N, device=images.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
                     rep = {k: (v.repeat_interleave(N, 0) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == Bc else v) for k, v in batch.items()
                            if k not in ("images", "sample_seed", "noise_seed")}
-                    out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": seeds}
-                    out["seeds"] = seeds
+                    out["batch"] = {**rep, "images": out.pop("first"), "sample_seed": out["seeds"]}      # (the candidates' seeds: sample_seed[b] + c)
                     if self.randomness:                      # the noise every row was drawn under: what policy_loss conditions on
                         vn = self.last_video_noise
                         out["video_noise"] = out["batch"]["video_noise"] = vn if vn.shape[0] == Bc * N else vn.repeat_interleave(N, 0)
@@ -1625,7 +1682,7 @@ class MAGE(nn.Module):
                     out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
                     giv = {"given": out["given"]} if masked else {}
                     if reference is not None:
-                        theirs = (getattr(reference, "sampling", None), reference.candidates)
+                        theirs = (reference.sampling, reference.candidates)
                         try:
                             reference.sampling, reference.candidates = self.sampling, 1
                             out["reference_logprobs"] = reference.token_policy_logprobs(out["batch"], out["tokens"], **giv)
@@ -1641,8 +1698,7 @@ class MAGE(nn.Module):
                             out["reference_clip_logprobs"] = reference.clip_logprobs(out["batch"], out["tokens"], **giv)
                     ops.check_device_errors(images.device)
             finally:
-                self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy = settings
-                self.context_frames = ctx_setting
+                self.candidates, self.logprobs, self.logprob_policy, self.logprob_entropy, self.context_frames = settings
         return out
 
     def _sample_seeds(self, batch) -> dict:
@@ -1672,14 +1728,6 @@ class MAGE(nn.Module):
         if seeds.dtype != torch.int64 or tuple(seeds.shape) != (B,):
             raise ValueError(f"batch['noise_seed'] must be int64 [{B}], got {seeds.dtype} {tuple(seeds.shape)}")
         return {**batch, "noise_seed": seeds.to(images.device).contiguous()}
-
-    def _pick(self, logits, out, seeds: Optional[torch.Tensor], *, rows: int, K: int, pos_off: int, **kw) -> None:
-        """Tokens of `rows` logits rows: the sampler with the clip seeds when sampling is on, argmax otherwise (argmax's row addressing)."""
-        if seeds is None:
-            ops.argmax(logits, out, rows=rows, K=K, **kw)
-        else:
-            t, k, p = self.sampling
-            ops.sample_tokens(logits, out, seeds, rows=rows, K=K, temperature=t, top_k=k, top_p=p, pos_off=pos_off, **kw)
 
     def _dt(self) -> torch.dtype:
         return PRECISIONS[self.precision][0]
@@ -1779,7 +1827,7 @@ class MAGE(nn.Module):
     def _frame_source(self, tokens: torch.Tensor, dt: torch.dtype):
         """What the decoder gets for its frame slots: FrameTokens (table sum, in_linear folded) or the convolved features."""
         ft = self._frame_tables()
-        if ft["ft.T2"] is not None and getattr(self, "frame_table", True):
+        if ft["ft.T2"] is not None and self.frame_table:
             T2 = ft["ft.T2"]
             if dt in HALF_TYPES and self._sk() == 0:
                 # bf16 / f16 mode: the table itself in that type (half the L2 / Infinity-Cache bytes per gathered row; entries rounded once,
@@ -1802,7 +1850,7 @@ class MAGE(nn.Module):
         n = tokens.numel() // (R * R)
         if dt == F32 and not split:
             ft = self._frame_tables()
-            if ft["ft.T"] is not None and getattr(self, "frame_table", True):                  # the once-per-clip prologue: fp32 features
+            if ft["ft.T"] is not None and self.frame_table:                                                  # the once-per-clip prologue: fp32 features
                 return ops.table_conv(tokens.reshape(-1).contiguous(), ft["ft.T"], torch.empty(n * R * R, Cc, device=tokens.device, dtype=F32),
                                       n_img=n, H=R, W=R, pos=d["hwpos"])
         sk = self._sk() if split else 0
@@ -1916,11 +1964,10 @@ class MAGE(nn.Module):
         images = batch["images"]
         _need_gpu(images, "MAGE.autoregressive_generate")
         self.last_sample_seeds = None
-        self._set_logprob_results([None] * len(self._LOGPROB_RESULTS))
+        self._set_generation_results([None] * len(self._GENERATION_RESULTS))
         self._want_stats()                               # (refuses policy without sampling before anything runs)
-        self.last_video_noise = None
         batch = self._noise_seeds(batch)
-        if getattr(self, "sampling", None) is not None and self.use_cids:
+        if self.sampling is not None and self.use_cids:
             batch = self._sample_seeds(batch)            # before the graph path keys on the batch and copies it into its static inputs
         self.last_guidance_scale = None
         batch = self._guidance_inputs(batch)             # (likewise: the scales and the negative caption are inputs of a captured graph)
@@ -1928,10 +1975,8 @@ class MAGE(nn.Module):
         # (weights_frozen: no parameter changes during one inference call -- the derived caches validate once, not at each of their ~40 fetches)
         with torch.cuda.device(images.device), weights_frozen():
             ug = self._graph_auto(batch) if self.use_graph is None else bool(self.use_graph)
-            # (clip groups on several streams are captured too when `graph_multistream` is set: fork / join edges inside ONE graph -- the probe of
-            # tools/inc_streams_graph_probe.py; off by default: measured slower than one stream at every size, DESIGN finding 94)
-            if (ug and (int(getattr(self, "streams", 1)) == 1 or getattr(self, "graph_multistream", False))
-                    and not torch.cuda.is_current_stream_capturing()):
+            # (clip groups on several streams are not captured: slower than one stream at every size, DESIGN finding 94)
+            if ug and int(self.streams) == 1 and not torch.cuda.is_current_stream_capturing():
                 out = self._generate_graphed(batch)
             else:
                 self.last_call_mode = "eager"
@@ -1968,7 +2013,7 @@ class MAGE(nn.Module):
         images = batch["images"]
         _need_gpu(images, "MAGE.generate_long")
         base = dict(batch)
-        if getattr(self, "sampling", None) is not None:
+        if self.sampling is not None:
             base = self._sample_seeds(base)              # drawn once when absent: every window derives its seeds from these
         seeds0, nseed0 = base.get("sample_seed"), base.get("noise_seed")
         k0 = self.context_frames
@@ -2027,19 +2072,19 @@ class MAGE(nn.Module):
     def _graph_fingerprint(self, batch=None):
         """Everything besides shapes, precision, AR mode and weights that selects kernels: a captured graph replays only under the same."""
         fs = self.first_stage_model
-        return (int(getattr(self, "streams", 1)), bool(getattr(self, "frame_table", True)), self.generate_model._stream_bf16(), bool(getattr(self.ma_encoder, "mage_plus", False)),
+        return (int(self.streams), bool(self.frame_table), self.generate_model._stream_bf16(), bool(getattr(self.ma_encoder, "mage_plus", False)),
                 getattr(self.ma_encoder, "split_kind", 0), getattr(self.text_encoder, "split_kind", 0),
                 tuple(str(getattr(fs, a, None)) for a in ("decode_dtype", "encode_split", "decode_split")),
-                config.get(), tuple(sorted(config.lib_options().items())), getattr(self, "sampling", None),
-                self._want_logprobs(), self._n_cand(), bool(getattr(self, "logprob_policy", False)), bool(getattr(self, "logprob_entropy", False)),
+                config.get(), tuple(sorted(config.lib_options().items())), self.sampling,
+                self._want_logprobs(), self._n_cand(), bool(self.logprob_policy), bool(self.logprob_entropy),
                 self._guided(),                          # (on / off selects the launches; the scales themselves are a batch tensor)
-                self._ctx(), bool(getattr(self, "context_prefill", True)),       # (likewise: the given tokens are batch tensors)
+                self._ctx(), bool(self.context_prefill),                                     # (likewise: the given tokens are batch tensors)
                 batch is not None and "known_tokens" in batch, batch is not None and "context_tokens" in batch)
 
     def _generate_eager(self, batch):
         if not self.use_cids:
             return self._generate_latent(batch)
-        n = int(getattr(self, "streams", 1))
+        n = int(self.streams)
         if n > 1 and batch["images"].shape[0] >= 2 * n and batch["images"].shape[0] % n == 0:
             return self._generate_multistream(batch, n)
         return self._generate_one(batch)
@@ -2089,8 +2134,7 @@ class MAGE(nn.Module):
             try:
                 with torch.cuda.graph(g):
                     out = self._generate_eager(static)
-                    toks, logits = self.last_tokens, self.last_logits
-                    lps, vn = self._logprob_results(), self.last_video_noise
+                    results = self._generation_results()
             except Exception:
                 if self.use_graph:                       # asked for explicitly: loud
                     raise
@@ -2101,7 +2145,7 @@ class MAGE(nn.Module):
                 if gc_was:
                     gc.enable()
                 recs = ops.PROFILE.capture_end(saved)
-            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "tok": toks, "logits": logits, "lps": lps, "vn": vn, "recs": recs}
+            ent = self._graphs[key] = {"g": g, "in": static, "out": out, "results": results, "recs": recs}
         else:
             for k, v in batch.items():
                 ent["in"][k].copy_(v)
@@ -2110,23 +2154,23 @@ class MAGE(nn.Module):
         if ent["recs"] and ops.PROFILE.enabled:
             torch.cuda.current_stream().synchronize()
             ops.PROFILE.absorb(ent["recs"])
-        self.last_tokens = None if ent["tok"] is None else ent["tok"].clone()
-        # cloned like the tokens and the output: graph replay is the DEFAULT for small calls (use_graph = None), and a caller that keeps
+        # every result is cloned like the output: graph replay is the DEFAULT for small calls (use_graph = None), and a caller that keeps
         # last_logits across two generations must not find the first one overwritten by the second (0.5 MB per clip at cfg2)
-        self.last_logits = None if ent["logits"] is None else ent["logits"].clone()
-        self._set_logprob_results([None if t_ is None else t_.clone() for t_ in ent["lps"]])
-        self.last_video_noise = None if ent["vn"] is None else ent["vn"].clone()
+        self._set_generation_results([None if t_ is None else t_.clone() for t_ in ent["results"]])
         return ent["out"].clone()
 
     _LOGPROB_RESULTS = ("last_token_logprobs", "last_clip_logprob", "last_candidate_scores", "last_candidate_index",
                         "last_token_policy_logprobs", "last_clip_policy_logprob", "last_token_kept", "last_candidate_policy_scores",
                         "last_token_entropy", "last_token_policy_entropy")
 
-    def _logprob_results(self) -> list:
-        return [getattr(self, a, None) for a in self._LOGPROB_RESULTS]
+    # what a generation leaves behind: reset when one starts, kept by a captured graph, cloned out of its replay, joined across streams
+    _GENERATION_RESULTS = ("last_tokens", "last_logits", "last_video_noise") + _LOGPROB_RESULTS
 
-    def _set_logprob_results(self, vals) -> None:
-        for a, v in zip(self._LOGPROB_RESULTS, vals):
+    def _generation_results(self) -> list:
+        return [getattr(self, a) for a in self._GENERATION_RESULTS]
+
+    def _set_generation_results(self, vals) -> None:
+        for a, v in zip(self._GENERATION_RESULTS, vals):
             setattr(self, a, v)
 
     def _warm_derived(self) -> None:
@@ -2158,22 +2202,19 @@ class MAGE(nn.Module):
         main = torch.cuda.current_stream(batch["images"].device)
         if getattr(self, "_side_streams", None) is None or len(self._side_streams) != n:
             self._side_streams = [torch.cuda.Stream(device=batch["images"].device) for _ in range(n)]
-        outs, toks, lps, vns = [None] * n, [None] * n, [None] * n, [None] * n
+        outs, results = [None] * n, [None] * n
         for g, st in enumerate(self._side_streams):
             st.wait_stream(main)                                      # inputs were produced on the caller's stream
             with torch.cuda.stream(st):
                 sub = {k: v[g * per:(g + 1) * per] for k, v in batch.items()}
                 outs[g] = self._generate_one(sub)
-                toks[g] = self.last_tokens
-                lps[g] = self._logprob_results()
-                vns[g] = self.last_video_noise
+                self.last_logits = None                               # (not joined: last_logits is None after a multi-stream call)
+                results[g] = self._generation_results()
         for st in self._side_streams:
             main.wait_stream(st)
-        for t_ in outs + toks + [t_ for l_ in lps for t_ in l_ if t_ is not None] + [t_ for t_ in vns if t_ is not None]:
+        for t_ in outs + [t_ for r_ in results for t_ in r_ if t_ is not None]:
             t_.record_stream(main)                                    # allocator plumbing: consumed on the caller's stream
-        self.last_video_noise = None if vns[0] is None else torch.cat(vns, 0)
-        self.last_tokens, self.last_logits = torch.cat(toks, 0), None
-        self._set_logprob_results([None if col[0] is None else torch.cat(col, 0) for col in zip(*lps)])
+        self._set_generation_results([None if col[0] is None else torch.cat(col, 0) for col in zip(*results)])
         return torch.cat(outs, 0)
 
     @torch.no_grad()
@@ -2208,34 +2249,47 @@ class MAGE(nn.Module):
 
     @torch.no_grad()
     def _generate_one(self, batch, keep_all: bool = False, candidate_noise: bool = False):
+        """One eager generation of the batch on the current stream: the once-per-clip prologue, the AR loop of self.ar_mode, _finish.
+        keep_all / candidate_noise: MAGE.rollout's (every candidate kept; a noise draw per candidate); the dict then carries 'seeds'."""
+        c = self._prologue(batch, candidate_noise)
+        gen, logits = (self._ar_incremental if self.ar_mode == "incremental" else self._ar_full)(c)
+        out = self._finish(c.images, gen, logits, c.lp, c.Bc, c.N, c.st, keep_all, c.k)
+        if keep_all:
+            out["seeds"] = c.seeds
+        return out
+
+    def _prologue(self, batch, candidate_noise: bool = False) -> "_Generation":
+        """What is computed once per call: the tokens of the k given frames, the given token of every slot, the candidate seeds and the
+        motion anchor -- plain, guided ([cond | uncond]: 2 Bc clips) or with a noise draw per candidate -- expanded to N candidates."""
         images = batch["images"]
-        B = images.shape[0]
-        R, L, K = self.image_resolution, self.frames_length, self.codebook_size
-        hw, Lm1 = R * R, self.frames_length - 1
-        dt = self._dt()
-        # k given frames (set_context; 1: frame 0 alone): one encode of all B * k, or batch['context_tokens'] in its place
+        Bc, hw, Lm1 = images.shape[0], self.image_resolution ** 2, self.frames_length - 1
+        # k given frames (set_context; 1: frame 0 alone): one encode of all Bc * k, or batch['context_tokens'] in its place
         k = self._ctx()
         ctx = batch.get("context_tokens")
-        ctx = (self.first_stage_encode(images[:, 0:k]) if ctx is None else ctx).reshape(B, k, hw)      # :642
+        ctx = (self.first_stage_encode(images[:, 0:k]) if ctx is None else ctx).reshape(Bc, k, hw)      # :642
         tok0 = ctx[:, 0].contiguous()
-        # kn [B, (L-1) * hw]: the given token of every slot, negative where the slot is free (None: nothing given) -- batch['known_tokens']
+        # kn [Bc, (L-1) * hw]: the given token of every slot, negative where the slot is free (None: nothing given) -- batch['known_tokens']
         # with the given frames 1 .. k-1 merged into slots 0 .. k-2 on the device
         kn = batch.get("known_tokens")
         if kn is not None or k > 1:
-            kn = torch.full((B, Lm1, hw), -1, device=images.device, dtype=torch.int64) if kn is None else kn.reshape(B, Lm1, hw).clone()
+            kn = torch.full((Bc, Lm1, hw), -1, device=images.device, dtype=torch.int64) if kn is None else kn.reshape(Bc, Lm1, hw).clone()
             kn[:, :k - 1] = ctx[:, 1:]
-        seeds = batch.get("sample_seed") if getattr(self, "sampling", None) is not None else None     # None: greedy
-        N, Bc = self._n_cand(), B
+        # best of N: from the anchor on every clip is N adjacent rows of a batch of Bc * N, candidate c drawing with seed + c (int64 wrap-around)
+        N = self._n_cand()
+        expand = lambda t_: t_ if N == 1 else t_[:, None].expand(t_.shape[0], N, *t_.shape[1:]).reshape(t_.shape[0] * N, *t_.shape[1:])   # noqa: E731
+        seeds = batch.get("sample_seed") if self.sampling is not None else None               # None: greedy
+        if N > 1:
+            seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(Bc * N)
         gs = batch.get("guidance_scale") if self._guided() else None                          # None: no guidance
         if gs is not None:
-            # classifier-free guidance: the prologue runs once over 2 B captions -- [the clips under their caption | the same clips under the
-            # negative caption], clip b's second copy with clip b's frame 0, noise and speed -- and from here the batch is [cond | uncond]
-            assert not candidate_noise and not keep_all                                       # (rollout is refused while guidance is on)
+            # classifier-free guidance: the prologue runs once over 2 Bc captions -- [the clips under their caption | the same clips under
+            # the negative caption], clip b's second copy with clip b's frame 0, noise and speed -- and from here the batch is [cond | uncond]
+            assert not candidate_noise                                                        # (rollout is refused while guidance is on)
             two = lambda t_: torch.cat([t_, t_], 0)      # noqa: E731
             tok0, ctx = two(tok0), two(ctx)
             noise, nseed = batch.get("video_noise"), batch.get("noise_seed")
             if self.randomness and noise is None and nseed is None:
-                noise = torch.randn([Bc, 64, R, R], device=images.device)                     # mage_model.py:661, one draw per clip
+                noise = torch.randn([Bc, 64, self.image_resolution, self.image_resolution], device=images.device)   # mage_model.py:661, one draw per clip
             ma = self._anchor_head(tok0, {"text": torch.cat([batch["text"].to(torch.int64), batch["negative_text"]], 0)})
             ma = self._anchor_tail(ma, {}, None if noise is None else two(noise), 2 * Bc, noise_seed=None if nseed is None else two(nseed),
                                    speed=two(batch["speed"]) if "speed" in batch else None)
@@ -2243,144 +2297,93 @@ class MAGE(nn.Module):
                 self.last_video_noise = self.last_video_noise[:Bc]
         elif candidate_noise:
             # rollout(noise='candidate'): the text and MA encoders run once per clip; every candidate then draws its own noise -- under the
-            # seed that also drives its sampler -- and conv_d2, ADAIN and the speed term run on the B * N rows
-            B = Bc * N
-            seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
-            ma = self._anchor_head(tok0, batch)
-            ma = ma.view(Bc, 1, hw, -1).expand(Bc, N, hw, ma.shape[-1]).reshape(B * hw, -1)
-            speed = batch["speed"].repeat_interleave(N, 0) if "speed" in batch else None
-            ma = self._anchor_tail(ma, {}, None, B, noise_seed=seeds, speed=speed)
-            tok0 = tok0[:, None, :].expand(Bc, N, hw).reshape(B, hw)
-            ctx = ctx[:, None].expand(Bc, N, k, hw).reshape(B, k, hw)
+            # seed that also drives its sampler -- and conv_d2, ADAIN and the speed term run on the Bc * N rows
+            ma = expand(self._anchor_head(tok0, batch).view(Bc, hw, -1)).reshape(Bc * N * hw, -1)
+            ma = self._anchor_tail(ma, {}, None, Bc * N, noise_seed=seeds, speed=expand(batch["speed"]) if "speed" in batch else None)
         else:
             ma = self._motion_anchor(tok0, batch, batch.get("video_noise"))
-        if N > 1 and not candidate_noise:
-            # best of N: the once-per-clip prologue above ran once; from here every clip is N adjacent rows of a batch of B * N, candidate c
-            # drawing with seed + c (int64 wrap-around), and only the winners are decoded
-            B = Bc * N
-            Bp = tok0.shape[0]                                                                # Bc, or 2 Bc under guidance: each half expands alike
-            tok0 = tok0[:, None, :].expand(Bp, N, hw).reshape(Bp * N, hw)
-            ctx = ctx[:, None].expand(Bp, N, k, hw).reshape(Bp * N, k, hw)
-            ma = ma.view(Bp, 1, hw, -1).expand(Bp, N, hw, ma.shape[-1]).reshape(Bp * N * hw, -1)
-            seeds = (seeds[:, None] + torch.arange(N, device=seeds.device, dtype=torch.int64)[None, :]).reshape(B)
-        ma_dt = _to_dt(ma, dt)
-        gen = torch.empty(B, Lm1, R, R, device=images.device, dtype=torch.int64)
-        want_lp = self._want_logprobs()
-        # B: the clips (x candidates) whose tokens are picked; Bd: the decoder's batch -- under guidance 2 B, rows B .. 2 B the uncond half,
-        # which is fed the tokens of the cond half.  Every pick / logprob / stats launch below addresses the first B clips only.
-        Bd = B if gs is None else 2 * B
-        # one launch per frame stores the given tokens over the picked ones (and the certain policy's 0 / 0 / 1 over their results): the
-        # first B clips, a clip's N candidates sharing its row of kn; `a` is token_logprob's token addressing of the slot
-        force = lambda tokens, res, rows, **a: ops.apply_known_tokens(      # noqa: E731
-            tokens, kn, rows=rows, K=K, known_group_stride=Lm1 * hw, known_clip_div=N, **res, **a)
-        res_of = lambda lp_, st_, sel: {**({} if lp_ is None else {"logprob": sel(lp_)}),      # noqa: E731
-                                        **({} if st_ is None else {n: None if b is None else sel(b) for n, b in st_.items()})}
-        if self.ar_mode == "incremental":
-            # each position once, temporal K,V cached; bit-identical tokens to the reference loop below
-            st = self.generate_model._inc_begin(Bd, R, R)
-            prev = tok0.contiguous() if k == 1 else ctx.contiguous()                          # [Bd, k, hw]: the given frames
-            lp_t = torch.empty(Lm1, B, hw, device=images.device, dtype=F32) if want_lp else None
-            st_t = self._stats_alloc((Lm1, B, hw), images.device)
-            gen_t = torch.empty(Lm1, Bd, hw, device=images.device, dtype=torch.int64)        # frame-major: a frame's tokens are contiguous,
-            for i in range(k - 1):                        # the given frames' own slots: nothing is decoded or picked for them
-                force(gen_t[i], res_of(lp_t, st_t, lambda b: b[i]), B * hw, group=hw, known_off=i * hw)
-            for i in range(k - 1, Lm1):                                                       # the argmax writes them where the next step reads them
-                if i > k - 1 or k == 1 or getattr(self, "context_prefill", True):
-                    # newest frame only; the first step takes the anchor and all k given frames as one window, the head on its last slot
-                    feats = self._frame_source(prev, dt)
-                    step_logits = self.generate_model._inc_step(st, ma_dt if i == k - 1 else None, feats, nf=k if i == k - 1 else 1)
-                else:                                     # context_prefill off: the given frames one position at a time, no pick
-                    for j in range(k):
-                        step_logits = self.generate_model._inc_step(st, ma_dt if j == 0 else None, self._frame_source(prev[:, j].contiguous(), dt))
-                prev = gen_t[i]
-                if gs is not None:                        # in place on the cond half's rows: one value per clip covers its N candidates
-                    ops.guide_logits(step_logits, step_logits[B * hw:], gs, rows=B * hw, K=K, scale_div=N * hw)
-                if seeds is None:
-                    ops.argmax(step_logits, prev, rows=B * hw, K=K)
-                else:                                                                         # clip = row // hw, position i*hw + pixel
-                    self._pick(step_logits, prev, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw)
-                if want_lp:                                                                   # the tokens just picked, under the logits they came from
-                    ops.token_logprob(step_logits, prev, lp_t[i], rows=B * hw, K=K)
-                if st_t is not None:
-                    self._stats(step_logits, prev, st_t, lambda b: b[i], rows=B * hw, K=K)
-                if kn is not None:
-                    force(prev, res_of(lp_t, st_t, lambda b: b[i]), B * hw, group=hw, known_off=i * hw)
-                if gs is not None and i != Lm1 - 1:
-                    prev[B:].copy_(prev[:B])              # the uncond half conditions on the same tokens (one small int64 copy per frame)
-            if gs is not None:
-                gen_t = gen_t[:, :B]
-            gen = gen_t.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else gen_t.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # index plumbing, once
-            clip_major = lambda t_: t_.permute(1, 0, 2).reshape(B, Lm1, R, R) if B == 1 else t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)   # noqa: E731
-            lp = clip_major(lp_t) if want_lp else None
-            st = None if st_t is None else {n: None if b is None else clip_major(b) for n, b in st_t.items()}
-            return self._finish(images, gen, None, lp, Bc, N, st, keep_all, k)
-        cur = tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                                 # :670 future slots hold frame 0
+        if N > 1:
+            tok0, ctx = expand(tok0), expand(ctx)                                             # (under guidance each half expands alike)
+            if not candidate_noise:
+                ma = expand(ma.view(-1, hw, ma.shape[-1])).reshape(-1, ma.shape[-1])
+        shape = (Lm1, Bc * N, hw) if self.ar_mode == "incremental" else (Bc * N, Lm1, self.image_resolution, self.image_resolution)
+        lp = torch.empty(shape, device=images.device, dtype=F32) if self._want_logprobs() else None
+        return _Generation(self, images, Bc, N, k, tok0, ctx, _to_dt(ma, self._dt()), seeds, gs, kn, lp, self._stats_alloc(shape, images.device))
+
+    def _ar_incremental(self, c: "_Generation"):
+        """each position once, temporal K,V cached; bit-identical tokens to the reference loop (_ar_full).  Tokens and results
+        are frame-major while the loop runs: a frame's tokens are contiguous, and the pick writes them where the next step reads them."""
+        R, Lm1, B, hw, k = self.image_resolution, c.Lm1, c.B, c.hw, c.k
+        dec, dt = self.generate_model, self._dt()
+        st = dec._inc_begin(c.Bd, R, R)
+        gen_t = torch.empty(Lm1, c.Bd, hw, device=c.images.device, dtype=torch.int64)
+        prev = c.tok0.contiguous() if k == 1 else c.ctx.contiguous()                          # [Bd, k, hw]: the given frames
+        for i in range(k - 1):                            # the given frames' own slots: nothing is decoded or picked for them
+            c.hold(gen_t[i], lambda b: b[i], B * hw, group=hw, known_off=i * hw)
+        for i in range(k - 1, Lm1):
+            first = i == k - 1
+            if not first or k == 1 or self.context_prefill:
+                # newest frame only; the first step takes the anchor and all k given frames as one window, the head on its last slot
+                logits = dec._inc_step(st, c.ma if first else None, self._frame_source(prev, dt), nf=k if first else 1)
+            else:                                         # context_prefill off: the given frames one position at a time, no pick
+                for j in range(k):
+                    logits = dec._inc_step(st, c.ma if j == 0 else None, self._frame_source(prev[:, j].contiguous(), dt))
+            prev = gen_t[i]                               # clip = row // hw; the last frame's tokens condition nothing
+            c.frame(i, logits, prev, lambda b: b[i], in_group_stride=hw, tok_group_stride=hw, slot=None if i == Lm1 - 1 else prev)
+        clip_major = lambda t_: t_.permute(1, 0, 2).contiguous().view(B, Lm1, R, R)          # noqa: E731  (index plumbing, once; no copy at B = 1)
+        c.lp = None if c.lp is None else clip_major(c.lp)
+        c.st = None if c.st is None else {n: None if b is None else clip_major(b) for n, b in c.st.items()}
+        return clip_major(gen_t[:, :B]), None
+
+    def _ar_full(self, c: "_Generation"):
+        """The reference's loop (:670-687): every iteration recomputes all L-1 slots and takes frame i's tokens into slot i + 1.  What it
+        keeps from the reference's shape: a greedy call scores all frames at once after the loop, a sampled one draws only the last frame
+        there (the others are the tokens the loop conditioned on), and last_logits are the last iteration's."""
+        R, Lm1, B, hw, k, K = self.image_resolution, c.Lm1, c.B, c.hw, c.k, self.codebook_size
+        dt, clip = self._dt(), c.Lm1 * c.hw
+        cur = c.tok0[:, None, :].repeat(1, Lm1, 1).contiguous()                               # :670 future slots hold frame 0
         if k > 1:
-            cur[:, 1:k] = ctx[:, 1:]                                                          # slots 1 .. k-1: the given frames
-        logits = None
-        lp = torch.empty(B, Lm1, R, R, device=images.device, dtype=F32) if want_lp else None
-        st = self._stats_alloc((B, Lm1, R, R), images.device)
+            cur[:, 1:k] = c.ctx[:, 1:]                                                        # slots 1 .. k-1: the given frames
         flat = lambda b: b.view(-1)      # noqa: E731
-        frame = dict(rows=B * hw, K=K, group=hw, in_group_stride=Lm1 * hw)                  # frame i of every clip: (in_ / tok_) off = i * hw
+        nxt = cur.view(-1)[hw:]                           # frame i's tokens go to slot i + 1: index i * hw of the flat view one frame on
         for i in range(k - 1, Lm1):                                                           # :673-684
             feats = self._frame_source(cur, dt)
             ev = ops.PROFILE.begin() if ops.PROFILE.wants("decoder_step") else None          # bench.py: the transformer step on its own
-            logits = self.generate_model._run(ma_dt, feats, B=Bd, hh=R, ww=R)                 # [Bd*(L-1)*hw, K]
+            logits = self.generate_model._run(c.ma, feats, B=c.Bd, hh=R, ww=R)                # [Bd*(L-1)*hw, K]
             if ev is not None:
                 ops.PROFILE.end("decoder_step", ev, 0.0)
-            if gs is not None:
-                # in place on the cond half.  Frame i's rows (argmax's regrouped addressing) are all the pick needs; the last iteration
-                # guides every frame, so that the greedy final argmax and last_logits see guided logits throughout
-                unc = logits[B * Lm1 * hw:]
-                if i != Lm1 - 1:
-                    ops.guide_logits(logits, unc, gs, rows=B * hw, K=K, scale_div=N * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw)
-                else:
-                    ops.guide_logits(logits, unc, gs, rows=B * Lm1 * hw, K=K, scale_div=N * Lm1 * hw)
-            if i != Lm1 - 1:                                                                  # argmax of frame i -> slot i+1
-                self._pick(logits, cur, seeds, rows=B * hw, K=K, pos_off=i * hw, group=hw, in_group_stride=Lm1 * hw, in_off=i * hw,
-                           out_group_stride=Lm1 * hw, out_off=(i + 1) * hw)
-                if want_lp and seeds is not None:         # sampled: frame i's tokens (slot i+1 of cur) under the logits they were drawn from
-                    ops.token_logprob(logits, cur.view(-1)[hw:], lp.view(-1), in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
-                if st is not None and seeds is not None:
-                    self._stats(logits, cur.view(-1)[hw:], st, flat, in_off=i * hw, tok_group_stride=Lm1 * hw, tok_off=i * hw, **frame)
-                if kn is not None:                        # (slot i+1 of cur is index i*hw of the flat view one frame on, as for the two above)
-                    force(cur.view(-1)[hw:], res_of(lp, st, flat) if seeds is not None else {}, B * hw, group=hw,
-                          tok_group_stride=Lm1 * hw, tok_off=i * hw, known_off=i * hw)
-                if gs is not None:
-                    cur[B:, i + 1].copy_(cur[:B, i + 1])  # the picked slot goes to both halves
-        if seeds is None:
-            ops.argmax(logits, gen, rows=B * Lm1 * hw, K=K)                                   # :687
-            if want_lp:
-                ops.token_logprob(logits, gen, lp, rows=B * Lm1 * hw, K=K)
-            if st is not None:
-                self._stats(logits, gen, st, flat, rows=B * Lm1 * hw, K=K)
+            if i != Lm1 - 1:                              # frame i's rows of the logits are all its pick needs
+                c.frame(i, logits, nxt, flat, in_group_stride=clip, in_off=i * hw, tok_group_stride=clip, tok_off=i * hw, slot=cur[:, i + 1],
+                        scored=c.seeds is not None)
+        c.guide(logits, frames=Lm1)                       # the last iteration's: every frame, for the final pick and last_logits
+        gen = torch.empty(B, Lm1, R, R, device=c.images.device, dtype=torch.int64)
+        if c.seeds is None:
+            c.pick(logits, gen, flat, rows=B * clip)                                          # :687
         else:
-            # sampled: frames 0..L-3 are the tokens the loop conditioned on (slots 1..L-2); only the last frame is drawn from these logits
             gen.view(B, Lm1, hw)[:, :Lm1 - 1].copy_(cur[:B, 1:])
-            self._pick(logits, gen, seeds, rows=B * hw, K=K, pos_off=(Lm1 - 1) * hw, group=hw, in_group_stride=Lm1 * hw,
-                       in_off=(Lm1 - 1) * hw, out_group_stride=Lm1 * hw, out_off=(Lm1 - 1) * hw)
-            if want_lp:
-                ops.token_logprob(logits, gen, lp, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-            if st is not None:
-                self._stats(logits, gen, st, flat, in_off=(Lm1 - 1) * hw, tok_group_stride=Lm1 * hw, tok_off=(Lm1 - 1) * hw, **frame)
-        if kn is not None:                                # every slot at once: the final pick's tokens and results, the given frames' slots
-            force(gen, res_of(lp, st, flat), B * Lm1 * hw, group=Lm1 * hw)
-        return self._finish(images, gen, logits[:B * Lm1 * hw].view(B, Lm1, R, R, K), lp, Bc, N, st, keep_all, k)
+            last = (Lm1 - 1) * hw
+            c.pick(logits, gen, flat, rows=B * hw, pos_off=last, group=hw, in_group_stride=clip, in_off=last, tok_group_stride=clip, tok_off=last)
+        c.hold(gen, flat, B * clip, group=clip)           # every slot at once: the final pick's tokens and results, the given frames' slots
+        return gen, logits[:B * clip].view(B, Lm1, R, R, K)
+
+    def _video(self, head: torch.Tensor, gen: torch.Tensor, k: int) -> torch.Tensor:
+        """The first k frames of head [rows, >= k, C, H, W] verbatim, then the decode of the generated slots k-1 .. of gen (:690-691)."""
+        if k == 1:
+            return _assemble(head, self.first_stage_decode(gen))
+        video = self.first_stage_decode(gen[:, k - 1:])
+        return torch.cat([head[:, :k].to(video.dtype), video], 1)
 
     def _finish(self, images, gen, logits, lp, Bc: int, N: int, st: Optional[dict] = None, keep_all: bool = False, k: int = 1):
         """The end of _generate_one: the per-clip scores of the token log-probabilities lp (None: the feature is off), with N > 1 the winners
-        of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (:690-691).  st: the
+        of every clip's N adjacent candidates (a device-side gather: no host decision), the results, the decode (_video).  st: the
         mage_token_stats buffers of set_logprobs(policy=, entropy=), [B * N, L-1, h, w] each (None: off); the winner's rows are kept.
-        keep_all (MAGE.rollout only): no winner is picked -- all B * N candidates are decoded and handed back with their tokens and
-        log-probabilities as a dict, and no result attribute is written."""
+        keep_all (MAGE.rollout only): no winner is picked -- all B * N candidates are decoded, each behind its clip's given frames, and handed
+        back with their tokens and log-probabilities as a dict, and no result attribute is written."""
         if keep_all:
-            first = images[:, 0:1] if N == 1 else images[:, 0:1].repeat_interleave(N, 0)       # every candidate starts from its clip's frame 0
-            if k > 1:                                     # rollout(context=k): the k given frames verbatim, only the generated ones decoded
-                dec = self.first_stage_decode(gen[:, k - 1:])
-                video = torch.cat([images[:, :k].repeat_interleave(N, 0).to(dec.dtype), dec], 1)
-            else:
-                video = _assemble(first, self.first_stage_decode(gen))
-            return {"video": video, "tokens": gen, "token_logprobs": lp, "first": first, "behaviour_logprobs": st["policy_logprob"]}
+            first = images[:, 0:1] if N == 1 else images[:, 0:1].repeat_interleave(N, 0)
+            head = first if k == 1 else images[:, :k].repeat_interleave(N, 0)
+            return {"video": self._video(head, gen, k), "tokens": gen, "token_logprobs": lp, "first": first,
+                    "behaviour_logprobs": st["policy_logprob"]}
         if lp is not None:
             scores, best = ops.clip_scores(lp, n_clips=Bc, n_cand=N)
             pscores = None
@@ -2406,11 +2409,7 @@ class MAGE(nn.Module):
                 for name, attr in self._STATS_RESULTS:
                     setattr(self, attr, st[name])
         self.last_tokens, self.last_logits = gen, logits
-        if k > 1:                                         # the k given frames verbatim, then the generated ones: only those are decoded
-            video = self.first_stage_decode(gen[:, k - 1:])
-            return torch.cat([images[:, :k].to(video.dtype), video], 1)
-        video = self.first_stage_decode(gen)
-        return _assemble(images, video)
+        return self._video(images, gen, k)
 
     # ------------------------------------------------------------------ teacher-forced pass (mage_model.py:575-639)
     @torch.no_grad()
