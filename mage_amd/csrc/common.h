@@ -286,6 +286,10 @@ __device__ __forceinline__ unsigned hash32(unsigned long long v) {
     v ^= v >> 33;
     return (unsigned)v;
 }
+// -log(u) of the 24-bit uniform u = (m + 0.5) 2^-24, never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
+__device__ __forceinline__ float sample_neglog_u(unsigned m) {
+    return m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f) : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -296,4 +300,23 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// best (smallest) value of a wave, its index (the lowest on ties) and the second-best value: the quantiser's and mage_argmax's reduction
+struct Best {
+    float d0; int i0; float d1;     // best distance, its index, second-best distance
+};
+__device__ __forceinline__ void best_push(Best& b, float d, int i) {
+    if (d < b.d0 || (d == b.d0 && i < b.i0)) { b.d1 = b.d0; b.d0 = d; b.i0 = i; }
+    else if (d < b.d1) b.d1 = d;
+}
+__device__ __forceinline__ Best best_wave_reduce(Best b) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od0 = __shfl_xor(b.d0, o, 64), od1 = __shfl_xor(b.d1, o, 64);
+        const int oi0 = __shfl_xor(b.i0, o, 64);
+        if (od0 < b.d0 || (od0 == b.d0 && oi0 < b.i0)) { b.d1 = fminf(b.d0, od1); b.d0 = od0; b.i0 = oi0; }
+        else b.d1 = fminf(b.d1, od0);
+    }
+    return b;
 }

@@ -1,8 +1,7 @@
 // Preference fine-tuning on ranked pairs of clips (DPO / IPO): the pair stage (mage_preference_loss) and the gradient of weighted token
 // log-probabilities with respect to the logits (mage_token_logprob_bwd).  include/mage_hip_ext.h states the rules; no site in the reference
 // (it trains on cross-entropy only).
-#include "common.h"
-#include "../../include/mage_hip_ext.h"
+#include "token_row.h"
 #include <math.h>
 
 // The fp64 terms are written out operation by operation: the header gives them as formulas, and the test's restatement follows the same ones.
@@ -173,7 +172,7 @@ __device__ __forceinline__ void logprob_bwd_store(OT* __restrict__ o, int lane, 
     }
 }
 
-// dlogits_ij = c_i (1[j = t] - p_ij): token_logprob_kernel's maximum and sum (vq.hip: the same layout, the same order), ce_bwd_kernel's
+// dlogits_ij = c_i (1[j = t] - p_ij): token_logprob_kernel's maximum and sum (row_logsumexp, token_row.h), ce_bwd_kernel's
 // p = expf(z - max) * (1 / sum) (train.hip).  c_i == 0: the row is zeros and its logits are not read.
 template <int NV, typename OT>
 __global__ __launch_bounds__(256) void token_logprob_bwd_kernel(const float* __restrict__ logits, long rows, int K, long ld,
@@ -185,8 +184,7 @@ __global__ __launch_bounds__(256) void token_logprob_bwd_kernel(const float* __r
     const int lane = threadIdx.x & 63;
     OT* o = dl + i * (long)K;
     // (mage_token_logprob_bwd_masked: a given row is a row of c_i == 0; a null mask, the unmasked entry point, has none)
-    const bool gv = given && __builtin_amdgcn_readfirstlane((int)given[i]) != 0;
-    const float ci = gv ? 0.f : __fmul_rn(gout[0], weight[i / weight_div]);
+    const float ci = row_given(given, i) ? 0.f : __fmul_rn(gout[0], weight[i / weight_div]);
     float d[NV];
     if (ci == 0.f) {                                    // (wave-uniform)
 #pragma unroll
@@ -195,28 +193,8 @@ __global__ __launch_bounds__(256) void token_logprob_bwd_kernel(const float* __r
         return;
     }
     const float* p = logits + i * ld;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) {
-        const int k = c * 256 + lane * 4;
-        const f32x4 v = k < K ? *(const f32x4*)(p + k) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            d[c * 4 + e] = v[e];
-            mx = fmaxf(mx, v[e]);                       // (a NaN is skipped here and caught by the sum)
-        }
-    }
-    mx = wave_max(mx);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) {
-        d[e] = expf(d[e] - mx);
-        s = __fadd_rn(s, d[e]);
-    }
-    s = wave_sum(s);
-    const float inv = 1.0f / s;
-    long tg = tokens[i];
-    if (tg < 0 || tg >= K) tg = -1;                     // no one-hot (reported by mage_token_logprob, which ran before)
+    const float inv = 1.0f / row_logsumexp<NV>([=](int c) { return row_chunk_inf(p, lane, K, c); }, d).zs;
+    const long tg = row_token<false>(tokens, i, K, nullptr);            // (a bad token: no one-hot; mage_token_logprob, which ran before, reported it)
 #pragma unroll
     for (int e = 0; e < NV; ++e) {
         const int k = (e >> 2) * 256 + lane * 4 + (e & 3);
@@ -261,10 +239,7 @@ static int token_logprob_backward(const char* who, const float* logits, int64_t 
                                   const float* weight, int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype,
                                   const uint8_t* given, void* stream) {
     MAGE_CHECK_ARG(logits && tokens && weight && grad_out && dlogits, "%s: null pointer", who);
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && weight_div > 0 &&
-                   (((uintptr_t)logits) & 15) == 0 && (((uintptr_t)dlogits) & 15) == 0,
-                   "%s: bad sizes rows=%ld K=%d ld=%ld weight_div=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", who,
-                   (long)rows, K, (long)ld, (long)weight_div, MAGE_SAMPLE_MAX_K);
+    if (int rc = token_rows_check(who, logits, rows, K, ld, (((uintptr_t)dlogits) & 15) == 0, "weight_div", weight_div)) return rc;
     MAGE_CHECK_ARG((((uintptr_t)tokens) & 7) == 0 && ((((uintptr_t)weight) | ((uintptr_t)grad_out)) & 3) == 0,
                    "%s: tokens must be 8-byte, weight and grad_out 4-byte aligned", who);
     MAGE_CHECK_ARG(dl_dtype == MAGE_F32 || dl_dtype == MAGE_BF16, "%s: bad dtype %d", who, dl_dtype);
@@ -279,11 +254,7 @@ static int token_logprob_backward(const char* who, const float* logits, int64_t 
         if (dl_dtype == MAGE_F32) MAGE_LPB(NV, float);   \
         else MAGE_LPB(NV, unsigned short);               \
     } while (0)
-    if (K <= 256) MAGE_LPB_NV(4);
-    else if (K <= 512) MAGE_LPB_NV(8);
-    else if (K <= 1024) MAGE_LPB_NV(16);
-    else if (K <= 2048) MAGE_LPB_NV(32);
-    else MAGE_LPB_NV(64);
+    MAGE_ROW_LADDER(K, MAGE_LPB_NV);
 #undef MAGE_LPB_NV
 #undef MAGE_LPB
     MAGE_CHECK_LAUNCH(who);

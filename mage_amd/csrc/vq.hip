@@ -1,4 +1,4 @@
-// Codebook quantiser (nearest neighbour), embedding gathers, row argmax and cross entropy.
+// Codebook quantiser (nearest neighbour), embedding gathers, the table convolution and the seeded video noise.
 // Integer/index outputs here must be bit-exact against the reference, so the distance follows the
 // reference FORMULA (vqvae_model.py:14-21): fl32(fl32(|c|^2 + |z|^2) - 2*<z,c>), first minimum wins.
 #include "common.h"
@@ -17,24 +17,6 @@ __global__ __launch_bounds__(256) void vq_prepare_kernel(const float* __restrict
         s += (double)v * (double)v;
     }
     c2[k] = (float)s;
-}
-
-struct Best {
-    float d0; int i0; float d1;     // best distance, its index, second-best distance
-};
-__device__ __forceinline__ void best_push(Best& b, float d, int i) {
-    if (d < b.d0 || (d == b.d0 && i < b.i0)) { b.d1 = b.d0; b.d0 = d; b.i0 = i; }
-    else if (d < b.d1) b.d1 = d;
-}
-__device__ __forceinline__ Best best_wave_reduce(Best b) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float od0 = __shfl_xor(b.d0, o, 64), od1 = __shfl_xor(b.d1, o, 64);
-        const int oi0 = __shfl_xor(b.i0, o, 64);
-        if (od0 < b.d0 || (od0 == b.d0 && oi0 < b.i0)) { b.d1 = fminf(b.d0, od1); b.d0 = od0; b.i0 = oi0; }
-        else b.d1 = fminf(b.d1, od0);
-    }
-    return b;
 }
 
 // 16 rows of z per workgroup; every thread owns KPT codes (k = tid + 256*kk) for all 16 rows.
@@ -230,749 +212,6 @@ __global__ __launch_bounds__(256) void embedding_kernel(const int64_t* __restric
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }
         store4(dst + c, v);
-    }
-}
-
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
-                                                     long in_stride, long in_off, int64_t* __restrict__ out,
-                                                     long out_stride, long out_off, float* __restrict__ margin) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const long gi = i / group, gr = i - gi * group;
-    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
-    Best b{INFINITY, 0x7fffffff, INFINITY};          // minimise the negated logit: first maximum wins
-    for (int k = lane * 4; k < K; k += 256) {
-        const f32x4 v = *(const f32x4*)(p + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (k + e < K) best_push(b, -v[e], k + e);
-    }
-    b = best_wave_reduce(b);
-    if (lane == 0) {
-        out[gi * out_stride + gr + out_off] = b.i0;
-        if (margin) margin[i] = b.d1 - b.d0;
-    }
-}
-
-// ---- seeded token sampling (mage_sample_tokens): temperature, top-k, top-p, Gumbel-max.  The rule, for one row:
-//   inputs: fp32 logits z[0..K), inv_t = (float)(1.0 / temperature) (host), top_k (0 = off), top_p in (0, 1] (1 = off), the row's clip
-//   seed (uint64) and the token position pos = frame * h*w + pixel (frame = index of the generated frame, 0 .. L-2).
-//   1. s_j = z_j * inv_t (one fp32 multiply).  A NaN logit is never selected (it is in no set below).
-//   2. top-k: if 0 < top_k < K, A = { j : s_j >= the top_k-th largest s } (ties at the boundary kept: |A| may exceed top_k; fewer than
-//      top_k non-NaN logits: A = all of them); otherwise A = every code.
-//   3. top-p: if top_p < 1, w_j = exp(s_j - max_A s) for j in A, W = sum_A w_j, tau = the largest value v among { s_j : j in A } with
-//      sum_{j in A, s_j >= v} w_j >= top_p * W, N = { j in A : s_j >= tau } (ties kept); otherwise N = A.
-//   4. Gumbel-max on a stateless counter (hash32, common.h):
-//      u_j = ((hash32(seed * 0x9e3779b97f4a7c15 + (pos * K + j)) >> 8) + 0.5) * 2^-24   (uint64 wrap-around arithmetic),
-//      g_j = -log(-log(u_j)), token = the smallest j in N that maximises s_j + g_j (no selectable code at all: token 0).
-// A token's random stream depends on its clip's seed, frame, pixel and code only: not on the batch size, the clip's place in the batch,
-// the AR mode, the number of streams or graph replay.  top_k == 1 is greedy by definition: mage_argmax's kernel (first maximum wins).
-// One wave per row, the row in registers (NV values per lane, 16-byte loads; code k = c*256 + lane*4 + e of chunk c).  The selections are
-// bit-by-bit bisections over order-preserving uint keys of s: top-k counts with ballots (a scalar count, no shuffles), top-p sums the w_j
-// with fixed-order butterflies (every lane holds the same bits).  Where the sums are rounded (W, the masses) a row whose boundary mass is
-// within fp32 rounding of top_p * W may keep one value more or less than the exact rule; nothing else is approximate.
-__device__ __forceinline__ unsigned sample_key(float s) {       // order-preserving; -0 == +0; NaN -> 0 (below every number: never kept)
-    unsigned u = __float_as_uint(s);
-    if (s != s) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sample_key_value(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-// -log(u) of the 24-bit uniform u = (m + 0.5) 2^-24, never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
-__device__ __forceinline__ float sample_neglog_u(unsigned m) {
-    return m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f) : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
-}
-// g = -log(-log(u))
-__device__ __forceinline__ float sample_gumbel(unsigned long long ctr) {
-    return -logf(sample_neglog_u(hash32(ctr) >> 8));
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
-// Chunk c of a row in sample_kernel's layout: one 16-byte load, codes k = c*256 + lane*4 + e, 0 past K.
-__device__ __forceinline__ f32x4 sample_row_chunk(const float* __restrict__ p, int lane, int K, int c) {
-    const int k = c * 256 + lane * 4;
-    return k < K ? *(const f32x4*)(p + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-// Steps 1-3 of the rule for one row: s (the scaled logits), key (0: not selectable -- NaN, or past K) and the returned threshold lo >= 1
-// with N = { j : key_j >= lo }.  row(c) gives chunk c of the row (sample_kernel loads it there and then, token_stats_kernel hands over the
-// registers it read once).  THE filter: mage_sample_tokens draws from this set and mage_token_stats reports on it, so the two agree bit
-// for bit on every row, the ones whose rounded top-p masses keep a value more or less than the exact rule included.
-template <int NV, bool TOPK, bool TOPP, typename ROW>
-__device__ __forceinline__ unsigned sample_filter(ROW row, int lane, int K, float inv_t, int top_k, float top_p, float (&s)[NV],
-                                                  unsigned (&key)[NV]) {
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) {
-        const int k = c * 256 + lane * 4;
-        const f32x4 v = row(c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            s[c * 4 + e] = __fmul_rn(v[e], inv_t);
-            key[c * 4 + e] = k < K ? sample_key(s[c * 4 + e]) : 0u;
-        }
-    }
-    unsigned lo = 1u;                                   // the candidate set: key >= lo
-    if constexpr (TOPK) {                               // the largest t with #{key >= t} >= top_k: the top_k-th largest key
-        unsigned t = 0u;
-        auto bit = [&](int b) {
-            const unsigned c = t | (1u << b);
-            int n = 0;
-#pragma unroll
-            for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= c));
-            if (n >= top_k) t = c;
-        };
-        // NV = 4, 32 x 4 ballots: straight-line code, which the compiler chose by itself while this loop stood in sample_kernel (K = 256,
-        // top-k only: 40 against 43 us as a loop); every other instance is the loop it always was
-        if constexpr (NV == 4) {
-#pragma unroll
-            for (int b = 31; b >= 0; --b) bit(b);
-        } else {
-            for (int b = 31; b >= 0; --b) bit(b);
-        }
-        lo = max(t, 1u);
-    }
-    if constexpr (TOPP) {
-        unsigned km = 0u;
-#pragma unroll
-        for (int e = 0; e < NV; ++e) km = max(km, key[e]);
-        km = wave_max_u32(km);
-        if (km >= lo) {                                 // else: nothing selectable
-            const float smax = sample_key_value(km);
-            float w[NV], wl = 0.f;
-#pragma unroll
-            for (int e = 0; e < NV; ++e) {
-                w[e] = key[e] >= lo ? expf(s[e] - smax) : 0.f;
-                wl += w[e];
-            }
-            const float target = __fmul_rn(top_p, wave_sum(wl));
-            // the largest key t in [lo, km] with mass(key >= t) >= target; mass(>= lo) = W >= target.  The bits above the highest one in which
-            // lo and km differ are common to every key in between: the bisection starts below them (mass(>= t) = W there too).
-            const unsigned d = lo ^ km;
-            const int hb = d ? 31 - __builtin_clz(d) : -1;
-            unsigned t = hb >= 0 ? (km & ~((2u << hb) - 1u)) : km;
-            for (int b = hb; b >= 0; --b) {
-                const unsigned c = t | (1u << b);
-                float ml = 0.f;
-#pragma unroll
-                for (int e = 0; e < NV; ++e) ml += key[e] >= c ? w[e] : 0.f;
-                const float m = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_sum(ml))));
-                if (m >= target) t = c;
-            }
-            lo = max(t, lo);
-        }
-    }
-    return lo;
-}
-
-template <int NV, bool TOPK, bool TOPP>
-__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
-                                                     long in_stride, long in_off, int64_t* __restrict__ out, long out_stride,
-                                                     long out_off, const int64_t* __restrict__ seeds, long pos_off, float inv_t,
-                                                     int top_k, float top_p) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const long gi = i / group, gr = i - gi * group;
-    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
-    float s[NV];
-    unsigned key[NV];
-    const unsigned lo = sample_filter<NV, TOPK, TOPP>([=](int c) { return sample_row_chunk(p, lane, K, c); }, lane, K, inv_t, top_k, top_p,
-                                                      s, key);                                    // the candidate set: key >= lo
-    const unsigned long long ctr = (unsigned long long)seeds[gi] * 0x9e3779b97f4a7c15ULL
-                                   + (unsigned long long)(pos_off + gr) * (unsigned long long)K;
-    float best = -INFINITY;
-    int bj = 0x7fffffff;
-    if constexpr (TOPK || TOPP) {
-        // a filtered set is small: each lane draws for its own candidates one at a time (the wave runs as many rounds as the fullest lane
-        // holds), instead of paying the Gumbel transform -- the dominant cost -- in every slot some lane of the wave needs
-        unsigned long long pend = 0;
-#pragma unroll
-        for (int e = 0; e < NV; ++e) pend |= (unsigned long long)(key[e] >= lo) << e;
-        while (pend) {
-            const int e0 = __builtin_ctzll(pend);
-            pend &= pend - 1;
-            float sv = 0.f;
-#pragma unroll
-            for (int e = 0; e < NV; ++e) sv = e == e0 ? s[e] : sv;
-            const int j = (e0 >> 2) * 256 + lane * 4 + (e0 & 3);
-            const float v = sv + sample_gumbel(ctr + (unsigned long long)j);
-            if (v > best || (v == best && j < bj)) { best = v; bj = j; }
-        }
-    } else {
-        // nothing filtered: lo == 1, and key >= 1 says no more than "a code of the row, not NaN" (sample_key) -- asked of s itself, so that
-        // this instance holds no key registers through the Gumbel transforms
-#pragma unroll
-        for (int e = 0; e < NV; ++e) {
-            const int j = (e >> 2) * 256 + lane * 4 + (e & 3);
-            if (j < K && s[e] == s[e]) {
-                const float v = s[e] + sample_gumbel(ctr + (unsigned long long)j);
-                if (v > best || (v == best && j < bj)) { best = v; bj = j; }
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oj = __shfl_xor(bj, o, 64);
-        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-    }
-    if (lane == 0) out[gi * out_stride + gr + out_off] = bj == 0x7fffffff ? 0 : bj;
-}
-
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                      long rows, int K, float* __restrict__ row_loss, int* __restrict__ err) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* p = logits + i * K;
-    float mx = -INFINITY;
-    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, p[k]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int k = lane; k < K; k += 64) s += expf(p[k] - mx);
-    s = wave_sum(s);
-    if (lane == 0) {
-        long tg = target[i];
-        if (tg < 0 || tg >= K) {
-            mage_raise(err, MAGE_DEVERR_CE_TARGET, tg, K);
-            tg = 0;
-        }
-        row_loss[i] = (logf(s) + mx) - p[tg];
-    }
-}
-
-__global__ __launch_bounds__(1024) void sum_kernel(const float* __restrict__ v, long n, float* __restrict__ out, double inv) {
-    __shared__ double red[16];
-    double s = 0.0;
-    for (long i = threadIdx.x; i < n; i += 1024) s += (double)v[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        out[0] = (float)(t * inv);
-    }
-}
-
-// ---- token log-probabilities (mage_token_logprob) and per-clip scores (mage_clip_scores).
-// lp = z_t - (m + log sum_j exp(z_j - m)), m = max_j z_j: the log-softmax of a row gathered at its token.  One wave per row, the row in
-// registers in sample_kernel's layout (code k = c*256 + lane*4 + e of chunk c).  Every reduction has a fixed order (a lane adds its own
-// terms in register order, the lanes meet in an xor butterfly), so a row's bits depend on the row alone.  -inf logits add exp(-inf) = 0;
-// a NaN logit, or a row whose maximum is not finite (inf - inf), makes the sum NaN and so the result; z_t = -inf gives -inf.  expf / logf
-// are the accurate ones.
-template <int NV>
-__global__ __launch_bounds__(256) void token_logprob_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group,
-                                                            long in_stride, long in_off, const int64_t* __restrict__ tokens,
-                                                            float* __restrict__ logprob, long tok_stride, long tok_off,
-                                                            int* __restrict__ err) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const long gi = i / group, gr = i - gi * group;
-    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
-    float z[NV];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) {
-        const int k = c * 256 + lane * 4;
-        const f32x4 v = k < K ? *(const f32x4*)(p + k) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            z[c * 4 + e] = v[e];
-            mx = fmaxf(mx, v[e]);                       // (a NaN is skipped here and caught by the sum)
-        }
-    }
-    mx = wave_max(mx);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) s = __fadd_rn(s, expf(z[e] - mx));
-    s = wave_sum(s);
-    if (lane == 0) {
-        const long ti = gi * tok_stride + gr + tok_off;
-        long tg = tokens[ti];
-        if (tg < 0 || tg >= K) {                        // reported by mage_check_device_errors, as mage_cross_entropy's targets are
-            mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
-            tg = tg < 0 ? 0 : K - 1;
-        }
-        logprob[ti] = p[tg] - (mx + logf(s));
-    }
-}
-
-// ---- per-token statistics of the sampling policy (mage_token_stats, include/mage_hip_ext.h): what mage_sample_tokens' filter kept and how
-// the kept set weighs the given token.  Per row, with s, A, N of steps 1-3 of the sampling rule above (sample_filter: the sampler's own code,
-// so N is the sampler's bit for bit), s_max = max_N s, w_j = exp(s_j - s_max), Z = sum_{j in N} w_j:
-//   kept           = |N|                                                (a ballot count: exact)
-//   policy_logprob = s_t - (s_max + log Z) for t in N, -inf otherwise   (s_t = z_t * inv_t, the sampler's multiply)
-//   policy_entropy = log Z - (sum_{j in N} w_j (s_j - s_max)) / Z       (nats; exactly 0 when |N| = 1)
-//   entropy        = the same formula over the whole row of z itself: temperature 1, no filter -- the distribution mage_token_logprob scores under
-// top_k == 1 is greedy by definition, as in the sampler: N = { mage_argmax's first maximum of z }, kept = 1, policy_logprob = 0 for that code
-// and -inf for any other, policy_entropy = 0.
-// Special values: a NaN logit is in no set and adds nothing to Z (it makes `entropy` NaN, as it does mage_token_logprob's result); a -inf
-// logit in N counts in `kept` and adds a zero term to both sums (never 0 * inf); a row with no selectable code (every logit NaN) gives
-// kept = 0 and NaN for policy_logprob and policy_entropy; s_max = +-inf (a +inf logit, a row of -inf only) gives NaN through
-// inf - inf, as in mage_token_logprob; a token outside [0, K) is raised (MAGE_DEVERR_TOKEN_ID) and clamped.
-// One wave per row, the row read once into registers in sample_kernel's layout whatever outputs are asked for (a null output costs a
-// wave-uniform branch), one instance per filter combination.  Every sum has a fixed order: a lane adds its own terms in register order (adding
-// 0 for a code outside N), the lanes meet in an xor butterfly; expf / logf are the accurate ones.  With temperature 1 and no filter, s = z,
-// s_max = the row maximum and Z is token_logprob_kernel's sum operation for operation: policy_logprob equals mage_token_logprob's result bit
-// for bit on NaN-free rows.
-enum { STATS_TOPK = 1, STATS_TOPP = 2, STATS_GREEDY = 4 };
-template <int NV, int MODE>
-__global__ __launch_bounds__(256) void token_stats_kernel(const float* __restrict__ logits, long rows, int K, long ld, long group, long in_stride,
-                                                          long in_off, const int64_t* __restrict__ tokens, long tok_stride, long tok_off,
-                                                          float inv_t, int top_k, float top_p, float* __restrict__ policy_logprob,
-                                                          float* __restrict__ policy_entropy, int32_t* __restrict__ kept,
-                                                          float* __restrict__ entropy, int* __restrict__ err) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const long gi = i / group, gr = i - gi * group;
-    const float* p = logits + (gi * in_stride + gr + in_off) * ld;
-    const long ti = gi * tok_stride + gr + tok_off;
-    f32x4 zc[NV / 4];
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) zc[c] = sample_row_chunk(p, lane, K, c);
-    if (entropy) {                                      // the whole row at temperature 1: token_logprob_kernel's maximum and sum
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < NV; ++e)
-            if ((e >> 2) * 256 + lane * 4 < K) mx = fmaxf(mx, zc[e >> 2][e & 3]);          // (a NaN is skipped here and caught by the sum)
-        mx = wave_max(mx);
-        float zs = 0.f, ts = 0.f;
-#pragma unroll
-        for (int e = 0; e < NV; ++e) {
-            const float d = zc[e >> 2][e & 3] - mx;
-            const float w = (e >> 2) * 256 + lane * 4 < K ? expf(d) : 0.f;
-            zs = __fadd_rn(zs, w);
-            ts = w == 0.f ? ts : __fmaf_rn(w, d, ts);   // exp(-inf) = 0 adds nothing: not 0 * inf
-        }
-        zs = wave_sum(zs);
-        ts = wave_sum(ts);
-        if (lane == 0) entropy[ti] = logf(zs) - ts / zs;
-    }
-    if (!policy_logprob && !policy_entropy && !kept) return;
-    float s[NV];
-    unsigned key[NV];
-    const unsigned lo = sample_filter<NV, (MODE & STATS_TOPK) != 0, (MODE & STATS_TOPP) != 0>([&](int c) { return zc[c]; }, lane, K, inv_t, top_k,
-                                                                                              top_p, s, key);
-    unsigned km = 0u;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) km = max(km, key[e]);
-    km = wave_max_u32(km);                              // km >= lo unless nothing is selectable (then every key is 0)
-    if constexpr (MODE == STATS_GREEDY) {               // (inv_t = 1 here: s = z) N = the first maximum, NaNs skipped: argmax_kernel's pick
-        int bj = 0x7fffffff;
-#pragma unroll
-        for (int e = NV - 1; e >= 0; --e)
-            if (key[e] == km) bj = (e >> 2) * 256 + lane * 4 + (e & 3);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) bj = min(bj, __shfl_xor(bj, o, 64));
-        if (lane == 0) {
-            const bool any = km != 0u;
-            if (kept) kept[ti] = any ? 1 : 0;
-            if (policy_entropy) policy_entropy[ti] = any ? 0.f : __builtin_nanf("");
-            if (policy_logprob) {
-                long tg = tokens[ti];
-                if (tg < 0 || tg >= K) {
-                    mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
-                    tg = tg < 0 ? 0 : K - 1;
-                }
-                policy_logprob[ti] = !any ? __builtin_nanf("") : tg == bj ? 0.f : -INFINITY;
-            }
-        }
-    } else {
-        int n = 0;
-#pragma unroll
-        for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= lo));
-        float zs = 0.f, ts = 0.f;
-        const float smax = sample_key_value(km);
-        if (policy_logprob || policy_entropy) {
-#pragma unroll
-            for (int e = 0; e < NV; ++e) {
-                const float d = s[e] - smax;
-                const float w = key[e] >= lo ? expf(d) : 0.f;
-                zs = __fadd_rn(zs, w);
-                ts = w == 0.f ? ts : __fmaf_rn(w, d, ts);
-            }
-            zs = wave_sum(zs);
-            if (policy_entropy) ts = wave_sum(ts);
-        }
-        if (lane == 0) {
-            if (kept) kept[ti] = n;
-            const float lz = logf(zs);
-            if (policy_entropy) policy_entropy[ti] = n ? lz - ts / zs : __builtin_nanf("");
-            if (policy_logprob) {
-                long tg = tokens[ti];
-                if (tg < 0 || tg >= K) {
-                    mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);
-                    tg = tg < 0 ? 0 : K - 1;
-                }
-                const float st = __fmul_rn(p[tg], inv_t);
-                policy_logprob[ti] = !n ? __builtin_nanf("") : sample_key(st) >= lo ? st - (smax + lz) : -INFINITY;
-            }
-        }
-    }
-}
-
-// ---- policy-gradient loss over given tokens (mage_policy_loss / mage_policy_loss_bwd, include/mage_hip_ext.h states the rule).  The policy
-// is the sampler's: s, N of steps 1-3 of the sampling rule above by sample_filter itself, logprob and entropy by token_stats_kernel's
-// operations in token_stats_kernel's order, so on the same inputs they carry mage_token_stats' bits.  One wave per row, the row read once
-// into registers in sample_kernel's layout, one instance per filter combination; the forward kernel leaves the filter's threshold in cut[i]
-// and the backward kernel keeps j iff sample_key(s_j) >= cut[i]: no second bisection, and the same set bit for bit.
-
-// w_j = exp(s_j - smax) over the kept set (0 outside it), Z = sum w_j and sum w_j (s_j - smax): token_stats_kernel's sums, term for term
-template <int NV>
-__device__ __forceinline__ void policy_sums(const float (&s)[NV], const unsigned (&key)[NV], unsigned lo, float smax, float (&w)[NV], float& zs,
-                                            float& ts) {
-    zs = 0.f;
-    ts = 0.f;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) {
-        const float d = s[e] - smax;
-        w[e] = key[e] >= lo ? expf(d) : 0.f;
-        zs = __fadd_rn(zs, w[e]);
-        ts = w[e] == 0.f ? ts : __fmaf_rn(w[e], d, ts);
-    }
-    zs = wave_sum(zs);
-    ts = wave_sum(ts);
-}
-
-// One row's loss term and the factor g of its gradient from logprob lp, entropy H, advantage A and (clipped form) the behaviour
-// log-probability b.  rho = expf(lp - b) is the one fp32 value both passes use to decide which branch of the surrogate is active; the
-// products and the final sum are taken in fp64 and rounded once.  An outside row (lp = -inf: a token the filter cannot draw) gives 0, 0.
-struct PolicyTerm { float loss, g; bool outside, off; double sum; };   // sum: the loss before its one rounding (the anchored form adds to it)
-__device__ __forceinline__ PolicyTerm policy_term(float lp, float H, float A, bool clipped, float b, float cmin, float cmax, float ent_coef) {
-    PolicyTerm t{0.f, 0.f, lp == -INFINITY, false, 0.0};
-    if (t.outside) return t;
-    double surr;
-    if (!clipped) {
-        surr = (double)A * (double)lp;
-        t.g = -A;
-    } else {
-        const float rho = expf(lp - b);
-        const bool active = (A >= 0.f && rho <= cmax) || (A < 0.f && rho >= cmin);
-        const double u = (double)rho * (double)A, c = (double)fminf(fmaxf(rho, cmin), cmax) * (double)A;
-        surr = u < c ? u : (c < u ? c : (u != u ? u : c));              // min; a NaN stays a NaN
-        t.g = active ? -(A * rho) : 0.f;
-        t.off = !active;
-    }
-    t.sum = -surr - (double)ent_coef * (double)H;
-    t.loss = (float)t.sum;
-    return t;
-}
-
-// The anchor of mage_policy_loss_anchored: d = r - lp (one fp32 subtraction) against the reference log-probability r, in fp64
-//   kl = exp(d) - d - 1 (the k3 estimator, >= 0)   and   gfac = 1 - exp(d) = d kl / d lp.
-// gfac = -expm1(d) has no cancellation anywhere.  kl = expm1(d) - d for |d| >= 2^-8: the subtraction cancels at most the leading
-// 2 / |d| <= 2^9 of the operands, a relative error below 2^-42; below 2^-8 the series d^2 (1/2 + d (1/6 + d (1/24 + d (1/120 + d / 720))))
-// whose first dropped term d^7 / 5040 is below 2^-51 of the sum.  Both are far inside one fp32 ulp (2^-24), and d = 0 gives 0, 0 exactly.
-// An outside row (lp = -inf) and a row whose r is not finite (an unanchored row) have no anchor: kl = 0, no gradient.
-struct PolicyAnchor { double kl, gfac; bool on; };
-__device__ __forceinline__ PolicyAnchor policy_anchor(float lp, float r) {
-    PolicyAnchor a{0.0, 0.0, false};
-    if (lp == -INFINITY || !__builtin_isfinite(r)) return a;
-    a.on = true;
-    const double d = (double)(r - lp), em = expm1(d);
-    a.gfac = -em;
-    a.kl = fabs(d) < 0x1p-8 ? d * d * (1.0 / 2 + d * (1.0 / 6 + d * (1.0 / 24 + d * (1.0 / 120 + d * (1.0 / 720))))) : em - d;
-    return a;
-}
-
-// policy_term plus kl_coef times the anchor: the loss from the fp64 sum, g from g's fp32 value and the fp64 factor, one rounding each.  A
-// zero term is not added at all (kl_coef = 0, d = 0, no anchor), so such a row carries policy_term's bits -- also its -0 and its NaN.
-__device__ __forceinline__ PolicyTerm policy_term_anchored(PolicyTerm t, const PolicyAnchor& a, float kl_coef) {
-    if (!a.on || kl_coef == 0.f) return t;
-    if (a.kl != 0.0) t.loss = (float)(t.sum + (double)kl_coef * a.kl);
-    if (a.gfac != 0.0) t.g = (float)((double)t.g + (double)kl_coef * a.gfac);
-    return t;
-}
-
-__device__ __forceinline__ long policy_token(const int64_t* __restrict__ tokens, long i, int K, int* err) {
-    long tg = tokens[i];
-    if (tg < 0 || tg >= K) {
-        if (err) mage_raise(err, MAGE_DEVERR_TOKEN_ID, tg, K);          // (the backward pass clamps alike and leaves the report to the forward one)
-        tg = tg < 0 ? 0 : K - 1;
-    }
-    return tg;
-}
-
-// mage_policy_loss_masked's per-row byte, one scalar value per wave (the row index is the wave's); a null mask (the unmasked entry points) has
-// no given row
-__device__ __forceinline__ bool policy_row_given(const uint8_t* __restrict__ given, long i) {
-    return given && __builtin_amdgcn_readfirstlane((int)given[i]) != 0;
-}
-
-template <int NV, bool TOPK, bool TOPP, bool ANCH>
-__global__ __launch_bounds__(256) void policy_loss_kernel(const float* __restrict__ logits, long rows, int K, long ld,
-                                                          const int64_t* __restrict__ tokens, const float* __restrict__ adv, long adv_div,
-                                                          const float* __restrict__ blp, float inv_t, int top_k, float top_p, float cmin,
-                                                          float cmax, float ent_coef, float* __restrict__ row_loss,
-                                                          float* __restrict__ logprob, float* __restrict__ entropy,
-                                                          unsigned* __restrict__ cut, int* __restrict__ err,
-                                                          const float* __restrict__ ref, float kl_coef, float* __restrict__ kl,
-                                                          const uint8_t* __restrict__ given) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    if (policy_row_given(given, i)) {                   // (wave-uniform) mage_policy_loss_masked: nothing of the row is read
-        if (lane == 0) {
-            cut[i] = 0u;
-            logprob[i] = 0.f;
-            entropy[i] = 0.f;
-            row_loss[i] = 0.f;
-            if (kl) kl[i] = 0.f;
-        }
-        return;
-    }
-    const float* p = logits + i * ld;
-    float s[NV], w[NV];
-    unsigned key[NV];
-    const unsigned lo = sample_filter<NV, TOPK, TOPP>([=](int c) { return sample_row_chunk(p, lane, K, c); }, lane, K, inv_t, top_k, top_p, s,
-                                                      key);
-    unsigned km = 0u;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) km = max(km, key[e]);
-    km = wave_max_u32(km);                              // km >= lo unless nothing is selectable (then every key is 0)
-    int n = 0;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) n += __popcll(__ballot(key[e] >= lo));
-    const float smax = sample_key_value(km);
-    float zs, ts;
-    policy_sums<NV>(s, key, lo, smax, w, zs, ts);
-    if (lane == 0) {
-        const float lz = logf(zs);
-        const float H = n ? lz - ts / zs : __builtin_nanf("");
-        const long tg = policy_token(tokens, i, K, err);
-        const float st = __fmul_rn(p[tg], inv_t);
-        const float lp = !n ? __builtin_nanf("") : sample_key(st) >= lo ? st - (smax + lz) : -INFINITY;
-        cut[i] = lo;
-        logprob[i] = lp;
-        entropy[i] = H;
-        const PolicyTerm t = policy_term(lp, H, adv[i / adv_div], blp != nullptr, blp ? blp[i] : 0.f, cmin, cmax, ent_coef);
-        if constexpr (ANCH) {
-            const PolicyAnchor a = policy_anchor(lp, ref[i]);
-            kl[i] = (float)a.kl;
-            row_loss[i] = policy_term_anchored(t, a, kl_coef).loss;
-        } else {
-            row_loss[i] = t.loss;
-        }
-    }
-}
-
-// summary, stage 1 of 2: workgroup b owns rows [b * chunk, (b + 1) * chunk) and leaves W fp64 sums in part[b * W ..]: the loss terms, the
-// entropies, b - logprob, the rows whose gradient the clip switched off, the outside rows (an outside row counts in the last one only) and,
-// for the anchored call (W = 7), the KL estimates and the unanchored rows (a reference log-probability that is not finite).
-// A thread adds its rows in ascending order, the lanes meet in an xor butterfly, thread 0 adds the four waves in order: a fixed order.
-// The masked call (W = 8) adds the free rows only, in the same order, and counts the given ones in an eighth sum; its kl and ref may be null
-// (the plain rule: sums 5 and 6 stay 0).
-enum { POLICY_PARTS = 256, POLICY_MEANS = 7, POLICY_MASKED = 8 };
-__device__ double g_policy_part[POLICY_PARTS * POLICY_MASKED];     // stage 1 -> stage 2, within one mage_policy_loss* call (stream order)
-template <int W>
-__global__ __launch_bounds__(256) void policy_part_kernel(const float* __restrict__ row_loss, const float* __restrict__ logprob,
-                                                          const float* __restrict__ entropy, const float* __restrict__ adv, long adv_div,
-                                                          const float* __restrict__ blp, float cmin, float cmax, long rows, long chunk,
-                                                          const float* __restrict__ kl, const float* __restrict__ ref,
-                                                          const uint8_t* __restrict__ given) {
-    __shared__ double red[4][W];
-    const long r0 = (long)blockIdx.x * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
-    double a[W] = {};
-    for (long i = r0 + threadIdx.x; i < r1; i += 256) {
-        if constexpr (W == POLICY_MASKED) {
-            if (given[i]) {
-                a[7] += 1.0;
-                continue;
-            }
-        }
-        const float lp = logprob[i];
-        if (lp == -INFINITY) {
-            a[4] += 1.0;
-            continue;
-        }
-        a[0] += (double)row_loss[i];
-        a[1] += (double)entropy[i];
-        if (blp) {
-            const float b = blp[i];
-            a[2] += (double)b - (double)lp;
-            a[3] += policy_term(lp, 0.f, adv[i / adv_div], true, b, cmin, cmax, 0.f).off ? 1.0 : 0.0;
-        }
-        if constexpr (W >= POLICY_MEANS) {
-            if (W == POLICY_MEANS || ref) {
-                a[5] += (double)kl[i];
-                a[6] += __builtin_isfinite(ref[i]) ? 0.0 : 1.0;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < W; ++q) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = a[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int q = threadIdx.x;
-        g_policy_part[blockIdx.x * W + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-    }
-}
-
-// stage 2: thread t holds workgroup t's sums; the same butterfly and wave order, one multiply by 1 / rows, one rounding to fp32
-template <int W>
-__global__ __launch_bounds__(256) void policy_summary_kernel(float* __restrict__ summary, double inv) {
-    __shared__ double red[4][W];
-#pragma unroll
-    for (int q = 0; q < W; ++q) {
-        double v = g_policy_part[threadIdx.x * W + q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int q = threadIdx.x;
-        summary[q] = (float)((((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) * inv);
-    }
-}
-
-// stage 2 of the masked call: the same sums; the eighth one is the number of given rows (exact in fp64), so n_free = rows - given.  The seven
-// means are multiplied by 1 / n_free (the unmasked call's 1.0 / rows when nothing is given; 0 when everything is), summary[7] is the given
-// share, and norm[0] = 1.0f / (float)n_free is left for the backward call: the value the unmasked one forms on the host for its `rows`.
-__global__ __launch_bounds__(256) void policy_summary_masked_kernel(float* __restrict__ summary, float* __restrict__ norm, long rows) {
-    constexpr int W = POLICY_MASKED;
-    __shared__ double red[4][W];
-#pragma unroll
-    for (int q = 0; q < W; ++q) {
-        double v = g_policy_part[threadIdx.x * W + q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int q = threadIdx.x;
-        const double ng = ((red[0][7] + red[1][7]) + red[2][7]) + red[3][7];
-        const long n_free = rows - (long)ng;
-        if (q < POLICY_MEANS) {
-            const double inv = n_free > 0 ? 1.0 / (double)n_free : 0.0;
-            summary[q] = (float)((((red[0][q] + red[1][q]) + red[2][q]) + red[3][q]) * inv);
-        } else {
-            summary[7] = (float)(ng / (double)rows);
-            norm[0] = n_free > 0 ? __fdiv_rn(1.0f, (float)n_free) : 0.f;
-        }
-    }
-}
-
-// dlogits_ij = scale * [ g_i (1[j = t] - p_j) + ent_coef p_j (log p_j + H_i) ] for j in N, 0 outside N and in outside rows; scale =
-// grad_out[0] / rows * inv_t, p_j = w_j / Z, log p_j + H_i = (s_j - smax) - (sum_N w (s - smax)) / Z; a p_j = 0 term is 0.  Z, H, logprob are
-// recomputed with the forward kernel's operations (policy_sums), so g_i is decided by the forward pass's rho.
-template <int NV, typename OT, bool ANCH>
-__global__ __launch_bounds__(256) void policy_loss_bwd_kernel(const float* __restrict__ logits, long rows, int K, long ld,
-                                                              const int64_t* __restrict__ tokens, const float* __restrict__ adv, long adv_div,
-                                                              const float* __restrict__ blp, const unsigned* __restrict__ cut, float inv_t,
-                                                              float cmin, float cmax, float ent_coef, const float* __restrict__ gout,
-                                                              float inv_rows, OT* __restrict__ dl, const float* __restrict__ ref,
-                                                              float kl_coef, const uint8_t* __restrict__ given,
-                                                              const float* __restrict__ norm) {
-    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* p = logits + i * ld;
-    OT* o = dl + i * (long)K;
-    if (policy_row_given(given, i)) {                                   // (wave-uniform) a zero row by the free rows' stores, nothing read
-#pragma unroll
-        for (int c = 0; c < NV / 4; ++c) {
-            const int k = c * 256 + lane * 4;
-            if (k < K) store4(o + k, f32x4{0.f, 0.f, 0.f, 0.f});
-        }
-        return;
-    }
-    if (norm) inv_rows = norm[0];                                       // the masked call: 1 / n_free, left by its forward call
-    const unsigned lo = cut[i];
-    float s[NV], w[NV];
-    unsigned key[NV];
-    unsigned km = 0u;
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) {
-        const int k = c * 256 + lane * 4;
-        const f32x4 v = sample_row_chunk(p, lane, K, c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            s[c * 4 + e] = __fmul_rn(v[e], inv_t);                      // sample_filter's s and key
-            key[c * 4 + e] = k < K ? sample_key(s[c * 4 + e]) : 0u;
-            km = max(km, key[c * 4 + e]);
-        }
-    }
-    km = wave_max_u32(km);
-    const float smax = sample_key_value(km);
-    float zs, ts;
-    policy_sums<NV>(s, key, lo, smax, w, zs, ts);
-    const long tg = policy_token(tokens, i, K, nullptr);
-    const float st = __fmul_rn(p[tg], inv_t);
-    const bool out_n = sample_key(st) < lo;                             // t outside N (or no selectable code at all: st is NaN, key 0)
-    const float lz = logf(zs);
-    const float H = lz - ts / zs;
-    const float lp = st - (smax + lz);
-    PolicyTerm t = policy_term(lp, H, adv[i / adv_div], blp != nullptr, blp ? blp[i] : 0.f, cmin, cmax, ent_coef);
-    if constexpr (ANCH) {
-        // (lp is only the forward pass's logprob where the token is in N: any other row is zeroed below whatever g is)
-        if (!out_n) t = policy_term_anchored(t, policy_anchor(lp, ref[i]), kl_coef);
-    }
-    // 1 - p_t = (Z - w_t) / Z from the sum of the OTHER kept terms (same fixed order): no cancellation where the token holds nearly all the mass
-    float zo = 0.f;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) zo = __fadd_rn(zo, (e >> 2) * 256 + lane * 4 + (e & 3) == tg ? 0.f : w[e]);
-    zo = wave_sum(zo);
-    const float scale = gout[0] * inv_rows * inv_t, inv_z = 1.0f / zs;
-    const float hx = ts / zs;                                           // log p_j + H = (s_j - smax) - hx: log Z drops out
-    const bool zero = out_n || t.outside;                               // an outside row (t.outside: a kept token of logit -inf)
-#pragma unroll
-    for (int c = 0; c < NV / 4; ++c) {
-        const int k = c * 256 + lane * 4;
-        if (k >= K) break;
-        f32x4 d;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int j = c * 4 + e;
-            const float pj = w[j] * inv_z;
-            float v = t.g * (k + e == tg ? zo * inv_z : -pj);
-            if (ent_coef != 0.f && pj != 0.f) v += ent_coef * pj * ((s[j] - smax) - hx);
-            d[e] = (zero || key[j] < lo) ? 0.f : v * scale;
-        }
-        store4(o + k, d);
-    }
-}
-
-// One workgroup per clip: wave w sums candidates w, w + 4, ... (a lane adds values lane, lane + 64, ... in fp64, the lanes meet in an xor
-// butterfly, one rounding to fp32), then thread 0 picks the largest score: first on ties, a NaN only if every score is NaN.
-__global__ __launch_bounds__(256) void clip_scores_kernel(const float* __restrict__ logprob, int n_cand, long per_clip,
-                                                          float* __restrict__ scores, int64_t* __restrict__ best) {
-    const long clip = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int c = wave; c < n_cand; c += 4) {
-        const float* v = logprob + (clip * n_cand + c) * per_clip;
-        double s = 0.0;
-        for (long j = lane; j < per_clip; j += 64) s += (double)v[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) scores[clip * n_cand + c] = (float)s;
-    }
-    if (!best) return;
-    __syncthreads();                                    // (workgroup-uniform: `best` is a kernel argument)
-    if (threadIdx.x == 0) {
-        int bi = 0;
-        float bs = scores[clip * n_cand];
-        for (int c = 1; c < n_cand; ++c) {
-            const float sc = scores[clip * n_cand + c];
-            if (sc > bs || (bs != bs && sc == sc)) { bs = sc; bi = c; }
-        }
-        best[clip] = bi;
     }
 }
 
@@ -1238,66 +477,11 @@ extern "C" int mage_embedding(const int64_t* ids, const float* table, void* out,
     return MAGE_OK;
 }
 
-extern "C" int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
-                           int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, float* margin,
-                           void* stream) {
-    MAGE_CHECK_ARG(logits && out, "mage_argmax: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && ld % 4 == 0 && group > 0, "mage_argmax: bad sizes rows=%ld K=%d", (long)rows, K);
-    hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)rows,
-                       K, (long)ld, (long)group, (long)in_group_stride, (long)in_off, out, (long)out_group_stride,
-                       (long)out_off, margin);
-    MAGE_CHECK_LAUNCH("mage_argmax");
-    return MAGE_OK;
-}
-
-template <int NV>
-static void sample_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, long group,
-                          long in_stride, long in_off, int64_t* out, long out_stride, long out_off, const int64_t* seeds, long pos_off,
-                          float inv_t, int top_k, float top_p) {
-#define MAGE_SAMPLE(TK, TP)                                                                                                          \
-    hipLaunchKernelGGL((sample_kernel<NV, TK, TP>), grid, dim3(256), 0, s, logits, rows, K, ld, group, in_stride, in_off, out,   \
-                       out_stride, out_off, seeds, pos_off, inv_t, top_k, top_p)
-    if (topk && topp) MAGE_SAMPLE(true, true);
-    else if (topk) MAGE_SAMPLE(true, false);
-    else if (topp) MAGE_SAMPLE(false, true);
-    else MAGE_SAMPLE(false, false);
-#undef MAGE_SAMPLE
-}
-
-extern "C" int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
-                                  int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, const int64_t* seeds,
-                                  int64_t pos_off, float temperature, int32_t top_k, float top_p, void* stream) {
-    MAGE_CHECK_ARG(logits && out && seeds, "mage_sample_tokens: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && pos_off >= 0 &&
-                   (((uintptr_t)logits) & 15) == 0,
-                   "mage_sample_tokens: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K,
-                   (long)ld, MAGE_SAMPLE_MAX_K);
-    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "mage_sample_tokens: top_k=%d outside [0, K=%d]", top_k, K);
-    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mage_sample_tokens: top_p=%g outside (0, 1]", (double)top_p);
-    const float inv_t = (float)(1.0 / (double)temperature);
-    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
-                   "mage_sample_tokens: temperature=%g must be finite and > 0", (double)temperature);
-    if (top_k == 1)                                     // greedy by definition: first maximum of the logits
-        return mage_argmax(logits, rows, K, ld, group, in_group_stride, in_off, out, out_group_stride, out_off, nullptr, stream);
-    const bool topk = top_k > 0 && top_k < K, topp = top_p < 1.f;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-    const long a[] = {(long)rows, (long)ld, (long)group, (long)in_group_stride, (long)in_off, (long)out_group_stride, (long)out_off,
-                      (long)pos_off};
-    if (K <= 256) sample_launch<4>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
-    else if (K <= 512) sample_launch<8>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
-    else if (K <= 1024) sample_launch<16>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
-    else if (K <= 2048) sample_launch<32>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
-    else sample_launch<64>(topk, topp, grid, s, logits, a[0], K, a[1], a[2], a[3], a[4], out, a[5], a[6], seeds, a[7], inv_t, top_k, top_p);
-    MAGE_CHECK_LAUNCH("mage_sample_tokens");
-    return MAGE_OK;
-}
-
 // ---- seeded standard-normal noise of the randomness branch (mage_video_noise; include/mage_hip_ext.h states the rule).  Element
 // e = channel * hw + pixel of a clip with seed s takes the two counters base + 2e and base + 2e + 1, base = (s ^ 2^63) * 0x9e3779b97f4a7c15
 // (uint64 wrap-around): the sampler's counters of the same seed start at s * 0x9e3779b97f4a7c15, exactly 2^63 away (the constant is odd), so
 // the two streams of one seed cannot meet while either is shorter than 2^63.  Box-Muller, one normal per element: the radius from the 24-bit
-// uniform of the first counter through sample_neglog_u (never rounded), the angle from the 23-bit one of the second through cospif of the
+// uniform of the first counter through sample_neglog_u (common.h: never rounded), the angle from the 23-bit one of the second through cospif of the
 // exactly representable (m2 + 0.5) 2^-22.
 // One lane owns a tile of 4 channels x 4 pixels and computes its 16 values ONCE: four 16-byte stores along the pixels into the NCHW tensor
 // and / or four along the channels into the channel-last rows, so the two layouts hold the same bits by construction.  Lanes run along the
@@ -1376,410 +560,4 @@ extern "C" int mage_video_noise(const int64_t* seeds, int64_t B, int32_t C, int6
     video_noise_kernel<<<dim3((unsigned)((tiles + 255) / 256)), 256, 0, (hipStream_t)stream>>>(seeds, tiles, C, (int)hw, CQ, PQ, nchw, rows);
     MAGE_CHECK_LAUNCH("mage_video_noise");
     return MAGE_OK;
-}
-
-extern "C" int mage_token_logprob(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
-                                  int64_t in_off, const int64_t* tokens, float* logprob, int64_t tok_group_stride, int64_t tok_off,
-                                  void* stream) {
-    MAGE_CHECK_ARG(logits && tokens && logprob, "mage_token_logprob: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
-                   in_off >= 0 && tok_group_stride >= 0 && tok_off >= 0 && (((uintptr_t)logits) & 15) == 0,
-                   "mage_token_logprob: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K, (long)ld,
-                   MAGE_SAMPLE_MAX_K);
-    int* err = mage_error_word();
-    MAGE_CHECK_ARG(err != nullptr, "mage_token_logprob: mage_init() has not been called");
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-#define MAGE_LOGPROB(NV)                                                                                                             \
-    hipLaunchKernelGGL((token_logprob_kernel<NV>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, (long)group,              \
-                       (long)in_group_stride, (long)in_off, tokens, logprob, (long)tok_group_stride, (long)tok_off, err)
-    if (K <= 256) MAGE_LOGPROB(4);
-    else if (K <= 512) MAGE_LOGPROB(8);
-    else if (K <= 1024) MAGE_LOGPROB(16);
-    else if (K <= 2048) MAGE_LOGPROB(32);
-    else MAGE_LOGPROB(64);
-#undef MAGE_LOGPROB
-    MAGE_CHECK_LAUNCH("mage_token_logprob");
-    return MAGE_OK;
-}
-
-template <int NV>
-static void stats_launch(int mode, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, long group, long in_stride, long in_off,
-                         const int64_t* tokens, long tok_stride, long tok_off, float inv_t, int top_k, float top_p, float* policy_logprob,
-                         float* policy_entropy, int32_t* kept, float* entropy, int* err) {
-#define MAGE_STATS(M)                                                                                                                 \
-    hipLaunchKernelGGL((token_stats_kernel<NV, M>), grid, dim3(256), 0, s, logits, rows, K, ld, group, in_stride, in_off, tokens, tok_stride, \
-                       tok_off, inv_t, top_k, top_p, policy_logprob, policy_entropy, kept, entropy, err)
-    if (mode == STATS_GREEDY) MAGE_STATS(STATS_GREEDY);
-    else if (mode == (STATS_TOPK | STATS_TOPP)) MAGE_STATS(STATS_TOPK | STATS_TOPP);
-    else if (mode == STATS_TOPK) MAGE_STATS(STATS_TOPK);
-    else if (mode == STATS_TOPP) MAGE_STATS(STATS_TOPP);
-    else MAGE_STATS(0);
-#undef MAGE_STATS
-}
-
-extern "C" int mage_token_stats(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride, int64_t in_off,
-                                const int64_t* tokens, int64_t tok_group_stride, int64_t tok_off, float temperature, int32_t top_k, float top_p,
-                                float* policy_logprob, float* policy_entropy, int32_t* kept, float* entropy, void* stream) {
-    MAGE_CHECK_ARG(logits && (policy_logprob || policy_entropy || kept || entropy), "mage_token_stats: null logits, or no output asked for");
-    MAGE_CHECK_ARG(tokens || !policy_logprob, "mage_token_stats: policy_logprob needs tokens");
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
-                   in_off >= 0 && tok_group_stride >= 0 && tok_off >= 0 && (((uintptr_t)logits) & 15) == 0,
-                   "mage_token_stats: bad sizes rows=%ld K=%d ld=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", (long)rows, K, (long)ld,
-                   MAGE_SAMPLE_MAX_K);
-    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "mage_token_stats: top_k=%d outside [0, K=%d]", top_k, K);
-    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mage_token_stats: top_p=%g outside (0, 1]", (double)top_p);
-    const float inv_t = (float)(1.0 / (double)temperature);
-    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
-                   "mage_token_stats: temperature=%g must be finite and > 0", (double)temperature);
-    int* err = mage_error_word();
-    MAGE_CHECK_ARG(err != nullptr, "mage_token_stats: mage_init() has not been called");
-    const int mode = top_k == 1 ? STATS_GREEDY : (top_k > 0 && top_k < K ? STATS_TOPK : 0) | (top_p < 1.f ? STATS_TOPP : 0);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-#define MAGE_STATS_NV(NV)                                                                                                              \
-    stats_launch<NV>(mode, grid, s, logits, (long)rows, K, (long)ld, (long)group, (long)in_group_stride, (long)in_off, tokens,         \
-                     (long)tok_group_stride, (long)tok_off, mode == STATS_GREEDY ? 1.f : inv_t, top_k, top_p, policy_logprob, policy_entropy, kept, entropy, err)
-    if (K <= 256) MAGE_STATS_NV(4);
-    else if (K <= 512) MAGE_STATS_NV(8);
-    else if (K <= 1024) MAGE_STATS_NV(16);
-    else if (K <= 2048) MAGE_STATS_NV(32);
-    else MAGE_STATS_NV(64);
-#undef MAGE_STATS_NV
-    MAGE_CHECK_LAUNCH("mage_token_stats");
-    return MAGE_OK;
-}
-
-// ---- classifier-free guidance of the logits (mage_guide_logits; include/mage_hip_ext.h states the rule): z = c + (s - 1)(c - u) per element,
-// one explicit fma behind two selects that make scale 1 and u == c return c's bits.  Pure streaming, 12 bytes per element: no reduction, no
-// LDS, no atomics.  A workgroup owns RB whole rows (RB * K/4 quads, about 1024: four per lane); consecutive lanes take consecutive quads, so a
-// wave-instruction moves 1 KiB of one row (or of adjacent rows), and a lane issues all of its up to eight 16-byte loads before the first
-// store: ~32 KiB in flight per workgroup.  A lane reads the quads it writes and no other, before it writes them: out may be cond itself.
-namespace {
-
-constexpr int GUIDE_QUADS = 4;                                              // quads per lane
-
-__global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, const float* uncond, float* out, long rows, int KQ, long ld, long group,
-                                                           long in_stride, long in_off, const float* __restrict__ scale, long scale_div, int RB) {
-    const long row0 = (long)blockIdx.x * RB;
-    const long left = rows - row0;
-    const int n = (int)(left < RB ? left : RB) * KQ;                        // this workgroup's quads
-    long at[GUIDE_QUADS];
-    float w[GUIDE_QUADS];
-    f32x4 c[GUIDE_QUADS], u[GUIDE_QUADS];
-#pragma unroll
-    for (int j = 0; j < GUIDE_QUADS; ++j) {
-        const int idx = (int)threadIdx.x + j * 256;
-        if (idx < n) {
-            const int r = idx / KQ;
-            const long row = row0 + r;
-            at[j] = ((row / group) * in_stride + row % group + in_off) * ld + 4 * (idx - r * KQ);
-            w[j] = __fsub_rn(scale[row / scale_div], 1.0f);
-            c[j] = load4(cond + at[j]);
-            u[j] = load4(uncond + at[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < GUIDE_QUADS; ++j) {
-        if ((int)threadIdx.x + j * 256 < n) {
-            f32x4 z;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = __fsub_rn(c[j][e], u[j][e]);
-                z[e] = (w[j] == 0.f || d == 0.f) ? c[j][e] : __fmaf_rn(w[j], d, c[j][e]);
-            }
-            store4(out + at[j], z);
-        }
-    }
-}
-
-}  // namespace
-
-extern "C" int mage_guide_logits(const float* cond, const float* uncond, float* out, int64_t rows, int32_t K, int64_t ld, int64_t group,
-                                 int64_t in_group_stride, int64_t in_off, const float* scale, int64_t scale_div, void* stream) {
-    MAGE_CHECK_ARG(cond && uncond && out && scale, "mage_guide_logits: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && group > 0 && in_group_stride >= 0 &&
-                   in_off >= 0 && scale_div > 0,
-                   "mage_guide_logits: bad sizes rows=%ld K=%d ld=%ld group=%ld scale_div=%ld (K %% 4 == 0, K <= %d, ld %% 4 == 0, ld >= K)",
-                   (long)rows, K, (long)ld, (long)group, (long)scale_div, MAGE_SAMPLE_MAX_K);
-    MAGE_CHECK_ARG(((((uintptr_t)cond) | ((uintptr_t)uncond) | ((uintptr_t)out)) & 15) == 0 && (((uintptr_t)scale) & 3) == 0,
-                   "mage_guide_logits: cond, uncond and out must be 16-byte aligned, scale 4-byte aligned");
-    const int KQ = K / 4;
-    const int RB = KQ >= 256 * GUIDE_QUADS ? 1 : 256 * GUIDE_QUADS / KQ;    // whole rows per workgroup, RB * KQ <= 1024 quads
-    const int64_t blocks = (rows + RB - 1) / RB;
-    MAGE_CHECK_ARG(blocks <= 0x7fffffffLL, "mage_guide_logits: rows=%ld is more than one launch covers", (long)rows);
-    guide_logits_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(cond, uncond, out, (long)rows, KQ, (long)ld, (long)group,
-                                                                                (long)in_group_stride, (long)in_off, scale, (long)scale_div, RB);
-    MAGE_CHECK_LAUNCH("mage_guide_logits");
-    return MAGE_OK;
-}
-
-// ---- given tokens over picked ones (mage_apply_known_tokens; include/mage_hip_ext.h states the rule).  One thread per row: it reads its
-// `known` value and, where that is >= 0, stores it and the certain policy's results (log-probabilities 0, entropies 0, kept 1) at the row's
-// token index.  A free row stores nothing.  8 bytes read and at most 28 written per row: launch-bound at a frame's size.  No LDS, no atomics.
-namespace {
-
-__global__ __launch_bounds__(256) void apply_known_kernel(int64_t* __restrict__ tokens, long rows, long group, long tok_stride, long tok_off,
-                                                          const int64_t* __restrict__ known, long known_stride, long known_off, long known_div,
-                                                          int K, float* __restrict__ logprob, float* __restrict__ policy_logprob,
-                                                          float* __restrict__ entropy, float* __restrict__ policy_entropy,
-                                                          int32_t* __restrict__ kept, int* __restrict__ err) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    const long c = i / group, j = i - c * group;
-    long k = known[(c / known_div) * known_stride + j + known_off];
-    if (k < 0) return;
-    if (k >= K) {                                       // reported by mage_check_device_errors, as mage_token_logprob's bad token is
-        mage_raise(err, MAGE_DEVERR_TOKEN_ID, k, K);
-        k = K - 1;
-    }
-    const long t = c * tok_stride + j + tok_off;
-    tokens[t] = k;
-    if (logprob) logprob[t] = 0.f;
-    if (policy_logprob) policy_logprob[t] = 0.f;
-    if (entropy) entropy[t] = 0.f;
-    if (policy_entropy) policy_entropy[t] = 0.f;
-    if (kept) kept[t] = 1;
-}
-
-}  // namespace
-
-extern "C" int mage_apply_known_tokens(int64_t* tokens, int64_t rows, int64_t group, int64_t tok_group_stride, int64_t tok_off,
-                                       const int64_t* known, int64_t known_group_stride, int64_t known_off, int64_t known_clip_div, int32_t K,
-                                       float* logprob, float* policy_logprob, float* entropy, float* policy_entropy, int32_t* kept,
-                                       void* stream) {
-    MAGE_CHECK_ARG(tokens && known, "mage_apply_known_tokens: null pointer");
-    MAGE_CHECK_ARG(rows >= 0 && group > 0 && known_clip_div > 0 && tok_group_stride >= 0 && tok_off >= 0 && known_group_stride >= 0 &&
-                   known_off >= 0 && K > 0,
-                   "mage_apply_known_tokens: bad sizes rows=%ld group=%ld known_clip_div=%ld K=%d (strides and offsets >= 0)", (long)rows,
-                   (long)group, (long)known_clip_div, K);
-    if (rows == 0) return MAGE_OK;
-    const int64_t blocks = (rows + 255) / 256;
-    MAGE_CHECK_ARG(blocks <= 0x7fffffffLL, "mage_apply_known_tokens: rows=%ld is more than one launch covers", (long)rows);
-    int* err = mage_error_word();
-    MAGE_CHECK_ARG(err != nullptr, "mage_apply_known_tokens: mage_init() has not been called");
-    apply_known_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(tokens, (long)rows, (long)group, (long)tok_group_stride,
-                                                                               (long)tok_off, known, (long)known_group_stride, (long)known_off,
-                                                                               (long)known_clip_div, K, logprob, policy_logprob, entropy,
-                                                                               policy_entropy, kept, err);
-    MAGE_CHECK_LAUNCH("mage_apply_known_tokens");
-    return MAGE_OK;
-}
-
-extern "C" int mage_clip_scores(const float* logprob, int64_t n_clips, int32_t n_cand, int64_t per_clip, float* scores, int64_t* best,
-                                void* stream) {
-    MAGE_CHECK_ARG(logprob && scores, "mage_clip_scores: null pointer");
-    MAGE_CHECK_ARG(n_clips > 0 && n_clips <= 0x7fffffffL && n_cand > 0 && per_clip > 0, "mage_clip_scores: bad sizes n_clips=%ld n_cand=%d per_clip=%ld",
-                   (long)n_clips, n_cand, (long)per_clip);
-    MAGE_CHECK_ARG(n_cand == 1 || best, "mage_clip_scores: n_cand=%d > 1 needs `best`", n_cand);
-    hipLaunchKernelGGL(clip_scores_kernel, dim3((unsigned)n_clips), dim3(256), 0, (hipStream_t)stream, logprob, n_cand, (long)per_clip, scores,
-                       n_cand > 1 ? best : nullptr);
-    MAGE_CHECK_LAUNCH("mage_clip_scores");
-    return MAGE_OK;
-}
-
-extern "C" int mage_cross_entropy(const float* logits, const int64_t* target, int64_t rows, int32_t K, float* row_loss,
-                                  float* loss_mean, void* stream) {
-    MAGE_CHECK_ARG(logits && target && row_loss && loss_mean, "mage_cross_entropy: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && K > 0, "mage_cross_entropy: bad sizes");
-    hipStream_t s = (hipStream_t)stream;
-    int* err = mage_error_word();
-    MAGE_CHECK_ARG(err != nullptr, "mage_cross_entropy: mage_init() has not been called");
-    hipLaunchKernelGGL(ce_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, target, (long)rows, K, row_loss, err);
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, s, row_loss, (long)rows, loss_mean, 1.0 / (double)rows);
-    MAGE_CHECK_LAUNCH("mage_cross_entropy");
-    return MAGE_OK;
-}
-
-// the argument rules mage_policy_loss and mage_policy_loss_bwd share (mage_token_stats' sizes and temperature, the clip and the entropy weight)
-static int policy_check(const char* who, const void* logits, int64_t rows, int32_t K, int64_t ld, int64_t adv_div, float temperature,
-                        float inv_t, float clip_lo, float clip_hi, float entropy_coef) {
-    MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && K <= MAGE_SAMPLE_MAX_K && ld % 4 == 0 && ld >= K && adv_div > 0 &&
-                   (((uintptr_t)logits) & 15) == 0,
-                   "%s: bad sizes rows=%ld K=%d ld=%ld adv_div=%ld (K %% 4 == 0, K <= %d, 16-byte aligned rows)", who, (long)rows, K, (long)ld,
-                   (long)adv_div, MAGE_SAMPLE_MAX_K);
-    MAGE_CHECK_ARG(__builtin_isfinite(temperature) && temperature > 0.f && __builtin_isfinite(inv_t),
-                   "%s: temperature=%g must be finite and > 0", who, (double)temperature);
-    MAGE_CHECK_ARG(clip_lo >= 0.f && clip_lo <= 1.f && clip_hi >= 0.f, "%s: clip_lo=%g outside [0, 1] or clip_hi=%g < 0", who, (double)clip_lo,
-                   (double)clip_hi);
-    MAGE_CHECK_ARG(__builtin_isfinite(entropy_coef), "%s: entropy_coef=%g must be finite", who, (double)entropy_coef);
-    return MAGE_OK;
-}
-
-// what the anchored pair asks in addition: a reference log-probability per row and a weight that is a number
-static int policy_anchor_check(const char* who, const float* reference_logprob, float kl_coef) {
-    MAGE_CHECK_ARG(reference_logprob && (((uintptr_t)reference_logprob) & 3) == 0, "%s: reference_logprob must be a 4-byte aligned pointer", who);
-    MAGE_CHECK_ARG(__builtin_isfinite(kl_coef) && kl_coef >= 0.f, "%s: kl_coef=%g must be finite and >= 0", who, (double)kl_coef);
-    return MAGE_OK;
-}
-
-template <int NV, bool ANCH>
-static void policy_launch(bool topk, bool topp, dim3 grid, hipStream_t s, const float* logits, long rows, int K, long ld, const int64_t* tokens,
-                          const float* adv, long adv_div, const float* blp, float inv_t, int top_k, float top_p, float cmin, float cmax,
-                          float ent_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, int* err, const float* ref,
-                          float kl_coef, float* kl, const uint8_t* given) {
-#define MAGE_POLICY(TK, TP)                                                                                                                  \
-    hipLaunchKernelGGL((policy_loss_kernel<NV, TK, TP, ANCH>), grid, dim3(256), 0, s, logits, rows, K, ld, tokens, adv, adv_div, blp, inv_t, \
-                       top_k, top_p, cmin, cmax, ent_coef, row_loss, logprob, entropy, cut, err, ref, kl_coef, kl, given)
-    if (topk && topp) MAGE_POLICY(true, true);
-    else if (topk) MAGE_POLICY(true, false);
-    else if (topp) MAGE_POLICY(false, true);
-    else MAGE_POLICY(false, false);
-#undef MAGE_POLICY
-}
-
-// mage_policy_loss (ANCH false: reference_logprob, kl_coef and kl unused) and mage_policy_loss_anchored behind their own argument rules;
-// given non-null: mage_policy_loss_masked in either form (the masked reduction, norm written)
-template <bool ANCH>
-static int policy_forward(const char* who, const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
-                          int64_t adv_div, const float* behaviour_logprob, float temperature, int32_t top_k, float top_p, float clip_lo,
-                          float clip_hi, float entropy_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* summary,
-                          const float* reference_logprob, float kl_coef, float* kl, void* stream, const uint8_t* given = nullptr,
-                          float* norm = nullptr) {
-    MAGE_CHECK_ARG(logits && tokens && advantage && row_loss && logprob && entropy && cut && summary, "%s: null pointer", who);
-    const float inv_t = (float)(1.0 / (double)temperature);
-    if (int rc = policy_check(who, logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
-    MAGE_CHECK_ARG(top_k >= 0 && top_k <= K, "%s: top_k=%d outside [0, K=%d]", who, top_k, K);
-    MAGE_CHECK_ARG(top_k != 1, "%s: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient", who);
-    MAGE_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g outside (0, 1]", who, (double)top_p);
-    if (ANCH)
-        if (int rc = policy_anchor_check(who, reference_logprob, kl_coef)) return rc;
-    MAGE_CHECK_ARG(!ANCH || (kl && (((uintptr_t)kl) & 3) == 0), "%s: kl must be a 4-byte aligned pointer", who);
-    int* err = mage_error_word();
-    MAGE_CHECK_ARG(err != nullptr, "%s: mage_init() has not been called", who);
-    const bool topk = top_k > 0 && top_k < K, topp = top_p < 1.f;
-    const float cmin = (float)(1.0 - (double)clip_lo), cmax = (float)(1.0 + (double)clip_hi);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-#define MAGE_POLICY_NV(NV)                                                                                                                   \
-    policy_launch<NV, ANCH>(topk, topp, grid, s, logits, (long)rows, K, (long)ld, tokens, advantage, (long)adv_div, behaviour_logprob, inv_t, \
-                            top_k, top_p, cmin, cmax, entropy_coef, row_loss, logprob, entropy, cut, err, reference_logprob, kl_coef, kl, \
-                            given)
-    if (K <= 256) MAGE_POLICY_NV(4);
-    else if (K <= 512) MAGE_POLICY_NV(8);
-    else if (K <= 1024) MAGE_POLICY_NV(16);
-    else if (K <= 2048) MAGE_POLICY_NV(32);
-    else MAGE_POLICY_NV(64);
-#undef MAGE_POLICY_NV
-    constexpr int W = ANCH ? POLICY_MEANS : 5;
-    const long chunk = (long)((rows + POLICY_PARTS - 1) / POLICY_PARTS);
-    if (given) {
-        hipLaunchKernelGGL(policy_part_kernel<POLICY_MASKED>, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage,
-                           (long)adv_div, behaviour_logprob, cmin, cmax, (long)rows, chunk, kl, reference_logprob, given);
-        hipLaunchKernelGGL(policy_summary_masked_kernel, dim3(1), dim3(POLICY_PARTS), 0, s, summary, norm, (long)rows);
-    } else {
-        hipLaunchKernelGGL(policy_part_kernel<W>, dim3(POLICY_PARTS), dim3(256), 0, s, row_loss, logprob, entropy, advantage, (long)adv_div,
-                           behaviour_logprob, cmin, cmax, (long)rows, chunk, kl, reference_logprob, given);
-        hipLaunchKernelGGL(policy_summary_kernel<W>, dim3(1), dim3(POLICY_PARTS), 0, s, summary, 1.0 / (double)rows);
-    }
-    MAGE_CHECK_LAUNCH(who);
-    return MAGE_OK;
-}
-
-template <bool ANCH>
-static int policy_backward(const char* who, const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
-                           const float* advantage, int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature,
-                           float clip_lo, float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype,
-                           const float* reference_logprob, float kl_coef, void* stream, const uint8_t* given = nullptr,
-                           const float* norm = nullptr) {
-    MAGE_CHECK_ARG(logits && tokens && advantage && cut && grad_out && dlogits, "%s: null pointer", who);
-    const float inv_t = (float)(1.0 / (double)temperature);
-    if (int rc = policy_check(who, logits, rows, K, ld, adv_div, temperature, inv_t, clip_lo, clip_hi, entropy_coef)) return rc;
-    MAGE_CHECK_ARG((dl_dtype == MAGE_F32 || dl_dtype == MAGE_BF16) && (((uintptr_t)dlogits) & 15) == 0,
-                   "%s: dlogits must be 16-byte aligned fp32 or bf16 (dtype %d)", who, dl_dtype);
-    if (ANCH)
-        if (int rc = policy_anchor_check(who, reference_logprob, kl_coef)) return rc;
-    const float cmin = (float)(1.0 - (double)clip_lo), cmax = (float)(1.0 + (double)clip_hi);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-#define MAGE_POLICY_BWD(NV, OT)                                                                                                            \
-    hipLaunchKernelGGL((policy_loss_bwd_kernel<NV, OT, ANCH>), grid, dim3(256), 0, s, logits, (long)rows, K, (long)ld, tokens, advantage, \
-                       (long)adv_div, behaviour_logprob, cut, inv_t, cmin, cmax, entropy_coef, grad_out, 1.0f / (float)rows, (OT*)dlogits, \
-                       reference_logprob, kl_coef, given, norm)
-#define MAGE_POLICY_BWD_NV(NV)                                  \
-    do {                                                        \
-        if (dl_dtype == MAGE_F32) MAGE_POLICY_BWD(NV, float);   \
-        else MAGE_POLICY_BWD(NV, unsigned short);               \
-    } while (0)
-    if (K <= 256) MAGE_POLICY_BWD_NV(4);
-    else if (K <= 512) MAGE_POLICY_BWD_NV(8);
-    else if (K <= 1024) MAGE_POLICY_BWD_NV(16);
-    else if (K <= 2048) MAGE_POLICY_BWD_NV(32);
-    else MAGE_POLICY_BWD_NV(64);
-#undef MAGE_POLICY_BWD_NV
-#undef MAGE_POLICY_BWD
-    MAGE_CHECK_LAUNCH(who);
-    return MAGE_OK;
-}
-
-extern "C" int mage_policy_loss(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
-                                int64_t adv_div, const float* behaviour_logprob, float temperature, int32_t top_k, float top_p, float clip_lo,
-                                float clip_hi, float entropy_coef, float* row_loss, float* logprob, float* entropy, uint32_t* cut,
-                                float* summary, void* stream) {
-    return policy_forward<false>("mage_policy_loss", logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k, top_p,
-                                 clip_lo, clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, nullptr, 0.f, nullptr, stream);
-}
-
-extern "C" int mage_policy_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
-                                    int64_t adv_div, const float* behaviour_logprob, const uint32_t* cut, float temperature, float clip_lo,
-                                    float clip_hi, float entropy_coef, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream) {
-    return policy_backward<false>("mage_policy_loss_bwd", logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut, temperature,
-                                  clip_lo, clip_hi, entropy_coef, grad_out, dlogits, dl_dtype, nullptr, 0.f, stream);
-}
-
-extern "C" int mage_policy_loss_anchored(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
-                                         int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature,
-                                         int32_t top_k, float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef,
-                                         float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* kl, float* summary,
-                                         void* stream) {
-    return policy_forward<true>("mage_policy_loss_anchored", logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k,
-                                top_p, clip_lo, clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, reference_logprob, kl_coef, kl,
-                                stream);
-}
-
-extern "C" int mage_policy_loss_anchored_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
-                                             const float* advantage, int64_t adv_div, const float* behaviour_logprob,
-                                             const float* reference_logprob, const uint32_t* cut, float temperature, float clip_lo,
-                                             float clip_hi, float entropy_coef, float kl_coef, const float* grad_out, void* dlogits,
-                                             int32_t dl_dtype, void* stream) {
-    return policy_backward<true>("mage_policy_loss_anchored_bwd", logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut,
-                                 temperature, clip_lo, clip_hi, entropy_coef, grad_out, dlogits, dl_dtype, reference_logprob, kl_coef, stream);
-}
-
-// the mask and the normaliser of the masked pair, and its one rule about the anchor: reference_logprob and kl come together or not at all
-static int policy_masked_check(const char* who, const uint8_t* given, const float* norm, bool has_ref, bool has_kl, float kl_coef) {
-    MAGE_CHECK_ARG(given != nullptr, "%s: given must not be null (the unmasked entry points take no mask)", who);
-    MAGE_CHECK_ARG(norm && (((uintptr_t)norm) & 3) == 0, "%s: norm must be a 4-byte aligned pointer", who);
-    MAGE_CHECK_ARG(has_ref == has_kl, "%s: reference_logprob and kl are given together (the anchored rule) or both null (the plain rule)", who);
-    MAGE_CHECK_ARG(has_ref || kl_coef == 0.f, "%s: kl_coef=%g needs reference_logprob", who, (double)kl_coef);
-    return MAGE_OK;
-}
-
-extern "C" int mage_policy_loss_masked(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
-                                       int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature,
-                                       int32_t top_k, float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef,
-                                       float* row_loss, float* logprob, float* entropy, uint32_t* cut, float* kl, float* summary, float* norm,
-                                       const uint8_t* given, void* stream) {
-    const char* who = "mage_policy_loss_masked";
-    if (int rc = policy_masked_check(who, given, norm, reference_logprob != nullptr, kl != nullptr, kl_coef)) return rc;
-    if (reference_logprob)
-        return policy_forward<true>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k, top_p, clip_lo,
-                                    clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, reference_logprob, kl_coef, kl, stream, given,
-                                    norm);
-    return policy_forward<false>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, temperature, top_k, top_p, clip_lo,
-                                 clip_hi, entropy_coef, row_loss, logprob, entropy, cut, summary, nullptr, 0.f, nullptr, stream, given, norm);
-}
-
-extern "C" int mage_policy_loss_masked_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens,
-                                           const float* advantage, int64_t adv_div, const float* behaviour_logprob,
-                                           const float* reference_logprob, const uint32_t* cut, float temperature, float clip_lo, float clip_hi,
-                                           float entropy_coef, float kl_coef, const float* grad_out, const float* norm, void* dlogits,
-                                           int32_t dl_dtype, const uint8_t* given, void* stream) {
-    const char* who = "mage_policy_loss_masked_bwd";
-    if (int rc = policy_masked_check(who, given, norm, reference_logprob != nullptr, reference_logprob != nullptr, kl_coef)) return rc;
-    if (reference_logprob)
-        return policy_backward<true>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut, temperature, clip_lo, clip_hi,
-                                     entropy_coef, grad_out, dlogits, dl_dtype, reference_logprob, kl_coef, stream, given, norm);
-    return policy_backward<false>(who, logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob, cut, temperature, clip_lo, clip_hi,
-                                  entropy_coef, grad_out, dlogits, dl_dtype, nullptr, 0.f, stream, given, norm);
 }

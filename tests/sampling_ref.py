@@ -1,4 +1,4 @@
-"""NumPy / fp64 restatement of the token-sampling rule of mage_sample_tokens (mage_amd/csrc/vq.hip states it; include/mage_hip.h).
+"""NumPy / fp64 restatement of the token-sampling rule of mage_sample_tokens (mage_amd/csrc/token_row.h states it; include/mage_hip.h).
 
 For one row: s = fp32(z * inv_t), inv_t = fp32(1 / temperature); top-k keeps every code whose s is >= the top_k-th largest (ties kept);
 top-p keeps, of those, every code whose s is >= tau, the largest value whose softmax mass from above reaches top_p * W (ties kept); the

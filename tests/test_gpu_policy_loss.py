@@ -58,7 +58,7 @@ def _logits(rows, K, seed):
 
 
 def _keys(s):
-    """The sampler's order-preserving key of fp32 values (sample_key, mage_amd/csrc/vq.hip): NaN -> 0, -0 == +0."""
+    """The sampler's order-preserving key of fp32 values (sample_key, mage_amd/csrc/token_row.h): NaN -> 0, -0 == +0."""
     u = np.ascontiguousarray(s, np.float32).view(np.uint32).copy()
     u[u == 0x80000000] = 0
     k = np.where(u & 0x80000000, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
