@@ -350,6 +350,49 @@ int mage_token_logprob_bwd_masked(const float* logits, int64_t rows, int32_t K, 
                                   int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, const uint8_t* given,
                                   void* stream);
 
+/* Distillation loss: the KL divergence between a teacher's and a student's whole distribution over the K codes, per row: no site in the
+ * reference (its only objective is the cross-entropy of one token per row).  Serves MAGE.distill_loss (mage_amd/modules/mage_train.py:
+ * train_forward / train_backward with a DistillHead) against the logits MAGE.distill_targets returned.
+ * Row i is the K fp32 student logits z at logits + i*ld and the K fp32 teacher logits at teacher + i*ld_t.  The rule for one row, in fp32,
+ * with inv_t = (float)(1.0 / temperature) formed on the host:
+ *   s_j = z_j * inv_t, t_j = teacher_j * inv_t (one multiply each: step 1 of the sampling rule); each row then goes through the
+ *   arithmetic of mage_token_logprob's log-sum-exp (csrc/token_row.h: row_logsumexp): m = max_j (a NaN skipped), d_j = s_j - m,
+ *   w_j = expf(d_j), Z = sum_j w_j, and sum_j w_j d_j for the entropy H = log Z - (sum_j w_j d_j) / Z; every sum in ONE order (a lane adds
+ *   its own terms in register order with explicit roundings, the lanes meet in an xor butterfly).
+ *   mode 0, forward KL(teacher || student):  row_kl = A / Z_T + (log Z_S - log Z_T),  A = sum_j w_T,j (d_T,j - d_S,j);
+ *   mode 1, reverse KL(student || teacher):  the same with the two rows' roles exchanged.
+ *   A term whose weight is 0 is not added (never 0 * inf).  A code to which the first distribution gives positive mass and the second
+ *   gives a logit of -inf makes the row +inf.  The result is not clamped at 0: rounding may leave a small negative value.
+ *   EQUAL ROWS GIVE EXACTLY +0: with the same bits in both rows every difference above is x - x = +0, A = +0 and row_kl = +0 + +0; the
+ *   backward call's differences vanish the same way, so a model distilled against its own logits has a loss and a gradient of exactly 0
+ *   (tests rely on this).  A NaN in either row makes row_kl NaN; so does a row of -inf only (inf - inf).
+ * summary [5]: summary[0..4) are means over the free rows of row_kl, of the teacher's entropy and of the student's entropy (both at the
+ *   given temperature) and of 1[argmax_j z_j == argmax_j teacher_j] (on the raw logits, mage_argmax's rule: NaNs skipped, the first maximum
+ *   wins); summary[4] is the share of given rows over `rows`.  Each is a fixed-order fp64 sum, rounded once: workgroup b of the one
+ *   row-reading launch owns the row quads b, b + G, ... (G = min(ceil(rows / 4), 16384)), a wave adds its rows in ascending order, the four
+ *   waves meet in order; a second launch adds the G partial sums the same way through a per-device buffer of the library (calls of
+ *   mage_distill_loss on one device must be ordered: one stream, or events).  The geometry depends on rows alone: two launches give the
+ *   same bits, and there are no floating-point atomics.
+ * norm[0] = 1.0f / (float)n_free (0 when every row is given: the four means are then +0 and nothing is NaN), the backward call's input.
+ * given (uint8 [rows], may be null: every row free; a torch.bool tensor as it is): mage_policy_loss_masked's contract.  A given row is
+ *   never read in either buffer (a NaN there does not show); its row_kl is +0 and its dlogits row is +0, written with the stores the free
+ *   rows use.  A free row's bits depend on its two rows alone.
+ * mage_distill_loss_bwd: dlogits [rows, K] contiguous, MAGE_F32 or MAGE_BF16, the gradient of grad_out[0] * summary[0] with respect to
+ *   the student's logits.  With c = grad_out[0] * norm[0] * inv_t and p = w * (1 / Z) recomputed by the forward call's operations:
+ *   mode 0:  c (p_S,j - p_T,j);    mode 1:  c p_S,j ((log p_S,j - log p_T,j) - row_kl_i), 0 where p_S,j == 0, with
+ *   log p_S,j - log p_T,j = (d_S,j - d_T,j) - (log Z_S - log Z_T).  A row whose row_kl is not finite (+inf: the second distribution
+ *   excludes a code the first one holds; NaN) is written as +0 throughout, without being read: such a row has no finite gradient, and
+ *   zeros let the rest of the batch train (the forward call's summary[0] still shows the inf or NaN).
+ * Both rows of a pair are read once with 16-byte loads; outputs are written once (fp32: 16 bytes, bf16: 8 bytes per lane and chunk).
+ * mage_token_stats' size rules on both buffers: rows > 0, K % 4 == 0, 0 < K <= MAGE_SAMPLE_MAX_K, ld and ld_t % 4 == 0 and >= K, logits,
+ * teacher and dlogits 16-byte aligned; temperature finite and > 0; mode 0 or 1; row_kl, summary, norm, grad_out non-null and 4-byte
+ * aligned: MAGE_EINVAL otherwise, nothing launched. */
+int mage_distill_loss(const float* logits, int64_t rows, int32_t K, int64_t ld, const float* teacher, int64_t ld_t, float temperature,
+                      int32_t mode, const uint8_t* given, float* row_kl, float* summary, float* norm, void* stream);
+int mage_distill_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const float* teacher, int64_t ld_t, float temperature,
+                          int32_t mode, const uint8_t* given, const float* row_kl, const float* grad_out, const float* norm, void* dlogits,
+                          int32_t dl_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

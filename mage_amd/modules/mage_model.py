@@ -984,6 +984,7 @@ class MAGE(nn.Module):
         self.last_preference_pair_loss: Optional[torch.Tensor] = None        # fp32 [P]
         self.last_preference_pair_margin: Optional[torch.Tensor] = None      # fp32 [P]: beta * ((s_w - r_w) - (s_l - r_l))
         self.last_preference_token_logprobs: Optional[torch.Tensor] = None   # fp32 [B, L-1, h, w]: the given tokens at temperature 1, no filter
+        self.last_distill_token_kl: Optional[torch.Tensor] = None        # distill_loss: fp32 [B, L-1, h, w], every token's KL against the teacher
         self._last_head_out = None                                       # mage_train.MageLossFn -> _run_head: (loss dict, what the head saved)
         self.guidance: Optional[float] = None                            # set_guidance: the classifier-free guidance scale; None: off
         self.last_guidance_scale: Optional[torch.Tensor] = None          # guidance on: fp32 [B], the per-clip scales the last generation used
@@ -1061,7 +1062,8 @@ class MAGE(nn.Module):
         caption_dropout teaches a model fine-tuned here.  Both keys are ignored while guidance is off.  On a randomness=True model clip b's
         negative half uses clip b's noise and speed.
         While guidance is on, score, policy_loss, token_policy_logprobs and rollout are refused: a guided behaviour policy against an
-        unguided learner is a different estimator."""
+        unguided learner is a different estimator.  distill_targets is the one pass over given tokens that runs guided: it returns the guided
+        logits themselves, for a student's distill_loss."""
         if scale is None:
             self.guidance = None
             return self
@@ -1360,13 +1362,15 @@ class MAGE(nn.Module):
             ops.check_device_errors(images.device)
         return loss, info
 
-    def _given_tokens_inputs(self, who, batch, tokens):
+    def _given_tokens_inputs(self, who, batch, tokens, guided_ok: bool = False):
         """The refusals every pass over given tokens shares (policy_loss and preference_loss, under the name `who`), all before the first
-        launch.  Returns (images, B, the tokens' shape (B, L-1, h, w), batch['video_noise'] on a randomness=True model or None)."""
+        launch.  Returns (images, B, the tokens' shape (B, L-1, h, w), batch['video_noise'] on a randomness=True model or None).
+        guided_ok: distill_targets alone, whose result is the guided logits."""
         L, R = self.frames_length, self.image_resolution
         if not self.use_cids:
             raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
-        self._refuse_guided(who)
+        if not guided_ok:
+            self._refuse_guided(who)
         self._refuse_known(who, batch)
         if not isinstance(batch, dict):
             raise ValueError(f"{who}: batch must be a dict with 'images' and 'text'")
@@ -1514,6 +1518,69 @@ class MAGE(nn.Module):
             self._preference("clip_logprobs", batch, tokens, torch.zeros(1, 2, device=images.device, dtype=torch.int64),   # (0, 0): no preference
                              torch.zeros(images.shape[0], device=images.device, dtype=F32), 1.0, 0.0, "sigmoid", given)
             return self.last_preference_clip_logprobs
+
+    @torch.no_grad()
+    def distill_targets(self, batch, tokens) -> torch.Tensor:
+        """fp32 [B*(L-1)*h*w, K]: this model's logits for given tokens (int64 [B, L-1, h, w]), by the teacher-forced pass policy_loss runs --
+        frame 0 of batch['images'], batch['text'], the optional batch['speed'] and batch['video_noise'] on a randomness=True model, followed
+        by `tokens`.  What a teacher hands a student's distill_loss; a model is its own exact teacher (the same pass, the same bits).
+        Allowed while guidance is on, and that is the point: the pass then runs once under batch['text'] and once under
+        batch['negative_text'] (the null caption when absent), and one mage_guide_logits launch combines the two in place with the per-clip
+        scales of set_guidance / batch['guidance_scale'] -- the distribution a guided generation picks from, for a student that runs once.
+        Scale 1 gives the unguided result bit for bit.  Values only; every last_* result is left as found.  Refused under
+        set_context(k > 1) and the known-token batch keys, as policy_loss is."""
+        from . import mage_train
+        images, B, tshape, vn = self._given_tokens_inputs("distill_targets", batch, tokens, guided_ok=True)
+        self._refuse_off_gpu("distill_targets", batch, images, tokens, vn, ())
+        with self._last_results_kept(), torch.cuda.device(images.device):
+            gb = self._guidance_inputs(batch)
+            run = lambda b: self._run_head(b, mage_train.LogitsHead(tokens.contiguous()))[1][1]      # noqa: E731
+            logits = run(gb)
+            if self._guided():
+                rows, K = logits.shape
+                ops.guide_logits(logits, run({**gb, "text": gb["negative_text"]}), gb["guidance_scale"], rows=rows, K=K, scale_div=rows // B)
+            ops.check_device_errors(images.device)
+        return logits
+
+    _DISTILL_MODES = {"forward": 0, "reverse": 1}
+
+    def distill_loss(self, batch, tokens, teacher_logits, *, temperature: float = 1.0, mode: str = "forward", given=None):
+        """Distillation loss against a teacher's whole distribution: (loss, info) of policy_loss' teacher-forced pass over frame 0 of
+        batch['images'] (plus batch['text'], the optional batch['speed'], and batch['video_noise'] on a randomness=True model) followed by
+        `tokens` (int64 [B, L-1, h, w]: what to distil on, e.g. the teacher's own generation), ending in mage_distill_loss
+        (include/mage_hip_ext.h states the rule).  teacher_logits: fp32 [B*(L-1)*h*w, K] on the model's GPU, teacher.distill_targets(batch,
+        tokens) -- a guided teacher's, a higher-precision copy's, the model's own starting point's.  The loss is the mean over the tokens
+        of the KL between the two softmaxes at `temperature` (both rows divided by it): mode 'forward' KL(teacher || student), 'reverse'
+        KL(student || teacher).  It is not multiplied by temperature^2: `loss * t * t` does that through the gradient.  Equal logits give
+        exactly 0.0 and exactly zero gradients.
+        In grad mode the loss carries one autograd node over the trainable parameters, as policy_loss' does; under torch.no_grad(): values
+        only.  info = {'loss', 'teacher_entropy', 'entropy' (the student's), 'agreement' (the share of tokens where both argmax codes
+        coincide), 'given_fraction'} as floats; last_distill_token_kl keeps the per-token KL (fp32 [B, L-1, h, w]).
+        given bool [B, L-1, h, w] (policy_loss'): the given slots are not read, count 0 and get no gradient; the means are over the free
+        tokens.  Refused while guidance is on in THIS model (the student runs unguided: that is what it is trained for), under
+        set_context(k > 1) and the known-token batch keys."""
+        from . import mage_train
+        images, B, tshape, vn = self._given_tokens_inputs("distill_loss", batch, tokens)
+        rows = B * tshape[1] * tshape[2] * tshape[3]
+        tl = teacher_logits
+        if not (torch.is_tensor(tl) and tl.dtype == F32 and tuple(tl.shape) == (rows, self.codebook_size)):
+            raise ValueError(f"distill_loss: teacher_logits must be fp32 {[rows, self.codebook_size]} (distill_targets of the teacher)")
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not (
+                math.isfinite(temperature) and 1e-30 <= temperature < 3.4e38):
+            raise ValueError(f"distill_loss: temperature must be finite and > 0, got {temperature!r}")
+        if mode not in self._DISTILL_MODES:
+            raise ValueError(f"distill_loss: mode must be one of {list(self._DISTILL_MODES)}, got {mode!r}")
+        given = self._given_mask("distill_loss", given, tshape)
+        self._refuse_off_gpu("distill_loss", batch, images, tokens, vn, (("teacher_logits", tl), ("given", given)))
+        if tl.stride(1) != 1 or tl.stride(0) % 4 or tl.data_ptr() % 16:
+            tl = tl.contiguous()
+        head = mage_train.DistillHead(tokens.contiguous(), teacher=tl, temperature=float(temperature), mode=self._DISTILL_MODES[mode],
+                                      given=None if given is None else given.reshape(-1))
+        with torch.cuda.device(images.device):
+            loss, (info, res) = self._run_head(batch, head)
+            self.last_distill_token_kl = res["row_kl"].view(tshape)
+            ops.check_device_errors(images.device)
+        return loss, info
 
     @torch.no_grad()
     def video_metrics(self, video, target, data_range: float = 2.0) -> dict:

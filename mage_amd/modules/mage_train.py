@@ -674,6 +674,35 @@ class PreferenceHead:
         return ops.token_logprob_bwd(logits, target, saved["clip_coef"], gout, _dlogits(logits, dt), given=self.args.get("given"))
 
 
+class DistillHead:
+    """MAGE.distill_loss: mage_distill_loss of the pass's logits against a teacher's (fp32 [rows, K], MAGE.distill_targets' result) at
+    `temperature`; mode 0: KL(teacher || student), 1: KL(student || teacher) (include/mage_hip_ext.h).  given (bool per token, or None): the
+    token's row is left out; the means are over the free tokens.  saved: the kernel's results (row_kl, summary, norm)."""
+    PARTS = ("loss", "teacher_entropy", "entropy", "agreement", "given_fraction")
+
+    def __init__(self, tokens, *, teacher, temperature=1.0, mode=0, given=None):
+        self.tokens, self.teacher, self.temperature, self.mode, self.given = tokens, teacher, temperature, mode, given
+
+    def forward(self, model, logits, target, B):
+        res = ops.distill_loss(logits, self.teacher, temperature=self.temperature, mode=self.mode, given=self.given)
+        return res["summary"][0], dict(zip(self.PARTS, res["summary"].tolist())), res
+
+    def backward(self, logits, target, saved, gout, dt):
+        return ops.distill_loss_bwd(logits, self.teacher, saved["row_kl"], saved["norm"], gout, _dlogits(logits, dt),
+                                    temperature=self.temperature, mode=self.mode, given=self.given)
+
+
+class LogitsHead:
+    """MAGE.distill_targets: the pass's logits themselves, fp32 [rows, K], handed back as `saved`; no loss of its own (a zero) and no
+    backward pass."""
+
+    def __init__(self, tokens):
+        self.tokens = tokens
+
+    def forward(self, model, logits, target, B):
+        return torch.zeros((), device=logits.device, dtype=F32), {}, logits
+
+
 def train_forward(model, batch, head=None):
     """Teacher-forced pass of MAGE.forward (mage_model.py:575-639) with the activations the backward pass needs.
     Returns (loss 0-dim fp32 tensor, tape).

@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -847,6 +847,48 @@ def token_logprob_bwd(logits: torch.Tensor, tokens: torch.Tensor, weight: torch.
         return dlogits
     _lib.check(l.mage_token_logprob_bwd(logits.data_ptr(), rows, K, logits.stride(0), tokens.data_ptr(), weight.data_ptr(), weight_div,
                                         grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
+    return dlogits
+
+
+def _distill_args(logits, teacher, given):
+    """The asserts distill_loss and distill_loss_bwd share; returns (rows, K)."""
+    _given_rows(given, logits)
+    for x in (logits, teacher):
+        assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.device == logits.device
+    assert teacher.shape == logits.shape, "one teacher row per student row"
+    return logits.shape
+
+
+def distill_loss(logits: torch.Tensor, teacher: torch.Tensor, *, temperature: float = 1.0, mode: int = 0,
+                 given: Optional[torch.Tensor] = None) -> dict:
+    """mage_distill_loss over student logits and teacher logits, both [rows, K] fp32 (row strides >= K, each its own): the per-row KL at
+    `temperature`, mode 0 KL(teacher || student), mode 1 KL(student || teacher).  Returns fp32 'row_kl' [rows], 'summary' [5] (the means over
+    the free rows of the KL, the teacher's entropy, the student's entropy and the argmax agreement; the given share) and 'norm' [1] = 1 / the
+    number of free rows, distill_loss_bwd's input.  given bool [rows] (True: the row is left out, not read, and gets zeros); None: every row
+    is free."""
+    rows, K = _distill_args(logits, teacher, given)
+    l, s = _dev(logits)
+    mk = lambda n: torch.empty(n, device=logits.device, dtype=torch.float32)      # noqa: E731
+    out = dict(row_kl=mk(rows), summary=mk(5), norm=mk(1))
+    _lib.check(l.mage_distill_loss(logits.data_ptr(), rows, K, logits.stride(0), teacher.data_ptr(), teacher.stride(0), float(temperature),
+                                   int(mode), _p(given), out["row_kl"].data_ptr(), out["summary"].data_ptr(), out["norm"].data_ptr(), s), l)
+    return out
+
+
+def distill_loss_bwd(logits: torch.Tensor, teacher: torch.Tensor, row_kl: torch.Tensor, norm: torch.Tensor, grad_out: torch.Tensor,
+                     dlogits: torch.Tensor, *, temperature: float = 1.0, mode: int = 0, given: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mage_distill_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16, the gradient of grad_out (fp32 [1]) times distill_loss' mean KL with
+    respect to the student's logits, from distill_loss' inputs and its 'row_kl' and 'norm'."""
+    rows, K = _distill_args(logits, teacher, given)
+    l, s = _dev(logits)
+    assert row_kl.dtype == torch.float32 and row_kl.is_contiguous() and row_kl.numel() == rows and row_kl.device == logits.device
+    for x in (norm, grad_out):
+        assert x.dtype == torch.float32 and x.numel() == 1 and x.device == logits.device
+    assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
+    assert dlogits.device == logits.device
+    _lib.check(l.mage_distill_loss_bwd(logits.data_ptr(), rows, K, logits.stride(0), teacher.data_ptr(), teacher.stride(0), float(temperature),
+                                       int(mode), _p(given), row_kl.data_ptr(), grad_out.data_ptr(), norm.data_ptr(), dlogits.data_ptr(),
+                                       code(dlogits), s), l)
     return dlogits
 
 
