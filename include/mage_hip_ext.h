@@ -293,6 +293,17 @@ int mage_gemm_attn_fused(const mage_gemm_desc* desc, int32_t phase, int32_t axis
 /* The symbol of the kernel mage_gemm_attn_fused(desc, phase, axis, ...) launches, named as mage_gemm_kernel_name names mage_gemm's. */
 int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* desc, int32_t phase, int32_t axis, char* buf, int32_t len);
 
+/* The pair above as ONE launch: the softmax numerators stay in the registers of the wave that computed them, the frame's rows and their
+ * LayerNorm statistics are fetched once per (frame, group of 4 heads), no scratch buffer.  `desc` as for mage_gemm_attn_fused with
+ *   N = 3C, W = the folded in_proj rows PACKED per group g of 4 heads as 384 rows: rows 384g .. 384g+255 = rows 256g .. 256g+255 of phase 1's
+ *            packed [q | k] weight, rows 384g+256 .. 384g+383 = the v rows 128g .. 128g+127 (natural order); bias and ln_colsum in the same order;
+ *   Y[yrow(m)][C] = the attention output rows, ldy >= C.
+ * C % 128 == 0 (N % 384 == 0); M, K, a_off, the row regrouping, dtype, axis and scale as above.  Per output element the operations are those
+ * of the two-launch pair in their order: Y holds the same bits.  Anything else: MAGE_EINVAL, nothing launched. */
+int mage_gemm_attn_fused_qkv(const mage_gemm_desc* desc, int32_t axis, float scale, void* stream);
+/* The symbol of the kernel mage_gemm_attn_fused_qkv(desc, axis, ...) launches. */
+int mage_gemm_attn_fused_qkv_kernel_name(const mage_gemm_desc* desc, int32_t axis, char* buf, int32_t len);
+
 /* Given tokens over picked ones: no site in the reference (it generates every token after frame 0).  Serves MAGE.set_context and
  * batch['known_tokens'] (mage_amd/modules/mage_model.py: _generate_one, after each frame's pick and its log-probability / statistics
  * launches).

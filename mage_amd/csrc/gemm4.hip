@@ -118,6 +118,11 @@ __device__ __forceinline__ void g4_mfma32(const u32x4& w, const u32x4& x) {
 //     k order): an accumulator block then holds V^T the way the P V MFMA takes it (lane = head dim, register = key).  Same epilogue
 //     arithmetic per element, then den, P = hi + lo, O^T = V^T P_hi^T + V^T P_lo^T, the lane swap, 1 / den and the 16-byte row stores of
 //     attention_mfma_kernel: the same bits in `ao`.
+//   QF = 3 (mage_gemm_attn_fused_qkv), the pair in ONE launch, N = 3C packed per group of 4 heads as 384 rows [the group's 256 QF 1 columns | its
+//     128 v columns]: one entry of the tile list per (frame, group) = a QF 1 tile whose epilogue keeps p in the wave's accumulator registers
+//     instead of storing it, then a half-width QF 2 tile over the same rows (replayed from L2) whose epilogue takes p from there: the lane that
+//     computed a numerator is the lane that multiplies it.  P never reaches memory, the row statistics are fetched once per entry.  Every
+//     element takes the pair's operations in the pair's order: the same bits in `ao`.
 // The epilogue MFMAs of the fused attention pair (QF): attention_mfma_kernel's instructions (attn_mfma_qk / attn_mfma_pv in attn_mfma.h) on the
 // same operands, but as inline asm on VGPRs: given the builtins, hipcc puts their results into the accumulator registers it believes free
 // (a[0:3] -- live accumulators of the tile).  Wait states inside the strings: a just-written operand (1), the result before any reader (16);
@@ -190,7 +195,9 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
         voffW[u] = (unsigned)(r * g.ldw * 2 + ch * 16 + 8192 - u * 1024);
     }
     auto a_base = [&](int tile) { return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + (QF ? 0 : wave * 64)) + g.a_off) * g.lda * 2 - 4096; };
-    auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * 256 + wave * 64) * g.ldw * 2 - 4096; };
+    auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * (QF == 3 ? 384 : 256) + wave * 64) * g.ldw * 2 - 4096; };
+    // QF = 3: the 128 v rows behind a group's 256 [q | k] rows -- 4 units (32 rows) per wave, LDS rows wave*32 .. +31 of the W half of a stage
+    [[maybe_unused]] auto w_base_v = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * 384 + 256 + wave * 32) * g.ldw * 2 - 4096; };
     // two cursors: A pieces run 2 slabs ahead of the compute cursor, W pieces 1; at a tile's end they jump to the next tile's bases
     const char* a_src = a_base(c_tile);
     const char* w_src = w_base(c_tile);
@@ -200,6 +207,8 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     auto dma_m0 = [&](unsigned lds_group) __attribute__((always_inline)) {       // lds_group: stage * G4_STAGE (+ G4_WOFF)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(lds0 + lds_group) : "memory");      // (m0 cannot be named as a clobber: the compiler treats it as reserved and warns; check4 audits its writers)
     };
+    // the W half of a stage: all 8 units of the wave's 64 rows, or (half: the V part of QF = 3) 4 units at rows wave*32
+    auto dma_m0w = [&](unsigned stage_off, bool half) __attribute__((always_inline)) { dma_m0(stage_off + G4_WOFF - (half ? wave * 4096 : 0)); };
 
     // ---- compute state: wave (wm, wn) owns rows [wm*128, +128) x columns [wn*128, +128) of the tile
     const int wm = wave >> 1, wn = wave & 1;
@@ -208,11 +217,15 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     const int pc[2] = {((grp + 0) ^ rsw) * 16, ((grp + 4) ^ rsw) * 16};
     const int x_off = (wm * 128 + l15) * 128;
     const int w_off = G4_WOFF + (wn * 128 + l15) * 128;
+    [[maybe_unused]] const int w_off_v = G4_WOFF + (wn * 64 + l15) * 128;      // QF = 3, V part: the wave's 64 of the 128 v rows
     u32x4 wf[2][8], xf[2][4];
     // accumulator block of (column half h, 16-row tile mt, 16-column block j): columns h*64 + j*16 + grp*4 + {0..3} of row mt*16 + l15
     // index = (h*8 + mt)*4 + j
     auto rd_w1 = [&](int buf, int stage, int t, int nt) __attribute__((always_inline)) {
         wf[buf][nt] = *(const u32x4*)(smem + stage * G4_STAGE + w_off + nt * 2048 + pc[t]);
+    };
+    [[maybe_unused]] auto rd_wv = [&](int buf, int stage, int t, int nt) __attribute__((always_inline)) {
+        wf[buf][nt] = *(const u32x4*)(smem + stage * G4_STAGE + w_off_v + nt * 2048 + pc[t]);
     };
     auto rd_x1 = [&](int buf, int stage, int t, int mt) __attribute__((always_inline)) {
         xf[buf][mt & 3] = *(const u32x4*)(smem + stage * G4_STAGE + x_off + mt * 2048 + pc[t]);
@@ -265,239 +278,409 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     for (; c_tile < chunk1; c_tile += nwg8, ++it) {
         G4_STAMP(it, 0);
         const int tm = c_tile / g.ntiles_n, tn = c_tile - tm * g.ntiles_n;
-        MAGE_DASSERT(c_tile >= 0 && c_tile < g.ntiles && tm * 256 < g.M && tn * 256 < g.N);
-        const int m0 = ((MAGE4_ABL & 32) ? (int)blockIdx.x : tm) * 256 + wm * 128, n0 = ((MAGE4_ABL & 32) ? 0 : tn) * 256 + wn * 128;
-        {
-            const int nt_tile = c_tile + nwg8 > last_tile ? last_tile : c_tile + nwg8;     // past the end: re-fetch the last tile (never read)
-            a_next = a_base(nt_tile);
-            w_next = w_base(nt_tile);
-        }
-        f32x4 biasm[2][4];
+        MAGE_DASSERT(c_tile >= 0 && c_tile < g.ntiles && tm * 256 < g.M && tn * (QF == 3 ? 384 : 256) < g.N);
         [[maybe_unused]] float ln_mean[8], ln_rstd[8];
-        [[maybe_unused]] f32x4 lns[2][4];
-        // QF = 2: the probabilities of one epilogue step (column half h = 2 heads, row half mh = 4 sequences) as the QF = 1 launch left them:
-        // lane (l15, grp) reads p of query l15, keys 4 grp .. 4 grp + 3 -- 16 bytes per lane, 1 KiB contiguous per (sequence, head).  Requested one step ahead: step 0's in the
-        // last quarter of the last slab, a later step's sequence mt as soon as the step before has consumed its own (ahead of that sequence's row stores, which a
-        // load issued behind them would wait for).
-        [[maybe_unused]] f32x4 pl[4][2];
-        // (the lane's coordinates, opaque once per tile: the per-lane 64-bit addresses of P and of the output rows built from them are then
-        // recomputed where they are used instead of living in registers across the K loop, which this instantiation does not have)
-        [[maybe_unused]] int ql15 = l15, qgrp = grp;
-        if constexpr (QF != 0) asm volatile("" : "+v"(ql15), "+v"(qgrp));
-        [[maybe_unused]] auto qf_p_request = [&](int mt, int h, int mh) __attribute__((always_inline)) {
-            const float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4 + mt) * (g.N >> 5) + (n0 >> 5) + h * 2) * 256 + (qgrp * 16 + ql15) * 4;
-#pragma unroll
-            for (int hd = 0; hd < 2; ++hd) pl[mt][hd] = *(const f32x4*)(pp + hd * 256);
-        };
-        // One slab.  j = its index in the tile (runtime; only the cursors' tile jumps depend on it), S = its stage.
-        // LDS-DMA issue points: W(j+1) in Q0 and A(j+2) in Q3, one instruction per four MFMAs.  A tile's FIRST slab issues no W: the
-        // previous tile's LAST slab sent W of this tile's slab 1 together with its A in Q3, BEFORE the epilogue's stores -- memory
-        // operations retire in order, so a wait for pieces issued after the stores would also wait for every store acknowledgement
-        // (the 8-wave kernels' "first-slab wait", 3.3 k cycles per tile); with both operands of slab 1 older than the stores the FIRST
-        // slab waits with a count that leaves the stores in flight.
-        auto slab = [&](auto S_, auto FIRST_, auto LAST_, int j) __attribute__((always_inline)) {
-            constexpr int S = decltype(S_)::value;
-            constexpr bool FIRST = decltype(FIRST_)::value, LAST = decltype(LAST_)::value;
-            // ---- Q0: (t0, rows 0-63) from wf[0], xf[0]
-            g4_for<32>([&](auto i_) {
-                constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mm<QF == 2, ((nt >> 2) * 8 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[0][m]);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MAGE4_ABL & 4) && i < 4) {
-                    rd_x1(1, S, 0, 4 + i);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (!(MAGE4_ABL & 2) && !FIRST && i == 4) {
-                    dma_m0((S ^ 1) * G4_STAGE + G4_WOFF);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (!(MAGE4_ABL & 2) && !FIRST && (i & 3) == 1 && i > 4) {
-                    g4_dma<(i >> 2) - 1>(voffW[(i >> 2) - 1], w_src);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-            if constexpr (!(MAGE4_ABL & 2) && !FIRST) {
-                g4_dma<7>(voffW[7], w_src);
-                __builtin_amdgcn_sched_barrier(0);
+        // One tile of kind PH.  QF 0 .. 2: the entry is this one tile, PH = QF.  QF = 3: the entry (frame, group of 4 heads) is a PH = 1 tile (the
+        // 256 packed [q | k] columns of the group; KEEP: the softmax numerators stay in this wave's registers) followed by a PH = 2 tile of HALF width
+        // over the same rows (the group's 128 v columns; wave (wm, wn) takes the 64 columns of the two heads whose q and k it has just multiplied).
+        // The HALF tile accumulates in a128..a255 (the blocks of column half 1); the numerators wait in a0..a63, which the Q K part's first
+        // epilogue chunk has read out before the first of them is written: block c*4 + mt = chunk c (head c >> 1 of the wave, row half c & 1), sequence mt.
+        auto tile = [&](auto PH_) __attribute__((always_inline)) {
+            constexpr int PH = decltype(PH_)::value;
+            constexpr bool HALF = QF == 3 && PH == 2, KEEP = QF == 3 && PH == 1;
+            constexpr int NW = HALF ? 4 : 8;               // W fragments per k-half = 16-column blocks of the wave
+            const int m0 = ((MAGE4_ABL & 32) ? (int)blockIdx.x : tm) * 256 + wm * 128;
+            // n0: the wave's first column -- of W, bias and ln_colsum; ny0: of the output rows
+            const int n0 = QF == 3 ? tn * 384 + (HALF ? 256 + wn * 64 : wn * 128) : ((MAGE4_ABL & 32) ? 0 : tn) * 256 + wn * 128;
+            [[maybe_unused]] const int ny0 = HALF ? tn * 128 + wn * 64 : n0;
+            if constexpr (KEEP) {                          // the V part replays the frame's panel (from L2: the frame's groups stream it together)
+                a_next = a_base(c_tile);
+                w_next = w_base_v(c_tile);
+            } else {
+                const int nt_tile = c_tile + nwg8 > last_tile ? last_tile : c_tile + nwg8;     // past the end: re-fetch the last tile (never read)
+                a_next = a_base(nt_tile);
+                w_next = w_base(nt_tile);
             }
-            if constexpr (!(MAGE4_ABL & 8) && !FIRST) w_src = (j == nk - 2) ? w_next : w_src + 128;
-            // ---- Q1: (t0, rows 64-127) from wf[0], xf[1]
-            g4_for<32>([&](auto i_) {
-                constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mm<QF == 2, ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[1][m]);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MAGE4_ABL & 4) && i < 12) {
-                    if constexpr (i < 4) rd_x1(0, S, 1, i);
-                    else rd_w1(1, S, 1, i - 4);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-            // ---- Q2: (t1, rows 0-63) from wf[1], xf[0]
-            if constexpr (LAST) {                      // the epilogue's vectors, late: their registers are free during the K loop
+            auto rd_w = [&](int buf, int stage, int t, int nt) __attribute__((always_inline)) {
+                if constexpr (HALF) rd_wv(buf, stage, t, nt);
+                else rd_w1(buf, stage, t, nt);
+            };
+            f32x4 biasm[2][4];
+            [[maybe_unused]] f32x4 lns[2][4];
+            // QF = 2: the probabilities of one epilogue step (column half h = 2 heads, row half mh = 4 sequences) as the QF = 1 launch left them:
+            // lane (l15, grp) reads p of query l15, keys 4 grp .. 4 grp + 3 -- 16 bytes per lane, 1 KiB contiguous per (sequence, head).  Requested one step ahead: step 0's in the
+            // last quarter of the last slab, a later step's sequence mt as soon as the step before has consumed its own (ahead of that sequence's row stores, which a
+            // load issued behind them would wait for).
+            [[maybe_unused]] f32x4 pl[4][2];
+            // (the lane's coordinates, opaque once per tile: the per-lane 64-bit addresses of P and of the output rows built from them are then
+            // recomputed where they are used instead of living in registers across the K loop, which this instantiation does not have)
+            [[maybe_unused]] int ql15 = l15, qgrp = grp;
+            if constexpr (QF != 0) asm volatile("" : "+v"(ql15), "+v"(qgrp));
+            [[maybe_unused]] auto qf_p_request = [&](int mt, int h, int mh) __attribute__((always_inline)) {
+                const float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4 + mt) * (g.N >> 5) + (n0 >> 5) + h * 2) * 256 + (qgrp * 16 + ql15) * 4;
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {          // column half 0 (half 1: requested in the epilogue, under half 0's arithmetic)
-                    if constexpr (QF == 2) {           // transposed blocks: this lane's column of block b is b*16 + l15
-                        biasm[0][0][b] = g.bias[n0 + b * 16 + l15];
-                        lns[0][0][b] = g.ln_colsum[n0 + b * 16 + l15];
-                        continue;
-                    }
-                    const int n = n0 + b * 16 + grp * 4;
-                    biasm[0][b] = *(const f32x4*)(g.bias + n);                         // bias != null (host)
-                    if constexpr (LN == LN_CONSUME) lns[0][b] = *(const f32x4*)(g.ln_colsum + n);
-                }
-                if constexpr (LN == LN_CONSUME) {
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) {
-                        const long row = QF ? (long)tm * 256 + frame_row(wm * 128 + a * 16 + ql15) : (long)(m0 + a * 16 + l15);
-                        const float2 st = *(const float2*)(g.ln_stats + 2 * row);
-                        ln_mean[a] = st.x;
-                        ln_rstd[a] = st.y;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            g4_for<32>([&](auto i_) {
-                constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mm<QF == 2, ((nt >> 2) * 8 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[0][m]);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MAGE4_ABL & 4) && i < 4) {
-                    rd_x1(1, S, 1, 4 + i);
+                for (int hd = 0; hd < 2; ++hd) pl[mt][hd] = *(const f32x4*)(pp + hd * 256);
+            };
+            // One slab.  j = its index in the tile (runtime; only the cursors' tile jumps depend on it), S = its stage.
+            // LDS-DMA issue points: W(j+1) in Q0 and A(j+2) in Q3, one instruction per four MFMAs.  A tile's FIRST slab issues no W: the
+            // previous tile's LAST slab sent W of this tile's slab 1 together with its A in Q3, BEFORE the epilogue's stores -- memory
+            // operations retire in order, so a wait for pieces issued after the stores would also wait for every store acknowledgement
+            // (the 8-wave kernels' "first-slab wait", 3.3 k cycles per tile); with both operands of slab 1 older than the stores the FIRST
+            // slab waits with a count that leaves the stores in flight.
+            auto slab = [&](auto S_, auto FIRST_, auto LAST_, int j) __attribute__((always_inline)) {
+                constexpr int S = decltype(S_)::value;
+                constexpr bool FIRST = decltype(FIRST_)::value, LAST = decltype(LAST_)::value;
+                // HALF (the V part of QF = 3): a quarter is 16 MFMAs on the 4 W fragments of column half 0 -- per slab 16 + 8 fragment reads, 8 A units
+                // and 4 W units per wave.  ACC0: the first accumulator block.  The W pieces this slab sends belong to the next slab of this tile, or
+                // (LAST) to the next tile: WH_ = that tile is a HALF one (4 units at their own LDS rows, dma_m0w).
+                constexpr int ACC0 = HALF ? 32 : 0;
+                constexpr bool WH_ = QF == 3 && (LAST ? KEEP : HALF);
+                constexpr int WU = WH_ ? 4 : 8;
+                // ---- Q0: (t0, rows 0-63) from wf[0], xf[0]
+                g4_for<4 * NW>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value, m = i / NW, nt = i % NW;
+                    g4_mm<PH == 2, ACC0 + ((nt >> 2) * 8 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[0][m]);
                     __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-            // my reads of this stage are done and my share of the next slab has landed.  FIRST: the next slab's 16 pieces are older than
-            // the previous tile's epilogue traffic (4 or 8 vector loads and >= 32 stores per wave), which may stay in flight (the count waited
-            // for is four below that traffic: a margin against any reordering of the epilogue's last stores)
-            if constexpr (MAGE4_ABL & 16) __builtin_amdgcn_s_waitcnt(0xC07F);
-            // QF: only the instructions whose place behind the pieces the source fixes are counted -- the stores, which follow the accumulator
-            // reads (asm statements), not the epilogue's loads, which hipcc is free to issue earlier: QF 1: the 16 stores of P, four below
-            // = vmcnt(12) (with the 8 vector loads 24 lie behind the pieces); QF 2: the 32 row stores = vmcnt(32), the largest count the
-            // encoding below keeps simple (8 + 24 loads as well: 64 behind the pieces).  A too-low count only waits for some store
-            // acknowledgements; tightening them is unmeasured.
-            else if constexpr (FIRST && QF == 1) __builtin_amdgcn_s_waitcnt(0x007C);
-            else if constexpr (FIRST && QF == 2) __builtin_amdgcn_s_waitcnt(0x8070);
-            else if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(LN == LN_CONSUME ? 0x8074 : 0x8070);       // vmcnt(36 | 32) lgkmcnt(0): four below the count
-            else __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
-            ring_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            // ---- Q3: (t1, rows 64-127) from wf[1], xf[1]; next slab's first fragments into wf[0], xf[0]
-            g4_for<32>([&](auto i_) {
-                constexpr int i = decltype(i_)::value, m = i >> 3, nt = i & 7;
-                g4_mm<QF == 2, ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[1][m]);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MAGE4_ABL & 4) && i < 12 && !LAST) {     // (a tile's last slab: after the epilogue, whose registers these would occupy)
-                    if constexpr (i < 4) rd_x1(0, S ^ 1, 0, i);
-                    else rd_w1(0, S ^ 1, 0, i - 4);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (!(MAGE4_ABL & 2) && !LAST) {               // A(j+2): 8 pieces
-                    if constexpr (i == 2) dma_m0(S * G4_STAGE);
-                    if constexpr ((i & 3) == 3) g4_dma<(i >> 2)>(voffA[i >> 2], a_src);
-                    if constexpr (i == 2 || (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (!(MAGE4_ABL & 2) && LAST) {                // A and W of the next tile's slab 1: 16 pieces
-                    if constexpr (i == 0) dma_m0(S * G4_STAGE);
-                    if constexpr (i == 16) dma_m0(S * G4_STAGE + G4_WOFF);
-                    if constexpr ((i & 1) == 1 && i < 16) g4_dma<(i >> 1)>(voffA[i >> 1], a_src);
-                    if constexpr ((i & 1) == 1 && i > 16) g4_dma<((i - 16) >> 1)>(voffW[(i - 16) >> 1], w_src);
-                    if constexpr (i == 0 || i == 16 || (i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (QF == 2 && LAST && (i & 7) == 6) {         // the first epilogue step's probabilities (the slab's other fragment registers are free)
-                    qf_p_request(i >> 3, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-            if constexpr (!(MAGE4_ABL & 8)) a_src = (j == nk - 3) ? a_next : a_src + 128;
-            if constexpr (!(MAGE4_ABL & 8) && LAST) w_src += 128;
-        };
-#ifdef MAGE4_MFMA32
-        // the same slab on 32 x 32 x 16 MFMAs: quarter q = k-step q (16 of the slab's 64 k), 16 MFMAs over the 4 x 4 blocks; the next k-step's 8
-        // fragments are read during the quarter, the DMA issue points, the barrier and the waits are the 16 x 16 schedule's
-        auto slab32 = [&](auto S_, auto FIRST_, auto LAST_, int j) __attribute__((always_inline)) {
-            constexpr int S = decltype(S_)::value;
-            constexpr bool FIRST = decltype(FIRST_)::value, LAST = decltype(LAST_)::value;
-            auto quarter = [&](auto Q_) __attribute__((always_inline)) {
-                constexpr int Q = decltype(Q_)::value, buf = Q & 1;
-                g4_for<16>([&](auto i_) {
-                    constexpr int i = decltype(i_)::value, mb = i >> 2, nb = i & 3;
-                    g4_mfma32<mb * 4 + nb, FIRST && Q == 0, i == 0>(wq[buf][nb], xq[buf][mb]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (!(MAGE4_ABL & 4) && i < 8 && !(Q == 3 && LAST)) {        // next k-step's fragments (Q3: the next slab's first, other stage)
-                        constexpr int st = Q == 3 ? (S ^ 1) : S, ks = (Q + 1) & 3;
-                        if constexpr (i < 4) rd_x32(buf ^ 1, st, ks, i);
-                        else rd_w32(buf ^ 1, st, ks, i - 4);
+                    if constexpr (!(MAGE4_ABL & 4) && i < 4) {
+                        rd_x1(1, S, 0, 4 + i);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    if constexpr (Q == 0 && !(MAGE4_ABL & 2) && !FIRST) {                  // W(j+1): 8 pieces
-                        if constexpr (i == 4) dma_m0((S ^ 1) * G4_STAGE + G4_WOFF);
-                        if constexpr (i >= 5 && i < 13) g4_dma<i - 5>(voffW[i - 5], w_src);
-                        if constexpr (i >= 4 && i < 13) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!(MAGE4_ABL & 2) && !FIRST && i == 4) {
+                        dma_m0w((S ^ 1) * G4_STAGE, WH_);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    if constexpr (Q == 3 && !(MAGE4_ABL & 2) && !LAST) {                   // A(j+2): 8 pieces
-                        if constexpr (i == 1) dma_m0(S * G4_STAGE);
-                        if constexpr (i >= 2 && i < 10) g4_dma<i - 2>(voffA[i - 2], a_src);
-                        if constexpr (i >= 1 && i < 10) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!HALF) {                 // one piece per four MFMAs
+                        if constexpr (!(MAGE4_ABL & 2) && !FIRST && (i & 3) == 1 && i > 4 && (i >> 2) - 1 < WU) {
+                            g4_dma<(i >> 2) - 1>(voffW[(i >> 2) - 1], w_src);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    } else {                               // 16 MFMAs: one piece per MFMA behind the fragment reads
+                        if constexpr (!FIRST && i > 4 && i - 5 < WU) {
+                            g4_dma<i - 5>(voffW[i - 5], w_src);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
                     }
                 });
+                if constexpr (!(MAGE4_ABL & 2) && !FIRST && !HALF && WU == 8) {
+                    g4_dma<7>(voffW[7], w_src);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (!(MAGE4_ABL & 8) && !FIRST) w_src = (j == nk - 2) ? w_next : w_src + 128;
+                // ---- Q1: (t0, rows 64-127) from wf[0], xf[1]
+                g4_for<4 * NW>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value, m = i / NW, nt = i % NW;
+                    g4_mm<PH == 2, ACC0 + ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), FIRST, i == 0, HF>(wf[0][nt], xf[1][m]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!(MAGE4_ABL & 4) && i < 4 + NW) {
+                        if constexpr (i < 4) rd_x1(0, S, 1, i);
+                        else rd_w(1, S, 1, i - 4);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                // ---- Q2: (t1, rows 0-63) from wf[1], xf[0]
+                if constexpr (LAST) {                      // the epilogue's vectors, late: their registers are free during the K loop
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {          // column half 0 (half 1: requested in the epilogue, under half 0's arithmetic)
+                        if constexpr (PH == 2) {           // transposed blocks: this lane's column of block b is b*16 + l15
+                            biasm[0][0][b] = g.bias[n0 + b * 16 + l15];
+                            lns[0][0][b] = g.ln_colsum[n0 + b * 16 + l15];
+                            continue;
+                        }
+                        const int n = n0 + b * 16 + grp * 4;
+                        biasm[0][b] = *(const f32x4*)(g.bias + n);                         // bias != null (host)
+                        if constexpr (LN == LN_CONSUME) lns[0][b] = *(const f32x4*)(g.ln_colsum + n);
+                    }
+                    if constexpr (LN == LN_CONSUME && !HALF) {      // (HALF: the Q K part's are kept)
+#pragma unroll
+                        for (int a = 0; a < 8; ++a) {
+                            const long row = QF ? (long)tm * 256 + frame_row(wm * 128 + a * 16 + ql15) : (long)(m0 + a * 16 + l15);
+                            const float2 st = *(const float2*)(g.ln_stats + 2 * row);
+                            ln_mean[a] = st.x;
+                            ln_rstd[a] = st.y;
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                g4_for<4 * NW>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value, m = i / NW, nt = i % NW;
+                    g4_mm<PH == 2, ACC0 + ((nt >> 2) * 8 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[0][m]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!(MAGE4_ABL & 4) && i < 4) {
+                        rd_x1(1, S, 1, 4 + i);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                // my reads of this stage are done and my share of the next slab has landed.  FIRST: the next slab's 16 pieces are older than
+                // the previous tile's epilogue traffic (4 or 8 vector loads and >= 32 stores per wave), which may stay in flight (the count waited
+                // for is four below that traffic: a margin against any reordering of the epilogue's last stores)
+                if constexpr (MAGE4_ABL & 16) __builtin_amdgcn_s_waitcnt(0xC07F);
+                // QF: only the instructions whose place behind the pieces the source fixes are counted -- the stores, which follow the accumulator
+                // reads (asm statements), not the epilogue's loads, which hipcc is free to issue earlier: QF 1: the 16 stores of P, four below
+                // = vmcnt(12) (with the 8 vector loads 24 lie behind the pieces); QF 2: the 32 row stores = vmcnt(32), the largest count the
+                // encoding below keeps simple (8 + 24 loads as well: 64 behind the pieces).  A too-low count only waits for some store
+                // acknowledgements; tightening them is unmeasured.
+                // QF 3: the Q K part follows a V part's 16 row stores = vmcnt(12); the V part follows a Q K part that stores nothing = vmcnt(0).
+                else if constexpr (FIRST && QF == 3) __builtin_amdgcn_s_waitcnt(PH == 1 ? 0x007C : 0x0070);
+                else if constexpr (FIRST && QF == 1) __builtin_amdgcn_s_waitcnt(0x007C);
+                else if constexpr (FIRST && QF == 2) __builtin_amdgcn_s_waitcnt(0x8070);
+                else if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(LN == LN_CONSUME ? 0x8074 : 0x8070);       // vmcnt(36 | 32) lgkmcnt(0): four below the count
+                else __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
+                ring_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                // ---- Q3: (t1, rows 64-127) from wf[1], xf[1]; next slab's first fragments into wf[0], xf[0]
+                g4_for<4 * NW>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value, m = i / NW, nt = i % NW;
+                    g4_mm<PH == 2, ACC0 + ((nt >> 2) * 8 + 4 + m) * 4 + (nt & 3), false, i == 0, HF>(wf[1][nt], xf[1][m]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!(MAGE4_ABL & 4) && i < 4 + NW && !LAST) {     // (a tile's last slab: after the epilogue, whose registers these would occupy)
+                        if constexpr (i < 4) rd_x1(0, S ^ 1, 0, i);
+                        else rd_w(0, S ^ 1, 0, i - 4);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (!(MAGE4_ABL & 2) && !LAST && !HALF) {      // A(j+2): 8 pieces
+                        if constexpr (i == 2) dma_m0(S * G4_STAGE);
+                        if constexpr ((i & 3) == 3) g4_dma<(i >> 2)>(voffA[i >> 2], a_src);
+                        if constexpr (i == 2 || (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (!(MAGE4_ABL & 2) && LAST && !HALF) {       // A and W of the next tile's slab 1: 16 pieces (KEEP: 8 + the V part's 4)
+                        if constexpr (i == 0) dma_m0(S * G4_STAGE);
+                        if constexpr (i == 16) dma_m0w(S * G4_STAGE, WH_);
+                        if constexpr ((i & 1) == 1 && i < 16) g4_dma<(i >> 1)>(voffA[i >> 1], a_src);
+                        if constexpr ((i & 1) == 1 && i > 16 && ((i - 16) >> 1) < WU) g4_dma<((i - 16) >> 1)>(voffW[(i - 16) >> 1], w_src);
+                        if constexpr (i == 0 || i == 16 || (i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (HALF && !LAST) {                           // A(j+2): 8 pieces, one per two MFMAs
+                        if constexpr (i == 0) dma_m0(S * G4_STAGE);
+                        if constexpr ((i & 1) == 1) g4_dma<(i >> 1)>(voffA[i >> 1], a_src);
+                        if constexpr (i == 0 || (i & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (HALF && LAST) {                            // A and W of the next entry's slab 1: 16 pieces, one per MFMA
+                        if constexpr (i == 0) dma_m0(S * G4_STAGE);
+                        if constexpr (i == 8) dma_m0w(S * G4_STAGE, false);
+                        if constexpr (i < 8) g4_dma<i>(voffA[i], a_src);
+                        else g4_dma<i - 8>(voffW[i - 8], w_src);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (PH == 2 && !HALF && LAST && (i & 7) == 6) {         // the first epilogue step's probabilities (the slab's other fragment registers are free)
+                        qf_p_request(i >> 3, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                if constexpr (!(MAGE4_ABL & 8)) a_src = (j == nk - 3) ? a_next : a_src + 128;
+                if constexpr (!(MAGE4_ABL & 8) && LAST) w_src += 128;
             };
-            quarter(std::integral_constant<int, 0>{});
-            if constexpr (!(MAGE4_ABL & 8) && !FIRST) w_src = (j == nk - 2) ? w_next : w_src + 128;
-            quarter(std::integral_constant<int, 1>{});
-            quarter(std::integral_constant<int, 2>{});
-            if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(0x8070);
-            else __builtin_amdgcn_s_waitcnt(0x0070);
-            ring_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            quarter(std::integral_constant<int, 3>{});
-            if constexpr (LAST && !(MAGE4_ABL & 2)) {                                       // the next tile's slab 1 (A and W), as the 16 x 16 schedule sends it
-                dma_m0(S * G4_STAGE);
-                g4_for<8>([&](auto u_) { g4_dma<decltype(u_)::value>(voffA[decltype(u_)::value], a_src); });
-                dma_m0(S * G4_STAGE + G4_WOFF);
-                g4_for<8>([&](auto u_) { g4_dma<decltype(u_)::value>(voffW[decltype(u_)::value], w_src); });
-            }
-            if constexpr (!(MAGE4_ABL & 8)) a_src = (j == nk - 3) ? a_next : a_src + 128;
-            if constexpr (!(MAGE4_ABL & 8) && LAST) w_src += 128;
-        };
+#ifdef MAGE4_MFMA32
+            // the same slab on 32 x 32 x 16 MFMAs: quarter q = k-step q (16 of the slab's 64 k), 16 MFMAs over the 4 x 4 blocks; the next k-step's 8
+            // fragments are read during the quarter, the DMA issue points, the barrier and the waits are the 16 x 16 schedule's
+            auto slab32 = [&](auto S_, auto FIRST_, auto LAST_, int j) __attribute__((always_inline)) {
+                constexpr int S = decltype(S_)::value;
+                constexpr bool FIRST = decltype(FIRST_)::value, LAST = decltype(LAST_)::value;
+                auto quarter = [&](auto Q_) __attribute__((always_inline)) {
+                    constexpr int Q = decltype(Q_)::value, buf = Q & 1;
+                    g4_for<16>([&](auto i_) {
+                        constexpr int i = decltype(i_)::value, mb = i >> 2, nb = i & 3;
+                        g4_mfma32<mb * 4 + nb, FIRST && Q == 0, i == 0>(wq[buf][nb], xq[buf][mb]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (!(MAGE4_ABL & 4) && i < 8 && !(Q == 3 && LAST)) {        // next k-step's fragments (Q3: the next slab's first, other stage)
+                            constexpr int st = Q == 3 ? (S ^ 1) : S, ks = (Q + 1) & 3;
+                            if constexpr (i < 4) rd_x32(buf ^ 1, st, ks, i);
+                            else rd_w32(buf ^ 1, st, ks, i - 4);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        if constexpr (Q == 0 && !(MAGE4_ABL & 2) && !FIRST) {                  // W(j+1): 8 pieces
+                            if constexpr (i == 4) dma_m0((S ^ 1) * G4_STAGE + G4_WOFF);
+                            if constexpr (i >= 5 && i < 13) g4_dma<i - 5>(voffW[i - 5], w_src);
+                            if constexpr (i >= 4 && i < 13) __builtin_amdgcn_sched_barrier(0);
+                        }
+                        if constexpr (Q == 3 && !(MAGE4_ABL & 2) && !LAST) {                   // A(j+2): 8 pieces
+                            if constexpr (i == 1) dma_m0(S * G4_STAGE);
+                            if constexpr (i >= 2 && i < 10) g4_dma<i - 2>(voffA[i - 2], a_src);
+                            if constexpr (i >= 1 && i < 10) __builtin_amdgcn_sched_barrier(0);
+                        }
+                    });
+                };
+                quarter(std::integral_constant<int, 0>{});
+                if constexpr (!(MAGE4_ABL & 8) && !FIRST) w_src = (j == nk - 2) ? w_next : w_src + 128;
+                quarter(std::integral_constant<int, 1>{});
+                quarter(std::integral_constant<int, 2>{});
+                if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(0x8070);
+                else __builtin_amdgcn_s_waitcnt(0x0070);
+                ring_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                quarter(std::integral_constant<int, 3>{});
+                if constexpr (LAST && !(MAGE4_ABL & 2)) {                                       // the next tile's slab 1 (A and W), as the 16 x 16 schedule sends it
+                    dma_m0(S * G4_STAGE);
+                    g4_for<8>([&](auto u_) { g4_dma<decltype(u_)::value>(voffA[decltype(u_)::value], a_src); });
+                    dma_m0(S * G4_STAGE + G4_WOFF);
+                    g4_for<8>([&](auto u_) { g4_dma<decltype(u_)::value>(voffW[decltype(u_)::value], w_src); });
+                }
+                if constexpr (!(MAGE4_ABL & 8)) a_src = (j == nk - 3) ? a_next : a_src + 128;
+                if constexpr (!(MAGE4_ABL & 8) && LAST) w_src += 128;
+            };
 #define slab slab32
 #endif
-        typedef std::integral_constant<int, 0> S0;
-        typedef std::integral_constant<int, 1> S1;
-        slab(S0{}, std::true_type{}, std::false_type{}, 0);
-        slab(S1{}, std::false_type{}, std::false_type{}, 1);
-        for (int j = 2; j < nk - 2; j += 2) {
-            slab(S0{}, std::false_type{}, std::false_type{}, j);
-            slab(S1{}, std::false_type{}, std::false_type{}, j + 1);
-        }
-        slab(S0{}, std::false_type{}, std::false_type{}, nk - 2);
-        slab(S1{}, std::false_type{}, std::true_type{}, nk - 1);
+            typedef std::integral_constant<int, 0> S0;
+            typedef std::integral_constant<int, 1> S1;
+            slab(S0{}, std::true_type{}, std::false_type{}, 0);
+            slab(S1{}, std::false_type{}, std::false_type{}, 1);
+            for (int j = 2; j < nk - 2; j += 2) {
+                slab(S0{}, std::false_type{}, std::false_type{}, j);
+                slab(S1{}, std::false_type{}, std::false_type{}, j + 1);
+            }
+            slab(S0{}, std::false_type{}, std::false_type{}, nk - 2);
+            slab(S1{}, std::false_type{}, std::true_type{}, nk - 1);
 #ifdef MAGE4_MFMA32
 #undef slab
 #endif
-        // the last MFMAs' results must have left the matrix pipe before an accumulator is read (an asm statement gets no hazard padding)
-        asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-        G4_STAMP(it, 1);
+            // the last MFMAs' results must have left the matrix pipe before an accumulator is read (an asm statement gets no hazard padding)
+            asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+            G4_STAMP(it, 1);
 #if MAGE4_ABL & 1
-        {
-            f32x4 t = g4_acc_read<0>() + g4_acc_read<17>() + g4_acc_read<63>();
-            if (t[0] + t[1] + t[2] + t[3] == 123456.789f) ((float*)g.Y)[0] = t[0] + biasm[0][0][0];
-        }
-#else
-        char* win = smem + G4_RING + wave * 4096;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            if constexpr (QF == 2) {
-                biasm[1][0][b] = g.bias[n0 + 64 + b * 16 + l15];
-                lns[1][0][b] = g.ln_colsum[n0 + 64 + b * 16 + l15];
-                continue;
+            {
+                f32x4 t = g4_acc_read<0>() + g4_acc_read<17>() + g4_acc_read<63>();
+                if (t[0] + t[1] + t[2] + t[3] == 123456.789f) ((float*)g.Y)[0] = t[0] + biasm[0][0][0];
             }
-            const int n = n0 + 64 + b * 16 + grp * 4;
-            biasm[1][b] = *(const f32x4*)(g.bias + n);
-            if constexpr (LN == LN_CONSUME) lns[1][b] = *(const f32x4*)(g.ln_colsum + n);
-        }
-        // gemm.hip's epilogue_lean, 64 x 64 outputs = 64 accumulator registers at a time.  (A software-pipelined rewrite -- 64 rows of staging
-        // writes, then their reads under the next 64 rows' arithmetic -- was built and measured 5 % SLOWER per launch: the epilogue is not
-        // waiting for its LDS round trips, it is issue-bound on the vector ALU at the clock the K loop's power draw leaves: 1.5 GHz.)
-        if constexpr (QF != 0) {
+#else
+            char* win = smem + G4_RING + wave * 4096;
+#pragma unroll
+            for (int b = 0; b < (HALF ? 0 : 4); ++b) {
+                if constexpr (PH == 2) {
+                    biasm[1][0][b] = g.bias[n0 + 64 + b * 16 + l15];
+                    lns[1][0][b] = g.ln_colsum[n0 + 64 + b * 16 + l15];
+                    continue;
+                }
+                const int n = n0 + 64 + b * 16 + grp * 4;
+                biasm[1][b] = *(const f32x4*)(g.bias + n);
+                if constexpr (LN == LN_CONSUME) lns[1][b] = *(const f32x4*)(g.ln_colsum + n);
+            }
+            // gemm.hip's epilogue_lean, 64 x 64 outputs = 64 accumulator registers at a time.  (A software-pipelined rewrite -- 64 rows of staging
+            // writes, then their reads under the next 64 rows' arithmetic -- was built and measured 5 % SLOWER per launch: the epilogue is not
+            // waiting for its LDS round trips, it is issue-bound on the vector ALU at the clock the K loop's power draw leaves: 1.5 GHz.)
+            if constexpr (QF != 0) {
+                g4_for<(HALF ? 2 : 4)>([&](auto c_) {
+                    // h: the column half's index into biasm / lns, ha: into the accumulator blocks (HALF: the one half, kept in a128..a255)
+                    constexpr int c = decltype(c_)::value, h = HALF ? 0 : c >> 1, mh = c & 1, ha = HALF ? 1 : h;
+                    __builtin_amdgcn_sched_barrier(0);
+                    f32x4 t[4][4];
+                    g4_for<16>([&](auto q_) {
+                        constexpr int q = decltype(q_)::value;
+                        t[q >> 2][q & 3] = g4_acc_read<(ha * 8 + mh * 4 + (q >> 2)) * 4 + (q & 3), q == 0>();
+                    });
+                    if constexpr (PH == 1) {
+                        // N = 2C: 64 packed columns per head; P[frame][sequence][head][lane][4]: one store instruction = 1 KiB contiguous
+                        [[maybe_unused]] float* pp = KEEP ? nullptr : g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4) * (g.N >> 6) + (n0 >> 6) + h) * 256 + (qgrp * 16 + ql15) * 4;
+#pragma unroll
+                        for (int mt = 0; mt < 4; ++mt) {
+                            uint2 pk[4];
+#pragma unroll
+                            for (int nt = 0; nt < 4; ++nt) {
+                                const f32x4 v = (t[mt][nt] - lns[h][nt] * ln_mean[mh * 4 + mt]) * ln_rstd[mh * 4 + mt] + biasm[h][nt];      // epilogue_lean's LN_CONSUME
+                                pk[nt] = uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])};
+                            }
+                            // attention_mfma_kernel, one key block, every key visible: S^T = K Q^T, scale, max, exp
+                            f32x4 st = g4_epi_qk<HF>(u32x4{pk[2].x, pk[2].y, pk[3].x, pk[3].y}, u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y});
+                            // (no contraction: there the scaled scores pass a select before the maximum is taken off, so the product is rounded --
+                            // s * scale - max as ONE fma would give exp(> 0) at the maximum itself)
+                            f32x4 p;
+                            {
+#pragma clang fp contract(off)
+                                float mx = -INFINITY;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    st[e] = st[e] * g.attn_scale;
+                                    mx = fmaxf(mx, st[e]);
+                                }
+                                mx = fmaxf(mx, __shfl_xor(mx, 16));
+                                mx = fmaxf(mx, __shfl_xor(mx, 32));
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) p[e] = expf(st[e] - mx);
+                            }
+                            if constexpr (KEEP) pl[mt][0] = p;
+                            else *(f32x4*)(pp + (long)mt * (g.N >> 6) * 256) = p;
+                        }
+                        if constexpr (KEEP) g4_for<4>([&](auto mt_) { g4_acc_write<c * 4 + decltype(mt_)::value>(pl[decltype(mt_)::value][0]); });
+                    } else {
+                        const long shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
+                        // the two heads' 16 rows x 64 B through the wave's staging window (epilogue_lean's swizzle; a wave's DS operations execute in order):
+                        // stored as 2 x (8 rows x 128 B) instead of 2 x (16 rows x 64 B)
+                        const int srow = (qgrp * 16 + ql15) >> 3, scc = ql15 & 7;
+                        H16* op = (H16*)g.Y + ny0 + h * 64 + scc * 8;
+                        const int wchunk = (qgrp & 1) * 2 + (qgrp >> 1);
+                        if constexpr (HALF)                // the kept numerators of this row half: pl[mt][hd] as QF 2 loads them
+                            g4_for<8>([&](auto q_) {
+                                constexpr int q = decltype(q_)::value, hd = q >> 2, mt = q & 3;
+                                pl[mt][hd] = g4_acc_read<(hd * 2 + mh) * 4 + mt>();
+                            });
+#pragma unroll
+                        for (int mt = 0; mt < 4; ++mt) {
+                            f32x4 mean4, rstd4;            // the statistics of this lane's four rows of the transposed blocks: 4 grp + e
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                mean4[e] = __shfl(ln_mean[mh * 4 + mt], 4 * grp + e);
+                                rstd4[e] = __shfl(ln_rstd[mh * 4 + mt], 4 * grp + e);
+                            }
+#pragma unroll
+                            for (int hd = 0; hd < 2; ++hd) {
+                                const f32x4 p = pl[mt][hd];
+                                float den = 0.f;
+                                ashort4 phi, plo;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    den += p[e];
+                                    short ph, pw;
+                                    attn_p_split<H16>(p[e], ph, pw);
+                                    phi[e] = ph;
+                                    plo[e] = pw;
+                                }
+                                den += __shfl_xor(den, 16);
+                                den += __shfl_xor(den, 32);
+                                if constexpr (c < 3 && !HALF) {
+                                    if (hd == 1) qf_p_request(mt, (c + 1) >> 1, (c + 1) & 1);
+                                }
+                                f32x4 o[2];
+                                ashort4 vt[2];
+#pragma unroll
+                                for (int b = 0; b < 2; ++b) {
+                                    const int nt = hd * 2 + b;
+                                    const f32x4 v = (t[mt][nt] - mean4 * lns[h][0][nt]) * rstd4 + biasm[h][0][nt];
+                                    vt[b] = __builtin_bit_cast(ashort4, uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])});
+                                }
+                                g4_epi_pv<HF>(vt[0], vt[1], phi, plo, o[0], o[1]);
+                                const float inv = 1.0f / den;
+                                f32x4 v0, v1;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[0][e]), __float_as_uint(o[1][e]), false, false);
+                                    v0[e] = __uint_as_float(sw[0]) * inv;
+                                    v1[e] = __uint_as_float(sw[1]) * inv;
+                                }
+                                *(u32x4*)(win + ql15 * 128 + (((hd * 4 + wchunk) ^ ((ql15 >> 1) & 7)) << 4)) =
+                                    u32x4{pack16x2<H16>(v0[0], v0[1]), pack16x2<H16>(v0[2], v0[3]), pack16x2<H16>(v1[0], v1[1]), pack16x2<H16>(v1[2], v1[3])};
+                            }
+#pragma unroll
+                            for (int i = 0; i < 2; ++i) {
+                                const int r = srow + 8 * i;
+                                const long yrow = (long)tm * 256 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
+                                *(u32x4*)(op + yrow * g.ldy) = *(const u32x4*)(win + r * 128 + ((scc ^ ((r >> 1) & 7)) << 4));
+                            }
+                        }
+                    }
+                });
+            } else {
+            mage_gemm_desc e = {};
+            e.M = 0x7fffffff;
+            e.N = LN == LN_PRODUCE ? g.N : 0x7fffffff;
+            e.K = g.K;
+            e.Y = g.Y;
+            e.ldy = g.ldy;
+            e.y_dtype = g.y_dtype;
+            e.out_h = 1;
+            e.out_w = 0x7fffffff;
+            e.y_mul_x = 1;
+            e.y_off = g.y_off;
+            e.y2 = g.y2;
+            e.ldy2 = g.ldy2;
+            e.ln_part = g.ln_part;
             g4_for<4>([&](auto c_) {
                 constexpr int c = decltype(c_)::value, h = c >> 1, mh = c & 1;
                 __builtin_amdgcn_sched_barrier(0);
@@ -506,155 +689,51 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                     constexpr int q = decltype(q_)::value;
                     t[q >> 2][q & 3] = g4_acc_read<(h * 8 + mh * 4 + (q >> 2)) * 4 + (q & 3), q == 0>();
                 });
-                if constexpr (QF == 1) {
-                    // N = 2C: 64 packed columns per head; P[frame][sequence][head][lane][4]: one store instruction = 1 KiB contiguous
-                    float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4) * (g.N >> 6) + (n0 >> 6) + h) * 256 + (qgrp * 16 + ql15) * 4;
+                [[maybe_unused]] LnConsume lnc;
+                if constexpr (LN == LN_CONSUME) {
 #pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        uint2 pk[4];
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const f32x4 v = (t[mt][nt] - lns[h][nt] * ln_mean[mh * 4 + mt]) * ln_rstd[mh * 4 + mt] + biasm[h][nt];      // epilogue_lean's LN_CONSUME
-                            pk[nt] = uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])};
-                        }
-                        // attention_mfma_kernel, one key block, every key visible: S^T = K Q^T, scale, max, exp
-                        f32x4 st = g4_epi_qk<HF>(u32x4{pk[2].x, pk[2].y, pk[3].x, pk[3].y}, u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y});
-                        // (no contraction: there the scaled scores pass a select before the maximum is taken off, so the product is rounded --
-                        // s * scale - max as ONE fma would give exp(> 0) at the maximum itself)
-                        f32x4 p;
-                        {
-#pragma clang fp contract(off)
-                            float mx = -INFINITY;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                st[e] = st[e] * g.attn_scale;
-                                mx = fmaxf(mx, st[e]);
-                            }
-                            mx = fmaxf(mx, __shfl_xor(mx, 16));
-                            mx = fmaxf(mx, __shfl_xor(mx, 32));
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) p[e] = expf(st[e] - mx);
-                        }
-                        *(f32x4*)(pp + (long)mt * (g.N >> 6) * 256) = p;
+                    for (int a = 0; a < 4; ++a) {
+                        lnc.mean[a] = ln_mean[mh * 4 + a];
+                        lnc.rstd[a] = ln_rstd[mh * 4 + a];
                     }
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) lnc.s[b] = lns[h][b];
+                    if (g.y_dtype == MAGE_F32) epilogue_lean<ACT, float, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0, &lnc);
+                    else epilogue_lean<ACT, H16, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0, &lnc);
+                } else if constexpr (LN == LN_DUAL || LN == LN_GELUBWD) {
+                    epilogue_lean<ACT, unsigned short, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);       // bf16 rows (host check)
                 } else {
-                    const long shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
-                    // the two heads' 16 rows x 64 B through the wave's staging window (epilogue_lean's swizzle; a wave's DS operations execute in order):
-                    // stored as 2 x (8 rows x 128 B) instead of 2 x (16 rows x 64 B)
-                    const int srow = (qgrp * 16 + ql15) >> 3, scc = ql15 & 7;
-                    H16* op = (H16*)g.Y + n0 + h * 64 + scc * 8;
-                    const int wchunk = (qgrp & 1) * 2 + (qgrp >> 1);
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        f32x4 mean4, rstd4;            // the statistics of this lane's four rows of the transposed blocks: 4 grp + e
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            mean4[e] = __shfl(ln_mean[mh * 4 + mt], 4 * grp + e);
-                            rstd4[e] = __shfl(ln_rstd[mh * 4 + mt], 4 * grp + e);
-                        }
-#pragma unroll
-                        for (int hd = 0; hd < 2; ++hd) {
-                            const f32x4 p = pl[mt][hd];
-                            float den = 0.f;
-                            ashort4 phi, plo;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                den += p[e];
-                                short ph, pw;
-                                attn_p_split<H16>(p[e], ph, pw);
-                                phi[e] = ph;
-                                plo[e] = pw;
-                            }
-                            den += __shfl_xor(den, 16);
-                            den += __shfl_xor(den, 32);
-                            if constexpr (c < 3) {
-                                if (hd == 1) qf_p_request(mt, (c + 1) >> 1, (c + 1) & 1);
-                            }
-                            f32x4 o[2];
-                            ashort4 vt[2];
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) {
-                                const int nt = hd * 2 + b;
-                                const f32x4 v = (t[mt][nt] - mean4 * lns[h][0][nt]) * rstd4 + biasm[h][0][nt];
-                                vt[b] = __builtin_bit_cast(ashort4, uint2{pack16x2<H16>(v[0], v[1]), pack16x2<H16>(v[2], v[3])});
-                            }
-                            g4_epi_pv<HF>(vt[0], vt[1], phi, plo, o[0], o[1]);
-                            const float inv = 1.0f / den;
-                            f32x4 v0, v1;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[0][e]), __float_as_uint(o[1][e]), false, false);
-                                v0[e] = __uint_as_float(sw[0]) * inv;
-                                v1[e] = __uint_as_float(sw[1]) * inv;
-                            }
-                            *(u32x4*)(win + ql15 * 128 + (((hd * 4 + wchunk) ^ ((ql15 >> 1) & 7)) << 4)) =
-                                u32x4{pack16x2<H16>(v0[0], v0[1]), pack16x2<H16>(v0[2], v0[3]), pack16x2<H16>(v1[0], v1[1]), pack16x2<H16>(v1[2], v1[3])};
-                        }
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const int r = srow + 8 * i;
-                            const long yrow = (long)tm * 256 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
-                            *(u32x4*)(op + yrow * g.ldy) = *(const u32x4*)(win + r * 128 + ((scc ^ ((r >> 1) & 7)) << 4));
-                        }
-                    }
+                    if (g.y_dtype == MAGE_F32) epilogue_lean<ACT, float, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);
+                    else epilogue_lean<ACT, H16, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);
                 }
             });
-        } else {
-        mage_gemm_desc e = {};
-        e.M = 0x7fffffff;
-        e.N = LN == LN_PRODUCE ? g.N : 0x7fffffff;
-        e.K = g.K;
-        e.Y = g.Y;
-        e.ldy = g.ldy;
-        e.y_dtype = g.y_dtype;
-        e.out_h = 1;
-        e.out_w = 0x7fffffff;
-        e.y_mul_x = 1;
-        e.y_off = g.y_off;
-        e.y2 = g.y2;
-        e.ldy2 = g.ldy2;
-        e.ln_part = g.ln_part;
-        g4_for<4>([&](auto c_) {
-            constexpr int c = decltype(c_)::value, h = c >> 1, mh = c & 1;
-            __builtin_amdgcn_sched_barrier(0);
-            f32x4 t[4][4];
-            g4_for<16>([&](auto q_) {
-                constexpr int q = decltype(q_)::value;
-                t[q >> 2][q & 3] = g4_acc_read<(h * 8 + mh * 4 + (q >> 2)) * 4 + (q & 3), q == 0>();
-            });
-            [[maybe_unused]] LnConsume lnc;
-            if constexpr (LN == LN_CONSUME) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    lnc.mean[a] = ln_mean[mh * 4 + a];
-                    lnc.rstd[a] = ln_rstd[mh * 4 + a];
-                }
-#pragma unroll
-                for (int b = 0; b < 4; ++b) lnc.s[b] = lns[h][b];
-                if (g.y_dtype == MAGE_F32) epilogue_lean<ACT, float, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0, &lnc);
-                else epilogue_lean<ACT, H16, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0, &lnc);
-            } else if constexpr (LN == LN_DUAL || LN == LN_GELUBWD) {
-                epilogue_lean<ACT, unsigned short, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);       // bf16 rows (host check)
-            } else {
-                if (g.y_dtype == MAGE_F32) epilogue_lean<ACT, float, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);
-                else epilogue_lean<ACT, H16, 4, false, LN>(e, biasm[h], t, m0 + mh * 64, n0 + h * 64, lane, 1, win, 0);
             }
-        });
-        }
 #endif
-        G4_STAMP(it, 2);
-        // the next tile's first fragments (its slab 0 has been in stage 0 since the last slab's barrier)
-        __builtin_amdgcn_sched_barrier(0);
-        if (c_tile + nwg8 < chunk1) {
+            G4_STAMP(it, 2);
+            // the next tile's first fragments (its slab 0 has been in stage 0 since the last slab's barrier)
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (KEEP) {                          // the entry's V part
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) rd_wv(0, 0, 0, nt);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) rd_x1(0, 0, 0, m);
+            } else if (c_tile + nwg8 < chunk1) {
 #ifdef MAGE4_MFMA32
 #pragma unroll
-            for (int b = 0; b < 4; ++b) { rd_w32(0, 0, 0, b); rd_x32(0, 0, 0, b); }
+                for (int b = 0; b < 4; ++b) { rd_w32(0, 0, 0, b); rd_x32(0, 0, 0, b); }
 #else
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) rd_w1(0, 0, 0, nt);
+                for (int nt = 0; nt < 8; ++nt) rd_w1(0, 0, 0, nt);
 #pragma unroll
-            for (int m = 0; m < 4; ++m) rd_x1(0, 0, 0, m);
+                for (int m = 0; m < 4; ++m) rd_x1(0, 0, 0, m);
 #endif
+            }
+        };
+        if constexpr (QF == 3) {
+            tile(std::integral_constant<int, 1>{});
+            tile(std::integral_constant<int, 2>{});
+        } else {
+            tile(std::integral_constant<int, QF>{});
         }
     }
 }
@@ -663,7 +742,7 @@ template <int ACT, int EK, int LN, bool RB, bool HF = false>
 __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
     gemm4_body<ACT, EK, LN, RB, HF, 0>(g);
 }
-// QF = 1: the Q K launch, 2: the V launch of the fused H / W axial attention pair (see gemm4_body)
+// QF = 1: the Q K launch, 2: the V launch of the fused H / W axial attention pair, 3: both in one launch (see gemm4_body)
 template <bool HF, int QF>
 __global__ __launch_bounds__(256) void gemm4_attn_kernel(const Gemm4Args g) {
     gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, QF>(g);
@@ -697,7 +776,7 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, float* attn_p = nu
     a.y_dtype = d->y_dtype;
     a.a_off = d->a_off;
     a.y_off = d->y_off;
-    a.ntiles_n = d->N / 256;
+    a.ntiles_n = d->N / (QF == 3 ? 384 : 256);          // (QF 3: an entry = 256 [q | k] + 128 v rows of the packed weight)
     a.ntiles = (d->M / 256) * a.ntiles_n;
     // staggered start (gemm.hip, launch_tile): the workgroups of an XCD start in G groups spread over a fraction of one tile period, so that
     // the tiles' output bursts (128-256 KiB per CU at once: HBM-bound when all 256 CUs store together) fall under other groups' K loops
@@ -1045,6 +1124,46 @@ extern "C" int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* d, int32_t
     mage_gemm_plan = nullptr;
     if (r != MAGE_OK) return r;
     return mage_kernel_symbol_name(kernel, buf, len, "mage_gemm_attn_fused_kernel_name");
+}
+
+// The pair as ONE launch (include/mage_hip_ext.h): N = 3C, W / bias / ln_colsum packed per group of 4 heads, ao out; no P
+extern "C" int mage_gemm_attn_fused_qkv(const mage_gemm_desc* d, int32_t axis, float scale, void* stream) {
+    MAGE_CHECK_ARG(d != nullptr, "mage_gemm_attn_fused_qkv: null descriptor");
+    MAGE_CHECK_ARG(axis == 1 || axis == 2, "mage_gemm_attn_fused_qkv: axis %d (1 = H, 2 = W of 16 x 16 frames)", (int)axis);
+    MAGE_CHECK_ARG(d->dtype == MAGE_BF16 || d->dtype == MAGE_F16, "mage_gemm_attn_fused_qkv: bf16 or f16 operands");
+    MAGE_CHECK_ARG(d->A && d->W && d->Y && d->bias && d->ln_stats && d->ln_colsum, "mage_gemm_attn_fused_qkv: A, W, Y, bias, ln_stats, ln_colsum must be given");
+    MAGE_CHECK_ARG(d->M > 0 && d->M % 256 == 0 && d->N > 0 && d->N % 384 == 0 && d->K % 128 == 0 && d->K >= 256 && d->K <= 1024,
+                   "mage_gemm_attn_fused_qkv: M=%d a multiple of 256 (whole 16 x 16 frames), N=%d = 3C a multiple of 384 (groups of 4 heads of width 32), K=%d a "
+                   "multiple of 128 in [256, 1024]", d->M, d->N, d->K);
+    MAGE_CHECK_ARG(d->taps_h * d->taps_w == 1 && d->stride == 1 && !d->dy0 && !d->dx0 && d->in_h == 1 && d->out_h == 1 && d->in_w == d->out_w && !d->a_half &&
+                       d->y_mul_x == 1 && (d->out_w >= d->M || (d->out_w % 256 == 0 && d->a_img_stride == d->out_w)) && d->a_off % 256 == 0 && d->a_off >= 0,
+                   "mage_gemm_attn_fused_qkv: plain rows in (a_off a multiple of 256), output rows regrouped whole frames at a time");
+    MAGE_CHECK_ARG(!d->scale && !d->shift && !d->rowadd && !d->residual && !d->post_relu && !d->res_half && !d->y2 && !d->ln_part && !d->head_w && !d->a_relu &&
+                       d->n_split <= 1 && d->act == MAGE_ACT_NONE,
+                   "mage_gemm_attn_fused_qkv: the LayerNorm-consuming bias epilogue only");
+    MAGE_CHECK_ARG(d->y_dtype == d->dtype && d->ldy % 8 == 0 && d->ldy >= d->N / 3 && (((uintptr_t)d->Y) & 15) == 0 && d->y_off >= 0,
+                   "mage_gemm_attn_fused_qkv: 16-bit output rows of the operands' type, ldy a multiple of 8 and >= C, Y 16-byte aligned");
+    const int ldw = d->ldw ? d->ldw : d->K;
+    MAGE_CHECK_ARG(ldw == d->K && d->lda % 8 == 0 && d->lda >= d->K, "mage_gemm_attn_fused_qkv: W packed [N][K], lda a multiple of 8");
+    MAGE_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->bias | (uintptr_t)d->ln_colsum) & 15) == 0 && (((uintptr_t)d->ln_stats) & 7) == 0,
+                   "mage_gemm_attn_fused_qkv: operands must be 16-byte aligned");
+    MAGE_CHECK_ARG(((long)d->M + d->a_off) * d->lda * 2 + 16384 < (1L << 32) && (long)d->N * ldw * 2 + 16384 < (1L << 32),
+                   "mage_gemm_attn_fused_qkv: operands beyond the kernel's 32-bit lane offsets");
+    hipStream_t s = (hipStream_t)stream;
+    const int n_cu = mage_gemm_cu_count();
+    const int r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 3>(d, s, n_cu, nullptr, axis, scale)
+                                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 3>(d, s, n_cu, nullptr, axis, scale);
+    return r < 0 ? r : MAGE_OK;
+}
+
+extern "C" int mage_gemm_attn_fused_qkv_kernel_name(const mage_gemm_desc* d, int32_t axis, char* buf, int32_t len) {
+    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_attn_fused_qkv_kernel_name: no buffer");
+    const void* kernel = nullptr;
+    mage_gemm_plan = &kernel;
+    const int r = mage_gemm_attn_fused_qkv(d, axis, 1.f, nullptr);
+    mage_gemm_plan = nullptr;
+    if (r != MAGE_OK) return r;
+    return mage_kernel_symbol_name(kernel, buf, len, "mage_gemm_attn_fused_qkv_kernel_name");
 }
 
 // mage_gemm_tn on the one-wave-per-SIMD schedule: 1 = launched, 0 = not eligible (gemm_tn.hip then runs its 8-wave kernel)

@@ -423,6 +423,7 @@ class FlatAxialDecoder(nn.Module):
         self.split_kind = 0                    # ops.BF16X3 / ops.F16X3: the fast parity modes (compute_dtype stays fp32)
         self.stream_bf16 = True                # bf16 mode: x stays in bf16 between the blocks (_stream_bf16)
         self.qk_fuse_tiles = 4                 # H / W attention inside the in_proj GEMM from this many V-launch tiles per CU on (_qk_fuse)
+        self.qkv_fuse_tiles = 4                # ... as ONE launch from this many (frame, group of 4 heads) entries per CU on (_qkv_fuse)
         self._derived = _Derived(self)
 
     def initialize_parameters(self):
@@ -472,6 +473,8 @@ class FlatAxialDecoder(nn.Module):
                 d[f"b{i}.{lin}.lnc"] = ((w.double() * bt.double()[None, :]).sum(1) + d[f"b{i}.{lin}.b"].double()).float().contiguous()
             if i % 3 and self.model_channels % 64 == 0:         # H / W blocks: in_proj as the fused attention pair takes it (_qk_fuse)
                 self._qk_fuse_pack(d, f"b{i}", d[f"b{i}.in_proj.lnw"], d[f"b{i}.in_proj.lns"], "")
+            if i % 3 and self.model_channels % 128 == 0:        # ... and as the single launch takes it (_qkv_fuse)
+                self._qkv_fuse_pack(d, f"b{i}", d[f"b{i}.in_proj.lnw"], d[f"b{i}.in_proj.lns"], "")
         return d
 
     def _fold(self, dt, B: int, hw: int) -> bool:
@@ -543,6 +546,31 @@ class FlatAxialDecoder(nn.Module):
         d[f"{p}.in_proj.qk.w{sfx}"], d[f"{p}.in_proj.qk.s{sfx}"] = lnw[idx].contiguous(), lns[idx].contiguous()
         d[f"{p}.in_proj.v.w{sfx}"], d[f"{p}.in_proj.v.s{sfx}"] = lnw[2 * Cc:].contiguous(), lns[2 * Cc:].contiguous()
         d[f"{p}.in_proj.qk.c"], d[f"{p}.in_proj.v.c"] = lnc[idx].contiguous(), lnc[2 * Cc:].contiguous()       # (fp32: one copy serves both types)
+
+    def _qkv_fuse(self, xb, M: int, fuse: bool) -> bool:
+        """The fused pair of a pass (_qk_fuse, whose conditions hold: `fuse`) runs as ONE launch per block (ops.gemm_attn_fused_qkv): the softmax
+        numerators stay in registers, no scratch.  Its tile list has one entry per (frame, group of 4 heads); from qkv_fuse_tiles = four entries
+        per CU on (the persistent kernel's own rule; timed at the cfg2 full loop only, 15 per CU -- the threshold itself is not measured);
+        below it the two launches run.  Both write the same bits.  config qkv_fuse = False (MAGE_NO_QKV_FUSE=1) turns it off."""
+        if not (fuse and config.get().qkv_fuse):
+            return False
+        Cc = self.model_channels
+        return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 4) * torch.cuda.get_device_properties(xb.device).multi_processor_count
+
+    def _qkv_fuse_w(self, d, p, dt):
+        """Block p's LayerNorm-folded in_proj operands as the single launch takes them: all 3C rows in ops.qkv_pack_rows' order, with their colsum
+        and bias.  bf16: from _build; f16: on first use."""
+        sfx = ".f16" if dt == F16 else ""
+        if f"{p}.in_proj.qkv.w{sfx}" not in d:
+            lnw, lns = self._ln_fold_w(d, p, "in_proj", dt)
+            self._qkv_fuse_pack(d, p, lnw, lns, sfx)
+        q = f"{p}.in_proj.qkv."
+        return dict(w=d[q + "w" + sfx], s=d[q + "s" + sfx], c=d[q + "c"])
+
+    def _qkv_fuse_pack(self, d, p, lnw, lns, sfx: str) -> None:
+        idx = ops.qkv_pack_rows(self.model_channels, lnw.device)
+        d[f"{p}.in_proj.qkv.w{sfx}"], d[f"{p}.in_proj.qkv.s{sfx}"] = lnw[idx].contiguous(), lns[idx].contiguous()
+        d[f"{p}.in_proj.qkv.c"] = d[f"{p}.in_proj.lnc"][idx].contiguous()       # (fp32: one copy serves both types)
 
     def _stats_inline(self, xb, M: int) -> bool:
         """One clip per call: every Linear that follows a LayerNorm (N = C .. 4C) runs on the few-rows kernel, which reduces the
@@ -682,7 +710,8 @@ class FlatAxialDecoder(nn.Module):
         hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
         geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
         fuse = self._qk_fuse(xb, M, hh, ww, fold and not inl, cache)
-        pscr = torch.empty(M, Cc // 32, 16, device=dev, dtype=F32) if fuse else None      # the fused pair's probabilities
+        fuse1 = self._qkv_fuse(xb, M, fuse)             # ... as one launch per block: the probabilities stay in registers
+        pscr = torch.empty(M, Cc // 32, 16, device=dev, dtype=F32) if fuse and not fuse1 else None      # the fused pair's probabilities
         for i in range(self.layers):
             p = f"b{i}"
             ln1 = ln if i else ln0
@@ -691,10 +720,14 @@ class FlatAxialDecoder(nn.Module):
             if fuse and i % 3:
                 # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): a Q K launch that leaves the softmax
                 # numerators, a V launch that finishes P V -- the same bits in ao as the QKV GEMM + ops.attention below, q and k never stored
-                f = self._qk_fuse_w(d, p, dt)
                 kw = dict(axis=i % 3, M=M, K=Cc, lda=Cc, ln_stats=stats)
-                ops.gemm_attn_fused(xb, f["wqk"], None, pscr, phase=1, N=2 * Cc, bias=f["cqk"], ln_colsum=f["sqk"], **kw)
-                ops.gemm_attn_fused(xb, f["wv"], ao, pscr, phase=2, N=Cc, ldy=Cc, bias=f["cv"], ln_colsum=f["sv"], **kw)
+                if fuse1:                               # both in one launch (QF = 3): P never leaves the wave
+                    f = self._qkv_fuse_w(d, p, dt)
+                    ops.gemm_attn_fused_qkv(xb, f["w"], ao, C_=Cc, ldy=Cc, bias=f["c"], ln_colsum=f["s"], **kw)
+                else:
+                    f = self._qk_fuse_w(d, p, dt)
+                    ops.gemm_attn_fused(xb, f["wqk"], None, pscr, phase=1, N=2 * Cc, bias=f["cqk"], ln_colsum=f["sqk"], **kw)
+                    ops.gemm_attn_fused(xb, f["wv"], ao, pscr, phase=2, N=Cc, ldy=Cc, bias=f["cv"], ln_colsum=f["sv"], **kw)
             elif i % 3 == 0 and cache is not None:
                 # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
                 # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)

@@ -354,6 +354,54 @@ def gemm_attn_fused(a: torch.Tensor, w: torch.Tensor, y: Optional[torch.Tensor],
     return p if phase == 1 else y
 
 
+def qkv_pack_rows(C_: int, device=None) -> torch.Tensor:
+    """Row order of the packed weight of gemm_attn_fused_qkv (mage_gemm_attn_fused_qkv): packed row n of the 3C rows = row index[n] of
+    in_proj's [q; k; v] rows.  Group g of 4 heads takes rows 384g .. 384g+383: the 256 rows of its heads in qk_pack_rows' order, then its 128 v
+    rows in their natural order."""
+    qk = qk_pack_rows(C_, device).view(C_ // 128, 256)
+    v = (2 * C_ + torch.arange(C_, device=device)).view(C_ // 128, 128)
+    return torch.cat([qk, v], dim=1).reshape(-1)
+
+
+def gemm_attn_fused_qkv(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, axis: int, M: int, C_: int, K: int, lda: int, bias, ln_stats, ln_colsum,
+                        ldy: int, scale: Optional[float] = None, a_off: int = 0, out_w: Optional[int] = None, y_img_stride: Optional[int] = None,
+                        y_off: int = 0):
+    """The fused H / W axial attention pair as ONE launch (mage_gemm_attn_fused_qkv): w, bias and ln_colsum are the 3 C_ rows of the LayerNorm-folded
+    in_proj in qkv_pack_rows' order; writes the attention output rows y [.., C_] -- the bits of gemm_attn_fused's two launches.  axis 1 = H,
+    2 = W of 16 x 16 frames; scale as ops.attention's."""
+    l, s = _dev(a)
+    assert w.dtype == a.dtype and y.dtype == a.dtype, (w.dtype, y.dtype)
+    out_w = M if out_w is None else out_w
+    d = GemmDesc()
+    d.dtype, d.M, d.N, d.K = code(a), M, 3 * C_, K
+    d.A, d.W, d.Y = a.data_ptr(), w.data_ptr(), _p(y)
+    d.lda, d.ldy, d.y_dtype = lda, ldy, code(y)
+    d.out_h, d.out_w, d.in_h, d.in_w = 1, out_w, 1, out_w
+    d.a_img_stride, d.a_off = out_w, a_off
+    d.taps_h, d.taps_w, d.cin, d.stride = 1, 1, K, 1
+    d.dys, d.dxs = 1, 1
+    d.y_img_stride = out_w if y_img_stride is None else y_img_stride
+    d.y_mul_y, d.y_mul_x, d.y_off = out_w, 1, y_off
+    d.bias, d.ln_stats, d.ln_colsum = _p(bias), _p(ln_stats), _p(ln_colsum)
+    d.n_split = 1
+    sc = float(32 ** -0.5 if scale is None else scale)
+    ev = None
+    if PROFILE.enabled:
+        buf = C.create_string_buffer(256)
+        _lib.check(l.mage_gemm_attn_fused_qkv_kernel_name(C.byref(d), axis, buf, len(buf)), l)
+        key = buf.value.decode()
+        if PROFILE.wants(key):
+            ev = PROFILE.begin()
+    _lib.check(l.mage_gemm_attn_fused_qkv(C.byref(d), axis, sc, s), l)
+    if ev is not None:
+        # algorithmic HBM bytes: the rows a read once (their second pass comes from L2), the weights, y written.  q, k, v and P never appear.
+        es = a.element_size()
+        nb = float(M) * K * es + 3.0 * C_ * K * es + float(M) * C_ * y.element_size()
+        fl = 2.0 * M * 3 * C_ * K + 6.0 * M * 16 * C_
+        PROFILE.end(key, ev, fl, nb)
+    return y
+
+
 def gemm_is_small(a: torch.Tensor, M: int, N: int, K: int) -> bool:
     """True if a bf16 plain GEMM of this size runs on the few-rows kernel on a's device (mage_gemm_is_small): its LayerNorm-consuming form
     then takes (mean, rstd) straight from the producer's partial sums (ln_part + ln_eps) and the mage_ln_stats launch can be skipped."""
