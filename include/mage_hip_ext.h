@@ -178,6 +178,30 @@ int mage_video_metrics(const float* video, int64_t video_clip_stride, const floa
 int mage_group_advantages(const float* frame_reward, int64_t groups, int32_t N, int32_t T, int32_t mode, float eps, float* reward,
                           float* advantage, void* stream);
 
+/* Per-frame reward-to-go returns and their group-relative advantages: no site in the reference.  Serves MAGE.rollout(credit='frame'): a
+ * frame's tokens are drawn given the earlier frames only, so they are credited with the rewards of their own frame and the later ones.
+ * frame_reward is fp32 [groups*N*T] in mage_group_advantages' layout.  returns (fp32 [groups*N*T]), in fp64 with gamma widened from fp32:
+ *   S[c,T-1] = r[c,T-1];   S[c,t] = r[c,t] + gamma * S[c,t+1]  from the last frame down;   G[c,t] = S[c,t] / T, rounded once to fp32.
+ * The product and the sum are rounded separately (no fma: a numpy restatement has the same bits).  gamma == 0 forms no product,
+ * S[c,t] = r[c,t], so a non-finite later frame does not reach an earlier one as 0 * inf; at gamma == 1 frame 0's return is the candidate's
+ * mean reward (mage_group_advantages' reward up to the order of the sum).
+ * advantage is fp32 [groups*N*slots]: frame t of candidate c of group g goes to ((g*N + c)*slots) + slot_off + t, every slot outside
+ * [slot_off, slot_off + T) is written as +0 (slots = L-1 and slot_off = k-1 under a context of k given frames: the layout of tokens).  With
+ * mean and std the mean and the population standard deviation of a (group, frame)'s N returns AS STORED (the fp32 values widened to fp64,
+ * added in candidate order) -- so advantage is a function of returns alone --
+ *   mode 0:  d = G - mean;          mode 1:  d / (std + eps),
+ * and d == 0 gives exactly +0 in both modes, mage_group_advantages' rule: a frame whose candidates all earned the same rewards from there
+ * on is all +0, also with eps = 0.  A (group, frame) whose N returns hold a NaN or an infinity gets NaN for all N candidates at that
+ * frame; through the recursion a non-finite reward at frame s reaches the frames t <= s of its group (gamma > 0) and no later one.
+ * Nothing is checked on the host.  Two launches give the same bits, and the bits of a (group, frame) depend on that group's rewards
+ * alone, not on groups or the group's place in the launch.  No floating-point atomics, plain vector-memory stores.
+ * groups > 0, N >= 2, T >= 1, slot_off >= 0, slots >= slot_off + T, groups*N*slots (hence groups*N*T) below 2^31, gamma in [0, 1], mode 0
+ * or 1, eps finite and >= 0, pointers non-null and 4-byte aligned: MAGE_EINVAL otherwise, nothing launched.
+ * One launch, one wave per group: a lane per candidate walks the recursion and stores the returns, then, behind a workgroup barrier, a
+ * lane per slot reads its frame's returns back and forms the statistics -- N > 64 and slots > 64 wrap over the lanes. */
+int mage_frame_advantages(const float* frame_reward, int64_t groups, int32_t N, int32_t T, float gamma, int32_t mode, float eps, int32_t slots,
+                          int32_t slot_off, float* returns, float* advantage, void* stream);
+
 /* Seeded standard-normal noise of the randomness branch: the reference draws it with torch.randn (mage_model.py:661), unseeded and kept
  * nowhere.  Serves batch['noise_seed'] of MAGE.autoregressive_generate and MAGE.rollout(noise='candidate') (mage_amd/modules/mage_model.py:
  * _anchor_tail), whose recorded noise MAGE.policy_loss then conditions on.

@@ -136,6 +136,7 @@ EXT_SIGNATURES = {
     "mage_adam_clipped": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, vp, f32, vp, vp]),
     "mage_video_metrics": (C.c_int, [vp, i64, vp, i64, i64, i32, i32, i32, i32, i64, f32, vp, vp, vp, vp]),
     "mage_group_advantages": (C.c_int, [vp, i64, i32, i32, i32, f32, vp, vp, vp]),
+    "mage_frame_advantages": (C.c_int, [vp, i64, i32, i32, f32, i32, f32, i32, i32, vp, vp, vp]),
     "mage_video_noise": (C.c_int, [vp, i64, i32, i64, vp, vp, vp]),
     "mage_guide_logits": (C.c_int, [vp, vp, vp, i64, i32, i64, i64, i64, i64, vp, i64, vp]),
     "mage_preference_loss": (C.c_int, [vp, vp, i64, vp, i64, f32, f32, i32, vp, vp, vp, vp, vp]),

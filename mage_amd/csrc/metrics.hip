@@ -1,5 +1,5 @@
-// Per-frame video metrics (mage_video_metrics: MSE, PSNR, SSIM) and group-relative advantages (mage_group_advantages): the reward side of
-// MAGE.rollout.  include/mage_hip_ext.h states the rules; no site in the reference (it reports no metric and trains on cross-entropy only).
+// Per-frame video metrics (mage_video_metrics: MSE, PSNR, SSIM) and group-relative advantages (mage_group_advantages, per frame:
+// mage_frame_advantages): the reward side of MAGE.rollout.  include/mage_hip_ext.h states the rules; no site in the reference (it reports no metric and trains on cross-entropy only).
 #include "common.h"
 #include "../../include/mage_hip_ext.h"
 #include <math.h>
@@ -223,6 +223,58 @@ __global__ __launch_bounds__(64) void group_advantages_kernel(const float* __res
     }
 }
 
+// One wave per group.  Lane l first takes candidates l, l + 64, ...: a candidate's discounted sums run from its last frame down in fp64 (the
+// product and the sum rounded separately -- this file contracts nothing -- so numpy restates them bit for bit) and every return is rounded
+// once and stored.
+// Behind the barrier lane l takes slots l, l + 64, ... of the group's advantage rows: a slot inside the window reads its frame's N returns
+// back as stored (this workgroup's own stores; the barrier orders them) and adds them in candidate order, a slot outside it is zeros.
+__global__ __launch_bounds__(64) void frame_advantages_kernel(const float* __restrict__ frame_reward, int N, int T, double gamma, int mode,
+                                                              double eps, int slots, int slot_off, float* returns,
+                                                              float* __restrict__ advantage) {
+    const long g = blockIdx.x;
+    const int lane = threadIdx.x;
+    for (int c = lane; c < N; c += 64) {
+        const long row = (g * N + c) * T;
+        double s = (double)frame_reward[row + T - 1];
+        returns[row + T - 1] = (float)(s / (double)T);
+#pragma unroll 4
+        for (int t = T - 2; t >= 0; --t) {
+            const double r = (double)frame_reward[row + t];
+            s = gamma == 0.0 ? r : r + gamma * s;                // (gamma 0 forms no product: a later inf must not arrive as 0 * inf)
+            returns[row + t] = (float)(s / (double)T);
+        }
+    }
+    __syncthreads();
+    for (int j = lane; j < slots; j += 64) {
+        float* out = advantage + g * N * slots + j;
+        const int t = j - slot_off;
+        if (t < 0 || t >= T) {
+            for (int c = 0; c < N; ++c) out[(long)c * slots] = 0.f;
+            continue;
+        }
+        const float* v = returns + g * N * T + t;
+        double s = 0.0;
+#pragma unroll 4
+        for (int c = 0; c < N; ++c) s += (double)v[(long)c * T];
+        const double mean = s / (double)N;
+        double q = 0.0;
+#pragma unroll 4
+        for (int c = 0; c < N; ++c) {
+            const double d = (double)v[(long)c * T] - mean;
+            q += d * d;
+        }
+        const double sd = sqrt(q / (double)N);
+        const bool bad = !(fabs(s) <= 1.79769313486231570815e308);   // a NaN or an infinite return somewhere in this (group, frame)
+#pragma unroll 4
+        for (int c = 0; c < N; ++c) {
+            const double d = (double)v[(long)c * T] - mean;
+            double a = d == 0.0 ? 0.0 : mode == 0 ? d : d / (sd + eps);
+            if (bad) a = __builtin_nan("");
+            out[(long)c * slots] = (float)a;
+        }
+    }
+}
+
 bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 }  // namespace
@@ -278,5 +330,24 @@ extern "C" int mage_group_advantages(const float* frame_reward, int64_t groups, 
     hipLaunchKernelGGL(group_advantages_kernel, dim3((unsigned)groups), dim3(64), 0, (hipStream_t)stream, frame_reward, N, T, mode, (double)eps,
                        reward, advantage);
     MAGE_CHECK_LAUNCH("mage_group_advantages");
+    return MAGE_OK;
+}
+
+extern "C" int mage_frame_advantages(const float* frame_reward, int64_t groups, int32_t N, int32_t T, float gamma, int32_t mode, float eps,
+                                     int32_t slots, int32_t slot_off, float* returns, float* advantage, void* stream) {
+    MAGE_CHECK_ARG(frame_reward && returns && advantage, "mage_frame_advantages: null pointer");
+    MAGE_CHECK_ARG(aligned4(frame_reward) && aligned4(returns) && aligned4(advantage), "mage_frame_advantages: pointers must be 4-byte aligned");
+    MAGE_CHECK_ARG(groups > 0 && groups <= 0x7fffffffL && N >= 2 && T >= 1, "mage_frame_advantages: bad sizes groups=%ld N=%d (>= 2) T=%d (>= 1)",
+                   (long)groups, N, T);
+    MAGE_CHECK_ARG(slot_off >= 0 && (int64_t)slots >= (int64_t)slot_off + T,
+                   "mage_frame_advantages: slot_off=%d must be >= 0 and slots=%d >= slot_off + T (T=%d)", slot_off, slots, T);
+    MAGE_CHECK_ARG((int64_t)N * slots <= 0x7fffffffL / groups, "mage_frame_advantages: groups=%ld * N=%d * slots=%d must stay below 2^31",
+                   (long)groups, N, slots);                      // (slots >= T: groups * N * T stays below it too)
+    MAGE_CHECK_ARG(gamma >= 0.f && gamma <= 1.f, "mage_frame_advantages: gamma=%g must lie in [0, 1]", (double)gamma);
+    MAGE_CHECK_ARG(mode == 0 || mode == 1, "mage_frame_advantages: mode=%d is neither 0 (mean) nor 1 (mean and std)", mode);
+    MAGE_CHECK_ARG(eps >= 0.f && eps <= 3.4028234e38f, "mage_frame_advantages: eps=%g must be finite and >= 0", (double)eps);
+    hipLaunchKernelGGL(frame_advantages_kernel, dim3((unsigned)groups), dim3(64), 0, (hipStream_t)stream, frame_reward, N, T, (double)gamma, mode,
+                       (double)eps, slots, slot_off, returns, advantage);
+    MAGE_CHECK_LAUNCH("mage_frame_advantages");
     return MAGE_OK;
 }

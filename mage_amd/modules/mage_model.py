@@ -1325,7 +1325,8 @@ class MAGE(nn.Module):
         """Policy-gradient loss of given tokens under the policy set_sampling currently describes (sampling off: temperature 1, no filter):
         (loss, info) of one teacher-forced pass over frame 0 of batch['images'] (plus batch['text'] and the optional batch['speed'], as
         autoregressive_generate reads them) followed by `tokens` (int64 [B, L-1, h, w], e.g. last_tokens), ending in mage_policy_loss
-        (include/mage_hip_ext.h states the rule).  advantages: fp32 [B] (one per clip) or [B, L-1, h, w] (one per token).
+        (include/mage_hip_ext.h states the rule).  advantages: fp32 [B] (one per clip), [B, L-1] (one per frame:
+        rollout(credit='frame')'s) or [B, L-1, h, w] (one per token).
         behaviour_logprobs None: the reward-weighted likelihood, mean of -A logprob - entropy_coef entropy.  behaviour_logprobs fp32
         [B, L-1, h, w] (e.g. last_token_policy_logprobs of the call that drew the tokens): the clipped surrogate with the importance ratio
         rho = exp(logprob - behaviour), clipped to [1 - lo, 1 + hi]; clip is a float (lo = hi) or a (lo, hi) pair.  A token the current
@@ -1357,8 +1358,8 @@ class MAGE(nn.Module):
         t, k, p = self.sampling or (1.0, 0, 1.0)
         if k == 1:
             raise ValueError("policy_loss: top_k=1 is greedy decoding: its log-probability is 0 and has no gradient")
-        if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape)):
-            raise ValueError(f"policy_loss: advantages must be fp32 [{B}] or {list(tshape)}")
+        if not (torch.is_tensor(advantages) and advantages.dtype == F32 and tuple(advantages.shape) in ((B,), tshape[:2], tshape)):
+            raise ValueError(f"policy_loss: advantages must be fp32 [{B}], {list(tshape[:2])} or {list(tshape)}")
         b = behaviour_logprobs
         if b is not None and not (torch.is_tensor(b) and b.dtype == F32 and tuple(b.shape) == tshape):
             raise ValueError(f"policy_loss: behaviour_logprobs must be fp32 {list(tshape)} or None")
@@ -1647,7 +1648,8 @@ class MAGE(nn.Module):
 
     @torch.no_grad()
     def rollout(self, batch, candidates: int, reward="ssim", normalize="std", eps: float = 1e-6, reference: Optional["MAGE"] = None,
-                noise: str = "clip", pairs: Optional[str] = None, context: int = 1, known_tokens=None) -> dict:
+                noise: str = "clip", pairs: Optional[str] = None, context: int = 1, known_tokens=None, credit: str = "clip",
+                gamma: float = 1.0) -> dict:
         """What policy_loss consumes, from the model's own samples: `candidates` = N >= 2 sampled continuations of every clip of the batch
         under the sampler set_sampling describes, ALL of them kept and decoded (set_sampling(candidates=N) keeps only the likeliest), each
         rewarded on the device, and the rewards turned into group-relative advantages:
@@ -1691,6 +1693,14 @@ class MAGE(nn.Module):
         runs as written; the reference's scores leave the given slots out alike.  Under context=k the video holds the k given frames
         verbatim and the built-in rewards average over the generated frames k .. L-1 alone ('frame_metrics' is [B*N, L-k]: the given frames
         would add a constant); with known_tokens alone all L-1 frames count.
+        credit='frame' (with gamma in [0, 1]; the default 'clip' is everything above, launch for launch, and takes no gamma but 1): a
+        frame's tokens are drawn given the earlier frames only, so they are credited with their own frame's reward and the later ones',
+        not with the clip's.  'returns' (fp32 [B*N, L-k]) holds every generated frame's discounted reward-to-go over L-k, G[t] = (r[t] +
+        gamma r[t+1] + gamma^2 r[t+2] + ...) / (L-k), and 'advantages' becomes fp32 [B*N, L-1] in the layout of tokens and given (slot i is
+        frame i+1; the slots of given frames hold +0): each return against the same frame of its clip's N candidates, as normalize says
+        (mage_frame_advantages; None: the returns themselves) -- policy_loss takes that shape as it stands.  'rewards' stays the
+        per-candidate mean and pairs= its best and worst.  A callable reward must then return fp32 [B*N, L-k], one reward per generated
+        frame.  Generation does not depend on credit: the same seeds give the same tokens.
         One eager pass over B*N rows behind one prologue per clip, in either ar_mode: no graph replay and no multi-stream grouping
         (use_graph and streams are ignored).  The model's set_sampling / set_logprobs settings and every last_* result are left as found."""
         self._refuse_guided("rollout")
@@ -1706,6 +1716,12 @@ class MAGE(nn.Module):
                                  "tensor per clip and cannot describe N candidates -- drop it, or use noise='clip'")
         if pairs not in (None, "best_worst"):
             raise ValueError(f"rollout: pairs must be 'best_worst' or None, got {pairs!r}")
+        if credit not in ("clip", "frame"):
+            raise ValueError(f"rollout: credit must be 'clip' or 'frame', got {credit!r}")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"rollout: gamma must be a number in [0, 1], got {gamma!r}")
+        if credit == "clip" and gamma != 1:
+            raise ValueError(f"rollout: gamma={gamma!r} discounts per-frame returns: it needs credit='frame' (credit='clip' averages the frames)")
         if not self.use_cids:
             raise ValueError("rollout: a use_cids=False (MAGE+) model regresses continuous latents; it has no tokens to sample")
         if self.sampling is None:
@@ -1734,6 +1750,7 @@ class MAGE(nn.Module):
                 raise ValueError("rollout: known_tokens must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
         masked = context > 1 or known_tokens is not None
         builtin = not callable(reward)
+        per_frame = credit == "frame"
         if builtin and not (images.shape[1] >= L and images.dtype == F32 and min(images.shape[-2:]) >= 11):
             raise ValueError(f"rollout: reward '{reward}' compares with the ground truth: batch['images'] must be fp32 [B, {L}, C, H, W] with "
                              "H, W >= 11")
@@ -1775,11 +1792,20 @@ class MAGE(nn.Module):
                     else:
                         out["frame_metrics"] = None
                         fr = reward(video, out["batch"])
-                        if not (torch.is_tensor(fr) and fr.dtype == F32 and tuple(fr.shape) == (Bc * N,) and fr.device == images.device):
-                            raise ValueError(f"rollout: the reward callable must return fp32 [{Bc * N}] on the model's GPU")
+                        want = (Bc * N, L - context) if per_frame else (Bc * N,)
+                        if not (torch.is_tensor(fr) and fr.dtype == F32 and tuple(fr.shape) == want and fr.device == images.device):
+                            raise ValueError(f"rollout: the reward callable must return fp32 {list(want)} on the model's GPU"
+                                             + (" (credit='frame': one reward per generated frame)" if per_frame else ""))
                         fr = fr.contiguous()
                     out["rewards"], adv = ops.group_advantages(fr, groups=Bc, n_cand=N, mode=1 if normalize == "std" else 0, eps=float(eps))
-                    out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
+                    if per_frame:                            # slot i is frame i + 1: the generated frames start at slot context - 1
+                        out["returns"], adv = ops.frame_advantages(fr, groups=Bc, n_cand=N, gamma=float(gamma), mode=1 if normalize == "std" else 0,
+                                                                   eps=float(eps), slots=L - 1, slot_off=context - 1)
+                        if normalize is None:                # (the slots of the given frames stay the kernel's +0)
+                            adv[:, context - 1:] = out["returns"]
+                        out["advantages"] = adv
+                    else:
+                        out["advantages"] = adv if normalize is not None else out["rewards"].reshape(-1).clone()
                     giv = {"given": out["given"]} if masked else {}
                     if reference is not None:
                         theirs = (reference.sampling, reference.candidates)

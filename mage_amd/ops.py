@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "frame_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -990,6 +990,23 @@ def group_advantages(frame_reward: torch.Tensor, *, groups: int, n_cand: int, mo
     _lib.check(l.mage_group_advantages(frame_reward.data_ptr(), groups, n_cand, frame_reward.numel() // (groups * n_cand), int(mode), float(eps),
                                        reward.data_ptr(), advantage.data_ptr(), s), l)
     return reward, advantage
+
+
+def frame_advantages(frame_reward: torch.Tensor, *, groups: int, n_cand: int, gamma: float = 1.0, mode: int = 1, eps: float = 1e-6,
+                     slots: Optional[int] = None, slot_off: int = 0):
+    """(returns [groups * n_cand, T] fp32, advantage [groups * n_cand, slots] fp32) of frame_reward [groups * n_cand, T] fp32: each frame's
+    discounted reward-to-go over T, and it against the same frame of its group's candidates (mode 0: mean; mode 1: mean and standard
+    deviation), frame t in slot slot_off + t and +0 elsewhere; slots None: slot_off + T (mage_frame_advantages)."""
+    l, s = _dev(frame_reward)
+    assert frame_reward.dtype == torch.float32 and frame_reward.is_contiguous() and groups > 0 and n_cand > 0
+    assert frame_reward.numel() > 0 and frame_reward.numel() % (groups * n_cand) == 0
+    T = frame_reward.numel() // (groups * n_cand)
+    slots = int(slot_off) + T if slots is None else int(slots)
+    returns = torch.empty(groups * n_cand, T, device=frame_reward.device, dtype=torch.float32)
+    advantage = torch.empty(groups * n_cand, slots, device=frame_reward.device, dtype=torch.float32)
+    _lib.check(l.mage_frame_advantages(frame_reward.data_ptr(), groups, n_cand, T, float(gamma), int(mode), float(eps), slots, int(slot_off),
+                                       returns.data_ptr(), advantage.data_ptr(), s), l)
+    return returns, advantage
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
