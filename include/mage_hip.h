@@ -348,7 +348,13 @@ int mage_vq_prepare(const float* codebook, int32_t K, int32_t D, float* codebook
  * Row i in [0, rows) is read from logits row  (i / group)*in_group_stride + i % group + in_off  (fp32, leading
  * dim ld) and its index written to out[(i / group)*out_group_stride + i % group + out_off] (int64): this is how
  * frame i of every clip is picked out of [B, L-1, hw, K] logits and written into slot i+1 of the token buffer
- * without copies.  margin (optional, [rows] fp32) receives best minus second-best. */
+ * without copies.  margin (optional, [rows] fp32, margin[i]: no map) receives best minus second-best.
+ * NaN logits are skipped (never the maximum, never the second best); -0 == +0.  A row of NaNs only yields 0x7fffffff: no
+ * code; mage_sample_tokens' "token 0 for an empty set" does not apply here.  margin is ONE fp32 subtraction best - second:
+ * exactly 0 at a tie (with IEEE's sign: -0 when the pick is a -0 and its rival a +0), +inf where a single non-NaN code exists (its second best is -inf), NaN for inf - inf (two +inf
+ * logits, or no code above -inf).
+ * K % 4 == 0 (any K: no upper limit), ld % 4 == 0, ld >= K, logits 16-byte aligned (the rows are read as 16-byte vectors),
+ * group > 0, rows > 0: MAGE_EINVAL otherwise, nothing launched. */
 int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,
                 int64_t in_off, int64_t* out, int64_t out_group_stride, int64_t out_off, float* margin, void* stream);
 
@@ -358,7 +364,8 @@ int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_
  * (vq.hip states it in full): s = logits * (float)(1.0 / temperature); top_k in [0, K] (0 or K: off) keeps every code whose s is >= the
  * top_k-th largest; top_p in (0, 1] (1: off) keeps, of those, every code whose s is >= the largest value whose softmax mass from above
  * reaches top_p; the token is the smallest j of that set maximising s_j - log(-log(u_j)), u_j from hash32 of (seed, pos, j).  NaN logits
- * are never drawn.  top_k == 1 is greedy: mage_argmax.  K % 4 == 0, K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0, ld >= K, logits 16-byte aligned;
+ * are never drawn.  top_k == 1 is greedy: mage_argmax (its kernel: the "token 0" of an empty set does not apply on that path, a row of
+ * NaNs yields mage_argmax's 0x7fffffff).  K % 4 == 0, K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0, ld >= K, logits 16-byte aligned;
  * temperature finite and > 0: MAGE_EINVAL otherwise, nothing launched. */
 #define MAGE_SAMPLE_MAX_K 4096
 int mage_sample_tokens(const float* logits, int64_t rows, int32_t K, int64_t ld, int64_t group, int64_t in_group_stride,

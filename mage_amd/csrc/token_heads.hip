@@ -254,6 +254,9 @@ extern "C" int mage_argmax(const float* logits, int64_t rows, int32_t K, int64_t
                            void* stream) {
     MAGE_CHECK_ARG(logits && out, "mage_argmax: null pointer");
     MAGE_CHECK_ARG(rows > 0 && K > 0 && K % 4 == 0 && ld % 4 == 0 && group > 0, "mage_argmax: bad sizes rows=%ld K=%d", (long)rows, K);
+    // the rows are read as 16-byte vectors, K values of each: no K <= MAGE_SAMPLE_MAX_K here (token_rows_check), the kernel sweeps any K
+    MAGE_CHECK_ARG(ld >= K && (((uintptr_t)logits) & 15) == 0, "mage_argmax: K=%d ld=%ld logits=%p (ld >= K, logits 16-byte aligned)", K, (long)ld,
+                   (const void*)logits);
     hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)rows,
                        K, (long)ld, (long)group, (long)in_group_stride, (long)in_off, out, (long)out_group_stride,
                        (long)out_off, margin);

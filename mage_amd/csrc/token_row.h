@@ -22,7 +22,8 @@
 //      u_j = ((hash32(seed * 0x9e3779b97f4a7c15 + (pos * K + j)) >> 8) + 0.5) * 2^-24   (uint64 wrap-around arithmetic),
 //      g_j = -log(-log(u_j)), token = the smallest j in N that maximises s_j + g_j (no selectable code at all: token 0).
 // A token's random stream depends on its clip's seed, frame, pixel and code only: not on the batch size, the clip's place in the batch,
-// the AR mode, the number of streams or graph replay.  top_k == 1 is greedy by definition: mage_argmax's kernel (first maximum wins).
+// the AR mode, the number of streams or graph replay.  top_k == 1 is greedy by definition: mage_argmax's kernel (first maximum wins; step 4's
+// "token 0" does not apply on that path: a row of NaNs yields mage_argmax's 0x7fffffff).
 // The selections are bit-by-bit bisections over order-preserving uint keys of s: top-k counts with ballots (a scalar count, no shuffles),
 // top-p sums the w_j with fixed-order butterflies.  Where the sums are rounded (W, the masses) a row whose boundary mass is within fp32
 // rounding of top_p * W may keep one value more or less than the exact rule; nothing else is approximate.
