@@ -375,6 +375,55 @@ int mage_policy_loss_masked_bwd(const float* logits, int64_t rows, int32_t K, in
                                 float temperature, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, const float* grad_out,
                                 const float* norm, void* dlogits, int32_t dl_dtype, const uint8_t* given, void* stream);
 
+/* The clipped surrogate with ONE importance ratio per group of consecutive rows -- a frame or a clip -- in place of one per token: the
+ * length-normalised sequence ratio of GSPO (Zheng et al., "Group Sequence Policy Optimization", 2025) over the unit that is an action here
+ * (all h*w tokens of a frame are drawn in one step).  No site in the reference.  Serves MAGE.policy_loss(ratio='frame' | 'clip')
+ * (mage_amd/modules/mage_train.py: PolicyHead with a 'ratio_div' argument).
+ * The arguments are mage_policy_loss_masked's -- here given MAY be null (every row free) -- plus ratio_div, group_logratio (fp32
+ * [rows / ratio_div]) and group_count (int32 [rows / ratio_div]); the backward call takes mage_policy_loss_masked_bwd's plus ratio_div and
+ * group_logratio as the forward call left it.
+ *   Rows are ordered clip, frame, pixel; group g holds rows [g*ratio_div, (g+1)*ratio_div): ratio_div = h*w is a frame, (L-1)*h*w a clip.
+ *   cut, logprob, entropy and kl come from mage_policy_loss_masked's row kernel instances, unchanged: they carry, bit for bit, what that
+ *   call writes on the same inputs (without given and without a reference: what mage_policy_loss / mage_policy_loss_anchored write).
+ *   A row COUNTS in its group if it is free (given[i] == 0, or no mask) and inside (logprob != -inf).  For a counted row
+ *   d_i = logprob_i - b_i, one fp32 subtraction (the value the token rule feeds to expf).  Then
+ *     n_g = the number of counted rows -> group_count[g];
+ *     m_g = (float)((sum over the counted rows of (double)d_i) / n_g) -> group_logratio[g];   n_g == 0: m_g = +0.
+ *   The sum is fp64 in a fixed order: a thread adds its rows in ascending order, the lanes meet in an xor butterfly, the waves are added in
+ *   order.  A NaN d_i makes its group NaN.
+ *   rho_g = expf(m_g).  Every counted row takes the token rule's clipped term with rho_g for its own rho, A = advantage[i / adv_div]:
+ *     l_i = -min(rho_g A, clamp(rho_g, 1 - clip_lo, 1 + clip_hi) A) - entropy_coef H_i   [+ kl_coef kl_i under the anchored rule],
+ *   the products and sums in fp64 and rounded once, as mage_policy_loss / mage_policy_loss_anchored form them.  An outside row and a given
+ *   row are what they are in the masked call (+0).
+ *   summary and norm: the masked call's eight values by the same two-stage fixed-order reduction through the same per-device buffer (so
+ *   the ordering rule between calls holds); norm[0] = 1.0f / (float)n_free, n_free = rows without a mask.  summary[3], the clipped share,
+ *   stays a share of ROWS: the rows of the groups whose gradient the clip switched off.
+ *   Backward: rho_g = expf(group_logratio[g]) by the same operation, the same branch; g_i = -(A * rho_g) where the unclipped term is the
+ *   active one, 0 otherwise, plus the anchored part as in mage_policy_loss_anchored_bwd; the rest of dlogits is
+ *   mage_policy_loss_masked_bwd's formula.  Why g_i is not divided by n_g: the loss is (sum over rows of l_i) / n_free, the n_g counted rows
+ *   of a group ALL carry the term -rho_g A, and d rho_g / d logprob_i = rho_g / n_g; so d(sum) / d logprob_i = n_g (-A rho_g / n_g) =
+ *   -A rho_g -- the token rule's factor with rho_g substituted.
+ *   Exact cases.  ratio_div == 1: (float)(double)d_i == d_i, so every output of both calls carries mage_policy_loss_masked's bits (without
+ *   mask or reference: the plain / anchored pair's).  b_i with the bits of logprob_i on every counted row of a group: m_g = +0 and
+ *   rho_g = 1 exactly.
+ * Three steps on the stream: the row kernel, ONE group kernel (one wave per group up to 1024 rows, four groups per workgroup; one
+ * workgroup of 1024 threads per group above), the two summary stages.  The group kernel reads logprob, b, given and the group's advantage,
+ * writes group_logratio and group_count and rewrites row_loss of the counted rows.  No floating-point atomics, nothing read on the host:
+ * two launches on the same inputs give the same bits.
+ * The masked pair's argument rules (given aside); behaviour_logprob non-null; 1 <= ratio_div < 2^31; rows % ratio_div == 0;
+ * adv_div % ratio_div == 0 (a group has one advantage); group_logratio, group_count and norm non-null and 4-byte aligned: MAGE_EINVAL
+ * otherwise, nothing launched. */
+int mage_policy_loss_grouped(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                             int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, float temperature, int32_t top_k,
+                             float top_p, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, float* row_loss, float* logprob,
+                             float* entropy, uint32_t* cut, float* kl, float* summary, float* norm, const uint8_t* given, int64_t ratio_div,
+                             float* group_logratio, int32_t* group_count, void* stream);
+int mage_policy_loss_grouped_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* advantage,
+                                 int64_t adv_div, const float* behaviour_logprob, const float* reference_logprob, const uint32_t* cut,
+                                 float temperature, float clip_lo, float clip_hi, float entropy_coef, float kl_coef, const float* grad_out,
+                                 const float* norm, void* dlogits, int32_t dl_dtype, const uint8_t* given, int64_t ratio_div,
+                                 const float* group_logratio, void* stream);
+
 /* mage_token_logprob_bwd with given rows left out: no site in the reference.  Serves the backward pass of MAGE.preference_loss(given=).
  * mage_token_logprob_bwd's arguments plus given (uint8 [rows], as mage_policy_loss_masked's).  A given row is a row of c_i == 0: +0
  * throughout, its logits not read (a NaN there does not show); every other row carries mage_token_logprob_bwd's bits (one kernel template,

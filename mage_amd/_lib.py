@@ -149,6 +149,10 @@ EXT_SIGNATURES = {
     "mage_policy_loss_masked": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, f32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp]),
     "mage_policy_loss_masked_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp, vp]),
+    "mage_policy_loss_grouped": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, f32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, i64, vp, vp, vp]),
+    "mage_policy_loss_grouped_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp, i64, vp,
+                                               vp]),
     "mage_token_logprob_bwd_masked": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, i32, vp, vp]),
     "mage_distill_loss": (C.c_int, [vp, i64, i32, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp]),
     "mage_distill_loss_bwd": (C.c_int, [vp, i64, i32, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp, i32, vp]),

@@ -1011,6 +1011,7 @@ class MAGE(nn.Module):
         self.last_token_policy_entropy: Optional[torch.Tensor] = None    # entropy, sampling on: the filtered distribution's
         self.last_policy_token_logprobs: Optional[torch.Tensor] = None   # policy_loss: fp32 [B, L-1, h, w], the given tokens under the current policy
         self.last_policy_token_kl: Optional[torch.Tensor] = None         # policy_loss with a reference: fp32 [B, L-1, h, w], the k3 KL estimates
+        self.last_policy_group_logratio: Optional[torch.Tensor] = None   # policy_loss(ratio='frame' | 'clip'): fp32 [B, L-1] | [B], the groups' mean log-ratios
         self.last_video_noise: Optional[torch.Tensor] = None             # randomness: fp32 [B, 64, h, w], the noise the last generation used
         self.last_preference_clip_logprobs: Optional[torch.Tensor] = None    # preference_loss: fp32 [B], the clips' log-likelihoods under the model
         self.last_preference_clip_coef: Optional[torch.Tensor] = None        # fp32 [B]: d(loss) / d(clip log-likelihood)
@@ -1321,7 +1322,7 @@ class MAGE(nn.Module):
         return scores.view(B)
 
     def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0, reference_logprobs=None,
-                    kl_coef: float = 0.0, given=None):
+                    kl_coef: float = 0.0, given=None, ratio: str = "token"):
         """Policy-gradient loss of given tokens under the policy set_sampling currently describes (sampling off: temperature 1, no filter):
         (loss, info) of one teacher-forced pass over frame 0 of batch['images'] (plus batch['text'] and the optional batch['speed'], as
         autoregressive_generate reads them) followed by `tokens` (int64 [B, L-1, h, w], e.g. last_tokens), ending in mage_policy_loss
@@ -1352,6 +1353,18 @@ class MAGE(nn.Module):
         last_policy_token_logprobs / last_policy_token_kl hold 0 there.  With advantages 1, sampling off and entropy_coef 0 this is the
         cross-entropy over the free tokens only: the supervised loss for continuation fine-tuning.  Without given the call is the unmasked
         one in every launch.
+        ratio 'token' (the default: the calls above, launch for launch), 'frame' or 'clip': the unit that gets ONE importance ratio
+        (mage_policy_loss_grouped).  A frame's h*w tokens are drawn in one step, so a frame is one action: under 'frame' every token of a
+        frame is clipped by the frame's ratio rho_g = exp(mean over its free, drawable tokens of logprob - behaviour), the geometric mean
+        of their token ratios (GSPO's length-normalised sequence ratio); under 'clip' the group is all (L-1)*h*w tokens of a clip.
+        behaviour_logprobs is required (without one there is no ratio to group) and the advantages may not be finer than the group: [B] or
+        [B, L-1] under 'frame', [B] under 'clip'.  given, the reference KL, entropy_coef, the sampler's filter and randomness=True work as
+        under 'token', and info has the same keys ('clip_fraction' stays a share of tokens: those of the groups the clip switched off).
+        last_policy_group_logratio keeps the groups' mean log-ratios, fp32 [B, L-1] or [B] (0 for a group with nothing to count, e.g. a
+        frame given by a context); it is None under 'token'.
+            out = m.rollout(batch, 8, credit='frame', reference=ref)
+            m.policy_loss(out['batch'], out['tokens'], out['advantages'], out['behaviour_logprobs'],
+                          reference_logprobs=out['reference_logprobs'], kl_coef=0.1, given=out['given'], ratio='frame')
         Dropout follows self.training, as in forward: the ratios against a generation's log-probabilities are only meaningful in eval()."""
         from . import mage_train
         images, B, tshape, vn = self._given_tokens_inputs("policy_loss", batch, tokens)
@@ -1381,6 +1394,17 @@ class MAGE(nn.Module):
         if kl_coef > 0 and ref is None:
             raise ValueError("policy_loss: kl_coef > 0 needs reference_logprobs (the penalty is against a reference policy)")
         given = self._given_mask("policy_loss", given, tshape)
+        if ratio not in ("token", "frame", "clip"):
+            raise ValueError(f"policy_loss: ratio must be 'token', 'frame' or 'clip', got {ratio!r}")
+        ratio_div = None
+        if ratio != "token":
+            if b is None:
+                raise ValueError(f"policy_loss: ratio={ratio!r} needs behaviour_logprobs (without one there is no ratio to group)")
+            coarse = ((B,), tshape[:2]) if ratio == "frame" else ((B,),)
+            if tuple(advantages.shape) not in coarse:
+                raise ValueError(f"policy_loss: ratio={ratio!r} takes one ratio per {ratio}: advantages must be fp32 "
+                                 + " or ".join(str(list(c)) for c in coarse) + f", not finer than the group (got {list(advantages.shape)})")
+            ratio_div = tshape[2] * tshape[3] * (1 if ratio == "frame" else tshape[1])
         self._refuse_off_gpu("policy_loss", batch, images, tokens, vn, (("advantages", advantages), ("behaviour_logprobs", b),
                                                                        ("reference_logprobs", ref), ("given", given)))
         args = dict(advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo, clip_hi=hi,
@@ -1389,10 +1413,13 @@ class MAGE(nn.Module):
             args.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
         if given is not None:
             args.update(given=given.reshape(-1))
+        if ratio_div is not None:
+            args.update(ratio_div=ratio_div)
         with torch.cuda.device(images.device):
             loss, (info, res) = self._run_head(batch, mage_train.PolicyHead(tokens.contiguous(), **args))
             self.last_policy_token_logprobs = res["logprob"].view(tshape)
             self.last_policy_token_kl = None if res.get("kl") is None else res["kl"].view(tshape)
+            self.last_policy_group_logratio = None if ratio_div is None else res["group_logratio"].view(tshape[:2] if ratio == "frame" else (B,))
             ops.check_device_errors(images.device)
         return loss, info
 

@@ -582,6 +582,8 @@ def _policy_scalars(policy: dict) -> dict:
         kw.update(reference_logprob=policy["reference"], kl_coef=policy["kl_coef"])
     if policy.get("given") is not None:                  # the masked entry points, in either form
         kw.update(given=policy["given"])
+    if policy.get("ratio_div") is not None:              # the grouped entry points: one importance ratio per frame or clip
+        kw.update(ratio_div=policy["ratio_div"])
     return kw
 
 
@@ -625,7 +627,9 @@ class PolicyHead:
     rule).  args: advantage (fp32, one per clip or per token), behaviour (fp32 per token, or None) and the scalars temperature, top_k, top_p,
     clip_lo, clip_hi, entropy_coef [, reference (fp32 per token), kl_coef] of include/mage_hip_ext.h.  saved: the kernel's results
     (cut, logprob, summary [, kl]).  With a 'given' (bool per token: the token was given, not drawn) it is mage_policy_loss_masked: the means
-    are over the free tokens, parts gains 'given_fraction' and saved 'norm'."""
+    are over the free tokens, parts gains 'given_fraction' and saved 'norm'.  With a 'ratio_div' (rows per group) it is
+    mage_policy_loss_grouped, given or not: parts are what the same call reports without it, saved gains 'group_logratio' (backward's
+    input), 'group_count' and 'norm'."""
     PARTS = ("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction")
 
     def __init__(self, tokens, **args):
@@ -638,13 +642,17 @@ class PolicyHead:
         parts = dict(zip(self.PARTS, summary))
         if a.get("given") is not None:                   # summary [8]: the unmasked call's keys (5, or 7 with a reference) and the share
             parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary), given_fraction=summary[7])
+        elif a.get("ratio_div") is not None:             # summary [8] without a mask: the unmasked call's keys
+            parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary))
         return res["summary"][0], parts, res
 
     def backward(self, logits, target, saved, gout, dt):
         a = self.args
         kw = _policy_scalars(a)
-        if a.get("given") is not None:
+        if a.get("given") is not None or a.get("ratio_div") is not None:
             kw.update(norm=saved["norm"])
+        if a.get("ratio_div") is not None:
+            kw.update(group_logratio=saved["group_logratio"])
         return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **kw)
 
 

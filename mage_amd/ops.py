@@ -769,10 +769,21 @@ def _given_rows(given, logits):
         assert given.device == logits.device
 
 
+def _ratio_div(ratio_div, rows, adv_div, behaviour_logprob) -> int:
+    """The grouped pair's own rules (the library states them again): a ratio to group, groups that tile the rows inside one advantage each."""
+    if behaviour_logprob is None:
+        raise ValueError("policy_loss: ratio_div needs behaviour_logprob (without one there is no ratio to group)")
+    if isinstance(ratio_div, bool) or not isinstance(ratio_div, int) or ratio_div < 1:
+        raise ValueError(f"policy_loss: ratio_div must be an int >= 1, got {ratio_div!r}")
+    if rows % ratio_div or adv_div % ratio_div:
+        raise ValueError(f"policy_loss: rows={rows} and adv_div={adv_div} must be multiples of ratio_div={ratio_div} (a group has one advantage)")
+    return ratio_div
+
+
 def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor] = None, *,
                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, clip_lo: float = 0.2, clip_hi: float = 0.2,
                 entropy_coef: float = 0.0, adv_div: Optional[int] = None, reference_logprob: Optional[torch.Tensor] = None,
-                kl_coef: float = 0.0, given: Optional[torch.Tensor] = None) -> dict:
+                kl_coef: float = 0.0, given: Optional[torch.Tensor] = None, ratio_div: Optional[int] = None) -> dict:
     """mage_policy_loss over logits [rows, K] fp32 (row stride >= K) and tokens int64 [rows]; advantage fp32, row i using entry i // adv_div
     (default: rows / numel consecutive rows per entry); behaviour_logprob fp32 [rows] selects the clipped surrogate, None the reward-weighted likelihood.  Returns the per-row
     fp32 tensors 'row_loss', 'logprob', 'entropy', the uint32 thresholds 'cut' (kept as int32 storage: policy_loss_bwd's input) and
@@ -781,14 +792,29 @@ def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Ten
     against the reference policy, the result the per-row 'kl', and 'summary' is fp32 [7]: the five, the mean KL and the unanchored share.
     given bool [rows] (True: the row's token was given, not drawn): mage_policy_loss_masked in either form -- a given row is not read and
     gets zeros, 'summary' is fp32 [8]: the seven means over the free rows (the last two 0 without a reference) and the given share, and the
-    result gains 'norm' fp32 [1] = 1 / the number of free rows, policy_loss_bwd's input."""
+    result gains 'norm' fp32 [1] = 1 / the number of free rows, policy_loss_bwd's input.
+    ratio_div (None: the dispatch above, untouched): mage_policy_loss_grouped -- one importance ratio per group of ratio_div consecutive rows
+    (behaviour_logprob required; rows and adv_div multiples of ratio_div), with or without given and a reference; the masked call's results
+    plus 'group_logratio' fp32 and 'group_count' int32 [rows / ratio_div], policy_loss_bwd's input and the counted rows per group."""
     _policy_ref(reference_logprob, kl_coef, logits)
     _given_rows(given, logits)
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     mk = lambda n, dt: torch.empty(n, device=logits.device, dtype=dt)      # noqa: E731
     out = dict(row_loss=mk(rows, torch.float32), logprob=mk(rows, torch.float32), entropy=mk(rows, torch.float32), cut=mk(rows, torch.int32),
-               summary=mk(8 if given is not None else 5 if reference_logprob is None else 7, torch.float32))
+               summary=mk(8 if given is not None or ratio_div is not None else 5 if reference_logprob is None else 7, torch.float32))
+    if ratio_div is not None:
+        ratio_div = _ratio_div(ratio_div, rows, adv_div, behaviour_logprob)
+        out.update(norm=mk(1, torch.float32), group_logratio=mk(rows // ratio_div, torch.float32), group_count=mk(rows // ratio_div, torch.int32))
+        if reference_logprob is not None:
+            out["kl"] = mk(rows, torch.float32)
+        _lib.check(l.mage_policy_loss_grouped(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                              _p(behaviour_logprob), _p(reference_logprob), float(temperature), int(top_k), float(top_p),
+                                              float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
+                                              out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), _p(out.get("kl")),
+                                              out["summary"].data_ptr(), out["norm"].data_ptr(), _p(given), ratio_div,
+                                              out["group_logratio"].data_ptr(), out["group_count"].data_ptr(), s), l)
+        return out
     if given is not None:
         out["norm"] = mk(1, torch.float32)
         if reference_logprob is not None:
@@ -818,18 +844,32 @@ def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch
                     cut: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *, temperature: float = 1.0, clip_lo: float = 0.2,
                     clip_hi: float = 0.2, entropy_coef: float = 0.0, adv_div: Optional[int] = None,
                     reference_logprob: Optional[torch.Tensor] = None, kl_coef: float = 0.0, given: Optional[torch.Tensor] = None,
-                    norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    norm: Optional[torch.Tensor] = None, ratio_div: Optional[int] = None,
+                    group_logratio: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mage_policy_loss_bwd: dlogits [rows, K] contiguous fp32 or bf16 from policy_loss' inputs and its 'cut'; grad_out fp32 [1].  With
-    reference_logprob: mage_policy_loss_anchored_bwd.  With given (and the masked policy_loss' 'norm'): mage_policy_loss_masked_bwd."""
+    reference_logprob: mage_policy_loss_anchored_bwd.  With given (and the masked policy_loss' 'norm'): mage_policy_loss_masked_bwd.  With
+    ratio_div (and the grouped policy_loss' 'norm' and 'group_logratio'; given or not): mage_policy_loss_grouped_bwd."""
     _policy_ref(reference_logprob, kl_coef, logits)
     _given_rows(given, logits)
-    assert (given is None) == (norm is None), "given and norm come together (the masked forward call writes norm)"
+    assert (ratio_div is None) == (group_logratio is None), "ratio_div and group_logratio come together (the grouped forward call writes it)"
+    assert (given is None and ratio_div is None) == (norm is None), "given / ratio_div and norm come together (the forward call writes norm)"
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
     assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.numel() == rows and cut.device == logits.device
     assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
     assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
     assert dlogits.device == logits.device
+    if ratio_div is not None:
+        ratio_div = _ratio_div(ratio_div, rows, adv_div, behaviour_logprob)
+        assert norm.dtype == torch.float32 and norm.numel() == 1 and norm.device == logits.device
+        assert group_logratio.dtype == torch.float32 and group_logratio.is_contiguous() and group_logratio.numel() == rows // ratio_div
+        assert group_logratio.device == logits.device
+        _lib.check(l.mage_policy_loss_grouped_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
+                                                  _p(behaviour_logprob), _p(reference_logprob), cut.data_ptr(), float(temperature),
+                                                  float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(),
+                                                  norm.data_ptr(), dlogits.data_ptr(), code(dlogits), _p(given), ratio_div,
+                                                  group_logratio.data_ptr(), s), l)
+        return dlogits
     if given is not None:
         assert norm.dtype == torch.float32 and norm.numel() == 1 and norm.device == logits.device
         _lib.check(l.mage_policy_loss_masked_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
