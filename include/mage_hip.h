@@ -494,7 +494,8 @@ int mage_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t r
  * arow = img*img_stride + (oy+dy)*in_w + (ox+dx) + a_off, zero outside [0,in_h) x [0,in_w).  Plain transpose: out_h = 1,
  * out_w = M, dy = dx = 0, stride = 1.  The conv3x3 weight gradient (mage_model.py:485-488) stacks nine calls (dy, dx = tap - 1,
  * y_row0 = tap*C); with `stride` the gathered pixel is (oy*stride+dy, ox*stride+dx): the 4x4 / stride-2 convolutions and
- * transposed convolutions of the VQ-VAE (vqvae_model.py:173-188).  dtype: MAGE_F32 | MAGE_BF16 (x and y). */
+ * transposed convolutions of the VQ-VAE (vqvae_model.py:173-188).  dtype: MAGE_F32 | MAGE_BF16 (x and y).  ldx >= C (rows of x may not
+ * alias), here and in mage_transpose_colsum: MAGE_EINVAL otherwise, as mage_mse refuses lda < cols. */
 int mage_transpose(const void* x, int32_t dtype, int64_t ldx, void* y, int64_t ldy, int64_t y_row0, int64_t M, int64_t Mp, int32_t C,
                    int32_t out_h, int32_t out_w, int32_t in_h, int32_t in_w, int64_t img_stride, int64_t a_off, int32_t dy, int32_t dx,
                    int32_t stride, void* stream);
@@ -510,7 +511,8 @@ int mage_transpose_colsum(const void* x, int64_t ldx, void* y, int64_t ldy, int6
  * dW = dY^T X of every nn.Linear of the decoder stack (loss.backward(), main_mage.py:152): tiles go to LDS as stored and the MFMA
  * fragments are read with the transposing LDS load (ds_read_b64_tr_b16).  db_partials (optional, [n_split][N]): the bias gradient's
  * column sums of dY per slice, added up from the fragments the kernel holds anyway.  mage_colsum: the same column sums on their own,
- * partials[p][c] over the p-th of n_part row chunks (fp32; finished by mage_sum_partials). */
+ * partials[p][c] over the p-th of n_part row chunks (fp32; finished by mage_sum_partials); C and ld multiples of 8, ld >= C (rows may
+ * not alias: MAGE_EINVAL otherwise). */
 int mage_gemm_tn(const void* dY, int64_t lda, const void* X, int64_t ldb, int64_t T, int32_t N, int32_t K, int32_t n_split,
                  int64_t tokens_per_split, float* partials, float* db_partials, void* stream);
 int mage_colsum(const void* x, int64_t ld, int64_t T, int32_t C, float* partials, int32_t n_part, void* stream);

@@ -244,6 +244,7 @@ extern "C" int mage_gemm_tn(const void* dY, int64_t lda, const void* X, int64_t 
 extern "C" int mage_colsum(const void* x, int64_t ld, int64_t T, int32_t C, float* partials, int32_t n_part, void* stream) {
     MAGE_CHECK_ARG(x && partials && T > 0 && C > 0 && C % 8 == 0 && ld % 8 == 0 && n_part >= 1 && (((uintptr_t)x | (uintptr_t)partials) & 15) == 0,
                    "mage_colsum: C and ld multiples of 8, 16-byte aligned operands");
+    MAGE_CHECK_ARG(ld >= C, "mage_colsum: ld=%ld < C=%d (rows would alias)", (long)ld, C);
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((C + 511) / 512), (unsigned)n_part), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)x, (long)ld, (long)T, C, partials, n_part);
     MAGE_CHECK_LAUNCH("mage_colsum");

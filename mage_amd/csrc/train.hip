@@ -932,6 +932,7 @@ extern "C" int mage_transpose(const void* x, int32_t dtype, int64_t ldx, void* y
                               int32_t dy, int32_t dx, int32_t stride, void* stream) {
     MAGE_CHECK_ARG(x && y && M > 0 && Mp >= M && C > 0 && out_h >= 1 && out_w >= 1 && in_h >= 1 && in_w >= 1 && ldy >= Mp && stride >= 1,
                    "mage_transpose: bad arguments");
+    MAGE_CHECK_ARG(ldx >= C, "mage_transpose: ldx=%ld < C=%d (rows would alias)", (long)ldx, C);
     hipStream_t s = (hipStream_t)stream;
     DT_DISPATCH(dtype, (transpose_launch<float>(x, ldx, y, ldy, y_row0, M, Mp, C, out_h, out_w, in_h, in_w, img_stride, a_off, dy, dx, stride, s)),
                 (transpose_launch<unsigned short>(x, ldx, y, ldy, y_row0, M, Mp, C, out_h, out_w, in_h, in_w, img_stride, a_off, dy, dx, stride, s)),
@@ -943,6 +944,7 @@ extern "C" int mage_transpose_colsum(const void* x, int64_t ldx, void* y, int64_
                                      int64_t img_stride, int64_t a_off, float* colsum, int32_t n_part, void* stream) {
     const long tiles = (Mp + 63) / 64;
     MAGE_CHECK_ARG(x && y && colsum && M > 0 && Mp >= M && C > 0 && out_w >= 1 && ldy >= Mp, "mage_transpose_colsum: bad arguments");
+    MAGE_CHECK_ARG(ldx >= C, "mage_transpose_colsum: ldx=%ld < C=%d (rows would alias)", (long)ldx, C);
     MAGE_CHECK_ARG(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && Mp % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0,
                    "mage_transpose_colsum: bf16 operands with 16-byte rows");
     MAGE_CHECK_ARG(n_part == (int)((tiles + TRANSPOSE_TPW - 1) / TRANSPOSE_TPW), "mage_transpose_colsum: n_part must be ceil(ceil(Mp/64)/%d)",
