@@ -300,30 +300,23 @@ int mage_preference_loss(const float* clip_logprob, const float* reference_logpr
 int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* tokens, const float* weight,
                            int64_t weight_div, const float* grad_out, void* dlogits, int32_t dl_dtype, void* stream);
 
-/* The decoder's H / W axial attention fused into its in_proj GEMM: q and k never reach memory (mage_model.py:20,75 inside the axial blocks
- * :344,382; serves FlatAxialDecoder._pass for the blocks attending along H or W on the 16-bit LayerNorm-fold path).  Replaces the pair
- * mage_gemm (QKV, LayerNorm-consuming form) -> mage_attention for 16 x 16 frames and head width 32 by TWO launches of the one-wave-per-SIMD GEMM
- * (csrc/gemm4.hip), `desc` filled as for mage_gemm's LayerNorm-consuming form (A = the 16-bit rows, bias = W beta + b, ln_stats, ln_colsum):
- *   phase 1  W = the q and k rows of the folded in_proj weight, PACKED: N = 2C columns, head h at columns 64h .. 64h+63 as [q_h | k_h], and
- *            within each 32 columns j the head dim (j%16/4)*8 + (j/16)*4 + j%4 (bias and ln_colsum in the same order).  Writes
- *            p[M][C/32][16] (fp32: exp(s - max) of every (query row, head, key), rows in an order private to the pair); Y is not used.
- *   phase 2  W = the v rows (N = C), natural order.  Reads p, writes Y[yrow(m)][C] = the attention output rows, in desc->dtype.
+/* The decoder's H / W axial attention fused into its in_proj GEMM: q, k, v and the softmax numerators never reach memory (mage_model.py:20,75
+ * inside the axial blocks :344,382; serves FlatAxialDecoder._pass for the blocks attending along H or W on the 16-bit LayerNorm-fold path).
+ * Replaces the pair mage_gemm (QKV, LayerNorm-consuming form) -> mage_attention for 16 x 16 frames and head width 32 by ONE launch of the
+ * one-wave-per-SIMD GEMM (csrc/gemm4.hip): per (frame, group of 4 heads) a Q K tile whose numerators stay in the registers of the wave that
+ * computed them, then a half-width V tile over the same rows; the frame's LayerNorm statistics are fetched once per entry, no scratch buffer.
+ * `desc` is filled as for mage_gemm's LayerNorm-consuming form (A = the 16-bit rows, bias = W beta + b, ln_stats, ln_colsum) with
+ *   N = 3C, W = the folded in_proj rows [q; k; v] PACKED per group g of 4 heads (heads 4g .. 4g+3) as 384 rows:
+ *            rows 384g .. 384g+255: head h of the group at rows 64h .. 64h+63 as [q_h | k_h], and within each 32 rows j the head dim
+ *            (j%16/4)*8 + (j/16)*4 + j%4;
+ *            rows 384g+256 .. 384g+383: the v rows 128g .. 128g+127, natural order;
+ *            bias and ln_colsum in the same order;
+ *   Y[yrow(m)][C] = the attention output rows, in desc->dtype, ldy >= C.
  * A 256-row tile of A is one frame: M % 256 == 0, a_off % 256 == 0, plain rows in (in_w == out_w; out_w >= M, or a_img_stride == out_w); the
  * output rows may be regrouped whole frames at a time (out_w % 256 == 0, y_img_stride, y_off) as mage_gemm regroups them.  axis 1 = H (a
- * sequence is a column of the frame), 2 = W (a row).  N % 256 == 0, K % 128 == 0 in [256, 1024], dtype MAGE_BF16 or MAGE_F16, act none, no
- * other epilogue stage.  `scale` is mage_attn_desc::scale.  Per output element the operations are those of the replaced pair in their
- * order: Y holds the same bits.  Anything else: MAGE_EINVAL, nothing launched. */
-int mage_gemm_attn_fused(const mage_gemm_desc* desc, int32_t phase, int32_t axis, float scale, float* p, void* stream);
-/* The symbol of the kernel mage_gemm_attn_fused(desc, phase, axis, ...) launches, named as mage_gemm_kernel_name names mage_gemm's. */
-int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* desc, int32_t phase, int32_t axis, char* buf, int32_t len);
-
-/* The pair above as ONE launch: the softmax numerators stay in the registers of the wave that computed them, the frame's rows and their
- * LayerNorm statistics are fetched once per (frame, group of 4 heads), no scratch buffer.  `desc` as for mage_gemm_attn_fused with
- *   N = 3C, W = the folded in_proj rows PACKED per group g of 4 heads as 384 rows: rows 384g .. 384g+255 = rows 256g .. 256g+255 of phase 1's
- *            packed [q | k] weight, rows 384g+256 .. 384g+383 = the v rows 128g .. 128g+127 (natural order); bias and ln_colsum in the same order;
- *   Y[yrow(m)][C] = the attention output rows, ldy >= C.
- * C % 128 == 0 (N % 384 == 0); M, K, a_off, the row regrouping, dtype, axis and scale as above.  Per output element the operations are those
- * of the two-launch pair in their order: Y holds the same bits.  Anything else: MAGE_EINVAL, nothing launched. */
+ * sequence is a column of the frame), 2 = W (a row).  C % 128 == 0 (N % 384 == 0), K % 128 == 0 in [256, 1024], dtype MAGE_BF16 or MAGE_F16,
+ * act none, no other epilogue stage.  `scale` is mage_attn_desc::scale.  Per output element the operations are those of the replaced pair
+ * in their order: Y holds the same bits as mage_gemm followed by mage_attention.  Anything else: MAGE_EINVAL, nothing launched. */
 int mage_gemm_attn_fused_qkv(const mage_gemm_desc* desc, int32_t axis, float scale, void* stream);
 /* The symbol of the kernel mage_gemm_attn_fused_qkv(desc, axis, ...) launches. */
 int mage_gemm_attn_fused_qkv_kernel_name(const mage_gemm_desc* desc, int32_t axis, char* buf, int32_t len);

@@ -141,8 +141,6 @@ EXT_SIGNATURES = {
     "mage_guide_logits": (C.c_int, [vp, vp, vp, i64, i32, i64, i64, i64, i64, vp, i64, vp]),
     "mage_preference_loss": (C.c_int, [vp, vp, i64, vp, i64, f32, f32, i32, vp, vp, vp, vp, vp]),
     "mage_token_logprob_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, i32, vp]),
-    "mage_gemm_attn_fused": (C.c_int, [C.POINTER(GemmDesc), i32, i32, f32, vp, vp]),
-    "mage_gemm_attn_fused_kernel_name": (C.c_int, [C.POINTER(GemmDesc), i32, i32, C.c_char_p, i32]),
     "mage_gemm_attn_fused_qkv": (C.c_int, [C.POINTER(GemmDesc), i32, f32, vp]),
     "mage_gemm_attn_fused_qkv_kernel_name": (C.c_int, [C.POINTER(GemmDesc), i32, C.c_char_p, i32]),
     "mage_apply_known_tokens": (C.c_int, [vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp]),

@@ -60,10 +60,11 @@ struct Gemm4Args {
     int M, N, K, lda, ldw, ldy, ldr, ldy2, y_dtype, a_off, y_off;
     int ntiles_n, ntiles;
     int stagger_groups, stagger_sleeps;
-    // the fused H / W axial attention pair (QF != 0, see gemm4_body): P scratch [M][heads][16] fp32, 1 = H axis | 2 = W axis, softmax scale,
-    // the regrouping of the output rows (out_w rows at a time, y_img_stride apart)
-    float* attn_p;
-    int attn_axis;
+    // the fused H / W axial attention entry (QF, see gemm4_body): 1 = H axis | 2 = W axis, softmax scale, the regrouping of the output rows
+    // (out_w rows at a time, y_img_stride apart).  On a 16-byte boundary: the fused kernel fetches the four with one s_load_dwordx4 of their
+    // own.  Packed directly behind stagger_sleeps, hipcc merges the argument loads differently and the hand-scheduled kernel's scalar
+    // registers fall differently from there on (profiles/r19_retire_two_launch_pair.txt)
+    alignas(16) int attn_axis;
     float attn_scale;
     int out_w, y_img_stride;
 };
@@ -105,25 +106,22 @@ __device__ __forceinline__ void g4_mfma32(const u32x4& w, const u32x4& x) {
     else asm volatile("v_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(w), "v"(x), "i"(16 * B), "i"(16 * B + 15));
 }
 #endif
-// QF (the fused H / W axial attention of the decoder, 16 x 16 frames, head width 32, LayerNorm-consuming in_proj; mage_gemm_attn_fused): the pair
-// QKV GEMM -> attention_mfma_kernel as TWO launches of gemm4_attn_kernel, q and k never stored.  A 256-row tile is one frame; the loader fetches its
-// rows so that every 16-row m-fragment is one axial sequence (W axis: rows as they lie; H axis: tile row R = w*16 + h reads frame row
-// h*16 + w), the LayerNorm statistics and the output rows follow the same map.
-//   QF = 1, N = 2C, the in_proj rows of q and k packed per head as 64 columns [q_h | k_h], the 32 columns of each in the order that makes a
-//     lane's two packed accumulator blocks the 8 consecutive head dims the S MFMA wants (column nt*16 + g*4 + e = dim g*8 + nt*4 + e): the
-//     epilogue finishes the LayerNorm, adds the bias and rounds as epilogue_lean does (the values qkv held), then per m-fragment and head
-//     S^T = K Q^T by ONE 16x16x32 MFMA on those registers, scale and softmax in attention_mfma_kernel's order, and p = exp(s - max) leaves as
-//     fp32: P[m][head][16] (row m in TILE order: private to the pair).
-//   QF = 2, N = C, the v rows of in_proj, MFMA roles swapped (A operand = the activation rows, as gemm4h_kernel: the same products in the same
-//     k order): an accumulator block then holds V^T the way the P V MFMA takes it (lane = head dim, register = key).  Same epilogue
-//     arithmetic per element, then den, P = hi + lo, O^T = V^T P_hi^T + V^T P_lo^T, the lane swap, 1 / den and the 16-byte row stores of
-//     attention_mfma_kernel: the same bits in `ao`.
-//   QF = 3 (mage_gemm_attn_fused_qkv), the pair in ONE launch, N = 3C packed per group of 4 heads as 384 rows [the group's 256 QF 1 columns | its
-//     128 v columns]: one entry of the tile list per (frame, group) = a QF 1 tile whose epilogue keeps p in the wave's accumulator registers
-//     instead of storing it, then a half-width QF 2 tile over the same rows (replayed from L2) whose epilogue takes p from there: the lane that
-//     computed a numerator is the lane that multiplies it.  P never reaches memory, the row statistics are fetched once per entry.  Every
-//     element takes the pair's operations in the pair's order: the same bits in `ao`.
-// The epilogue MFMAs of the fused attention pair (QF): attention_mfma_kernel's instructions (attn_mfma_qk / attn_mfma_pv in attn_mfma.h) on the
+// QF (the fused H / W axial attention of the decoder, 16 x 16 frames, head width 32, LayerNorm-consuming in_proj; mage_gemm_attn_fused_qkv): the pair
+// QKV GEMM -> attention_mfma_kernel as ONE launch of gemm4_attn_kernel; q, k, v and the softmax numerators never reach memory.  A 256-row tile is
+// one frame; the loader fetches its rows so that every 16-row m-fragment is one axial sequence (W axis: rows as they lie; H axis: tile row
+// R = w*16 + h reads frame row h*16 + w), the LayerNorm statistics and the output rows follow the same map.  N = 3C, the in_proj rows packed per
+// group of 4 heads as 384 rows [256 q k rows | 128 v rows]; one entry of the tile list per (frame, group), run as two tiles over the same rows:
+//   the Q K part, the group's 256 rows: per head 64 columns [q_h | k_h], the 32 columns of each in the order that makes a lane's two packed
+//     accumulator blocks the 8 consecutive head dims the S MFMA wants (column nt*16 + g*4 + e = dim g*8 + nt*4 + e).  The epilogue finishes the
+//     LayerNorm, adds the bias and rounds as epilogue_lean does (the values qkv held), then per m-fragment and head S^T = K Q^T by ONE 16x16x32
+//     MFMA on those registers, scale and softmax in attention_mfma_kernel's order; the numerators p = exp(s - max) stay, as fp32, in the wave's
+//     accumulator registers.
+//   the V part, half width, the group's 128 v rows over the frame's panel again (replayed from L2), MFMA roles swapped (A operand = the
+//     activation rows, as gemm4h_kernel: the same products in the same k order): an accumulator block then holds V^T the way the P V MFMA takes it
+//     (lane = head dim, register = key).  Same epilogue arithmetic per element, then den, P = hi + lo, O^T = V^T P_hi^T + V^T P_lo^T, the lane
+//     swap, 1 / den and the 16-byte row stores of attention_mfma_kernel.  The lane that computed a numerator is the lane that multiplies it.
+// The row statistics are fetched once per entry.  Every element takes the unfused pair's operations in the pair's order: the same bits in `ao`.
+// The epilogue MFMAs of the fused attention entry (QF): attention_mfma_kernel's instructions (attn_mfma_qk / attn_mfma_pv in attn_mfma.h) on the
 // same operands, but as inline asm on VGPRs: given the builtins, hipcc puts their results into the accumulator registers it believes free
 // (a[0:3] -- live accumulators of the tile).  Wait states inside the strings: a just-written operand (1), the result before any reader (16);
 // an accumulate chain needs none.
@@ -147,17 +145,17 @@ __device__ __forceinline__ void g4_epi_pv(const ashort4& vt0, const ashort4& vt1
     else G4_EPI_PV("v_mfma_f32_16x16x16_bf16");
 }
 
-// one MFMA of the K loop: A operand = the W fragment, B operand = the activation fragment; SWAP (QF = 2): the roles swapped (transposed block)
+// one MFMA of the K loop: A operand = the W fragment, B operand = the activation fragment; SWAP (the V part of the fused entry): the roles swapped (transposed block)
 template <bool SWAP, int I, bool ZERO, bool CLOB, bool HF>
 __device__ __forceinline__ void g4_mm(const u32x4& w, const u32x4& x) {
     if constexpr (SWAP) g4_mfma<I, ZERO, CLOB, HF>(x, w);
     else g4_mfma<I, ZERO, CLOB, HF>(w, x);
 }
-// (the body of both kernels below: gemm4_kernel = QF 0, gemm4_attn_kernel = the fused pair's launches)
-template <int ACT, int EK, int LN, bool RB, bool HF, int QF>
+// (the body of both kernels below: gemm4_kernel = plain GEMM, gemm4_attn_kernel = QF, the fused attention entry)
+template <int ACT, int EK, int LN, bool RB, bool HF, bool QF>
 __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     static_assert(EK != EK_GENERAL, "lean epilogue kinds");
-    static_assert(QF == 0 || (LN == LN_CONSUME && ACT == MAGE_ACT_NONE), "fused attention pair: the LayerNorm-consuming in_proj");
+    static_assert(!QF || (LN == LN_CONSUME && ACT == MAGE_ACT_NONE), "fused attention: the LayerNorm-consuming in_proj");
     static_assert(!HF || (LN != LN_DUAL && LN != LN_GELUBWD), "f16 form: the generation path's epilogues");
     typedef std::conditional_t<HF, f16_t, unsigned short> H16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -195,8 +193,8 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
         voffW[u] = (unsigned)(r * g.ldw * 2 + ch * 16 + 8192 - u * 1024);
     }
     auto a_base = [&](int tile) { return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + (QF ? 0 : wave * 64)) + g.a_off) * g.lda * 2 - 4096; };
-    auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * (QF == 3 ? 384 : 256) + wave * 64) * g.ldw * 2 - 4096; };
-    // QF = 3: the 128 v rows behind a group's 256 [q | k] rows -- 4 units (32 rows) per wave, LDS rows wave*32 .. +31 of the W half of a stage
+    auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * (QF ? 384 : 256) + wave * 64) * g.ldw * 2 - 4096; };
+    // QF: the 128 v rows behind a group's 256 [q | k] rows -- 4 units (32 rows) per wave, LDS rows wave*32 .. +31 of the W half of a stage
     [[maybe_unused]] auto w_base_v = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * 384 + 256 + wave * 32) * g.ldw * 2 - 4096; };
     // two cursors: A pieces run 2 slabs ahead of the compute cursor, W pieces 1; at a tile's end they jump to the next tile's bases
     const char* a_src = a_base(c_tile);
@@ -207,7 +205,7 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     auto dma_m0 = [&](unsigned lds_group) __attribute__((always_inline)) {       // lds_group: stage * G4_STAGE (+ G4_WOFF)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(lds0 + lds_group) : "memory");      // (m0 cannot be named as a clobber: the compiler treats it as reserved and warns; check4 audits its writers)
     };
-    // the W half of a stage: all 8 units of the wave's 64 rows, or (half: the V part of QF = 3) 4 units at rows wave*32
+    // the W half of a stage: all 8 units of the wave's 64 rows, or (half: the V part of QF) 4 units at rows wave*32
     auto dma_m0w = [&](unsigned stage_off, bool half) __attribute__((always_inline)) { dma_m0(stage_off + G4_WOFF - (half ? wave * 4096 : 0)); };
 
     // ---- compute state: wave (wm, wn) owns rows [wm*128, +128) x columns [wn*128, +128) of the tile
@@ -217,7 +215,7 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     const int pc[2] = {((grp + 0) ^ rsw) * 16, ((grp + 4) ^ rsw) * 16};
     const int x_off = (wm * 128 + l15) * 128;
     const int w_off = G4_WOFF + (wn * 128 + l15) * 128;
-    [[maybe_unused]] const int w_off_v = G4_WOFF + (wn * 64 + l15) * 128;      // QF = 3, V part: the wave's 64 of the 128 v rows
+    [[maybe_unused]] const int w_off_v = G4_WOFF + (wn * 64 + l15) * 128;      // QF, V part: the wave's 64 of the 128 v rows
     u32x4 wf[2][8], xf[2][4];
     // accumulator block of (column half h, 16-row tile mt, 16-column block j): columns h*64 + j*16 + grp*4 + {0..3} of row mt*16 + l15
     // index = (h*8 + mt)*4 + j
@@ -278,20 +276,20 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     for (; c_tile < chunk1; c_tile += nwg8, ++it) {
         G4_STAMP(it, 0);
         const int tm = c_tile / g.ntiles_n, tn = c_tile - tm * g.ntiles_n;
-        MAGE_DASSERT(c_tile >= 0 && c_tile < g.ntiles && tm * 256 < g.M && tn * (QF == 3 ? 384 : 256) < g.N);
+        MAGE_DASSERT(c_tile >= 0 && c_tile < g.ntiles && tm * 256 < g.M && tn * (QF ? 384 : 256) < g.N);
         [[maybe_unused]] float ln_mean[8], ln_rstd[8];
-        // One tile of kind PH.  QF 0 .. 2: the entry is this one tile, PH = QF.  QF = 3: the entry (frame, group of 4 heads) is a PH = 1 tile (the
+        // One tile of kind PH.  Plain GEMM: the entry is this one tile, PH = 0.  QF: the entry (frame, group of 4 heads) is a PH = 1 tile (the
         // 256 packed [q | k] columns of the group; KEEP: the softmax numerators stay in this wave's registers) followed by a PH = 2 tile of HALF width
         // over the same rows (the group's 128 v columns; wave (wm, wn) takes the 64 columns of the two heads whose q and k it has just multiplied).
         // The HALF tile accumulates in a128..a255 (the blocks of column half 1); the numerators wait in a0..a63, which the Q K part's first
         // epilogue chunk has read out before the first of them is written: block c*4 + mt = chunk c (head c >> 1 of the wave, row half c & 1), sequence mt.
         auto tile = [&](auto PH_) __attribute__((always_inline)) {
             constexpr int PH = decltype(PH_)::value;
-            constexpr bool HALF = QF == 3 && PH == 2, KEEP = QF == 3 && PH == 1;
+            constexpr bool HALF = PH == 2, KEEP = PH == 1;
             constexpr int NW = HALF ? 4 : 8;               // W fragments per k-half = 16-column blocks of the wave
             const int m0 = ((MAGE4_ABL & 32) ? (int)blockIdx.x : tm) * 256 + wm * 128;
             // n0: the wave's first column -- of W, bias and ln_colsum; ny0: of the output rows
-            const int n0 = QF == 3 ? tn * 384 + (HALF ? 256 + wn * 64 : wn * 128) : ((MAGE4_ABL & 32) ? 0 : tn) * 256 + wn * 128;
+            const int n0 = QF ? tn * 384 + (HALF ? 256 + wn * 64 : wn * 128) : ((MAGE4_ABL & 32) ? 0 : tn) * 256 + wn * 128;
             [[maybe_unused]] const int ny0 = HALF ? tn * 128 + wn * 64 : n0;
             if constexpr (KEEP) {                          // the V part replays the frame's panel (from L2: the frame's groups stream it together)
                 a_next = a_base(c_tile);
@@ -307,20 +305,13 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
             };
             f32x4 biasm[2][4];
             [[maybe_unused]] f32x4 lns[2][4];
-            // QF = 2: the probabilities of one epilogue step (column half h = 2 heads, row half mh = 4 sequences) as the QF = 1 launch left them:
-            // lane (l15, grp) reads p of query l15, keys 4 grp .. 4 grp + 3 -- 16 bytes per lane, 1 KiB contiguous per (sequence, head).  Requested one step ahead: step 0's in the
-            // last quarter of the last slab, a later step's sequence mt as soon as the step before has consumed its own (ahead of that sequence's row stores, which a
-            // load issued behind them would wait for).
+            // QF: the softmax numerators of one epilogue step (row half mh = 4 sequences mt; KEEP: one head, [mt][0]; HALF: the wave's two heads hd):
+            // lane (l15, grp) holds p of query l15, keys 4 grp .. 4 grp + 3
             [[maybe_unused]] f32x4 pl[4][2];
-            // (the lane's coordinates, opaque once per tile: the per-lane 64-bit addresses of P and of the output rows built from them are then
+            // (the lane's coordinates, opaque once per tile: the per-lane 64-bit addresses of the output rows built from them are then
             // recomputed where they are used instead of living in registers across the K loop, which this instantiation does not have)
             [[maybe_unused]] int ql15 = l15, qgrp = grp;
-            if constexpr (QF != 0) asm volatile("" : "+v"(ql15), "+v"(qgrp));
-            [[maybe_unused]] auto qf_p_request = [&](int mt, int h, int mh) __attribute__((always_inline)) {
-                const float* pp = g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4 + mt) * (g.N >> 5) + (n0 >> 5) + h * 2) * 256 + (qgrp * 16 + ql15) * 4;
-#pragma unroll
-                for (int hd = 0; hd < 2; ++hd) pl[mt][hd] = *(const f32x4*)(pp + hd * 256);
-            };
+            if constexpr (QF) asm volatile("" : "+v"(ql15), "+v"(qgrp));
             // One slab.  j = its index in the tile (runtime; only the cursors' tile jumps depend on it), S = its stage.
             // LDS-DMA issue points: W(j+1) in Q0 and A(j+2) in Q3, one instruction per four MFMAs.  A tile's FIRST slab issues no W: the
             // previous tile's LAST slab sent W of this tile's slab 1 together with its A in Q3, BEFORE the epilogue's stores -- memory
@@ -330,11 +321,11 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
             auto slab = [&](auto S_, auto FIRST_, auto LAST_, int j) __attribute__((always_inline)) {
                 constexpr int S = decltype(S_)::value;
                 constexpr bool FIRST = decltype(FIRST_)::value, LAST = decltype(LAST_)::value;
-                // HALF (the V part of QF = 3): a quarter is 16 MFMAs on the 4 W fragments of column half 0 -- per slab 16 + 8 fragment reads, 8 A units
+                // HALF (the V part of QF): a quarter is 16 MFMAs on the 4 W fragments of column half 0 -- per slab 16 + 8 fragment reads, 8 A units
                 // and 4 W units per wave.  ACC0: the first accumulator block.  The W pieces this slab sends belong to the next slab of this tile, or
                 // (LAST) to the next tile: WH_ = that tile is a HALF one (4 units at their own LDS rows, dma_m0w).
                 constexpr int ACC0 = HALF ? 32 : 0;
-                constexpr bool WH_ = QF == 3 && (LAST ? KEEP : HALF);
+                constexpr bool WH_ = LAST ? KEEP : HALF;
                 constexpr int WU = WH_ ? 4 : 8;
                 // ---- Q0: (t0, rows 0-63) from wf[0], xf[0]
                 g4_for<4 * NW>([&](auto i_) {
@@ -415,14 +406,10 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                 // for is four below that traffic: a margin against any reordering of the epilogue's last stores)
                 if constexpr (MAGE4_ABL & 16) __builtin_amdgcn_s_waitcnt(0xC07F);
                 // QF: only the instructions whose place behind the pieces the source fixes are counted -- the stores, which follow the accumulator
-                // reads (asm statements), not the epilogue's loads, which hipcc is free to issue earlier: QF 1: the 16 stores of P, four below
-                // = vmcnt(12) (with the 8 vector loads 24 lie behind the pieces); QF 2: the 32 row stores = vmcnt(32), the largest count the
-                // encoding below keeps simple (8 + 24 loads as well: 64 behind the pieces).  A too-low count only waits for some store
-                // acknowledgements; tightening them is unmeasured.
-                // QF 3: the Q K part follows a V part's 16 row stores = vmcnt(12); the V part follows a Q K part that stores nothing = vmcnt(0).
-                else if constexpr (FIRST && QF == 3) __builtin_amdgcn_s_waitcnt(PH == 1 ? 0x007C : 0x0070);
-                else if constexpr (FIRST && QF == 1) __builtin_amdgcn_s_waitcnt(0x007C);
-                else if constexpr (FIRST && QF == 2) __builtin_amdgcn_s_waitcnt(0x8070);
+                // reads (asm statements), not the epilogue's loads, which hipcc is free to issue earlier.  The Q K part follows a V part's 16 row
+                // stores, four below = vmcnt(12); the V part follows a Q K part that stores nothing = vmcnt(0).  A too-low count only waits for
+                // some store acknowledgements; tightening them is unmeasured.
+                else if constexpr (FIRST && QF) __builtin_amdgcn_s_waitcnt(PH == 1 ? 0x007C : 0x0070);
                 else if constexpr (FIRST) __builtin_amdgcn_s_waitcnt(LN == LN_CONSUME ? 0x8074 : 0x8070);       // vmcnt(36 | 32) lgkmcnt(0): four below the count
                 else __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
                 ring_barrier();
@@ -459,10 +446,6 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                         if constexpr (i == 8) dma_m0w(S * G4_STAGE, false);
                         if constexpr (i < 8) g4_dma<i>(voffA[i], a_src);
                         else g4_dma<i - 8>(voffW[i - 8], w_src);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if constexpr (PH == 2 && !HALF && LAST && (i & 7) == 6) {         // the first epilogue step's probabilities (the slab's other fragment registers are free)
-                        qf_p_request(i >> 3, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 });
@@ -556,7 +539,7 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
             // gemm.hip's epilogue_lean, 64 x 64 outputs = 64 accumulator registers at a time.  (A software-pipelined rewrite -- 64 rows of staging
             // writes, then their reads under the next 64 rows' arithmetic -- was built and measured 5 % SLOWER per launch: the epilogue is not
             // waiting for its LDS round trips, it is issue-bound on the vector ALU at the clock the K loop's power draw leaves: 1.5 GHz.)
-            if constexpr (QF != 0) {
+            if constexpr (QF) {
                 g4_for<(HALF ? 2 : 4)>([&](auto c_) {
                     // h: the column half's index into biasm / lns, ha: into the accumulator blocks (HALF: the one half, kept in a128..a255)
                     constexpr int c = decltype(c_)::value, h = HALF ? 0 : c >> 1, mh = c & 1, ha = HALF ? 1 : h;
@@ -567,8 +550,7 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                         t[q >> 2][q & 3] = g4_acc_read<(ha * 8 + mh * 4 + (q >> 2)) * 4 + (q & 3), q == 0>();
                     });
                     if constexpr (PH == 1) {
-                        // N = 2C: 64 packed columns per head; P[frame][sequence][head][lane][4]: one store instruction = 1 KiB contiguous
-                        [[maybe_unused]] float* pp = KEEP ? nullptr : g.attn_p + (((long)tm * 16 + wm * 8 + mh * 4) * (g.N >> 6) + (n0 >> 6) + h) * 256 + (qgrp * 16 + ql15) * 4;
+                        // 64 packed columns [q_h | k_h] per head: this chunk is head h of the wave, sequences mh*4 .. mh*4 + 3
 #pragma unroll
                         for (int mt = 0; mt < 4; ++mt) {
                             uint2 pk[4];
@@ -595,10 +577,9 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) p[e] = expf(st[e] - mx);
                             }
-                            if constexpr (KEEP) pl[mt][0] = p;
-                            else *(f32x4*)(pp + (long)mt * (g.N >> 6) * 256) = p;
+                            pl[mt][0] = p;
                         }
-                        if constexpr (KEEP) g4_for<4>([&](auto mt_) { g4_acc_write<c * 4 + decltype(mt_)::value>(pl[decltype(mt_)::value][0]); });
+                        g4_for<4>([&](auto mt_) { g4_acc_write<c * 4 + decltype(mt_)::value>(pl[decltype(mt_)::value][0]); });
                     } else {
                         const long shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
                         // the two heads' 16 rows x 64 B through the wave's staging window (epilogue_lean's swizzle; a wave's DS operations execute in order):
@@ -606,11 +587,10 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                         const int srow = (qgrp * 16 + ql15) >> 3, scc = ql15 & 7;
                         H16* op = (H16*)g.Y + ny0 + h * 64 + scc * 8;
                         const int wchunk = (qgrp & 1) * 2 + (qgrp >> 1);
-                        if constexpr (HALF)                // the kept numerators of this row half: pl[mt][hd] as QF 2 loads them
-                            g4_for<8>([&](auto q_) {
-                                constexpr int q = decltype(q_)::value, hd = q >> 2, mt = q & 3;
-                                pl[mt][hd] = g4_acc_read<(hd * 2 + mh) * 4 + mt>();
-                            });
+                        g4_for<8>([&](auto q_) {           // the kept numerators of this row half
+                            constexpr int q = decltype(q_)::value, hd = q >> 2, mt = q & 3;
+                            pl[mt][hd] = g4_acc_read<(hd * 2 + mh) * 4 + mt>();
+                        });
 #pragma unroll
                         for (int mt = 0; mt < 4; ++mt) {
                             f32x4 mean4, rstd4;            // the statistics of this lane's four rows of the transposed blocks: 4 grp + e
@@ -634,9 +614,6 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                                 }
                                 den += __shfl_xor(den, 16);
                                 den += __shfl_xor(den, 32);
-                                if constexpr (c < 3 && !HALF) {
-                                    if (hd == 1) qf_p_request(mt, (c + 1) >> 1, (c + 1) & 1);
-                                }
                                 f32x4 o[2];
                                 ashort4 vt[2];
 #pragma unroll
@@ -729,29 +706,28 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
 #endif
             }
         };
-        if constexpr (QF == 3) {
+        if constexpr (QF) {
             tile(std::integral_constant<int, 1>{});
             tile(std::integral_constant<int, 2>{});
         } else {
-            tile(std::integral_constant<int, QF>{});
+            tile(std::integral_constant<int, 0>{});
         }
     }
 }
 
 template <int ACT, int EK, int LN, bool RB, bool HF = false>
 __global__ __launch_bounds__(256) void gemm4_kernel(const Gemm4Args g) {
-    gemm4_body<ACT, EK, LN, RB, HF, 0>(g);
+    gemm4_body<ACT, EK, LN, RB, HF, false>(g);
 }
-// QF = 1: the Q K launch, 2: the V launch of the fused H / W axial attention pair, 3: both in one launch (see gemm4_body)
-template <bool HF, int QF>
+// the fused H / W axial attention entry: in_proj and the attention in one launch (QF, see gemm4_body)
+template <bool HF>
 __global__ __launch_bounds__(256) void gemm4_attn_kernel(const Gemm4Args g) {
-    gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, QF>(g);
+    gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, true>(g);
 }
 
-template <int ACT, int EK, int LN, bool RB, bool HF = false, int QF = 0>
-int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, float* attn_p = nullptr, int attn_axis = 0, float attn_scale = 0.f) {
+template <int ACT, int EK, int LN, bool RB, bool HF = false, bool QF = false>
+int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, int attn_axis = 0, float attn_scale = 0.f) {
     Gemm4Args a;
-    a.attn_p = attn_p;
     a.attn_axis = attn_axis;
     a.attn_scale = attn_scale;
     a.out_w = d->out_w;
@@ -776,7 +752,7 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, float* attn_p = nu
     a.y_dtype = d->y_dtype;
     a.a_off = d->a_off;
     a.y_off = d->y_off;
-    a.ntiles_n = d->N / (QF == 3 ? 384 : 256);          // (QF 3: an entry = 256 [q | k] + 128 v rows of the packed weight)
+    a.ntiles_n = d->N / (QF ? 384 : 256);              // (QF: an entry = 256 [q | k] + 128 v rows of the packed weight)
     a.ntiles = (d->M / 256) * a.ntiles_n;
     // staggered start (gemm.hip, launch_tile): the workgroups of an XCD start in G groups spread over a fraction of one tile period, so that
     // the tiles' output bursts (128-256 KiB per CU at once: HBM-bound when all 256 CUs store together) fall under other groups' K loops
@@ -790,7 +766,7 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, float* attn_p = nu
         a.stagger_sleeps = (int)(period * st_percent / 100 / st_groups / 1024);
     }
     int r;
-    if constexpr (QF != 0) r = mage_gemm_launch<gemm4_attn_kernel<HF, QF>>(grid, 256, G4_LDS, s, a);
+    if constexpr (QF) r = mage_gemm_launch<gemm4_attn_kernel<HF>>(grid, 256, G4_LDS, s, a);
     else r = mage_gemm_launch<gemm4_kernel<ACT, EK, LN, RB, HF>>(grid, 256, G4_LDS, s, a);
     return r < 0 ? r : 1;
 }
@@ -1078,55 +1054,7 @@ int mage_gemm4_try(const mage_gemm_desc* d, hipStream_t s) {
     return launch4<MAGE_ACT_QUICKGELU, EK_BIAS, LN_NONE, false>(d, s, n_cu);
 }
 
-// The fused H / W axial attention pair (include/mage_hip_ext.h): phase 1 = the Q K launch (N = 2C, P out), phase 2 = the V launch (N = C, ao out)
-extern "C" int mage_gemm_attn_fused(const mage_gemm_desc* d, int32_t phase, int32_t axis, float scale, float* p, void* stream) {
-    MAGE_CHECK_ARG(d != nullptr, "mage_gemm_attn_fused: null descriptor");
-    MAGE_CHECK_ARG(phase == 1 || phase == 2, "mage_gemm_attn_fused: phase %d (1 = the Q K launch, 2 = the V launch)", (int)phase);
-    MAGE_CHECK_ARG(axis == 1 || axis == 2, "mage_gemm_attn_fused: axis %d (1 = H, 2 = W of 16 x 16 frames)", (int)axis);
-    MAGE_CHECK_ARG(d->dtype == MAGE_BF16 || d->dtype == MAGE_F16, "mage_gemm_attn_fused: bf16 or f16 operands");
-    MAGE_CHECK_ARG(d->A && d->W && p && d->bias && d->ln_stats && d->ln_colsum && (phase == 1 || d->Y),
-                   "mage_gemm_attn_fused: A, W, bias, ln_stats, ln_colsum, the P scratch%s must be given", phase == 2 ? " and Y" : "");
-    MAGE_CHECK_ARG(d->M > 0 && d->M % 256 == 0 && d->N % 256 == 0 && d->K % 128 == 0 && d->K >= 256 && d->K <= 1024,
-                   "mage_gemm_attn_fused: M=%d, N=%d multiples of 256 (whole 16 x 16 frames), K=%d a multiple of 128 in [256, 1024]", d->M, d->N, d->K);
-    MAGE_CHECK_ARG(d->taps_h * d->taps_w == 1 && d->stride == 1 && !d->dy0 && !d->dx0 && d->in_h == 1 && d->out_h == 1 && d->in_w == d->out_w && !d->a_half &&
-                       d->y_mul_x == 1 && (d->out_w >= d->M || (d->out_w % 256 == 0 && d->a_img_stride == d->out_w)) && d->a_off % 256 == 0 && d->a_off >= 0,
-                   "mage_gemm_attn_fused: plain rows in (a_off a multiple of 256), output rows regrouped whole frames at a time");
-    MAGE_CHECK_ARG(!d->scale && !d->shift && !d->rowadd && !d->residual && !d->post_relu && !d->res_half && !d->y2 && !d->ln_part && !d->head_w && !d->a_relu &&
-                       d->n_split <= 1 && d->act == MAGE_ACT_NONE,
-                   "mage_gemm_attn_fused: the LayerNorm-consuming bias epilogue only");
-    MAGE_CHECK_ARG(phase == 1 || (d->y_dtype == d->dtype && d->ldy % 8 == 0 && d->ldy >= d->N && (((uintptr_t)d->Y) & 15) == 0 && d->y_off >= 0),
-                   "mage_gemm_attn_fused: the V launch writes 16-bit rows of the operands' type, ldy a multiple of 8, Y 16-byte aligned");
-    const int ldw = d->ldw ? d->ldw : d->K;
-    MAGE_CHECK_ARG(ldw == d->K && d->lda % 8 == 0 && d->lda >= d->K, "mage_gemm_attn_fused: W packed [N][K], lda a multiple of 8");
-    MAGE_CHECK_ARG((((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->bias | (uintptr_t)d->ln_colsum | (uintptr_t)p) & 15) == 0 && (((uintptr_t)d->ln_stats) & 7) == 0,
-                   "mage_gemm_attn_fused: operands must be 16-byte aligned");
-    MAGE_CHECK_ARG(((long)d->M + d->a_off) * d->lda * 2 + 16384 < (1L << 32) && (long)d->N * ldw * 2 + 16384 < (1L << 32),
-                   "mage_gemm_attn_fused: operands beyond the kernel's 32-bit lane offsets");
-    hipStream_t s = (hipStream_t)stream;
-    const int n_cu = mage_gemm_cu_count();
-    int r;
-    if (d->dtype == MAGE_F16)
-        r = phase == 1 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 1>(d, s, n_cu, p, axis, scale)
-                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 2>(d, s, n_cu, p, axis, scale);
-    else
-        r = phase == 1 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 1>(d, s, n_cu, p, axis, scale)
-                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 2>(d, s, n_cu, p, axis, scale);
-    return r < 0 ? r : MAGE_OK;
-}
-
-// The kernel mage_gemm_attn_fused launches for this descriptor and phase, named as mage_gemm_kernel_name names mage_gemm's
-extern "C" int mage_gemm_attn_fused_kernel_name(const mage_gemm_desc* d, int32_t phase, int32_t axis, char* buf, int32_t len) {
-    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_gemm_attn_fused_kernel_name: no buffer");
-    float dummy_p[4] __attribute__((aligned(16)));
-    const void* kernel = nullptr;
-    mage_gemm_plan = &kernel;
-    const int r = mage_gemm_attn_fused(d, phase, axis, 1.f, dummy_p, nullptr);
-    mage_gemm_plan = nullptr;
-    if (r != MAGE_OK) return r;
-    return mage_kernel_symbol_name(kernel, buf, len, "mage_gemm_attn_fused_kernel_name");
-}
-
-// The pair as ONE launch (include/mage_hip_ext.h): N = 3C, W / bias / ln_colsum packed per group of 4 heads, ao out; no P
+// The fused H / W axial attention (include/mage_hip_ext.h): N = 3C, W / bias / ln_colsum packed per group of 4 heads, ao out
 extern "C" int mage_gemm_attn_fused_qkv(const mage_gemm_desc* d, int32_t axis, float scale, void* stream) {
     MAGE_CHECK_ARG(d != nullptr, "mage_gemm_attn_fused_qkv: null descriptor");
     MAGE_CHECK_ARG(axis == 1 || axis == 2, "mage_gemm_attn_fused_qkv: axis %d (1 = H, 2 = W of 16 x 16 frames)", (int)axis);
@@ -1151,8 +1079,8 @@ extern "C" int mage_gemm_attn_fused_qkv(const mage_gemm_desc* d, int32_t axis, f
                    "mage_gemm_attn_fused_qkv: operands beyond the kernel's 32-bit lane offsets");
     hipStream_t s = (hipStream_t)stream;
     const int n_cu = mage_gemm_cu_count();
-    const int r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, 3>(d, s, n_cu, nullptr, axis, scale)
-                                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, 3>(d, s, n_cu, nullptr, axis, scale);
+    const int r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, true>(d, s, n_cu, axis, scale)
+                                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, true>(d, s, n_cu, axis, scale);
     return r < 0 ? r : MAGE_OK;
 }
 

@@ -422,8 +422,7 @@ class FlatAxialDecoder(nn.Module):
         self.compute_dtype = F32
         self.split_kind = 0                    # ops.BF16X3 / ops.F16X3: the fast parity modes (compute_dtype stays fp32)
         self.stream_bf16 = True                # bf16 mode: x stays in bf16 between the blocks (_stream_bf16)
-        self.qk_fuse_tiles = 4                 # H / W attention inside the in_proj GEMM from this many V-launch tiles per CU on (_qk_fuse)
-        self.qkv_fuse_tiles = 4                # ... as ONE launch from this many (frame, group of 4 heads) entries per CU on (_qkv_fuse)
+        self.qkv_fuse_tiles = 8                # H / W attention inside the in_proj GEMM from this many (frame, group of 4 heads) entries per CU on (_qkv_fuse)
         self._derived = _Derived(self)
 
     def initialize_parameters(self):
@@ -471,9 +470,7 @@ class FlatAxialDecoder(nn.Module):
                 d[f"b{i}.{lin}.lns"] = wq.float().sum(dim=1).contiguous()
                 # c_n = sum_k W_nk beta_k + b_n in fp64 (a row-wise reduction: derived-cache bookkeeping, no BLAS call)
                 d[f"b{i}.{lin}.lnc"] = ((w.double() * bt.double()[None, :]).sum(1) + d[f"b{i}.{lin}.b"].double()).float().contiguous()
-            if i % 3 and self.model_channels % 64 == 0:         # H / W blocks: in_proj as the fused attention pair takes it (_qk_fuse)
-                self._qk_fuse_pack(d, f"b{i}", d[f"b{i}.in_proj.lnw"], d[f"b{i}.in_proj.lns"], "")
-            if i % 3 and self.model_channels % 128 == 0:        # ... and as the single launch takes it (_qkv_fuse)
+            if i % 3 and self.model_channels % 128 == 0:        # H / W blocks: in_proj as the fused attention launch takes it (_qkv_fuse)
                 self._qkv_fuse_pack(d, f"b{i}", d[f"b{i}.in_proj.lnw"], d[f"b{i}.in_proj.lns"], "")
         return d
 
@@ -515,50 +512,23 @@ class FlatAxialDecoder(nn.Module):
             d[kw_], d[ks_] = wq, wq.float().sum(dim=1).contiguous()
         return d[kw_], d[ks_]
 
-    def _qk_fuse(self, xb, M: int, hh: int, ww: int, stats_rows: bool, cache) -> bool:
-        """The H / W blocks of a pass run their attention inside the in_proj GEMM (ops.gemm_attn_fused): the 16-bit LayerNorm-fold path with
-        (mean, rstd) rows, 16 x 16 frames (a 256-row GEMM tile is one frame), head width 32, and at least qk_fuse_tiles = four tiles per CU in the V launch
-        (the one-wave-per-SIMD kernel's own rule: the full loop; the incremental step and small batches keep the QKV GEMM + attention pair --
-        both write the same bits; the pair has only been timed at the cfg2 full-loop size, where that threshold is not measured against
-        a lower one).  use_cids=False keeps the old pair.  config qk_fuse = False (MAGE_NO_QK_FUSE=1) turns it off."""
+    def _qkv_fuse(self, xb, M: int, hh: int, ww: int, stats_rows: bool, cache) -> bool:
+        """The H / W blocks of a pass run their attention inside the in_proj GEMM, one launch per block (ops.gemm_attn_fused_qkv; q, k, v and the
+        softmax numerators never reach memory): the 16-bit LayerNorm-fold path with (mean, rstd) rows, 16 x 16 frames (a 256-row GEMM tile is one
+        frame), head width 32.  Its tile list has one entry per (frame, group of 4 heads); from qkv_fuse_tiles = eight entries per CU on (the full
+        loop; the incremental step and small batches keep the QKV GEMM + attention pair -- both write the same bits).  The threshold is inherited
+        from the two-launch form this launch replaced (four 256-column tiles per CU in its V launch: the same inequality, C being a multiple of 256);
+        it is not measured against a lower one, and the launch has only been timed at the cfg2 full loop, 15 entries per CU.  use_cids=False keeps
+        the old pair.  config qk_fuse = False (MAGE_NO_QK_FUSE=1) turns it off."""
         Cc = self.model_channels
         if not (stats_rows and cache is None and hh == 16 and ww == 16 and self.use_cids and config.get().qk_fuse):
             return False
         if Cc % 256 or not 256 <= Cc <= 1024 or M % 256 or (M + 8) * Cc * 2 >= 2 ** 32:
             return False
-        return (M // 256) * (Cc // 256) >= getattr(self, "qk_fuse_tiles", 4) * torch.cuda.get_device_properties(xb.device).multi_processor_count
-
-    def _qk_fuse_w(self, d, p, dt):
-        """Block p's LayerNorm-folded in_proj operands (_ln_fold_w) as the fused pair takes them: the q and k rows packed per head
-        (ops.qk_pack_rows) with their colsum and bias in the same order, and the v rows.  bf16: from _build; f16: on first use."""
-        sfx = ".f16" if dt == F16 else ""
-        if f"{p}.in_proj.qk.w{sfx}" not in d:
-            lnw, lns = self._ln_fold_w(d, p, "in_proj", dt)
-            self._qk_fuse_pack(d, p, lnw, lns, sfx)
-        q = f"{p}.in_proj."
-        return dict(wqk=d[q + "qk.w" + sfx], sqk=d[q + "qk.s" + sfx], cqk=d[q + "qk.c"],
-                    wv=d[q + "v.w" + sfx], sv=d[q + "v.s" + sfx], cv=d[q + "v.c"])          # (the fp32 biases serve both types)
-
-    def _qk_fuse_pack(self, d, p, lnw, lns, sfx: str) -> None:
-        Cc = self.model_channels
-        idx = ops.qk_pack_rows(Cc, lnw.device)
-        lnc = d[f"{p}.in_proj.lnc"]
-        d[f"{p}.in_proj.qk.w{sfx}"], d[f"{p}.in_proj.qk.s{sfx}"] = lnw[idx].contiguous(), lns[idx].contiguous()
-        d[f"{p}.in_proj.v.w{sfx}"], d[f"{p}.in_proj.v.s{sfx}"] = lnw[2 * Cc:].contiguous(), lns[2 * Cc:].contiguous()
-        d[f"{p}.in_proj.qk.c"], d[f"{p}.in_proj.v.c"] = lnc[idx].contiguous(), lnc[2 * Cc:].contiguous()       # (fp32: one copy serves both types)
-
-    def _qkv_fuse(self, xb, M: int, fuse: bool) -> bool:
-        """The fused pair of a pass (_qk_fuse, whose conditions hold: `fuse`) runs as ONE launch per block (ops.gemm_attn_fused_qkv): the softmax
-        numerators stay in registers, no scratch.  Its tile list has one entry per (frame, group of 4 heads); from qkv_fuse_tiles = four entries
-        per CU on (the persistent kernel's own rule; timed at the cfg2 full loop only, 15 per CU -- the threshold itself is not measured);
-        below it the two launches run.  Both write the same bits.  config qkv_fuse = False (MAGE_NO_QKV_FUSE=1) turns it off."""
-        if not (fuse and config.get().qkv_fuse):
-            return False
-        Cc = self.model_channels
-        return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 4) * torch.cuda.get_device_properties(xb.device).multi_processor_count
+        return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 8) * torch.cuda.get_device_properties(xb.device).multi_processor_count
 
     def _qkv_fuse_w(self, d, p, dt):
-        """Block p's LayerNorm-folded in_proj operands as the single launch takes them: all 3C rows in ops.qkv_pack_rows' order, with their colsum
+        """Block p's LayerNorm-folded in_proj operands (_ln_fold_w) as the fused launch takes them: all 3C rows in ops.qkv_pack_rows' order, with their colsum
         and bias.  bf16: from _build; f16: on first use."""
         sfx = ".f16" if dt == F16 else ""
         if f"{p}.in_proj.qkv.w{sfx}" not in d:
@@ -709,25 +679,18 @@ class FlatAxialDecoder(nn.Module):
         ao = torch.empty(M, Cc, device=dev, dtype=dt)
         hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
         geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
-        fuse = self._qk_fuse(xb, M, hh, ww, fold and not inl, cache)
-        fuse1 = self._qkv_fuse(xb, M, fuse)             # ... as one launch per block: the probabilities stay in registers
-        pscr = torch.empty(M, Cc // 32, 16, device=dev, dtype=F32) if fuse and not fuse1 else None      # the fused pair's probabilities
+        fuse = self._qkv_fuse(xb, M, hh, ww, fold and not inl, cache)
         for i in range(self.layers):
             p = f"b{i}"
             ln1 = ln if i else ln0
             if ln1 is None:
                 ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5)
             if fuse and i % 3:
-                # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): a Q K launch that leaves the softmax
-                # numerators, a V launch that finishes P V -- the same bits in ao as the QKV GEMM + ops.attention below, q and k never stored
-                kw = dict(axis=i % 3, M=M, K=Cc, lda=Cc, ln_stats=stats)
-                if fuse1:                               # both in one launch (QF = 3): P never leaves the wave
-                    f = self._qkv_fuse_w(d, p, dt)
-                    ops.gemm_attn_fused_qkv(xb, f["w"], ao, C_=Cc, ldy=Cc, bias=f["c"], ln_colsum=f["s"], **kw)
-                else:
-                    f = self._qk_fuse_w(d, p, dt)
-                    ops.gemm_attn_fused(xb, f["wqk"], None, pscr, phase=1, N=2 * Cc, bias=f["cqk"], ln_colsum=f["sqk"], **kw)
-                    ops.gemm_attn_fused(xb, f["wv"], ao, pscr, phase=2, N=Cc, ldy=Cc, bias=f["cv"], ln_colsum=f["sv"], **kw)
+                # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): per (frame, group of 4 heads) a Q K tile that
+                # keeps the softmax numerators in registers, then a V tile that finishes P V -- the same bits in ao as the QKV GEMM +
+                # ops.attention below, q, k and v never stored
+                f = self._qkv_fuse_w(d, p, dt)
+                ops.gemm_attn_fused_qkv(xb, f["w"], ao, axis=i % 3, M=M, C_=Cc, K=Cc, lda=Cc, ldy=Cc, bias=f["c"], ln_stats=stats, ln_colsum=f["s"])
             elif i % 3 == 0 and cache is not None:
                 # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
                 # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)

@@ -303,62 +303,15 @@ def gemm(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, M: int, N: int, K
     return y
 
 
-def qk_pack_rows(C_: int, device=None) -> torch.Tensor:
-    """Row order of the packed [q | k] weight of gemm_attn_fused's phase 1 (mage_gemm_attn_fused, include/mage_hip_ext.h): packed row n of
-    the 2C rows = row index[n] of in_proj's [q; k; v] rows.  Head h takes rows 64h .. 64h+63 as [q_h | k_h]; inside each 32 rows, row j is
-    head dim (j % 16 // 4) * 8 + (j // 16) * 4 + j % 4 -- the order in which a lane's two packed accumulator blocks are 8 consecutive dims."""
+def qkv_pack_rows(C_: int, device=None) -> torch.Tensor:
+    """Row order of the packed weight of gemm_attn_fused_qkv (mage_gemm_attn_fused_qkv, include/mage_hip_ext.h): packed row n of the 3C rows =
+    row index[n] of in_proj's [q; k; v] rows.  Group g of 4 heads takes rows 384g .. 384g+383.  Its first 256 rows: head h of the group at rows
+    64h .. 64h+63 as [q_h | k_h]; inside each 32 rows, row j is head dim (j % 16 // 4) * 8 + (j // 16) * 4 + j % 4 -- the order in which a
+    lane's two packed accumulator blocks are 8 consecutive dims.  Then its 128 v rows in their natural order."""
     n = torch.arange(2 * C_, device=device)
     head, part, j = n // 64, (n % 64) // 32, n % 32
     dim = (j % 16 // 4) * 8 + (j // 16) * 4 + j % 4
-    return part * C_ + head * 32 + dim
-
-
-def gemm_attn_fused(a: torch.Tensor, w: torch.Tensor, y: Optional[torch.Tensor], p: torch.Tensor, *, phase: int, axis: int, M: int, N: int, K: int,
-                    lda: int, bias, ln_stats, ln_colsum, ldy: int = 0, scale: Optional[float] = None, a_off: int = 0, out_w: Optional[int] = None,
-                    y_img_stride: Optional[int] = None, y_off: int = 0):
-    """One launch of the fused H / W axial attention pair (mage_gemm_attn_fused): phase 1 = the Q K launch (w: the packed [q | k] rows of the
-    LayerNorm-folded in_proj weight, qk_pack_rows; N = 2C; writes the probabilities p [M, C/32, 16] fp32), phase 2 = the V launch (w: the v
-    rows, N = C; reads p, writes the attention output rows y).  axis 1 = H, 2 = W of 16 x 16 frames; scale as ops.attention's."""
-    l, s = _dev(a)
-    assert w.dtype == a.dtype and p.dtype == torch.float32 and p.is_contiguous() and p.numel() >= M * (N // (4 if phase == 1 else 2)), (w.dtype, p.shape)
-    out_w = M if out_w is None else out_w
-    d = GemmDesc()
-    d.dtype, d.M, d.N, d.K = code(a), M, N, K
-    d.A, d.W, d.Y = a.data_ptr(), w.data_ptr(), _p(y)
-    d.lda, d.ldy, d.y_dtype = lda, ldy, (code(y) if y is not None else code(a))
-    d.out_h, d.out_w, d.in_h, d.in_w = 1, out_w, 1, out_w
-    d.a_img_stride, d.a_off = out_w, a_off
-    d.taps_h, d.taps_w, d.cin, d.stride = 1, 1, K, 1
-    d.dys, d.dxs = 1, 1
-    d.y_img_stride = out_w if y_img_stride is None else y_img_stride
-    d.y_mul_y, d.y_mul_x, d.y_off = out_w, 1, y_off
-    d.bias, d.ln_stats, d.ln_colsum = _p(bias), _p(ln_stats), _p(ln_colsum)
-    d.n_split = 1
-    sc = float(32 ** -0.5 if scale is None else scale)
-    ev = None
-    if PROFILE.enabled:
-        buf = C.create_string_buffer(256)
-        _lib.check(l.mage_gemm_attn_fused_kernel_name(C.byref(d), phase, axis, buf, len(buf)), l)
-        key = buf.value.decode()
-        if PROFILE.wants(key):
-            ev = PROFILE.begin()
-    _lib.check(l.mage_gemm_attn_fused(C.byref(d), phase, axis, sc, p.data_ptr(), s), l)
-    if ev is not None:
-        # algorithmic HBM bytes: each launch reads the rows a (so the pair reads them twice) and its weights; phase 1 writes P, phase 2 reads
-        # it back and writes y.  q, k and v never appear.
-        es = a.element_size()
-        pb = float(M) * (N // (4 if phase == 1 else 2)) * 4
-        nb = float(M) * K * es + float(N) * K * es + pb + (float(M) * N * y.element_size() if phase == 2 else 0.0)
-        fl = 2.0 * M * N * K + (2.0 * M * 16 * (N // 2) if phase == 1 else 4.0 * M * 16 * N)
-        PROFILE.end(key, ev, fl, nb)
-    return p if phase == 1 else y
-
-
-def qkv_pack_rows(C_: int, device=None) -> torch.Tensor:
-    """Row order of the packed weight of gemm_attn_fused_qkv (mage_gemm_attn_fused_qkv): packed row n of the 3C rows = row index[n] of
-    in_proj's [q; k; v] rows.  Group g of 4 heads takes rows 384g .. 384g+383: the 256 rows of its heads in qk_pack_rows' order, then its 128 v
-    rows in their natural order."""
-    qk = qk_pack_rows(C_, device).view(C_ // 128, 256)
+    qk = (part * C_ + head * 32 + dim).view(C_ // 128, 256)
     v = (2 * C_ + torch.arange(C_, device=device)).view(C_ // 128, 128)
     return torch.cat([qk, v], dim=1).reshape(-1)
 
@@ -366,9 +319,9 @@ def qkv_pack_rows(C_: int, device=None) -> torch.Tensor:
 def gemm_attn_fused_qkv(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, axis: int, M: int, C_: int, K: int, lda: int, bias, ln_stats, ln_colsum,
                         ldy: int, scale: Optional[float] = None, a_off: int = 0, out_w: Optional[int] = None, y_img_stride: Optional[int] = None,
                         y_off: int = 0):
-    """The fused H / W axial attention pair as ONE launch (mage_gemm_attn_fused_qkv): w, bias and ln_colsum are the 3 C_ rows of the LayerNorm-folded
-    in_proj in qkv_pack_rows' order; writes the attention output rows y [.., C_] -- the bits of gemm_attn_fused's two launches.  axis 1 = H,
-    2 = W of 16 x 16 frames; scale as ops.attention's."""
+    """The H / W axial attention inside the in_proj GEMM, one launch (mage_gemm_attn_fused_qkv): w, bias and ln_colsum are the 3 C_ rows of the
+    LayerNorm-folded in_proj in qkv_pack_rows' order; writes the attention output rows y [.., C_] -- the bits of ops.gemm (QKV) followed by
+    ops.attention.  axis 1 = H, 2 = W of 16 x 16 frames; scale as ops.attention's."""
     l, s = _dev(a)
     assert w.dtype == a.dtype and y.dtype == a.dtype, (w.dtype, y.dtype)
     out_w = M if out_w is None else out_w

@@ -1,4 +1,4 @@
-"""GPU: the H / W axial attention and the in_proj GEMM in ONE launch (mage_gemm_attn_fused_qkv, csrc/gemm4.hip QF = 3: per (frame, group of 4
+"""GPU: the H / W axial attention and the in_proj GEMM in ONE launch (mage_gemm_attn_fused_qkv, csrc/gemm4.hip QF: per (frame, group of 4
 heads) a Q K tile that keeps the softmax numerators in registers, then a half-width V tile that finishes P V) against the pair it replaces --
 ops.gemm (QKV, LayerNorm-consuming form) + ops.attention -- BITWISE on the attention output rows `ao`.
 
@@ -7,9 +7,11 @@ ops.gemm (QKV, LayerNorm-consuming form) + ops.attention -- BITWISE on the atten
   * 600 frames at C = 256: 4.7 entries per workgroup -- the panel replay and the slab hand-over across Q K -> V -> next entry -> last entry;
   * a non-zero row offset on the input and regrouped output rows (out_w, y_img_stride, y_off);
   * ao is pre-filled with a sentinel and carries guard rows: every row of the window is written, nothing outside it is;
-  * the decoder itself: single-launch blocks == the two-launch pair bitwise, the off switch (config qkv_fuse), and a geometry outside both
-    fusions (hh = 8).
+  * the decoder itself: fused blocks == the QKV GEMM + attention pair bitwise, the off switch (config qk_fuse), the size rule
+    (qkv_fuse_tiles entries per CU) and a geometry outside the fusion (hh = 8) launch no fused kernel.
 """
+from fractions import Fraction
+
 import pytest
 import torch
 
@@ -33,7 +35,6 @@ def _geo(axis, frames, heads):
 
 
 def _operands(M, C, dt, a_rows):
-    """test_gpu_qk_fused's operand generator."""
     g = torch.Generator(device="cpu").manual_seed(1000 * M + C)
     xb = torch.randn(a_rows, C, generator=g).to(DEV).to(dt)
     w = (torch.randn(3 * C, C, generator=g) * C ** -0.5).to(DEV).to(dt)           # gamma * W, rounded: what the MFMA multiplies
@@ -75,7 +76,11 @@ def test_pack_rows_is_a_permutation_in_group_order():
     C = 256
     idx = ops.qkv_pack_rows(C).view(C // 128, 384)
     assert torch.equal(idx.reshape(-1).sort().values, torch.arange(3 * C))
-    assert torch.equal(idx[:, :256].reshape(-1), ops.qk_pack_rows(C))
+    # head h of group g (head 4g + h of the layer) at rows 64h .. 64h+63 as [q_h | k_h]; within each 32 rows, row j is head dim
+    # (j % 16 // 4) * 8 + (j // 16) * 4 + j % 4
+    want = [[part * C + (4 * g + h) * 32 + (j % 16 // 4) * 8 + (j // 16) * 4 + j % 4 for h in range(4) for part in (0, 1) for j in range(32)]
+            for g in range(C // 128)]
+    assert idx[:, :256].tolist() == want
     assert torch.equal(idx[:, 256:].reshape(-1), 2 * C + torch.arange(C))
 
 
@@ -122,12 +127,12 @@ def test_row_offset_and_regrouped_output_rows(axis):
     assert torch.equal(_bits(body[:, 1]), _bits(want.view(2, 256, C)))
 
 
-def _decoder(dt):
+def _decoder(dt, tiles=0):
     torch.manual_seed(7)
     m = FlatAxialDecoder(64, 256, 64, frames_length=2, layers=3, context_channels=64).to(DEV).eval()
     m.compute_dtype = dt
-    m.qk_fuse_tiles = 0                         # (the size rules keep calls this small on the QKV GEMM + attention)
-    m.qkv_fuse_tiles = 0
+    if tiles is not None:                       # (the size rule keeps calls this small on the QKV GEMM + attention)
+        m.qkv_fuse_tiles = tiles
     return m
 
 
@@ -145,14 +150,32 @@ def test_decoder_single_launch_blocks_and_the_off_switch(monkeypatch, dt):
     m = _decoder(dt)
     calls = count_lib_calls(monkeypatch)
     on = _logits(m, 4, 16, 16)
-    n_on = (calls.count("mage_gemm_attn_fused_qkv"), calls.count("mage_gemm_attn_fused"))
+    n_on = calls.count("mage_gemm_attn_fused_qkv")
     del calls[:]
-    with config.override(qkv_fuse=False):
+    with config.override(qk_fuse=False):
         off = _logits(m, 4, 16, 16)
-    n_off = (calls.count("mage_gemm_attn_fused_qkv"), calls.count("mage_gemm_attn_fused"))
+    n_off = calls.count("mage_gemm_attn_fused_qkv")
     monkeypatch.undo()
-    assert n_on == (2, 0) and n_off == (0, 4), (n_on, n_off)      # blocks 1 (H) and 2 (W): one launch each, or the pair's two
+    assert n_on == 2 and n_off == 0 and "mage_attention" in calls, (n_on, n_off)      # blocks 1 (H) and 2 (W): one launch each
     assert torch.equal(on, off)
+
+
+def test_size_rule_counts_entries_per_cu(monkeypatch):
+    """M = 2048 rows (8 frames) at C = 256 (2 groups of 4 heads) = 16 entries: fused from qkv_fuse_tiles * n_cu <= 16 on, and the default of
+    eight entries per CU keeps a call this small on the QKV GEMM + attention."""
+    n_cu = torch.cuda.get_device_properties(DEV).multi_processor_count
+    m = _decoder(torch.bfloat16, tiles=None)
+    assert m.qkv_fuse_tiles == 8
+    calls = count_lib_calls(monkeypatch)
+    n = []
+    for tiles in (None, Fraction(16, n_cu), Fraction(17, n_cu)):      # the default left in place, then exactly at and just above 16 entries
+        if tiles is not None:
+            m.qkv_fuse_tiles = tiles
+        del calls[:]
+        _logits(m, 4, 16, 16)
+        n.append(calls.count("mage_gemm_attn_fused_qkv"))
+    monkeypatch.undo()
+    assert n == [0, 2, 0], n
 
 
 def test_geometry_outside_the_fusion_takes_neither(monkeypatch):
@@ -160,8 +183,8 @@ def test_geometry_outside_the_fusion_takes_neither(monkeypatch):
     m = _decoder(torch.bfloat16)
     calls = count_lib_calls(monkeypatch)
     got = _logits(m, 4, 8, 32)
-    n = calls.count("mage_gemm_attn_fused_qkv") + calls.count("mage_gemm_attn_fused")
-    with config.override(qkv_fuse=False, qk_fuse=False):
+    n = calls.count("mage_gemm_attn_fused_qkv")
+    with config.override(qk_fuse=False):
         want = _logits(m, 4, 8, 32)
     monkeypatch.undo()
     assert n == 0 and "mage_attention" in calls
