@@ -321,6 +321,24 @@ int mage_gemm_attn_fused_qkv(const mage_gemm_desc* desc, int32_t axis, float sca
 /* The symbol of the kernel mage_gemm_attn_fused_qkv(desc, axis, ...) launches. */
 int mage_gemm_attn_fused_qkv_kernel_name(const mage_gemm_desc* desc, int32_t axis, char* buf, int32_t len);
 
+/* The decoder block's MLP, x + c_proj(QuickGELU(c_fc(ln_2(x)))) (mage_model.py:48-53), in ONE launch: the hidden rows never reach memory
+ * (serves FlatAxialDecoder._pass on the 16-bit LayerNorm-fold path with the 16-bit stream).  Replaces the pair mage_gemm (c_fc: LayerNorm-consuming
+ * form, QuickGELU) -> mage_gemm (c_proj: 16-bit residual added in the epilogue, optionally the LayerNorm partial sums) for C = 512, hidden = 2048
+ * (csrc/gemm4m.hip: a workgroup owns 128 rows for both products and walks the hidden dimension 32 units at a time).
+ *   x [.., ldx]: the 16-bit rows (row m of the call is row m + a_off); y [.., ldy]: the output rows m + y_off, y == x (in place, a_off == y_off) or
+ *   another buffer; w1 [4C][ldw1] = gamma * W_fc, c1 [4C] = W_fc beta + b_fc, s1 [4C] = the row sums of w1, ln_stats [M][2] = (mean, rstd) per row;
+ *   w2 [C][ldw2] = W_proj, b2 [C]; ln_part (may be null; [C/64][ln_part_rows][2], rows m + y_off) = mage_gemm's LayerNorm partial sums of the new rows.
+ * dtype = w_dtype = y_dtype = MAGE_BF16 or MAGE_F16; C == 512; M > 0, M % 128 == 0; ldx, ldy >= C, ldw1 >= C, ldw2 >= 4C, all multiples of 8;
+ * rows, weights and vectors 16-byte aligned, ln_stats and ln_part 8-byte aligned.  Per output element the operations are those of the replaced
+ * pair in their order: y and ln_part hold the same bits.  Anything else: MAGE_EINVAL, nothing launched. */
+int mage_mlp_fused(int32_t dtype, int32_t w_dtype, int32_t y_dtype, int64_t M, int32_t C, const void* x, int64_t ldx, int64_t a_off, void* y, int64_t ldy,
+                   int64_t y_off, const void* w1, int64_t ldw1, const float* c1, const float* s1, const float* ln_stats, const void* w2, int64_t ldw2,
+                   const float* b2, float* ln_part, int64_t ln_part_rows, void* stream);
+/* The symbol of the kernel mage_mlp_fused(...) launches; refuses what mage_mlp_fused refuses, launches nothing. */
+int mage_mlp_fused_kernel_name(int32_t dtype, int32_t w_dtype, int32_t y_dtype, int64_t M, int32_t C, const void* x, int64_t ldx, int64_t a_off, void* y,
+                               int64_t ldy, int64_t y_off, const void* w1, int64_t ldw1, const float* c1, const float* s1, const float* ln_stats,
+                               const void* w2, int64_t ldw2, const float* b2, float* ln_part, int64_t ln_part_rows, char* buf, int32_t len);
+
 /* Given tokens over picked ones: no site in the reference (it generates every token after frame 0).  Serves MAGE.set_context and
  * batch['known_tokens'] (mage_amd/modules/mage_model.py: _generate_one, after each frame's pick and its log-probability / statistics
  * launches).

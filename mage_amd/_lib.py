@@ -143,6 +143,9 @@ EXT_SIGNATURES = {
     "mage_token_logprob_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, i32, vp]),
     "mage_gemm_attn_fused_qkv": (C.c_int, [C.POINTER(GemmDesc), i32, f32, vp]),
     "mage_gemm_attn_fused_qkv_kernel_name": (C.c_int, [C.POINTER(GemmDesc), i32, C.c_char_p, i32]),
+    "mage_mlp_fused": (C.c_int, [i32, i32, i32, i64, i32, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "mage_mlp_fused_kernel_name": (C.c_int, [i32, i32, i32, i64, i32, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64,
+                                             C.c_char_p, i32]),
     "mage_apply_known_tokens": (C.c_int, [vp, i64, i64, i64, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
     "mage_policy_loss_masked": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, f32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp]),

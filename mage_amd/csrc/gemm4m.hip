@@ -1,0 +1,391 @@
+// gemm4m_kernel: the decoder MLP x + c_proj(QuickGELU(c_fc(LN(x)))) of one block in ONE launch (C = 512, hidden = 2048; mage_mlp_fused).
+//
+// The pair it replaces writes the hidden rows (M x 2048, 16 bit) to memory and reads them straight back.  Here a workgroup owns a 128-row tile
+// of the residual stream for both GEMMs and walks the hidden dimension in CHUNKS of 32 units; a chunk of h lives in registers only:
+//     GEMM 1 (chunk c): hacc[32 rows x 32 hidden units per wave] = x W1'^T over K = 512 (16 k-steps into one accumulator, k ascending)
+//     chunk epilogue  : h = QuickGELU(rstd (hacc - mean s) + c1), rounded to the 16-bit type: gemm4h's operations in gemm4h's order
+//     GEMM 2 (chunk c): out[32 rows x 512 columns per wave] += h W2^T -- ONE k-step (k = 32 c .. 32 c + 31) into each of the 64 accumulator blocks
+// so every output element sees c_proj's k-steps in ascending order into one accumulator, and every h element c_fc's: with the same MFMA and the
+// same epilogue operations (the closing epilogue IS epilogue_lean, residual in the epilogue + LN_PRODUCE) the bits are the pair's.
+//
+// Wave = 32 rows (two 16-row tiles mt) x all 512 output columns: 64 accumulator blocks = 256 literal AGPRs (gemm4_regs.h); its x rows are the
+// B-operand fragments of GEMM 1 for the whole tile (128 VGPRs, loaded once per tile, the next tile's under the closing epilogue).
+// Operand roles: GEMM 1 takes the W1 fragment as A-operand, so an accumulator block holds (lane = row l15, register e of lane group g = hidden unit
+// 4 g + e of the block's 16); W1's rows are gathered into LDS in the order  slot (t, r) <- hidden unit 8 (r / 4) + 4 t + r % 4  (t = block 0 | 1 of the
+// chunk), so that a lane's two packed blocks are the 8 CONSECUTIVE k = 8 g .. 8 g + 7 of GEMM 2's B-operand, in natural order (nothing is permuted
+// inside an MFMA).  GEMM 2 takes the W2 fragment as A-operand: the output accumulators have the layout of every other GEMM kernel (lane = row,
+// registers = 4 consecutive columns), which is what epilogue_lean expects.
+//
+// Schedule of chunk c (two phases of 64 MFMAs, one barrier in the middle of each; rings of two stages for W1 and for W2, 32 KB per stage):
+//     Pa(c): GEMM 1 (c)      || pack of chunk c-1 (8 converts)      second half: LDS-DMA of W2(c),   first fragments of GEMM 2 (c-1)
+//     Pb(c): GEMM 2 (c-1)    || activation of chunk c (in place)     second half: LDS-DMA of W1(c+2), first fragments of GEMM 1 (c+1)
+// A stage is requested one whole chunk before the barrier that publishes it (s_waitcnt vmcnt(8): the 8 pieces of the other ring are younger).
+// The epilogue arithmetic is single-instruction asm statements between the MFMA statements (gemm4h's way), two per MFMA slot.
+// LDS: 128 KB of rings, 16 KB of c_fc's epilogue constants (colsum, bias: loaded once per workgroup), 4 x 4 KB staging for epilogue_lean = 160 KB.
+#include "gemm_shared.h"
+#include "gemm4_regs.h"
+
+namespace {
+
+struct Gemm4mArgs {
+    const void* X;
+    void* Y;
+    const void* W1;
+    const void* W2;
+    const float* c1;
+    const float* s1;
+    const float* stats;
+    const float* b2;
+    float* ln_part;
+    long ln_part_rows;
+    int M, ldx, ldy, ldw1, ldw2, a_off, y_off, ntiles;
+};
+
+constexpr int M_C = 512, M_HID = 2048, M_NCH = M_HID / 32;
+constexpr int M_STG = 32768, M_W2OFF = 2 * M_STG, M_COFF = 4 * M_STG, M_SOFF = M_COFF + M_HID * 4, M_STGOFF = M_SOFF + M_HID * 4;
+constexpr int M_LDS = M_STGOFF + 4 * 4096;              // 160 KB
+
+#ifndef MAGE4M_XPRE
+#define MAGE4M_XPRE 1     // how many of the next tile's two 16-row fragment sets are requested BEFORE the closing epilogue (the rest after it)
+#endif
+
+// one LDS-DMA piece: 64 lanes x 16 B from (scalar base + per-lane offset) to LDS lds .. lds + 1023
+__device__ __forceinline__ void m_dma(unsigned lds, unsigned voff, const char* base) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(base) : "memory");
+}
+// GEMM 1's MFMA: accumulator block in VGPRs (the chunk's 16 registers), W fragment = A-operand, x fragment = B-operand
+template <bool ZERO, bool CLOB, bool HF>
+__device__ __forceinline__ void m_mfma1(f32x4& acc, const u32x4& w, const u32x4& x) {
+#define M_MFMA1(OP)                                                                                              \
+    do {                                                                                                         \
+        if constexpr (ZERO && CLOB) asm volatile(OP " %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(x) : G4_ALL_ACC); \
+        else if constexpr (ZERO) asm volatile(OP " %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(x));                 \
+        else if constexpr (CLOB) asm volatile(OP " %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(x) : G4_ALL_ACC);    \
+        else asm volatile(OP " %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(x));                                     \
+    } while (0)
+    if constexpr (HF) M_MFMA1("v_mfma_f32_16x16x32_f16");
+    else M_MFMA1("v_mfma_f32_16x16x32_bf16");
+#undef M_MFMA1
+}
+constexpr int m_wait_imm(int vm) { return (((vm >> 4) & 3) << 14) | (vm & 15) | 0x70; }      // vmcnt(vm) lgkmcnt(0)
+
+template <bool HF, bool LNP>
+__global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
+    typedef std::conditional_t<HF, f16_t, unsigned short> HT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    g4_claim_accumulators();
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, grp = lane >> 4;
+    const unsigned smem_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+
+    // ---- loader.  W1 chunk (32 hidden units x 512 k) in LDS: 8 slabs of 64 k, a slab = 32 row slots x 128 B, 16-byte chunk p of slot r at
+    // p ^ ((r >> 1) & 7).  A piece = 8 slots of one slab; this wave moves slabs 2 wave, 2 wave + 1.  Slot r = 16 t + rr holds hidden unit
+    // 8 (rr / 4) + 4 t + rr % 4 of the chunk.  W2 chunk (512 columns x 32 k): column block nb = 16 rows x 64 B = one piece, 16-byte chunk q of
+    // row r at q ^ ((4 - r / 4) & 3): a ds_read_b128's 16-lane groups then touch 16 distinct slots.  This wave moves blocks 8 wave .. 8 wave + 7.
+    const int lr = lane >> 3, lp = lane & 7;
+    unsigned voffW1[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        voffW1[h] = (unsigned)((8 * (lr >> 2) + (lr & 3)) * g.ldw1 * 2 + ((lp ^ ((h * 4 + (lr >> 1)) & 7)) << 4));
+    const unsigned voffW2 = (unsigned)((lane >> 2) * g.ldw2 * 2 + (((lane & 3) ^ ((4 - (lane >> 4)) & 3)) << 4));
+    auto dma_w1 = [&](int stage, int c, int u) __attribute__((always_inline)) {        // piece u (0..7) of chunk c -> stage
+        const int sl = 2 * wave + (u >> 2), u4 = u & 3;
+        const char* base = (const char*)g.W1 + (long)(32 * c + 16 * (u4 & 1) + 4 * (u4 >> 1)) * g.ldw1 * 2 + sl * 128;
+        m_dma(smem_addr + stage * M_STG + sl * 4096 + u4 * 1024, voffW1[u4 & 1], base);
+    };
+    auto dma_w2 = [&](int stage, int c, int u) __attribute__((always_inline)) {
+        const int nb = 8 * wave + u;
+        const char* base = (const char*)g.W2 + (long)(nb * 16) * g.ldw2 * 2 + c * 64;
+        m_dma(smem_addr + M_W2OFF + stage * M_STG + nb * 1024, voffW2, base);
+    };
+
+    // ---- fragment reads
+    const int rsw = (l15 >> 1) & 7;
+    const int w1_off = l15 * 128, w1_pc[2] = {((grp + 0) ^ rsw) * 16, ((grp + 4) ^ rsw) * 16};
+    const int w2_off = M_W2OFF + l15 * 64 + ((grp ^ ((4 - (l15 >> 2)) & 3)) << 4);
+    u32x4 wf[2][4];
+    auto rd_w1 = [&](int buf, int stage, int b, int j) __attribute__((always_inline)) {      // fragment j of batch b: k-step 2 b + (j >> 1), block t = j & 1
+        const int ks = 2 * b + (j >> 1), t = j & 1;
+        wf[buf][j] = *(const u32x4*)(smem + stage * M_STG + (ks >> 1) * 4096 + t * 2048 + w1_off + w1_pc[ks & 1]);
+    };
+    auto rd_w2 = [&](int buf, int stage, int b, int j) __attribute__((always_inline)) {      // column block 4 b + j
+        wf[buf][j] = *(const u32x4*)(smem + stage * M_STG + (4 * b + j) * 1024 + w2_off);
+    };
+
+    // ---- state
+    u32x4 xf[2][16];                   // the wave's 32 x rows as B-operand fragments: [16-row tile][k-step]
+    f32x4 hacc[2][2][2];               // [chunk parity][16-row tile][block t]
+    u32x4 hpk[2];                      // the packed chunk: GEMM 2's B-operand of each 16-row tile
+    f32x4 sv, cv;                      // c_fc's column sums and bias of 4 of the lane's 8 hidden units: block t = 0, then t = 1 of the chunk
+    float mean[2], rstd[2];
+    const unsigned xoff = (unsigned)((l15 * g.ldx + 8 * grp) * 2);      // per-lane byte offset inside a 16-row tile; the tile's position is scalar
+    auto load_x = [&](int tile, int mt0, int mt1) __attribute__((always_inline)) {
+#pragma unroll
+        for (int mt = mt0; mt < mt1; ++mt) {
+            const char* xp = (const char*)g.X + ((long)tile * 128 + wave * 32 + mt * 16 + g.a_off) * g.ldx * 2;
+#pragma unroll
+            for (int ks = 0; ks < 16; ++ks) xf[mt][ks] = *(const u32x4*)(xp + ks * 64 + xoff);
+        }
+    };
+    auto fence = [&]() __attribute__((always_inline)) { __builtin_amdgcn_sched_barrier(0); };
+    auto wait_barrier = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_s_waitcnt(m_wait_imm(8));
+        ring_barrier();
+        fence();
+    };
+    // The chunk epilogue as single-instruction asm statements (hipcc keeps those where they are written; plain arithmetic sinks to its consumer):
+    // gemm4h's operations in gemm4h's order.  Group G (block t = G >> 1, tile mt = G & 1: one accumulator block, 4 values j) has 28 ops K = 4 a + j:
+    // a = 0, 1 the LayerNorm fold, 2 the scaling, 3 exp, 4 (+ 1), 5 rcp, 6 the product -- a transcendental's result is read 4 instructions later.
+    float eu[4];
+    auto act_op = [&](auto PAR_, auto G_, auto K_) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(PAR_)::value, G = decltype(G_)::value, K = decltype(K_)::value;
+        constexpr int t = G >> 1, mt = G & 1, a = K >> 2, j = K & 3;
+        float v = hacc[PAR][mt][t][j];
+        if constexpr (a == 0) asm volatile("v_fma_f32 %0, -%1, %2, %0" : "+v"(v) : "v"(mean[mt]), "v"(sv[j]));
+        else if constexpr (a == 1) asm volatile("v_fma_f32 %0, %1, %0, %2" : "+v"(v) : "v"(rstd[mt]), "v"(cv[j]));
+        else if constexpr (a == 2) asm volatile("v_mul_f32 %0, 0xc01d265f, %1" : "=v"(eu[j]) : "v"(v));        // -1.702 log2(e) x
+        else if constexpr (a == 3) asm volatile("v_exp_f32 %0, %0" : "+v"(eu[j]));
+        else if constexpr (a == 4) asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(eu[j]));
+        else if constexpr (a == 5) asm volatile("v_rcp_f32 %0, %0" : "+v"(eu[j]));
+        else asm volatile("v_mul_f32 %0, %0, %1" : "+v"(v) : "v"(eu[j]));
+        if constexpr (a < 2 || a == 6) hacc[PAR][mt][t][j] = v;
+    };
+    auto pack_op = [&](auto PAR_, auto I_) __attribute__((always_inline)) {              // I = 0..7: tile I >> 2, word I & 3
+        constexpr int PAR = decltype(PAR_)::value, I = decltype(I_)::value, mt = I >> 2, w = I & 3;
+        const float a0 = hacc[PAR][mt][w >> 1][(w & 1) * 2], a1 = hacc[PAR][mt][w >> 1][(w & 1) * 2 + 1];
+        unsigned r;
+        if constexpr (HF) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a0), "v"(a1));
+        else asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a0), "v"(a1));
+        hpk[mt][w] = r;
+    };
+    auto consts_rd = [&](int c, int t, int i) __attribute__((always_inline)) {           // i = 0: column sums, 1: bias, of block t of chunk c
+        const char* p = smem + (i ? M_COFF : M_SOFF) + (32 * c + 8 * grp + 4 * t) * 4;
+        if (i) cv = *(const f32x4*)p;
+        else sv = *(const f32x4*)p;
+    };
+
+    // Pa(c): GEMM 1 of chunk c (parity PAR) || pack of chunk c - 1.  PACK = false: the tile's first chunk.
+    auto phase_a = [&](auto PAR_, auto PACK_, int c) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(PAR_)::value;
+        constexpr bool PACK = decltype(PACK_)::value;
+        g4_for<64>([&](auto i_) {
+            constexpr int i = decltype(i_)::value, b = i >> 3, k = i & 7, j = k >> 1, mt = k & 1, ks = 2 * b + (j >> 1), t = j & 1;
+            m_mfma1<ks == 0, k == 0, HF>(hacc[PAR][mt][t], wf[b & 1][j], xf[mt][ks]);
+            fence();
+            if constexpr (k < 4 && b < 7) rd_w1((b + 1) & 1, PAR, b + 1, k);
+            if constexpr (k < 4 && b == 7 && PACK) rd_w2(0, PAR ^ 1, 0, k);          // GEMM 2 (c - 1): W2 stage of parity PAR ^ 1
+            if constexpr (PACK && i >= 8 && i < 16) pack_op(std::integral_constant<int, PAR ^ 1>{}, std::integral_constant<int, i - 8>{});
+            if constexpr (b >= 4 && (k == 4 || k == 6)) dma_w2(PAR, c, (b - 4) * 2 + (k == 6));
+            fence();
+            if constexpr (i == 31) wait_barrier();
+        });
+    };
+    // Pb(c): GEMM 2 of chunk c - 1 (ZERO: the tile's first k-step) || activation of chunk c (parity PAR)
+    auto phase_b = [&](auto PAR_, auto ZERO_, int c) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(PAR_)::value;
+        constexpr bool ZERO = decltype(ZERO_)::value;
+        g4_for<64>([&](auto i_) {
+            constexpr int i = decltype(i_)::value, b = i >> 3, k = i & 7, j = k >> 1, mt = k & 1, nb = 4 * b + j;
+            g4_mfma<mt * 32 + nb, ZERO, k == 0, HF>(wf[b & 1][j], hpk[mt]);
+            fence();
+            if constexpr (i == 23 || i == 24) consts_rd(c, 1, i - 23);                         // block 1's constants, behind block 0's last use (slot 21)
+            if constexpr (i == 56 || i == 57) consts_rd((c + 1) & (M_NCH - 1), 0, i - 56);     // the next chunk's, behind block 1's last use (slot 49)
+            if constexpr (k < 4 && b < 7) rd_w2((b + 1) & 1, PAR ^ 1, b + 1, k);
+            if constexpr (k < 4 && b == 7) rd_w1(0, PAR ^ 1, 0, k);                  // GEMM 1 (c + 1)
+            if constexpr (i >= 4 && i < 60) {                                         // two ops per slot
+                constexpr int o = 2 * (i - 4);
+                fence();
+                act_op(PAR_, std::integral_constant<int, o / 28>{}, std::integral_constant<int, o % 28>{});
+                act_op(PAR_, std::integral_constant<int, (o + 1) / 28>{}, std::integral_constant<int, (o + 1) % 28>{});
+            }
+            if constexpr (b >= 4 && (k == 4 || k == 6)) dma_w1(PAR, (c + 2) & (M_NCH - 1), (b - 4) * 2 + (k == 6));
+            fence();
+            if constexpr (i == 31) wait_barrier();
+        });
+    };
+    typedef std::integral_constant<int, 0> I0;
+    typedef std::integral_constant<int, 1> I1;
+
+    // ---- prologue: c_fc's epilogue constants, W1(0), W1(1); the first tile's rows
+    for (int i = tid; i < M_HID / 4; i += 256) {
+        ((f32x4*)(smem + M_COFF))[i] = ((const f32x4*)g.c1)[i];
+        ((f32x4*)(smem + M_SOFF))[i] = ((const f32x4*)g.s1)[i];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dma_w1(0, 0, u);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dma_w1(1, 1, u);
+    load_x(blockIdx.x, 0, 2);
+    __builtin_amdgcn_s_waitcnt(0x0070);                // vmcnt(0) lgkmcnt(0)
+    ring_barrier();
+    fence();
+
+    for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+        MAGE_DASSERT(tile >= 0 && tile < g.ntiles);
+        const int m0 = tile * 128 + wave * 32;
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const float2 st = *(const float2*)((const char*)(g.stats + 2 * (long)(m0 + mt * 16)) + (unsigned)(l15 * 8));
+            mean[mt] = st.x;
+            rstd[mt] = st.y;
+        }
+        // ---- chunk 0: GEMM 1 alone, then its activation alone
+        g4_for<4>([&](auto j_) { rd_w1(0, 0, 0, decltype(j_)::value); });
+        fence();
+        phase_a(I0{}, std::false_type{}, 0);
+        consts_rd(0, 0, 0);
+        consts_rd(0, 0, 1);
+        asm volatile("s_nop 15" ::: "memory");         // the last MFMA's result -> VALU
+        fence();
+        g4_for<56>([&](auto k_) { act_op(I0{}, std::integral_constant<int, decltype(k_)::value / 28>{}, std::integral_constant<int, decltype(k_)::value % 28>{}); });
+        fence();
+        consts_rd(0, 1, 0);
+        consts_rd(0, 1, 1);
+        fence();
+        g4_for<56>([&](auto k_) { act_op(I0{}, std::integral_constant<int, 2 + decltype(k_)::value / 28>{}, std::integral_constant<int, decltype(k_)::value % 28>{}); });
+        fence();
+        consts_rd(1, 0, 0);
+        consts_rd(1, 0, 1);
+        fence();
+        wait_barrier();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) dma_w1(0, 2, u);
+        g4_for<4>([&](auto j_) { rd_w1(0, 1, 0, decltype(j_)::value); });
+        fence();
+        // ---- chunk 1: its GEMM 2 is the tile's first k-step
+        phase_a(I1{}, std::true_type{}, 1);
+        phase_b(I1{}, std::true_type{}, 1);
+        for (int c = 2; c < M_NCH; c += 2) {
+            phase_a(I0{}, std::true_type{}, c);
+            phase_b(I0{}, std::false_type{}, c);
+            phase_a(I1{}, std::true_type{}, c + 1);
+            phase_b(I1{}, std::false_type{}, c + 1);
+        }
+        // ---- the last chunk's pack and GEMM 2 (W2 stage 1); the next tile's rows are requested under it
+        asm volatile("s_nop 15" ::: "memory");
+        fence();
+        g4_for<8>([&](auto i_) { pack_op(I1{}, i_); });
+        fence();
+        wait_barrier();
+        g4_for<4>([&](auto j_) { rd_w2(0, 1, 0, decltype(j_)::value); });
+        fence();
+        const int ntile = tile + (int)gridDim.x < g.ntiles ? tile + (int)gridDim.x : tile;      // past the end: this tile's rows again (never used)
+        load_x(ntile, 0, MAGE4M_XPRE);
+        fence();
+        asm volatile("s_nop 1" ::: "memory");
+        g4_for<64>([&](auto i_) {
+            constexpr int i = decltype(i_)::value, b = i >> 3, k = i & 7, j = k >> 1, mt = k & 1, nb = 4 * b + j;
+            g4_mfma<mt * 32 + nb, false, k == 0, HF>(wf[b & 1][j], hpk[mt]);
+            fence();
+            if constexpr (k < 4 && b < 7) rd_w2((b + 1) & 1, 1, b + 1, k);
+            fence();
+        });
+        asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+        fence();
+        // ---- closing epilogue: (acc + b2) + x, the LayerNorm partial sums, whole-row stores: epilogue_lean on each 64-column slice
+        {
+            mage_gemm_desc d = {};
+            d.M = g.M;
+            d.N = M_C;
+            d.out_h = 1;
+            d.out_w = g.M;
+            d.y_mul_x = 1;
+            d.y_off = g.y_off;
+            d.ldy = g.ldy;
+            d.Y = g.Y;
+            d.residual = (const HT*)g.X + (long)(g.a_off - g.y_off) * g.ldx;
+            d.ldr = g.ldx;
+            d.ln_part = g.ln_part;
+            d.ln_part_rows = g.ln_part_rows;
+            char* stg = smem + M_STGOFF + wave * 4096;
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));               // keep the epilogue's lane-derived constants out of the chunk loop's registers
+            const int grp_e = lane_e >> 4;
+            g4_for<8>([&](auto sl_) {
+                constexpr int sl = decltype(sl_)::value;
+                f32x4 acc[2][4], biasm[4];
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) biasm[nt] = *(const f32x4*)(g.b2 + sl * 64 + nt * 16 + grp_e * 4);
+                g4_for<8>([&](auto q_) {
+                    constexpr int q = decltype(q_)::value, mt = q >> 2, nt = q & 3;
+                    acc[mt][nt] = g4_acc_read<mt * 32 + 4 * sl + nt, q == 0>();
+                });
+                epilogue_lean<MAGE_ACT_NONE, HT, 2, false, LNP ? LN_PRODUCE : LN_NONE, 0, HT, true>(d, biasm, acc, m0, sl * 64, lane_e, g.M, stg, 0);
+                fence();
+            });
+        }
+        fence();
+        load_x(ntile, MAGE4M_XPRE, 2);
+        fence();
+    }
+    __builtin_amdgcn_s_waitcnt(0x0070);                // the W1 pieces requested past the last tile land before the LDS is released
+}
+
+template <bool HF, bool LNP>
+int launch4m(const Gemm4mArgs& a, hipStream_t s, int n_cu) {
+    const int grid = a.ntiles >= n_cu ? n_cu : a.ntiles;
+    return mage_gemm_launch<gemm4m_kernel<HF, LNP>>(grid, 256, M_LDS, s, a);
+}
+
+}  // namespace
+
+extern "C" int mage_mlp_fused(int32_t dtype, int32_t w_dtype, int32_t y_dtype, int64_t M, int32_t C, const void* x, int64_t ldx, int64_t a_off, void* y, int64_t ldy, int64_t y_off,
+                              const void* w1, int64_t ldw1, const float* c1, const float* s1, const float* ln_stats, const void* w2, int64_t ldw2,
+                              const float* b2, float* ln_part, int64_t ln_part_rows, void* stream) {
+    MAGE_CHECK_ARG(dtype == MAGE_BF16 || dtype == MAGE_F16, "mage_mlp_fused: bf16 or f16 rows and weights (dtype %d)", (int)dtype);
+    MAGE_CHECK_ARG(w_dtype == dtype && y_dtype == dtype, "mage_mlp_fused: weights (dtype %d) and output rows (dtype %d) must have the type of x (%d)",
+                   (int)w_dtype, (int)y_dtype, (int)dtype);
+    MAGE_CHECK_ARG(C == M_C, "mage_mlp_fused: C=%d: the kernel is built for C = 512 (hidden = 2048)", (int)C);
+    MAGE_CHECK_ARG(M > 0 && M % 128 == 0, "mage_mlp_fused: M=%ld must be a positive multiple of 128 (whole row tiles)", (long)M);
+    MAGE_CHECK_ARG(x && y && w1 && c1 && s1 && ln_stats && w2 && b2, "mage_mlp_fused: x, y, w1, c1, s1, ln_stats, w2, b2 must be given");
+    MAGE_CHECK_ARG(ldx >= C && ldy >= C && ldx % 8 == 0 && ldy % 8 == 0, "mage_mlp_fused: ldx=%ld, ldy=%ld must be multiples of 8 and >= C", (long)ldx,
+                   (long)ldy);
+    MAGE_CHECK_ARG(ldw1 >= C && ldw2 >= 4 * C && ldw1 % 8 == 0 && ldw2 % 8 == 0, "mage_mlp_fused: ldw1=%ld >= C, ldw2=%ld >= 4C, multiples of 8",
+                   (long)ldw1, (long)ldw2);
+    MAGE_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)c1 | (uintptr_t)s1 | (uintptr_t)b2) & 15) == 0 &&
+                       (((uintptr_t)ln_stats | (uintptr_t)ln_part) & 7) == 0,
+                   "mage_mlp_fused: rows, weights and vectors must be 16-byte aligned, ln_stats and ln_part 8-byte aligned");
+    MAGE_CHECK_ARG(a_off >= 0 && y_off >= 0 && (x != y || a_off == y_off), "mage_mlp_fused: row offsets a_off=%ld, y_off=%ld (equal when in place)",
+                   (long)a_off, (long)y_off);
+    MAGE_CHECK_ARG(!ln_part || ln_part_rows >= M + y_off, "mage_mlp_fused: ln_part_rows=%ld must cover the output rows", (long)ln_part_rows);
+    MAGE_CHECK_ARG((M + a_off) * ldx < (1L << 31) && (M + y_off) * ldy < (1L << 31) && 2048 * ldw1 * 2 < (1L << 31) && 512 * ldw2 * 2 < (1L << 31),
+                   "mage_mlp_fused: operands beyond the kernel's 32-bit row arithmetic");
+    Gemm4mArgs a;
+    a.X = x;
+    a.Y = y;
+    a.W1 = w1;
+    a.W2 = w2;
+    a.c1 = c1;
+    a.s1 = s1;
+    a.stats = ln_stats;
+    a.b2 = b2;
+    a.ln_part = ln_part;
+    a.ln_part_rows = ln_part_rows;
+    a.M = (int)M;
+    a.ldx = (int)ldx;
+    a.ldy = (int)ldy;
+    a.ldw1 = (int)ldw1;
+    a.ldw2 = (int)ldw2;
+    a.a_off = (int)a_off;
+    a.y_off = (int)y_off;
+    a.ntiles = (int)(M / 128);
+    hipStream_t s = (hipStream_t)stream;
+    const int n_cu = mage_gemm_cu_count();
+    const bool hf = dtype == MAGE_F16;
+    if (ln_part) return hf ? launch4m<true, true>(a, s, n_cu) : launch4m<false, true>(a, s, n_cu);
+    return hf ? launch4m<true, false>(a, s, n_cu) : launch4m<false, false>(a, s, n_cu);
+}
+
+extern "C" int mage_mlp_fused_kernel_name(int32_t dtype, int32_t w_dtype, int32_t y_dtype, int64_t M, int32_t C, const void* x, int64_t ldx, int64_t a_off, void* y, int64_t ldy,
+                                          int64_t y_off, const void* w1, int64_t ldw1, const float* c1, const float* s1, const float* ln_stats,
+                                          const void* w2, int64_t ldw2, const float* b2, float* ln_part, int64_t ln_part_rows, char* buf, int32_t len) {
+    MAGE_CHECK_ARG(buf != nullptr && len > 0, "mage_mlp_fused_kernel_name: no buffer");
+    const void* kernel = nullptr;
+    mage_gemm_plan = &kernel;
+    const int r = mage_mlp_fused(dtype, w_dtype, y_dtype, M, C, x, ldx, a_off, y, ldy, y_off, w1, ldw1, c1, s1, ln_stats, w2, ldw2, b2, ln_part, ln_part_rows, nullptr);
+    mage_gemm_plan = nullptr;
+    if (r != MAGE_OK) return r;
+    return mage_kernel_symbol_name(kernel, buf, len, "mage_mlp_fused_kernel_name");
+}

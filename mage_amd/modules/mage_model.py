@@ -423,6 +423,7 @@ class FlatAxialDecoder(nn.Module):
         self.split_kind = 0                    # ops.BF16X3 / ops.F16X3: the fast parity modes (compute_dtype stays fp32)
         self.stream_bf16 = True                # bf16 mode: x stays in bf16 between the blocks (_stream_bf16)
         self.qkv_fuse_tiles = 8                # H / W attention inside the in_proj GEMM from this many (frame, group of 4 heads) entries per CU on (_qkv_fuse)
+        self.mlp_fuse_tiles = 8                # c_fc + QuickGELU + c_proj in one launch from this many 128-row tiles per CU on (_mlp_fuse)
         self._derived = _Derived(self)
 
     def initialize_parameters(self):
@@ -526,6 +527,19 @@ class FlatAxialDecoder(nn.Module):
         if Cc % 256 or not 256 <= Cc <= 1024 or M % 256 or (M + 8) * Cc * 2 >= 2 ** 32:
             return False
         return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 8) * torch.cuda.get_device_properties(xb.device).multi_processor_count
+
+    def _mlp_fuse(self, xb, M: int, stats_rows: bool, sb: bool) -> bool:
+        """The blocks of a pass run c_fc, QuickGELU and c_proj in ONE launch (ops.mlp_fused, csrc/gemm4m.hip: the hidden rows never reach memory): the
+        16-bit LayerNorm-fold path with (mean, rstd) rows and the 16-bit stream, C = 512 (the width the kernel is built for), whole 128-row tiles,
+        from mlp_fuse_tiles = eight tiles per CU on: the cfg2 full loop (262 144 rows: exactly eight on 256 CUs) qualifies, the incremental step's
+        16 k rows (half a tile per CU) and small batches keep the two GEMMs -- both write the same bits.  Only the cfg2 full loop was timed
+        (profiles/r20_mlp_fused.txt); no lower threshold, no other width and no f16 timing was measured.  use_cids=False (its head reads fp32 rows)
+        keeps the pair.  config mlp_fuse = False (MAGE_NO_MLP_FUSE=1) turns it off."""
+        if not (stats_rows and sb and self.use_cids and self.model_channels == 512 and config.get().mlp_fuse):
+            return False
+        if M % 128 or M * 512 >= 2 ** 31:
+            return False
+        return M // 128 >= getattr(self, "mlp_fuse_tiles", 8) * torch.cuda.get_device_properties(xb.device).multi_processor_count
 
     def _qkv_fuse_w(self, d, p, dt):
         """Block p's LayerNorm-folded in_proj operands (_ln_fold_w) as the fused launch takes them: all 3C rows in ops.qkv_pack_rows' order, with their colsum
@@ -677,9 +691,10 @@ class FlatAxialDecoder(nn.Module):
         xn = torch.empty(M, Cc, device=dev, dtype=dt)
         qkv = torch.empty(M, 3 * Cc, device=dev, dtype=dt)
         ao = torch.empty(M, Cc, device=dev, dtype=dt)
-        hdn = torch.empty(M, 4 * Cc, device=dev, dtype=dt)
         geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
         fuse = self._qkv_fuse(xb, M, hh, ww, fold and not inl, cache)
+        mfuse = self._mlp_fuse(xb, M, fold and not inl, sb)
+        hdn = None if mfuse else torch.empty(M, 4 * Cc, device=dev, dtype=dt)
         for i in range(self.layers):
             p = f"b{i}"
             ln1 = ln if i else ln0
@@ -709,6 +724,18 @@ class FlatAxialDecoder(nn.Module):
                 ops.ln_stats(part, Cc, 1e-5, stats)
             if ln is None:
                 ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5)
+            if mfuse:
+                # c_fc, QuickGELU and c_proj in one launch: a 128-row tile keeps its hidden rows on the CU (csrc/gemm4m.hip) -- the same bits in x
+                # and part as the two GEMMs below.  The last block writes the head's 16-bit rows xn, no partial sums.
+                lnw, lns = self._ln_fold_w(d, p, "c_fc", dt)
+                last = i == self.layers - 1
+                ops.mlp_fused(xb, xn if last else xb, M=M, C_=Cc, w1=lnw, c1=d[p + ".c_fc.lnc"], s1=lns, ln_stats=stats,
+                              w2=_wdt(d, p + ".c_proj", dt), b2=d[p + ".c_proj.b"], ln_part=None if last else part)
+                if last:
+                    xa = xn
+                else:
+                    ops.ln_stats(part, Cc, 1e-5, stats)
+                continue
             self._ln_linear(d, p, "c_fc", xn, xb, ln, hdn, M=M, N=4 * Cc, act=ops.ACT_QUICKGELU)
             if i < self.layers - 1:
                 _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, **res)

@@ -355,6 +355,38 @@ def gemm_attn_fused_qkv(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, ax
     return y
 
 
+def mlp_fused(x: torch.Tensor, y: torch.Tensor, *, M: int, C_: int, w1: torch.Tensor, c1, s1, ln_stats, w2: torch.Tensor, b2, ln_part=None,
+              ldx: Optional[int] = None, ldy: Optional[int] = None, a_off: int = 0, y_off: int = 0, ldw1: Optional[int] = None,
+              ldw2: Optional[int] = None):
+    """A decoder block's MLP in one launch (mage_mlp_fused, csrc/gemm4m.hip): y = x + c_proj(QuickGELU(c_fc(LN(x)))) on the 16-bit rows x with the
+    LayerNorm folded into c_fc (w1 = gamma * W_fc, c1 = W_fc beta + b, s1 = w1's row sums, ln_stats = (mean, rstd) rows), y is x (in place) or another
+    buffer; ln_part (optional, [C_/64, rows, 2]) receives the LayerNorm partial sums of the new rows.  The bits of ops.gemm (c_fc, QuickGELU)
+    followed by ops.gemm (c_proj with the 16-bit residual); the hidden rows are never stored.  C_ = 512, M % 128 == 0."""
+    l, s = _dev(x)
+    ldx, ldy = C_ if ldx is None else ldx, C_ if ldy is None else ldy
+    ldw1, ldw2 = C_ if ldw1 is None else ldw1, 4 * C_ if ldw2 is None else ldw2
+    lpr = 0
+    if ln_part is not None:
+        assert ln_part.dtype == torch.float32 and ln_part.dim() == 3 and ln_part.shape[2] == 2 and ln_part.is_contiguous(), tuple(ln_part.shape)
+        lpr = ln_part.shape[1]
+    args = (code(x), code(w1), code(y), M, C_, x.data_ptr(), ldx, a_off, y.data_ptr(), ldy, y_off, w1.data_ptr(), ldw1, _p(c1), _p(s1), _p(ln_stats),
+            w2.data_ptr(), ldw2, _p(b2), _p(ln_part), lpr)
+    ev = None
+    if PROFILE.enabled:
+        buf = C.create_string_buffer(256)
+        _lib.check(l.mage_mlp_fused_kernel_name(*args, buf, len(buf)), l)
+        key = buf.value.decode()
+        if PROFILE.wants(key):
+            ev = PROFILE.begin()
+    _lib.check(l.mage_mlp_fused(*args, s), l)
+    if ev is not None:
+        # algorithmic HBM bytes: x in, y out, both weights, the partial sums; the hidden rows never appear
+        es = x.element_size()
+        nb = 2.0 * M * C_ * es + 8.0 * C_ * C_ * es + (float(M) * (C_ // 64) * 8 if ln_part is not None else 0.0)
+        PROFILE.end(key, ev, 2.0 * M * C_ * 4 * C_ * 2, nb)
+    return y
+
+
 def gemm_is_small(a: torch.Tensor, M: int, N: int, K: int) -> bool:
     """True if a bf16 plain GEMM of this size runs on the few-rows kernel on a's device (mage_gemm_is_small): its LayerNorm-consuming form
     then takes (mean, rstd) straight from the producer's partial sums (ln_part + ln_eps) and the mage_ln_stats launch can be skipped."""
