@@ -1398,13 +1398,9 @@ class MAGE(nn.Module):
         self._refuse_off_gpu("policy_loss", batch, images, tokens, vn, (("advantages", advantages), ("behaviour_logprobs", b),
                                                                        ("reference_logprobs", ref), ("given", given)))
         args = dict(advantage=advantages.contiguous().reshape(-1), temperature=t, top_k=k, top_p=p, clip_lo=lo, clip_hi=hi,
-                    entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1))
-        if ref is not None:
-            args.update(reference=ref.contiguous().reshape(-1), kl_coef=float(kl_coef))
-        if given is not None:
-            args.update(given=given.reshape(-1))
-        if ratio_div is not None:
-            args.update(ratio_div=ratio_div)
+                    entropy_coef=float(entropy_coef), behaviour=None if b is None else b.contiguous().reshape(-1),
+                    reference=None if ref is None else ref.contiguous().reshape(-1), kl_coef=float(kl_coef),
+                    given=None if given is None else given.reshape(-1), ratio_div=ratio_div)
         with torch.cuda.device(images.device):
             loss, (info, res) = self._run_head(batch, mage_train.PolicyHead(tokens.contiguous(), **args))
             self.last_policy_token_logprobs = res["logprob"].view(tshape)

@@ -576,14 +576,11 @@ def _text_backward(te, run32: _Run, tape, dout, grads, pre: str = "text_encoder"
 
 # ----------------------------------------------------------------------------------------------------------------- whole model
 def _policy_scalars(policy: dict) -> dict:
-    """The scalar arguments mage_policy_loss and mage_policy_loss_bwd share."""
+    """The keyword arguments ops.policy_loss and ops.policy_loss_bwd share: the four scalars and the three options -- a reference (with its
+    kl_coef), a mask, a group -- each None where the head has none; ops picks the entry points from that."""
     kw = {k: policy[k] for k in ("temperature", "clip_lo", "clip_hi", "entropy_coef")}
-    if policy.get("reference") is not None:              # the anchored entry points; without a reference the plain ones, called as before
-        kw.update(reference_logprob=policy["reference"], kl_coef=policy["kl_coef"])
-    if policy.get("given") is not None:                  # the masked entry points, in either form
-        kw.update(given=policy["given"])
-    if policy.get("ratio_div") is not None:              # the grouped entry points: one importance ratio per frame or clip
-        kw.update(ratio_div=policy["ratio_div"])
+    kw.update(reference_logprob=policy.get("reference"), given=policy.get("given"), ratio_div=policy.get("ratio_div"))
+    kw["kl_coef"] = 0.0 if kw["reference_logprob"] is None else policy["kl_coef"]
     return kw
 
 
@@ -623,13 +620,14 @@ class MseHead:
 
 
 class PolicyHead:
-    """MAGE.policy_loss: mage_policy_loss over the given tokens, or mage_policy_loss_anchored when args holds a 'reference' (_policy_scalars'
-    rule).  args: advantage (fp32, one per clip or per token), behaviour (fp32 per token, or None) and the scalars temperature, top_k, top_p,
-    clip_lo, clip_hi, entropy_coef [, reference (fp32 per token), kl_coef] of include/mage_hip_ext.h.  saved: the kernel's results
-    (cut, logprob, summary [, kl]).  With a 'given' (bool per token: the token was given, not drawn) it is mage_policy_loss_masked: the means
-    are over the free tokens, parts gains 'given_fraction' and saved 'norm'.  With a 'ratio_div' (rows per group) it is
-    mage_policy_loss_grouped, given or not: parts are what the same call reports without it, saved gains 'group_logratio' (backward's
-    input), 'group_count' and 'norm'."""
+    """MAGE.policy_loss: the mage_policy_loss* pair that ops.policy_loss picks over the given tokens.  args: advantage (fp32, one per clip, frame
+    or token), behaviour (fp32 per token, or None), the scalars temperature, top_k, top_p, clip_lo, clip_hi, entropy_coef of
+    include/mage_hip_ext.h, and three options, each absent or None when not wanted:
+      reference (fp32 per token) with kl_coef   parts gains 'kl' and 'unanchored_fraction' (PARTS' last two), saved 'kl';
+      given (bool per token: given, not drawn)  the means are over the free tokens, parts gains 'given_fraction', saved 'norm';
+      ratio_div (rows per group)                one importance ratio per group: parts as without it, saved gains 'group_logratio',
+                                                'group_count' and 'norm'.
+    saved: the kernel's results (cut, logprob, summary and the options' own); backward hands back what policy_loss_bwd needs of them."""
     PARTS = ("loss", "entropy", "approx_kl", "clip_fraction", "outside_fraction", "kl", "unanchored_fraction")
 
     def __init__(self, tokens, **args):
@@ -638,22 +636,17 @@ class PolicyHead:
     def forward(self, model, logits, target, B):
         a = self.args
         res = ops.policy_loss(logits, target, a["advantage"], a["behaviour"], **_policy_scalars(a), top_k=a["top_k"], top_p=a["top_p"])
-        summary = res["summary"].tolist()
-        parts = dict(zip(self.PARTS, summary))
-        if a.get("given") is not None:                   # summary [8]: the unmasked call's keys (5, or 7 with a reference) and the share
-            parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary), given_fraction=summary[7])
-        elif a.get("ratio_div") is not None:             # summary [8] without a mask: the unmasked call's keys
-            parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary))
+        summary = res["summary"].tolist()                # [5], [7] with a reference, [8] with a mask or a group: the first 5 or 7 are the parts
+        parts = dict(zip(self.PARTS[:5 if a.get("reference") is None else 7], summary))
+        if a.get("given") is not None:
+            parts["given_fraction"] = summary[7]
         return res["summary"][0], parts, res
 
     def backward(self, logits, target, saved, gout, dt):
         a = self.args
-        kw = _policy_scalars(a)
-        if a.get("given") is not None or a.get("ratio_div") is not None:
-            kw.update(norm=saved["norm"])
-        if a.get("ratio_div") is not None:
-            kw.update(group_logratio=saved["group_logratio"])
-        return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **kw)
+        left = {k: saved[k] for k in ("norm", "group_logratio") if k in saved}        # what the forward call left for this one
+        return ops.policy_loss_bwd(logits, target, a["advantage"], a["behaviour"], saved["cut"], gout, _dlogits(logits, dt), **_policy_scalars(a),
+                                   **left)
 
 
 class PreferenceHead:

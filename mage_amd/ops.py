@@ -765,6 +765,22 @@ def _ratio_div(ratio_div, rows, adv_div, behaviour_logprob) -> int:
     return ratio_div
 
 
+# The four pairs of entry points: form -> (forward symbol; the backward one is it + "_bwd", summary length, outputs besides 'kl').  A call
+# has a reference, a mask and a group or not; the pair that takes the most of what is there serves it.
+_POLICY_FORMS = {"plain": ("mage_policy_loss", 5, ()), "anchored": ("mage_policy_loss_anchored", 7, ()),
+                 "masked": ("mage_policy_loss_masked", 8, ("norm",)),
+                 "grouped": ("mage_policy_loss_grouped", 8, ("norm", "group_logratio", "group_count"))}
+
+
+def _policy_form(reference_logprob, given, ratio_div) -> str:
+    return "grouped" if ratio_div is not None else "masked" if given is not None else "anchored" if reference_logprob is not None else "plain"
+
+
+def _policy_prefix(logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob) -> list:
+    """The arguments all eight entry points begin with."""
+    return [logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob)]
+
+
 def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Tensor, behaviour_logprob: Optional[torch.Tensor] = None, *,
                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, clip_lo: float = 0.2, clip_hi: float = 0.2,
                 entropy_coef: float = 0.0, adv_div: Optional[int] = None, reference_logprob: Optional[torch.Tensor] = None,
@@ -785,43 +801,29 @@ def policy_loss(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch.Ten
     _given_rows(given, logits)
     l, s = _dev(logits)
     rows, K, ld, adv_div = _policy_args(logits, tokens, advantage, behaviour_logprob, adv_div)
+    form = _policy_form(reference_logprob, given, ratio_div)
+    entry, n_summary, extra = _POLICY_FORMS[form]
     mk = lambda n, dt: torch.empty(n, device=logits.device, dtype=dt)      # noqa: E731
     out = dict(row_loss=mk(rows, torch.float32), logprob=mk(rows, torch.float32), entropy=mk(rows, torch.float32), cut=mk(rows, torch.int32),
-               summary=mk(8 if given is not None or ratio_div is not None else 5 if reference_logprob is None else 7, torch.float32))
-    if ratio_div is not None:
+               summary=mk(n_summary, torch.float32))
+    groups = 0
+    if form == "grouped":
         ratio_div = _ratio_div(ratio_div, rows, adv_div, behaviour_logprob)
-        out.update(norm=mk(1, torch.float32), group_logratio=mk(rows // ratio_div, torch.float32), group_count=mk(rows // ratio_div, torch.int32))
-        if reference_logprob is not None:
-            out["kl"] = mk(rows, torch.float32)
-        _lib.check(l.mage_policy_loss_grouped(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                              _p(behaviour_logprob), _p(reference_logprob), float(temperature), int(top_k), float(top_p),
-                                              float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
-                                              out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), _p(out.get("kl")),
-                                              out["summary"].data_ptr(), out["norm"].data_ptr(), _p(given), ratio_div,
-                                              out["group_logratio"].data_ptr(), out["group_count"].data_ptr(), s), l)
-        return out
-    if given is not None:
-        out["norm"] = mk(1, torch.float32)
-        if reference_logprob is not None:
-            out["kl"] = mk(rows, torch.float32)
-        _lib.check(l.mage_policy_loss_masked(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                             _p(behaviour_logprob), _p(reference_logprob), float(temperature), int(top_k), float(top_p),
-                                             float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
-                                             out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), _p(out.get("kl")),
-                                             out["summary"].data_ptr(), out["norm"].data_ptr(), given.data_ptr(), s), l)
-        return out
-    if reference_logprob is None:
-        _lib.check(l.mage_policy_loss(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
-                                      float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef),
-                                      out["row_loss"].data_ptr(), out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(),
-                                      out["summary"].data_ptr(), s), l)
-        return out
-    out["kl"] = mk(rows, torch.float32)
-    _lib.check(l.mage_policy_loss_anchored(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                           _p(behaviour_logprob), reference_logprob.data_ptr(), float(temperature), int(top_k), float(top_p),
-                                           float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), out["row_loss"].data_ptr(),
-                                           out["logprob"].data_ptr(), out["entropy"].data_ptr(), out["cut"].data_ptr(), out["kl"].data_ptr(),
-                                           out["summary"].data_ptr(), s), l)
+        groups = rows // ratio_div
+    sizes = dict(norm=(1, torch.float32), group_logratio=(groups, torch.float32), group_count=(groups, torch.int32))
+    out.update({k: mk(*sizes[k]) for k in extra})
+    if reference_logprob is not None:
+        out["kl"] = mk(rows, torch.float32)
+    plain = form == "plain"                                                 # the one entry point without the reference's three arguments
+    args = _policy_prefix(logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob) + ([] if plain else [_p(reference_logprob)])
+    args += [float(temperature), int(top_k), float(top_p), float(clip_lo), float(clip_hi), float(entropy_coef)]
+    args += ([] if plain else [float(kl_coef)]) + [out[k].data_ptr() for k in ("row_loss", "logprob", "entropy", "cut")]
+    args += ([] if plain else [_p(out.get("kl"))]) + [out["summary"].data_ptr()]
+    if form in ("masked", "grouped"):
+        args += [out["norm"].data_ptr(), _p(given)]
+    if form == "grouped":
+        args += [ratio_div, out["group_logratio"].data_ptr(), out["group_count"].data_ptr()]
+    _lib.check(getattr(l, entry)(*args, s), l)
     return out
 
 
@@ -844,33 +846,23 @@ def policy_loss_bwd(logits: torch.Tensor, tokens: torch.Tensor, advantage: torch
     assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
     assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
     assert dlogits.device == logits.device
-    if ratio_div is not None:
+    form = _policy_form(reference_logprob, given, ratio_div)
+    if form == "grouped":
         ratio_div = _ratio_div(ratio_div, rows, adv_div, behaviour_logprob)
+    if norm is not None:
         assert norm.dtype == torch.float32 and norm.numel() == 1 and norm.device == logits.device
+    if form == "grouped":
         assert group_logratio.dtype == torch.float32 and group_logratio.is_contiguous() and group_logratio.numel() == rows // ratio_div
         assert group_logratio.device == logits.device
-        _lib.check(l.mage_policy_loss_grouped_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                                  _p(behaviour_logprob), _p(reference_logprob), cut.data_ptr(), float(temperature),
-                                                  float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(),
-                                                  norm.data_ptr(), dlogits.data_ptr(), code(dlogits), _p(given), ratio_div,
-                                                  group_logratio.data_ptr(), s), l)
-        return dlogits
-    if given is not None:
-        assert norm.dtype == torch.float32 and norm.numel() == 1 and norm.device == logits.device
-        _lib.check(l.mage_policy_loss_masked_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                                 _p(behaviour_logprob), _p(reference_logprob), cut.data_ptr(), float(temperature), float(clip_lo),
-                                                 float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(), norm.data_ptr(),
-                                                 dlogits.data_ptr(), code(dlogits), given.data_ptr(), s), l)
-        return dlogits
-    if reference_logprob is None:
-        _lib.check(l.mage_policy_loss_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div, _p(behaviour_logprob),
-                                          cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef),
-                                          grad_out.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
-        return dlogits
-    _lib.check(l.mage_policy_loss_anchored_bwd(logits.data_ptr(), rows, K, ld, tokens.data_ptr(), advantage.data_ptr(), adv_div,
-                                               _p(behaviour_logprob), reference_logprob.data_ptr(), cut.data_ptr(), float(temperature),
-                                               float(clip_lo), float(clip_hi), float(entropy_coef), float(kl_coef), grad_out.data_ptr(),
-                                               dlogits.data_ptr(), code(dlogits), s), l)
+    plain = form == "plain"
+    args = _policy_prefix(logits, rows, K, ld, tokens, advantage, adv_div, behaviour_logprob) + ([] if plain else [_p(reference_logprob)])
+    args += [cut.data_ptr(), float(temperature), float(clip_lo), float(clip_hi), float(entropy_coef)] + ([] if plain else [float(kl_coef)])
+    args += [grad_out.data_ptr()] + ([norm.data_ptr()] if form in ("masked", "grouped") else []) + [dlogits.data_ptr(), code(dlogits)]
+    if form in ("masked", "grouped"):
+        args += [_p(given)]
+    if form == "grouped":
+        args += [ratio_div, group_logratio.data_ptr()]
+    _lib.check(getattr(l, _POLICY_FORMS[form][0] + "_bwd")(*args, s), l)
     return dlogits
 
 
