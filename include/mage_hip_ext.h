@@ -137,11 +137,42 @@ int mage_policy_loss_anchored_bwd(const float* logits, int64_t rows, int32_t K, 
  * and the update is mage_adam's with `scale` for grad_scale (the same code): a step whose norm is within the limit leaves mage_adam's bits
  * in p, m and v.  norm_out (device, fp32, may be null) receives (float)norm from one thread.  Nothing is read on the host.  A norm that is
  * not finite propagates (NaN: the scale is NaN; +inf: the scale is 0 and 0 * inf = NaN where the gradient is infinite), as
- * clip_grad_norm_(error_if_nonfinite=False) does; there is no skip-step guard.  max_norm finite and > 0, sumsq non-null and 8-byte aligned,
- * otherwise mage_adam's rules: MAGE_EINVAL otherwise, nothing launched. */
+ * clip_grad_norm_(error_if_nonfinite=False) does; the step that skips instead is mage_adam_guarded (below).  max_norm finite and > 0, sumsq
+ * non-null and 8-byte aligned, otherwise mage_adam's rules: MAGE_EINVAL otherwise, nothing launched. */
 int mage_sumsq(const float* g, int64_t n, double* out, void* stream);
 int mage_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int32_t step,
                       float grad_scale, const double* sumsq, float max_norm, float* norm_out, void* stream);
+
+/* The Adam step that can run unattended: mage_adam_clipped's launch with a skip of non-finite steps, AdamW's decoupled weight decay and an
+ * exponential moving average of the parameters: no site in the reference (bare Adam).  Serves FlatAdam(weight_decay=, no_decay=,
+ * ema_decay=, skip_nonfinite=) (mage_amd/optim.py).  One launch over a flat shard in mage_adam's grid; every thread reads the one device
+ * value *sumsq (when given) and derives the same decisions from it; nothing is read on the host.
+ * Norm and scale: with sumsq given, norm = sqrt(*sumsq) * grad_scale in fp64 and norm_out (device fp32, may be null) receives (float)norm
+ *   from one thread -- on a skipped step too, so the caller can see the inf or NaN.  max_norm > 0: the scale is mage_adam_clipped's, operation
+ *   for operation (coef = max_norm / (norm + 1e-6); grad_scale where coef >= 1, (float)(grad_scale * coef) otherwise).  max_norm == 0: no
+ *   clip, scale = grad_scale.
+ * Guard: with skip_nonfinite != 0, a *sumsq that is not finite makes every thread return before it loads p, g, m, v or ema: the five
+ *   buffers keep their bits.  Thread 0 of workgroup 0 then adds 1 to *skipped (device int64, may be null; one thread writes it and none
+ *   reads it).  mage_sumsq takes every square in fp64, where the square of an fp32 value cannot overflow, inf squared is inf and NaN stays
+ *   NaN, and adds non-negative terms: *sumsq is finite exactly when every gradient element is finite, so the guard is a test of the
+ *   gradient, not of its magnitude.  `step` counts CALLS: a skipped call still consumes its step number (the caller's counter advances, and
+ *   the bias corrections 1 - beta^step of the next call are those of step + 1).  This differs, on purpose, from "as if the call had not
+ *   happened": the corrections stay host values computed as mage_adam computes them, and the kernel stays one launch without device-side
+ *   state.  With skip_nonfinite == 0 a non-finite gradient propagates as in mage_adam / mage_adam_clipped.
+ * Decay: element i < n_decay gets p = p * decay_mul (one fp32 product, rounded on its own) before the Adam update -- torch.optim.AdamW's
+ *   order; the caller forms decay_mul = (float)(1.0 - (double)lr * weight_decay).  Elements >= n_decay are not decayed.  n_decay is any value
+ *   in [0, n]: the test is per element, a 16-byte chunk may straddle it.
+ * Update: the one statement mage_adam and mage_adam_clipped run (the same device function).  With finite gradients, ema null and
+ *   n_decay == 0 it leaves mage_adam_clipped's bits in p, m and v (max_norm > 0), or mage_adam's (max_norm == 0, whatever sumsq is).
+ * EMA: with ema (device fp32 [n], 16-byte aligned) non-null, ema = fma(ema_decay, ema, (1 - ema_decay) * p_new) after the update: 1 -
+ *   ema_decay one fp32 subtraction, the product rounded once, then one fused multiply-add; p_new is the value just stored.
+ * Arguments: mage_adam's rules (p, g, m, v non-null and 16-byte aligned, n > 0, step >= 1); ema null or 16-byte aligned; 0 <= n_decay <= n;
+ * decay_mul finite and in (0, 1]; ema_decay in (0, 1) when ema is given; max_norm finite and >= 0; sumsq non-null whenever max_norm > 0 or
+ * skip_nonfinite, 8-byte aligned when given; skipped null or 8-byte, norm_out null or 4-byte aligned: MAGE_EINVAL otherwise, nothing
+ * launched.  One kernel instance per (ema given, n_decay > 0): the plain form carries no load or test of the other two. */
+int mage_adam_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, int64_t n_decay, float lr, float beta1, float beta2,
+                      float eps, int32_t step, float grad_scale, float decay_mul, float ema_decay, const double* sumsq, float max_norm,
+                      int32_t skip_nonfinite, float* norm_out, int64_t* skipped, void* stream);
 
 /* Per-frame MSE, PSNR and SSIM between generated frames and their targets: no site in the reference (it reports no metric).  Serves
  * MAGE.video_metrics and the built-in rewards of MAGE.rollout (mage_amd/modules/mage_model.py).

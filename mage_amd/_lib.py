@@ -134,6 +134,7 @@ EXT_SIGNATURES = {
     "mage_policy_loss_anchored_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, i32, vp]),
     "mage_sumsq": (C.c_int, [vp, i64, vp, vp]),
     "mage_adam_clipped": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, vp, f32, vp, vp]),
+    "mage_adam_guarded": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, i32, f32, f32, f32, vp, f32, i32, vp, vp, vp]),
     "mage_video_metrics": (C.c_int, [vp, i64, vp, i64, i64, i32, i32, i32, i32, i64, f32, vp, vp, vp, vp]),
     "mage_group_advantages": (C.c_int, [vp, i64, i32, i32, i32, f32, vp, vp, vp]),
     "mage_frame_advantages": (C.c_int, [vp, i64, i32, i32, f32, i32, f32, i32, i32, vp, vp, vp]),

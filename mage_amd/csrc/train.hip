@@ -678,8 +678,18 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, Y
 // ------------------------------------------------------------------------------------------------ Adam
 // torch.optim.Adam semantics (main_mage.py:121: betas (0.9, 0.98), eps 1e-6, no weight decay, no amsgrad):
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
-// the four (or fewer, at the arena's tail) elements from index i on: the one statement of the update, shared by adam_kernel and
-// adam_clipped_kernel so that equal grad_scale values give equal bits
+// One element: the one statement of the update, shared by adam_kernel, adam_clipped_kernel and adam_guarded_kernel so that equal scales
+// give equal bits.  A macro, not a function: which of the two products of `a * x + b * y` the compiler fuses into the addition is its
+// choice per use site (the vector path, the two-wide loop it makes of the tail and that loop's remainder choose differently), and it
+// follows the shape of the code around the statement -- an inlined function taking references moved it in the tail.  The expansion is the
+// text the kernels have always had; P, M, V are lvalues, and lr, b1, b2, eps, bc1, bc2_sqrt are taken from the scope.
+#define ADAM_ELEMENT(P, G, M, V, SCALE)                                   \
+    const float ge = (G) * (SCALE);                                       \
+    (M) = b1 * (M) + (1.f - b1) * ge;                                     \
+    (V) = b2 * (V) + (1.f - b2) * ge * ge;                                \
+    (P) -= (lr / bc1) * ((M) / (sqrtf(V) / bc2_sqrt + eps));
+
+// the four (or fewer, at the arena's tail) elements from index i on
 __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                             long n, long i, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
                                             float grad_scale) {
@@ -687,20 +697,14 @@ __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* 
         f32x4 pp = *(f32x4*)(p + i), gg = *(const f32x4*)(g + i), mm = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float ge = gg[e] * grad_scale;
-            mm[e] = b1 * mm[e] + (1.f - b1) * ge;
-            vv[e] = b2 * vv[e] + (1.f - b2) * ge * ge;
-            pp[e] -= (lr / bc1) * (mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps));
+            ADAM_ELEMENT(pp[e], gg[e], mm[e], vv[e], grad_scale)
         }
         *(f32x4*)(p + i) = pp;
         *(f32x4*)(m + i) = mm;
         *(f32x4*)(v + i) = vv;
     } else {
         for (long j = i; j < n; ++j) {
-            const float ge = g[j] * grad_scale;
-            m[j] = b1 * m[j] + (1.f - b1) * ge;
-            v[j] = b2 * v[j] + (1.f - b2) * ge * ge;
-            p[j] -= (lr / bc1) * (m[j] / (sqrtf(v[j]) / bc2_sqrt + eps));
+            ADAM_ELEMENT(p[j], g[j], m[j], v[j], grad_scale)
         }
     }
 }
@@ -727,6 +731,62 @@ __global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ p
     const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
     adam_update(p, g, m, v, n, i, lr, b1, b2, eps, bc1, bc2_sqrt, scale);
+}
+
+// mage_adam_guarded (include/mage_hip_ext.h): adam_clipped_kernel's scale from the one device value *sumsq, and around the shared update
+// statement a skip of the whole step when *sumsq is not finite (every thread returns before it loads anything; one thread counts the skip),
+// AdamW's decoupled decay of the elements below n_decay (p * decay_mul, rounded on its own, before the update) and an exponential moving
+// average of the updated parameter, taken from the register on the vector path.  One instance per (EMA, DECAY): the plain form loads and
+// tests nothing extra.
+template <bool EMA, bool DECAY>
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, float* __restrict__ ema, long n, long n_decay, float lr,
+                                                           float b1, float b2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                                                           float decay_mul, float ema_decay, const double* __restrict__ sumsq, float max_norm,
+                                                           int skip_nonfinite, float* __restrict__ norm_out, long long* __restrict__ skipped) {
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    float scale = grad_scale;
+    if (sumsq) {
+        const double ss = sumsq[0];
+        const double norm = sqrt(ss) * (double)grad_scale;
+        if (norm_out && first) norm_out[0] = (float)norm;
+        if (skip_nonfinite && !__builtin_isfinite(ss)) {
+            if (skipped && first) skipped[0] += 1;
+            return;
+        }
+        if (max_norm > 0.f) {
+            const double coef = (double)max_norm / (norm + 1e-6);
+            scale = coef >= 1.0 ? grad_scale : (float)((double)grad_scale * coef);
+        }
+    }
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float ema_in = __fsub_rn(1.f, ema_decay);
+    if (i + 4 <= n) {
+        f32x4 pp = *(f32x4*)(p + i), gg = *(const f32x4*)(g + i), mm = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (DECAY && i + e < n_decay) pp[e] = __fmul_rn(pp[e], decay_mul);
+            ADAM_ELEMENT(pp[e], gg[e], mm[e], vv[e], scale)
+        }
+        *(f32x4*)(p + i) = pp;
+        *(f32x4*)(m + i) = mm;
+        *(f32x4*)(v + i) = vv;
+        if (EMA) {
+            f32x4 aa = *(f32x4*)(ema + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) aa[e] = __fmaf_rn(ema_decay, aa[e], __fmul_rn(ema_in, pp[e]));
+            *(f32x4*)(ema + i) = aa;
+        }
+    } else {
+        // the arena's last one to three elements, once per launch: the decay and the EMA in loops of their own around adam_update's own tail
+        // loop, so that the update between them is compiled as it is in the other two kernels (here p passes through the thread's own store)
+        if (DECAY)
+            for (long j = i; j < n && j < n_decay; ++j) p[j] = __fmul_rn(p[j], decay_mul);
+        adam_update(p, g, m, v, n, i, lr, b1, b2, eps, bc1, bc2_sqrt, scale);
+        if (EMA)
+            for (long j = i; j < n; ++j) ema[j] = __fmaf_rn(ema_decay, ema[j], __fmul_rn(ema_in, p[j]));
+    }
 }
 
 // mage_sumsq, stage 1 of 2: workgroup b owns elements [b * chunk, (b + 1) * chunk) and leaves their sum of squares in g_sumsq_part[b].
@@ -1489,6 +1549,36 @@ extern "C" int mage_adam_clipped(float* p, const float* g, float* m, float* v, i
     hipLaunchKernelGGL(adam_clipped_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
                        beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, sumsq, max_norm, norm_out);
     MAGE_CHECK_LAUNCH("mage_adam_clipped");
+    return MAGE_OK;
+}
+
+extern "C" int mage_adam_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, int64_t n_decay, float lr, float beta1,
+                                 float beta2, float eps, int32_t step, float grad_scale, float decay_mul, float ema_decay, const double* sumsq,
+                                 float max_norm, int32_t skip_nonfinite, float* norm_out, int64_t* skipped, void* stream) {
+    MAGE_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "mage_adam_guarded: bad arguments");
+    MAGE_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0,
+                   "mage_adam_guarded: arenas (and ema, when given) must be 16-byte aligned");
+    MAGE_CHECK_ARG(n_decay >= 0 && n_decay <= n, "mage_adam_guarded: n_decay=%ld outside [0, n=%ld]", (long)n_decay, (long)n);
+    MAGE_CHECK_ARG(__builtin_isfinite(decay_mul) && decay_mul > 0.f && decay_mul <= 1.f, "mage_adam_guarded: decay_mul=%g must lie in (0, 1]",
+                   (double)decay_mul);
+    MAGE_CHECK_ARG(!ema || (ema_decay > 0.f && ema_decay < 1.f), "mage_adam_guarded: ema_decay=%g must lie in (0, 1)", (double)ema_decay);
+    MAGE_CHECK_ARG(__builtin_isfinite(max_norm) && max_norm >= 0.f, "mage_adam_guarded: max_norm=%g must be finite and >= 0", (double)max_norm);
+    MAGE_CHECK_ARG(sumsq || !(max_norm > 0.f || skip_nonfinite), "mage_adam_guarded: max_norm > 0 and skip_nonfinite need sumsq");
+    MAGE_CHECK_ARG((((uintptr_t)sumsq) & 7) == 0 && (((uintptr_t)skipped) & 7) == 0 && (((uintptr_t)norm_out) & 3) == 0,
+                   "mage_adam_guarded: sumsq and skipped must be 8-byte aligned (or null), norm_out null or 4-byte aligned");
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    const dim3 grid((unsigned)((n / 4 + 256) / 256)), blk(256);
+#define GUARDED(E, D)                                                                                                                       \
+    hipLaunchKernelGGL((adam_guarded_kernel<E, D>), grid, blk, 0, (hipStream_t)stream, p, g, m, v, ema, (long)n, (long)n_decay, lr, beta1,  \
+                       beta2, eps, bc1, bc2_sqrt, grad_scale, decay_mul, ema_decay, sumsq, max_norm, (int)skip_nonfinite, norm_out,         \
+                       (long long*)skipped)
+    if (ema && n_decay > 0) GUARDED(true, true);
+    else if (ema) GUARDED(true, false);
+    else if (n_decay > 0) GUARDED(false, true);
+    else GUARDED(false, false);
+#undef GUARDED
+    MAGE_CHECK_LAUNCH("mage_adam_guarded");
     return MAGE_OK;
 }
 

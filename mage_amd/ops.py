@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT_RELU, ACT_TANH, BF16, BF16X3, F16, F16X3, F32, AttnDesc, GemmDesc
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
-           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
+           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "adam_guarded", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
            "token_logprob", "clip_scores", "video_metrics", "group_advantages", "frame_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
@@ -1488,6 +1488,25 @@ def adam_clipped(p, g, m, v, *, lr: float, beta1: float, beta2: float, eps: floa
     assert norm_out is None or (norm_out.dtype == torch.float32 and norm_out.numel() == 1 and norm_out.device == p.device)
     _lib.check(l.mage_adam_clipped(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1), float(beta2),
                                    float(eps), int(step), float(grad_scale), sumsq.data_ptr(), float(max_norm), _p(norm_out), s), l)
+    return p
+
+
+def adam_guarded(p, g, m, v, *, lr: float, beta1: float, beta2: float, eps: float, step: int, grad_scale: float = 1.0,
+                 ema: Optional[torch.Tensor] = None, ema_decay: float = 0.0, n_decay: int = 0, decay_mul: float = 1.0,
+                 sumsq: Optional[torch.Tensor] = None, max_norm: float = 0.0, skip_nonfinite: bool = False,
+                 norm_out: Optional[torch.Tensor] = None, skipped: Optional[torch.Tensor] = None):
+    """adam / adam_clipped in one launch that can also skip a step whose gradient is not finite (skip_nonfinite, decided on the device from
+    sumsq; skipped, int64 [1], counts the skips), decay the first n_decay elements by decay_mul before the update (AdamW's order) and keep an
+    exponential moving average of the updated parameters in ema (fp32, p's size).  max_norm 0: no clip (mage_adam_guarded)."""
+    l, s = _dev(p)
+    for t_ in (p, g, m, v) + (() if ema is None else (ema,)):
+        assert t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == p.numel() and t_.device == p.device
+    assert sumsq is None or (sumsq.dtype == torch.float64 and sumsq.numel() == 1 and sumsq.device == p.device)
+    assert norm_out is None or (norm_out.dtype == torch.float32 and norm_out.numel() == 1 and norm_out.device == p.device)
+    assert skipped is None or (skipped.dtype == torch.int64 and skipped.numel() == 1 and skipped.device == p.device)
+    _lib.check(l.mage_adam_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(ema), p.numel(), int(n_decay), float(lr),
+                                   float(beta1), float(beta2), float(eps), int(step), float(grad_scale), float(decay_mul), float(ema_decay),
+                                   _p(sumsq), float(max_norm), int(bool(skip_nonfinite)), _p(norm_out), _p(skipped), s), l)
     return p
 
 
