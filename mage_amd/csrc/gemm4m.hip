@@ -6,10 +6,13 @@
 //     chunk epilogue  : h = QuickGELU(rstd (hacc - mean s) + c1), rounded to the 16-bit type: gemm4h's operations in gemm4h's order
 //     GEMM 2 (chunk c): out[32 rows x 512 columns per wave] += h W2^T -- ONE k-step (k = 32 c .. 32 c + 31) into each of the 64 accumulator blocks
 // so every output element sees c_proj's k-steps in ascending order into one accumulator, and every h element c_fc's: with the same MFMA and the
-// same epilogue operations (the closing epilogue IS epilogue_lean, residual in the epilogue + LN_PRODUCE) the bits are the pair's.
+// same epilogue operations (the closing epilogue is epilogue_lean's two-tile form, residual in the epilogue + LN_PRODUCE, operation for operation)
+// the bits are the pair's.
 //
 // Wave = 32 rows (two 16-row tiles mt) x all 512 output columns: 64 accumulator blocks = 256 literal AGPRs (gemm4_regs.h); its x rows are the
-// B-operand fragments of GEMM 1 for the whole tile (128 VGPRs, loaded once per tile, the next tile's under the closing epilogue).
+// B-operand fragments of GEMM 1 for the whole tile (128 VGPRs, loaded once per tile).  The closing epilogue takes the residual from those same
+// registers (the rows are not read a second time) and hands each 64-column slice's registers to the next tile's rows as soon as the slice is
+// staged, so the next tile's rows arrive under the epilogue with nothing waiting for them; the first tile's are loaded in the prologue.
 // Operand roles: GEMM 1 takes the W1 fragment as A-operand, so an accumulator block holds (lane = row l15, register e of lane group g = hidden unit
 // 4 g + e of the block's 16); W1's rows are gathered into LDS in the order  slot (t, r) <- hidden unit 8 (r / 4) + 4 t + r % 4  (t = block 0 | 1 of the
 // chunk), so that a lane's two packed blocks are the 8 CONSECUTIVE k = 8 g .. 8 g + 7 of GEMM 2's B-operand, in natural order (nothing is permuted
@@ -21,7 +24,8 @@
 //     Pb(c): GEMM 2 (c-1)    || activation of chunk c (in place)     second half: LDS-DMA of W1(c+2), first fragments of GEMM 1 (c+1)
 // A stage is requested one whole chunk before the barrier that publishes it (s_waitcnt vmcnt(8): the 8 pieces of the other ring are younger).
 // The epilogue arithmetic is single-instruction asm statements between the MFMA statements (gemm4h's way), two per MFMA slot.
-// LDS: 128 KB of rings, 16 KB of c_fc's epilogue constants (colsum, bias: loaded once per workgroup), 4 x 4 KB staging for epilogue_lean = 160 KB.
+// LDS: 128 KB of rings, 16 KB of c_fc's epilogue constants (colsum, bias: loaded once per workgroup), 4 x 4 KB staging for the closing epilogue
+// (per wave: 2 KB for the transposed output rows, 2 KB for the residual fragments on their way into the accumulator layout) = 160 KB.
 #include "gemm_shared.h"
 #include "gemm4_regs.h"
 
@@ -45,8 +49,23 @@ constexpr int M_C = 512, M_HID = 2048, M_NCH = M_HID / 32;
 constexpr int M_STG = 32768, M_W2OFF = 2 * M_STG, M_COFF = 4 * M_STG, M_SOFF = M_COFF + M_HID * 4, M_STGOFF = M_SOFF + M_HID * 4;
 constexpr int M_LDS = M_STGOFF + 4 * 4096;              // 160 KB
 
-#ifndef MAGE4M_XPRE
-#define MAGE4M_XPRE 1     // how many of the next tile's two 16-row fragment sets are requested BEFORE the closing epilogue (the rest after it)
+#ifdef MAGE4M_STAMP
+// tuning build (tools/probes/gemm4m_probe.hip): wave 0 of each workgroup takes five 100 MHz wall-clock stamps per tile -- 0 tile start, 1 chunk loop done
+// (before the last pack), 2 last GEMM 2 done, 3 closing epilogue done, 4 tile end (where the kernel used to request the rest of the next tile's rows
+// after the epilogue; nothing lies between 3 and 4 now) -- into scalar registers and writes them at the tile's end: the stores are older than every
+// LDS-DMA piece of the next tile, so no counted wait of the chunk loop sees them.  [workgroup][tile of the workgroup][5]
+constexpr int M_STAMP_WG = 256, M_STAMP_TILES = 16;
+__device__ unsigned long long m_stamps[M_STAMP_WG * M_STAMP_TILES * 5];
+#define M_STAMP(k)                                         \
+    do {                                                   \
+        fence();                                           \
+        stamp[k] = __builtin_amdgcn_s_memrealtime();       \
+        fence();                                           \
+    } while (0)
+#else
+#define M_STAMP(k) \
+    do {           \
+    } while (0)
 #endif
 
 // one LDS-DMA piece: 64 lanes x 16 B from (scalar base + per-lane offset) to LDS lds .. lds + 1023
@@ -222,8 +241,13 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
     ring_barrier();
     fence();
 
+#ifdef MAGE4M_STAMP
+    unsigned long long stamp[5];
+    int stamp_tile = 0;
+#endif
     for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
         MAGE_DASSERT(tile >= 0 && tile < g.ntiles);
+        M_STAMP(0);
         const int m0 = tile * 128 + wave * 32;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -263,7 +287,8 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
             phase_a(I1{}, std::true_type{}, c + 1);
             phase_b(I1{}, std::false_type{}, c + 1);
         }
-        // ---- the last chunk's pack and GEMM 2 (W2 stage 1); the next tile's rows are requested under it
+        M_STAMP(1);
+        // ---- the last chunk's pack and GEMM 2 (W2 stage 1); the closing epilogue's first bias values are requested under it
         asm volatile("s_nop 15" ::: "memory");
         fence();
         g4_for<8>([&](auto i_) { pack_op(I1{}, i_); });
@@ -271,8 +296,12 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
         wait_barrier();
         g4_for<4>([&](auto j_) { rd_w2(0, 1, 0, decltype(j_)::value); });
         fence();
-        const int ntile = tile + (int)gridDim.x < g.ntiles ? tile + (int)gridDim.x : tile;      // past the end: this tile's rows again (never used)
-        load_x(ntile, 0, MAGE4M_XPRE);
+        int lane_e = lane;
+        asm volatile("" : "+v"(lane_e));               // keep the epilogue's lane-derived constants out of the chunk loop's registers
+        const int l15_e = lane_e & 15, grp_e = lane_e >> 4;
+        f32x4 bnext[4];                                // c_proj's bias of the NEXT slice of the closing epilogue: slice 0's lands under this GEMM 2
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) bnext[nt] = *(const f32x4*)(g.b2 + nt * 16 + grp_e * 4);
         fence();
         asm volatile("s_nop 1" ::: "memory");
         g4_for<64>([&](auto i_) {
@@ -284,41 +313,118 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
         });
         asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
         fence();
-        // ---- closing epilogue: (acc + b2) + x, the LayerNorm partial sums, whole-row stores: epilogue_lean on each 64-column slice
-        {
-            mage_gemm_desc d = {};
-            d.M = g.M;
-            d.N = M_C;
-            d.out_h = 1;
-            d.out_w = g.M;
-            d.y_mul_x = 1;
-            d.y_off = g.y_off;
-            d.ldy = g.ldy;
-            d.Y = g.Y;
-            d.residual = (const HT*)g.X + (long)(g.a_off - g.y_off) * g.ldx;
-            d.ldr = g.ldx;
-            d.ln_part = g.ln_part;
-            d.ln_part_rows = g.ln_part_rows;
+        M_STAMP(2);
+        // ---- closing epilogue: (acc + b2) + x, the LayerNorm partial sums, whole-row stores, 64-column slice by slice: epilogue_lean's two-tile
+        // form (16-bit rows, residual in the epilogue, LN_PRODUCE) operation for operation, except where the residual comes from: the slice's
+        // x values are the wave's own fragments xf[mt][2 sl], xf[mt][2 sl + 1] (lane (l15, grp): row l15, columns 32 ks + 8 grp .. + 7), written
+        // to the upper half of the staging window where epilogue_lean lands the rows it loads (row r, 16-byte chunk c at c ^ ((r >> 1) & 7)) and
+        // read back in the accumulator layout.  Nothing in a slice waits for memory that was requested in it: once a slice's fragments are
+        // staged their registers take the NEXT tile's (GEMM 1 walks k upward, so the youngest are needed last), and the next slice's bias is
+        // requested before this slice's rows are stored, so the counted wait at its use leaves the stores in flight.  NEXT = false (the
+        // workgroup's last tile): no rows are requested.  A template parameter, not a branch around the loads: the compiler's wait counts stay exact.
+        auto close_tile = [&](auto NEXT_) __attribute__((always_inline)) {
+            constexpr bool NEXT = decltype(NEXT_)::value;
             char* stg = smem + M_STGOFF + wave * 4096;
-            int lane_e = lane;
-            asm volatile("" : "+v"(lane_e));               // keep the epilogue's lane-derived constants out of the chunk loop's registers
-            const int grp_e = lane_e >> 4;
+            const int rr = lane_e >> 3, cc = lane_e & 7, rsw_e = (l15_e >> 1) & 7;
+            int woff[4], roff[2], xwoff[2];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) woff[nt] = l15_e * 128 + (((nt * 2 + (grp_e >> 1)) ^ rsw_e) << 4) + (grp_e & 1) * 8;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = rr + 8 * i;
+                roff[i] = r * 128 + ((cc ^ ((r >> 1) & 7)) << 4);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) xwoff[h] = 2048 + l15_e * 128 + (((4 * h + grp_e) ^ rsw_e) << 4);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) MAGE_DASSERT(woff[nt] >= 0 && woff[nt] + 8 <= 2048);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) MAGE_DASSERT(roff[i] >= 0 && roff[i] + 16 <= 2048 && xwoff[i] >= 2048 && xwoff[i] + 16 <= 4096);
+            HT* const yrow = (HT*)g.Y + ((long)(m0 + rr) + g.y_off) * g.ldy + cc * 8;           // row m0 + rr of the tile, the lane's 8 columns of slice 0
+            const long step = 8L * g.ldy;
+            [[maybe_unused]] float* const prow = g.ln_part + ((long)(m0 + l15_e) + g.y_off) * 2;
+            [[maybe_unused]] const char* xnext[2];
+            if constexpr (NEXT) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+                    xnext[mt] = (const char*)g.X + ((long)(tile + (int)gridDim.x) * 128 + wave * 32 + mt * 16 + g.a_off) * g.ldx * 2;
+            }
             g4_for<8>([&](auto sl_) {
                 constexpr int sl = decltype(sl_)::value;
-                f32x4 acc[2][4], biasm[4];
+                f32x4 biasm[4];
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) biasm[nt] = *(const f32x4*)(g.b2 + sl * 64 + nt * 16 + grp_e * 4);
-                g4_for<8>([&](auto q_) {
-                    constexpr int q = decltype(q_)::value, mt = q >> 2, nt = q & 3;
-                    acc[mt][nt] = g4_acc_read<mt * 32 + 4 * sl + nt, q == 0>();
-                });
-                epilogue_lean<MAGE_ACT_NONE, HT, 2, false, LNP ? LN_PRODUCE : LN_NONE, 0, HT, true>(d, biasm, acc, m0, sl * 64, lane_e, g.M, stg, 0);
+                for (int nt = 0; nt < 4; ++nt) biasm[nt] = bnext[nt];
+                auto stage = [&](auto mt_, u32x4(&o)[2]) __attribute__((always_inline)) {      // math + transpose of 16-row tile mt: results land in o[] (row-contiguous)
+                    constexpr int mt = decltype(mt_)::value;
+                    [[maybe_unused]] float s1 = 0.f, s2 = 0.f;
+                    uint2 auxb[4];
+                    f32x4 acc[4];                          // the tile's 16 accumulator registers of this slice, read when it is staged (16 VGPRs, not 32)
+                    g4_for<4>([&](auto nt_) {
+                        constexpr int nt = decltype(nt_)::value;
+                        acc[nt] = g4_acc_read<mt * 32 + 4 * sl + nt, mt == 0 && nt == 0>();
+                    });
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) *(u32x4*)(stg + xwoff[h]) = xf[mt][2 * sl + h];
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) auxb[nt] = *(const uint2*)(stg + 2048 + woff[nt]);
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        f32x4 v;
+                        v = acc[nt] + biasm[nt];
+                        v = v + widen4<HT>(auxb[nt]);
+                        if constexpr (LNP) {
+                            s1 += (v[0] + v[1]) + (v[2] + v[3]);
+                            s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+                        }
+                        *(uint2*)(stg + woff[nt]) = uint2{pack16x2<HT>(v[0], v[1]), pack16x2<HT>(v[2], v[3])};
+                    }
+                    if constexpr (LNP) {
+                        // the four lane groups hold four 16-column pieces of row l15: fixed-order sum, written by group 0
+                        s1 += __shfl_xor(s1, 16);
+                        s2 += __shfl_xor(s2, 16);
+                        s1 += __shfl_xor(s1, 32);
+                        s2 += __shfl_xor(s2, 32);
+                        if (grp_e == 0) *(float2*)(prow + ((long)sl * g.ln_part_rows + mt * 16) * 2) = float2{s1, s2};      // slice-major
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) o[i] = *(const u32x4*)(stg + roff[i]);
+                };
+                u32x4 o[2][2];
+                stage(I0{}, o[0]);
+                stage(I1{}, o[1]);
+                fence();
+                if constexpr (sl < 7) {
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) bnext[nt] = *(const f32x4*)(g.b2 + (sl + 1) * 64 + nt * 16 + grp_e * 4);
+                }
+                if constexpr (NEXT) {
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) xf[mt][2 * sl + h] = *(const u32x4*)(xnext[mt] + (2 * sl + h) * 64 + xoff);
+                }
+                fence();
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)      // streaming stores, as epilogue_lean's: the rows are not read again by this launch
+                        __builtin_nontemporal_store(o[mt][i], (u32x4*)(yrow + sl * 64 + (2 * mt + i) * step));
                 fence();
             });
+        };
+        if (tile + (int)gridDim.x < g.ntiles) close_tile(std::true_type{});
+        else close_tile(std::false_type{});
+        fence();
+        M_STAMP(3);
+        M_STAMP(4);
+#ifdef MAGE4M_STAMP
+        if (tid == 0 && blockIdx.x < M_STAMP_WG && stamp_tile < M_STAMP_TILES) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) m_stamps[((int)blockIdx.x * M_STAMP_TILES + stamp_tile) * 5 + k] = stamp[k];
         }
+        ++stamp_tile;
         fence();
-        load_x(ntile, MAGE4M_XPRE, 2);
-        fence();
+#endif
     }
     __builtin_amdgcn_s_waitcnt(0x0070);                // the W1 pieces requested past the last tile land before the LDS is released
 }
