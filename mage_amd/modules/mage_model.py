@@ -81,20 +81,6 @@ def _wsplit(d: Dict[str, torch.Tensor], name: str, kind: int) -> torch.Tensor:
     return w
 
 
-def _lin_fp32(a, d, name, y, *, M, N, K, sk=0, lo=0, hi=None, a_split=None, **kw):
-    """fp32-class Linear of the once-per-clip prologue (text encoder, motion-anchor encoder): y = a @ W[lo:hi]^T + b[lo:hi] (+ epilogue).
-    sk = 0: the exact-fp32 MFMA chain (precision 'fp32').  sk = F16X3: split-precision operands, three f16 MFMA products per K slab
-    (mage_hip.h) -- 3x the rate, and a smaller error than the fp32 chain's own accumulation (profiles/r03_split_probe.txt); `a` is split
-    here (one small pass) unless the producer already wrote split rows (a_split)."""
-    hi = d[name + ".f32"].shape[0] if hi is None else hi
-    b = d.get(name + ".b")
-    b = None if b is None else b[lo:hi]
-    if sk and K % 64 == 0 and kw.get("act", ops.ACT_NONE) in (ops.ACT_NONE, ops.ACT_QUICKGELU):
-        a_s = a_split if a_split is not None else ops.split(a, sk)
-        return ops.gemm(a_s, _wsplit(d, name, sk)[lo:hi], y, M=M, N=N, K=K, lda=2 * K, ldy=kw.pop("ldy", N), bias=b, split_kind=sk, **kw)
-    return ops.gemm(a, d[name + ".f32"][lo:hi], y, M=M, N=N, K=K, lda=K, ldy=kw.pop("ldy", N), bias=b, **kw)
-
-
 def _to_dt(x: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
     """fp32 rows in the decoder's compute dtype (mage_cast)."""
     return x if dt == x.dtype else ops.cast(x.contiguous(), torch.empty(x.shape, device=x.device, dtype=dt))
@@ -121,9 +107,27 @@ def _pack_linear(d: Dict[str, torch.Tensor], name: str, weight: torch.Tensor, bi
         d[name + ".b"] = bias.float().contiguous()
 
 
-def _linear(a, d, name, y, dt, *, M, N, K, **kw):
-    return ops.gemm(a, _wdt(d, name, dt), y, M=M, N=N, K=K, lda=kw.pop("lda", K), ldy=kw.pop("ldy", N),
-                    bias=d.get(name + ".b"), **kw)
+def _linear(a, d, name, y, dt, *, M, N, K, sk=0, lo=0, hi=None, **kw):
+    """The Linear layer `name` of the derived weights d: y = a @ W[lo:hi]^T + b[lo:hi] (+ the epilogue that kw asks of ops.gemm).
+    sk = 0: the weight copy in the compute dtype dt (fp32: the exact-fp32 MFMA chain).  sk = BF16X3 / F16X3 (the fast parity modes, and the
+    once-per-clip encoders outside precision 'fp32'; dt is fp32 there): split-precision operands, three 16-bit MFMA products per K slab
+    (mage_hip.h) -- 3x the fp32 chain's rate and a smaller error than its own accumulation (profiles/r03_split_probe.txt).  `a` is taken as
+    is where its producer wrote split rows and split here (one small pass) otherwise; y receives split rows if that is its dtype.  A K that
+    is no multiple of 64 and an epilogue the split GEMM does not have (the exact GELU) keep the dt chain."""
+    b = d.get(name + ".b")
+    if sk and K % 64 == 0 and kw.get("act", ops.ACT_NONE) in (ops.ACT_NONE, ops.ACT_QUICKGELU):
+        sdt = ops.split_dtype(sk)
+        assert dt == F32 and y.dtype in (F32, sdt)       # so the dtype alone tells split rows from plain ones
+        if a.dtype != sdt:
+            a = ops.split(a, sk)
+        y_split = y.dtype == sdt
+        w, lda, ldy = _wsplit(d, name, sk), 2 * K, 2 * N if y_split else N          # split rows: 2 16-bit elements per logical column
+        kw.update(split_kind=sk, y_split=y_split)
+    else:
+        w, lda, ldy = _wdt(d, name, dt), K, N
+    if lo or hi is not None:
+        w, b = w[lo:hi], (None if b is None else b[lo:hi])
+    return ops.gemm(a, w, y, M=M, N=N, K=K, lda=kw.pop("lda", lda), ldy=kw.pop("ldy", ldy), bias=b, **kw)
 
 
 class QuickGELU(nn.Module):
@@ -188,7 +192,7 @@ class MAEncoder(nn.Module):
         self.d_model, self.layers = d_model, layers
         self.blocks = nn.ModuleList([TransformerBlock(d_model, d_model // 32, dropout) for _ in range(layers)])
         self.mage_plus = False          # True = the ln_q/ln_kv variant of mage_model.py:93 (MAGE+); MAGE(use_cids=False) sets it
-        self.split_kind = 0             # ops.F16X3 outside precision 'fp32' (MAGE.set_precision): Linear layers on split operands (_lin_fp32)
+        self.split_kind = 0             # ops.F16X3 outside precision 'fp32' (MAGE.set_precision): Linear layers on split operands (_linear)
         self._derived = _Derived(self)
 
     def _build(self):
@@ -206,34 +210,28 @@ class MAEncoder(nn.Module):
         kv = kv.float().contiguous()
         inner, qo, qa, ko, ka = (B, 0, B, 0, B) if seq_first else (1, nq, 1, nk, 1)
         sk = self.split_kind if Cc % 64 == 0 else 0
+
+        def rows(n):
+            """The q rows of an operand of the next Linear (n columns): split rows straight from their producers -- the attention, LayerNorm,
+            the c_fc epilogue (QuickGELU) -- where the Linear layers take those."""
+            return ops.split_empty(B * nq, n, sk, dev) if sk else torch.empty(B * nq, n, device=dev, dtype=F32)
+
         for i in range(self.layers):
             p = f"b{i}"
             qin, kvin = x, kv
             if self.mage_plus:
                 qin = ops.layernorm(x, d[p + ".ln_q.w"], d[p + ".ln_q.b"], torch.empty_like(x), 1e-5)
                 kvin = ops.layernorm(kv, d[p + ".ln_kv.w"], d[p + ".ln_kv.b"], torch.empty_like(kv), 1e-5)
-            qp = _lin_fp32(qin, d, p + ".in_proj", torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc, sk=sk, lo=0, hi=Cc)
-            kvp = _lin_fp32(kvin, d, p + ".in_proj", torch.empty(B * nk, 2 * Cc, device=dev, dtype=F32), M=B * nk, N=2 * Cc, K=Cc, sk=sk,
-                            lo=Cc, hi=3 * Cc)
-            if sk:
-                # split rows straight from the producers: attention output, LayerNorm, the c_fc epilogue (QuickGELU)
-                ao = ops.split_empty(B * nq, Cc, sk, dev)
-                ops.attention(qp, kvp[:, :Cc], kvp[:, Cc:], ao, ldq=Cc, ldk=2 * Cc, ldv=2 * Cc, ldo=2 * Cc, n_seq=B, inner=inner,
-                              nq=nq, nk=nk, n_head=H, q_outer_stride=qo, q_axis_stride=qa, kv_outer_stride=ko, kv_axis_stride=ka, out_split=sk)
-                _lin_fp32(None, d, p + ".out_proj", x, M=B * nq, N=Cc, K=Cc, sk=sk, a_split=ao, residual=x, ldr=Cc)
-                xn = ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], ops.split_empty(B * nq, Cc, sk, dev), 1e-5, split_kind=sk)
-                hdn = _lin_fp32(None, d, p + ".c_fc", ops.split_empty(B * nq, 4 * Cc, sk, dev), M=B * nq, N=4 * Cc, K=Cc, sk=sk, a_split=xn,
-                                ldy=8 * Cc, act=ops.ACT_QUICKGELU, y_split=True)
-                _lin_fp32(None, d, p + ".c_proj", x, M=B * nq, N=Cc, K=4 * Cc, sk=sk, a_split=hdn, residual=x, ldr=Cc)
-                continue
-            ao = torch.empty(B * nq, Cc, device=dev, dtype=F32)
-            ops.attention(qp, kvp[:, :Cc], kvp[:, Cc:], ao, ldq=Cc, ldk=2 * Cc, ldv=2 * Cc, ldo=Cc, n_seq=B, inner=inner,
-                          nq=nq, nk=nk, n_head=H, q_outer_stride=qo, q_axis_stride=qa, kv_outer_stride=ko, kv_axis_stride=ka)
-            _linear(ao, d, p + ".out_proj", x, F32, M=B * nq, N=Cc, K=Cc, residual=x, ldr=Cc)
-            xn = ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], torch.empty_like(x), 1e-5)
-            hdn = _linear(xn, d, p + ".c_fc", torch.empty(B * nq, 4 * Cc, device=dev, dtype=F32), F32, M=B * nq, N=4 * Cc, K=Cc,
-                          act=ops.ACT_QUICKGELU)
-            _linear(hdn, d, p + ".c_proj", x, F32, M=B * nq, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
+            qp = _linear(qin, d, p + ".in_proj", torch.empty(B * nq, Cc, device=dev, dtype=F32), F32, M=B * nq, N=Cc, K=Cc, sk=sk, lo=0, hi=Cc)
+            kvp = _linear(kvin, d, p + ".in_proj", torch.empty(B * nk, 2 * Cc, device=dev, dtype=F32), F32, M=B * nk, N=2 * Cc, K=Cc, sk=sk,
+                          lo=Cc, hi=3 * Cc)
+            ao = rows(Cc)
+            ops.attention(qp, kvp[:, :Cc], kvp[:, Cc:], ao, ldq=Cc, ldk=2 * Cc, ldv=2 * Cc, ldo=ao.shape[1], n_seq=B, inner=inner,
+                          nq=nq, nk=nk, n_head=H, q_outer_stride=qo, q_axis_stride=qa, kv_outer_stride=ko, kv_axis_stride=ka, out_split=sk)
+            _linear(ao, d, p + ".out_proj", x, F32, M=B * nq, N=Cc, K=Cc, sk=sk, residual=x, ldr=Cc)
+            xn = ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], rows(Cc), 1e-5, split_kind=sk)
+            hdn = _linear(xn, d, p + ".c_fc", rows(4 * Cc), F32, M=B * nq, N=4 * Cc, K=Cc, sk=sk, act=ops.ACT_QUICKGELU)
+            _linear(hdn, d, p + ".c_proj", x, F32, M=B * nq, N=Cc, K=4 * Cc, sk=sk, residual=x, ldr=Cc)
         return x
 
     def forward(self, x: torch.Tensor, kv: torch.Tensor, key_mask=None, need_weights=False):
@@ -312,20 +310,20 @@ class TransformerTextEncoder(nn.Module):
         sk = getattr(self, "split_kind", 0) if Wd % 64 == 0 else 0
         for i in range(self.transformer_layers):
             p = f"l{i}"
-            qkv = _lin_fp32(x, d, p + ".in_proj", torch.empty(B * S, 3 * Wd, device=dev, dtype=F32), M=B * S, N=3 * Wd, K=Wd, sk=sk)
+            qkv = _linear(x, d, p + ".in_proj", torch.empty(B * S, 3 * Wd, device=dev, dtype=F32), F32, M=B * S, N=3 * Wd, K=Wd, sk=sk)
             ao = ops.split_empty(B * S, Wd, sk, dev) if sk else torch.empty(B * S, Wd, device=dev, dtype=F32)
-            ops.attention(qkv, qkv[:, Wd:], qkv[:, 2 * Wd:], ao, ldq=3 * Wd, ldk=3 * Wd, ldv=3 * Wd, ldo=2 * Wd if sk else Wd, n_seq=B, inner=1,
+            ops.attention(qkv, qkv[:, Wd:], qkv[:, 2 * Wd:], ao, ldq=3 * Wd, ldk=3 * Wd, ldv=3 * Wd, ldo=ao.shape[1], n_seq=B, inner=1,
                           nq=S, nk=S, n_head=H, q_outer_stride=S, q_axis_stride=1, kv_outer_stride=S, kv_axis_stride=1,
                           kv_len=kv_len, kv_len_div=1, out_split=sk)
-            _lin_fp32(ao, d, p + ".out_proj", x, M=B * S, N=Wd, K=Wd, sk=sk, a_split=ao if sk else None, residual=x, ldr=Wd)
+            _linear(ao, d, p + ".out_proj", x, F32, M=B * S, N=Wd, K=Wd, sk=sk, residual=x, ldr=Wd)
             ops.layernorm(x, d[p + ".norm1.w"], d[p + ".norm1.b"], x, d[p + ".norm1.eps"])
-            # the exact GELU is not a split-GEMM epilogue: its Linear keeps the fp32 chain in every mode
-            hdn = _linear(x, d, p + ".fc1", torch.empty(B * S, 4 * Wd, device=dev, dtype=F32), F32, M=B * S, N=4 * Wd, K=Wd,
+            # the exact GELU is not a split-GEMM epilogue: _linear keeps this Linear on the fp32 chain in every mode
+            hdn = _linear(x, d, p + ".fc1", torch.empty(B * S, 4 * Wd, device=dev, dtype=F32), F32, M=B * S, N=4 * Wd, K=Wd, sk=sk,
                           act=ops.ACT_GELU_ERF)
-            _lin_fp32(hdn, d, p + ".fc2", x, M=B * S, N=Wd, K=4 * Wd, sk=sk, residual=x, ldr=Wd)
+            _linear(hdn, d, p + ".fc2", x, F32, M=B * S, N=Wd, K=4 * Wd, sk=sk, residual=x, ldr=Wd)
             ops.layernorm(x, d[p + ".norm2.w"], d[p + ".norm2.b"], x, d[p + ".norm2.eps"])
         ops.layernorm(x, d["ln_text_final.w"], d["ln_text_final.b"], x, self.ln_text_final.eps)
-        out = _lin_fp32(x, d, "proj", torch.empty(B * S, self.output_dim, device=dev, dtype=F32), M=B * S, N=self.output_dim, K=Wd, sk=sk)
+        out = _linear(x, d, "proj", torch.empty(B * S, self.output_dim, device=dev, dtype=F32), F32, M=B * S, N=self.output_dim, K=Wd, sk=sk)
         return out.view(B, S, self.output_dim)
 
 
@@ -490,13 +488,13 @@ class FlatAxialDecoder(nn.Module):
         bf16 GEMM noise.  The incremental loop uses the same kernels on the same rows: still bit-identical to the full loop."""
         return getattr(self, "stream_bf16", True) and config.get().stream_16bit
 
-    def _ln_linear(self, d, p, lin, xn, xb, ln, y, *, M, N, **kw):
-        """y = Linear(LN(x)) for block p's in_proj / c_fc.  ln None: from xn, the output of a standalone layernorm.  Otherwise from the
-        16-bit rows xb, gamma folded into the weights and the normalisation finished in the epilogue; ln names the row statistics
-        (ln_stats) or the producer's partial sums that the few-rows kernel reduces in its prologue (ln_part; _stats_inline)."""
+    def _ln_linear(self, d, p, lin, xn, xb, ln, y, *, M, N, sk=0, **kw):
+        """y = Linear(LN(x)) for block p's in_proj / c_fc.  ln None: from xn, the output of a standalone layernorm (sk: split rows).
+        Otherwise from the 16-bit rows xb, gamma folded into the weights and the normalisation finished in the epilogue; ln names the row
+        statistics (ln_stats) or the producer's partial sums that the few-rows kernel reduces in its prologue (ln_part; _stats_inline)."""
         Cc, name = self.model_channels, f"{p}.{lin}"
         if ln is None:
-            return ops.gemm(xn, _wdt(d, name, self.compute_dtype), y, M=M, N=N, K=Cc, lda=Cc, ldy=N, bias=d[name + ".b"], **kw)
+            return _linear(xn, d, name, y, self.compute_dtype, M=M, N=N, K=Cc, sk=sk, **kw)
         lnw, lns = self._ln_fold_w(d, p, lin, xb.dtype)
         return ops.gemm(xb, lnw, y, M=M, N=N, K=Cc, lda=Cc, ldy=N, bias=d[name + ".lnc"], ln_colsum=lns, **ln, **kw)
 
@@ -563,7 +561,7 @@ class FlatAxialDecoder(nn.Module):
         Cc = self.model_channels
         return all(ops.gemm_is_small(xb, M, n, Cc) for n in (Cc, 2 * Cc, 3 * Cc, 4 * Cc))
 
-    # ------------------------------------------------------------------ the two loops: one pass per operand form serves both
+    # ------------------------------------------------------------------ the two loops: one pass serves both, in every precision
     # A pass computes positions p0 .. p0+P-1 of the L slots: the motion anchor goes to slot 0 when the window starts there, the nf new
     # frames to the last nf slots of the window.  The reference's full-recompute loop is p0 = 0, P = L, nf = L-1 (_run); the incremental
     # loop appends one frame per step (_inc_step).  Both loops run the same body on the same per-row arithmetic, so their tokens are
@@ -573,8 +571,7 @@ class FlatAxialDecoder(nn.Module):
         """motion [B*hw, Cc], imgs [B*(L-1)*hw, Ci] in the compute dtype -> logits [B*(L-1)*hw, K] fp32
         (use_cids=False: predicted latents [B*(L-1)*hw, 8] fp32 whose first out_channels columns are valid)."""
         L = self.frames_length
-        run = self._pass_split if self._split_on() else self._pass
-        return run(motion, imgs, B=B, hh=hh, ww=ww, p0=0, P=L, nf=L - 1, cache=None)
+        return self._pass(motion, imgs, B=B, hh=hh, ww=ww, p0=0, P=L, nf=L - 1, cache=None)
 
     # SURVEY.md 8f-1: the decoder is causal along L (temporal blocks masked, spatial blocks per frame), so the logits of
     # frame k do not depend on later slots.  Instead of recomputing all L positions in each of the L-1 iterations
@@ -593,8 +590,7 @@ class FlatAxialDecoder(nn.Module):
         P = nf + 1 if motion is not None else nf                            # new positions p0 .. p0+P-1
         # (the MAGE+ head's GroupNorm spans all frames of a clip: only the full loop is valid there)
         assert self.use_cids and nf >= 1 and (p0 == 0) == (motion is not None) and p0 + P <= self.frames_length
-        run = self._pass_split if self._split_on() else self._pass
-        logits = run(motion, imgs, B=st["B"], hh=st["hh"], ww=st["ww"], p0=p0, P=P, nf=nf, nh=1, cache=st["kv"])
+        logits = self._pass(motion, imgs, B=st["B"], hh=st["hh"], ww=st["ww"], p0=p0, P=P, nf=nf, nh=1, cache=st["kv"])
         st["p"] = p0 + P
         return logits
 
@@ -618,31 +614,26 @@ class FlatAxialDecoder(nn.Module):
             geo.update(o_outer_stride=P * hw, o_axis_stride=hw)
         return geo
 
-    def _embed(self, d, x, motion, imgs, *, B: int, hw: int, P: int, nf: int, tp: torch.Tensor, sk: int = 0) -> None:
+    def _embed(self, d, x, motion, imgs, *, B: int, hw: int, P: int, nf: int, tp: torch.Tensor) -> None:
         """The window's input rows of x [B*P*hw, C] (:375-378, no concat copy): context_linear(motion) -> slot 0 (if motion), in_linear
-        (frames) -> the last nf slots, + the window's T positions tp.  imgs: rows in the compute dtype, or FrameTokens.  sk (split modes):
-        motion is fp32 rows, split here where the padded-taps GEMM takes them; imgs split rows (_frame_features) or fp32 rows."""
-        dt, Cc = self.compute_dtype, self.model_channels
+        (frames) -> the last nf slots, + the window's T positions tp.  imgs: rows in the compute dtype, or FrameTokens.  Split modes: both
+        products take split operands only as the padded-taps form of the split GEMM (_taps_ok), else the fp32 chain: motion is fp32 rows,
+        split on the way in; imgs are split rows (_frame_features) where that form runs and fp32 rows where it does not."""
+        dt, Cc, sk = self.compute_dtype, self.model_channels, self._sk()
         if motion is not None:
-            if sk and self._taps_ok(B * hw):
-                self._lin_s(ops.split(motion, sk), d, "context_linear", x, M=B * hw, N=Cc, K=self.context_channels, out_w=hw,
-                            y_img_stride=P * hw, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
-            else:
-                _linear(motion, d, "context_linear", x, dt, M=B * hw, N=Cc, K=self.context_channels, out_w=hw, y_img_stride=P * hw,
-                        rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+            _linear(motion, d, "context_linear", x, dt, M=B * hw, N=Cc, K=self.context_channels, sk=sk if sk and self._taps_ok(B * hw) else 0,
+                    out_w=hw, y_img_stride=P * hw, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
         off = (P - nf) * hw
         if isinstance(imgs, FrameTokens):
             imgs.fill(x, n_img=B * nf, per_clip=nf, P=P, y_off=off, tp=tp)
-        elif sk and imgs.dtype != F32:
-            self._lin_s(imgs, d, "in_linear", x, M=B * nf * hw, N=Cc, K=self.in_channels, out_w=nf * hw, y_img_stride=P * hw, y_off=off,
-                        rowadd=tp, rowadd_div=hw, rowadd_mod=P)
         else:
-            _linear(imgs, d, "in_linear", x, dt, M=B * nf * hw, N=Cc, K=self.in_channels, out_w=nf * hw, y_img_stride=P * hw, y_off=off,
-                    rowadd=tp, rowadd_div=hw, rowadd_mod=P)
+            _linear(imgs, d, "in_linear", x, dt, M=B * nf * hw, N=Cc, K=self.in_channels, sk=sk if imgs.dtype != dt else 0, out_w=nf * hw,
+                    y_img_stride=P * hw, y_off=off, rowadd=tp, rowadd_div=hw, rowadd_mod=P)
 
-    def _head(self, d, xa, *, B: int, hw: int, P: int, nf: int, split: bool = False) -> torch.Tensor:
+    def _head(self, d, xa, *, B: int, hw: int, P: int, nf: int) -> torch.Tensor:
         """The head on the window's last nf slots (:385), reading the last block's output xa: logits [B*nf*hw, K] fp32 from rows in the
-        compute dtype (split: split rows); use_cids=False: predicted latents [B*nf*hw, 8] fp32 (first out_channels columns valid) from fp32 rows."""
+        compute dtype (split modes: split rows); use_cids=False: predicted latents [B*nf*hw, 8] fp32 (first out_channels columns valid) from
+        fp32 rows, on the compute dtype's chain in every mode."""
         dt, Cc, rows = self.compute_dtype, self.model_channels, B * nf * hw
         if not self.use_cids:
             # MAGE+: GroupNorm + SiLU + Conv3d 1x1x1 (:350-354); the GroupNorm statistics span all frames of a clip (:387-388): NOT causal along L
@@ -651,25 +642,33 @@ class FlatAxialDecoder(nn.Module):
             n8 = d["out.f32"].shape[0]
             return _linear(y, d, "out", torch.empty(rows, n8, device=xa.device, dtype=F32), dt, M=rows, N=n8, K=Cc)
         logits = torch.empty(rows, self.out_channels, device=xa.device, dtype=F32)
-        if split:
-            return self._lin_s(xa, d, "out", logits, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
-        return _linear(xa, d, "out", logits, dt, M=rows, N=self.out_channels, K=Cc, out_w=nf * hw, a_img_stride=P * hw, a_off=(P - nf) * hw)
+        return _linear(xa, d, "out", logits, dt, M=rows, N=self.out_channels, K=Cc, sk=self._sk(), out_w=nf * hw, a_img_stride=P * hw,
+                       a_off=(P - nf) * hw)
 
     def _pass(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict],
               nh: Optional[int] = None) -> torch.Tensor:
-        """fp32 / bf16 / f16: one window (see above) through the stack.  cache (incremental loop): block -> its [B, L, hw, q|k|v] rows.
-        nf frames are embedded into the window's last nf slots; the head runs on the last nh of them (None: all nf)."""
+        """One window (see above) through the stack, in every precision.  cache (incremental loop): block -> the temporal block's rows of
+        all L slots, [B, L, hw, q|k|v] (split modes: [B, L, hw, K|V]).  nf frames are embedded into the window's last nf slots; the head
+        runs on the last nh of them (None: all nf)."""
         d = self._derived.get(self._build)
         dt, Cc, L = self.compute_dtype, self.model_channels, self.frames_length
         dev = (imgs.tokens if isinstance(imgs, FrameTokens) else imgs).device
         hw = hh * ww
         M = B * P * hw
-        # The LayerNorm in front of in_proj and c_fc, decided once per pass.  Without the fold (_fold): a standalone layernorm of the fp32
-        # rows x into xn (ln None).  With it, every x + Linear(.) (res) also leaves per-row partial sums `part` and the 16-bit rows xb, and
-        # the Linear normalises xb itself (_ln_linear): from (mean, rstd) rows `stats` that an ln_stats launch reduces from `part`, or, on
-        # the few-rows kernel (inl), from `part` directly.  Block 0's in_proj (ln0) follows the fill: the statistics of one row_stats pass
-        # over the 16-bit stream (sb), else a layernorm of the fp32 rows.
-        fold = self._fold(dt, B, hw)
+        # The form of the Linear layers' operand rows, decided once per pass; the block loop below is the same for all three.
+        #   plain (fp32; 16-bit where the fold does not apply): rows in the compute dtype, written by a standalone layernorm of the fp32
+        #     rows x into xn (ln None), by the attention and by the c_fc epilogue.
+        #   split (sk: 'bf16x3' / 'f16x3'): plain with fp32 everywhere EXCEPT those rows, which their producers write as split-precision
+        #     rows (two 16-bit pieces per element, ops.split_empty) and the Linear layers multiply as three 16-bit MFMA products per K slab
+        #     (include/mage_hip.h).  qs (f16x3, _attn_split): q, k, v leave the QKV epilogue as split rows too, attention on the matrix cores.
+        #   fold (16-bit, _fold): no standalone layernorm.  Every x + Linear(.) (res) also leaves per-row partial sums `part` and the 16-bit
+        #     rows xb, and the Linear normalises xb itself (_ln_linear): from (mean, rstd) rows `stats` that an ln_stats launch reduces from
+        #     `part`, or, on the few-rows kernel (inl), from `part` directly.  Block 0's in_proj (ln0) follows the fill: the statistics of
+        #     one row_stats pass over the 16-bit stream (sb), else a layernorm of the fp32 rows.
+        sk = self._sk()
+        qs = bool(sk) and self._attn_split()
+        cw = 2 * Cc if qs else Cc                       # elements per row of each of q, k, v (split rows: 2 per logical column)
+        fold = not sk and self._fold(dt, B, hw)
         sb = fold and self._stream_bf16()
         xb = part = stats = None
         if fold:
@@ -688,42 +687,56 @@ class FlatAxialDecoder(nn.Module):
         self._embed(d, x, motion, imgs, B=B, hw=hw, P=P, nf=nf, tp=d["tpos"][p0:])
         if sb:
             ops.row_stats(xb, 1e-5, stats)
-        xn = torch.empty(M, Cc, device=dev, dtype=dt)
-        qkv = torch.empty(M, 3 * Cc, device=dev, dtype=dt)
-        ao = torch.empty(M, Cc, device=dev, dtype=dt)
-        geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None) for a in range(3)]
-        fuse = self._qkv_fuse(xb, M, hh, ww, fold and not inl, cache)
-        mfuse = self._mlp_fuse(xb, M, fold and not inl, sb)
-        hdn = None if mfuse else torch.empty(M, 4 * Cc, device=dev, dtype=dt)
+
+        def rows(n, split=bool(sk), m=M):
+            """m operand rows of n columns: split rows in the split modes (or where `split` says), else rows in the compute dtype."""
+            return ops.split_empty(m, n, sk, dev) if split else torch.empty(m, n, device=dev, dtype=dt)
+
+        xn, qkv, ao = rows(Cc), rows(3 * Cc, qs), rows(Cc)
+        geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None and not sk) for a in range(3)]
+        fuse = not sk and self._qkv_fuse(xb, M, hh, ww, fold and not inl, cache)
+        mfuse = not sk and self._mlp_fuse(xb, M, fold and not inl, sb)
+        hdn = None if mfuse else rows(4 * Cc)
         for i in range(self.layers):
             p = f"b{i}"
             ln1 = ln if i else ln0
             if ln1 is None:
-                ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5)
+                ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5, split_kind=sk)
             if fuse and i % 3:
                 # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): per (frame, group of 4 heads) a Q K tile that
                 # keeps the softmax numerators in registers, then a V tile that finishes P V -- the same bits in ao as the QKV GEMM +
                 # ops.attention below, q, k and v never stored
                 f = self._qkv_fuse_w(d, p, dt)
                 ops.gemm_attn_fused_qkv(xb, f["w"], ao, axis=i % 3, M=M, C_=Cc, K=Cc, lda=Cc, ldy=Cc, bias=f["c"], ln_stats=stats, ln_colsum=f["s"])
-            elif i % 3 == 0 and cache is not None:
+            elif i % 3 == 0 and cache is not None and not sk:
                 # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
                 # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)
                 if p0 == 0:
-                    cache[i] = torch.empty(B * L * hw, 3 * Cc, device=dev, dtype=dt)
+                    cache[i] = rows(3 * Cc, m=B * L * hw)
                 kv = cache[i]
                 self._ln_linear(d, p, "in_proj", xn, xb, ln1, kv, M=M, N=3 * Cc, out_w=P * hw, y_img_stride=L * hw, y_off=p0 * hw)
-                q = kv[p0 * hw:]
+                q, k, v = kv[p0 * hw:], kv[:, cw:], kv[:, 2 * cw:]
+            elif i % 3 == 0 and cache is not None:
+                # the split modes' layout: one row [K | V] per (clip, slot, pixel), fp32 or (qs) split rows; q of the new positions stays
+                # packed [M, C] in qkv; two launches
+                if p0 == 0:
+                    cache[i] = rows(2 * Cc, qs, B * L * hw)
+                k = cache[i]
+                q, v = qkv.view(-1)[:M * cw].view(M, cw), k[:, cw:]
+                _linear(xn, d, p + ".in_proj", q, dt, M=M, N=Cc, K=Cc, sk=sk, lo=0, hi=Cc)
+                _linear(xn, d, p + ".in_proj", k, dt, M=M, N=2 * Cc, K=Cc, sk=sk, lo=Cc, hi=3 * Cc, out_w=P * hw, y_img_stride=L * hw,
+                        y_off=p0 * hw)
             else:
-                q = kv = qkv
-                self._ln_linear(d, p, "in_proj", xn, xb, ln1, qkv, M=M, N=3 * Cc)
+                q, k, v = qkv, qkv[:, cw:], qkv[:, 2 * cw:]
+                self._ln_linear(d, p, "in_proj", xn, xb, ln1, qkv, M=M, N=3 * Cc, sk=sk)
             if not (fuse and i % 3):
-                ops.attention(q, kv[:, Cc:], kv[:, 2 * Cc:], ao, ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc, ldo=Cc, **geo[i % 3])
-            _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, **res)
+                ops.attention(q, k, v, ao, ldq=q.stride(0), ldk=k.stride(0), ldv=v.stride(0), ldo=ao.stride(0), out_split=sk,
+                              split_kind=sk if qs else 0, **geo[i % 3])
+            _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, sk=sk, **res)
             if fold and not inl:
                 ops.ln_stats(part, Cc, 1e-5, stats)
             if ln is None:
-                ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5)
+                ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5, split_kind=sk)
             if mfuse:
                 # c_fc, QuickGELU and c_proj in one launch: a 128-row tile keeps its hidden rows on the CU (csrc/gemm4m.hip) -- the same bits in x
                 # and part as the two GEMMs below.  The last block writes the head's 16-bit rows xn, no partial sums.
@@ -736,29 +749,30 @@ class FlatAxialDecoder(nn.Module):
                 else:
                     ops.ln_stats(part, Cc, 1e-5, stats)
                 continue
-            self._ln_linear(d, p, "c_fc", xn, xb, ln, hdn, M=M, N=4 * Cc, act=ops.ACT_QUICKGELU)
+            self._ln_linear(d, p, "c_fc", xn, xb, ln, hdn, M=M, N=4 * Cc, sk=sk, act=ops.ACT_QUICKGELU)
             if i < self.layers - 1:
-                _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, **res)
+                _linear(hdn, d, p + ".c_proj", x, dt, M=M, N=Cc, K=4 * Cc, sk=sk, **res)
                 if fold and not inl:
                     ops.ln_stats(part, Cc, 1e-5, stats)
             else:
-                # the last x + c_proj(.) is only read by the head.  16-bit logits head: the epilogue rounds it to the compute dtype on the way
-                # out (same fp32 sum, same round-to-nearest-even as a separate cast pass: bit-identical) instead of writing fp32 rows and
+                # the last x + c_proj(.) is only read by the head.  Logits head on 16-bit or split rows: the epilogue writes them as such
+                # (16-bit: same fp32 sum, same round-to-nearest-even as a separate cast pass: bit-identical) instead of writing fp32 rows and
                 # converting them in another launch.  MAGE+ head: its GroupNorm reads fp32 rows (fresh ones behind the 16-bit stream).
-                if self.use_cids and dt != F32:
+                if self.use_cids and (sk or dt != F32):
                     xa = xn
                 else:
                     xa = torch.empty(M, Cc, device=dev, dtype=F32) if sb else x
-                _linear(hdn, d, p + ".c_proj", xa, dt, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
+                _linear(hdn, d, p + ".c_proj", xa, dt, M=M, N=Cc, K=4 * Cc, sk=sk, residual=x, ldr=Cc)
         return self._head(d, xa, B=B, hw=hw, P=P, nf=nf if nh is None else nh)
 
-    # ------------------------------------------------------------------ the fast parity modes ('f16x3' / 'bf16x3')
-    # The stack of _pass with fp32 everywhere EXCEPT the operands of the Linear layers: those are split-precision
-    # tensors (two 16-bit pieces per element, ops.split_empty) written directly by their producers -- LayerNorm, the attention
-    # kernel, the c_fc epilogue (QuickGELU), the last c_proj epilogue -- and multiplied as three f16 / bf16 MFMA products per K
-    # slab (include/mage_hip.h, MAGE_F16X3).  Residual stream, q / k / v, softmax and logits are fp32 as in 'fp32' mode.
+    # ------------------------------------------------------------------ the fast parity modes ('f16x3' / 'bf16x3'): what selects _pass's split form
+    # Residual stream, q / k / v (bf16x3), softmax and logits are fp32 as in 'fp32' mode; only the operands of the Linear layers differ (_linear).
     def _split_on(self) -> bool:
         return bool(self.split_kind) and self.compute_dtype == F32 and self.model_channels % 64 == 0
+
+    def _sk(self) -> int:
+        """The split kind that the passes run on: split_kind in the fast parity modes, else 0."""
+        return self.split_kind if self._split_on() else 0
 
     def _warm_split(self) -> None:
         """Build every split-precision weight copy now (MAGE._warm_derived: on the caller's stream, before side streams fork)."""
@@ -779,58 +793,6 @@ class FlatAxialDecoder(nn.Module):
     def _taps_ok(self, rows: int) -> bool:
         """in_linear / context_linear (+ T positions) and the frame convolution run as the padded-taps form of the split GEMM."""
         return self.model_channels % 256 == 0 and rows % 256 == 0 and self.in_channels % 64 == 0 and self.context_channels % 64 == 0
-
-    def _lin_s(self, a, d, name, y, *, M, N, K, lo=0, hi=None, **kw):
-        sk = self.split_kind
-        w, b = _wsplit(d, name, sk), d.get(name + ".b")
-        if hi is not None or lo:
-            w, b = w[lo:hi], (None if b is None else b[lo:hi])
-        y_split = kw.pop("y_split", False)
-        return ops.gemm(a, w, y, M=M, N=N, K=K, lda=kw.pop("lda", 2 * K), ldy=kw.pop("ldy", 2 * N if y_split else N), bias=b,
-                        split_kind=sk, y_split=y_split, **kw)
-
-    def _pass_split(self, motion, imgs, *, B: int, hh: int, ww: int, p0: int, P: int, nf: int, cache: Optional[dict],
-                    nh: Optional[int] = None) -> torch.Tensor:
-        """f16x3 / bf16x3: one window through the stack.  cache (incremental loop): block -> its [B, L, hw, K|V] rows, fp32 or (when the
-        attention reads split operands) split rows; q of the new positions stays packed in qkv."""
-        d = self._derived.get(self._build)
-        sk, Cc, L = self.split_kind, self.model_channels, self.frames_length
-        dev = (imgs.tokens if isinstance(imgs, FrameTokens) else imgs).device
-        hw = hh * ww
-        M = B * P * hw
-        x = torch.empty(M, Cc, device=dev, dtype=F32)
-        self._embed(d, x, motion, imgs, B=B, hw=hw, P=P, nf=nf, tp=d["tpos"][p0:], sk=sk)
-        xn = ops.split_empty(M, Cc, sk, dev)
-        qs = self._attn_split()                # f16x3: q, k, v leave the QKV epilogue as split rows, attention on the matrix cores
-        m_ = 2 if qs else 1                    # split rows: 2 16-bit elements per logical column
-        qkv = ops.split_empty(M, 3 * Cc, sk, dev) if qs else torch.empty(M, 3 * Cc, device=dev, dtype=F32)
-        ao = ops.split_empty(M, Cc, sk, dev)
-        hdn = ops.split_empty(M, 4 * Cc, sk, dev)
-        geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None) for a in range(3)]
-        for i in range(self.layers):
-            p = f"b{i}"
-            ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5, split_kind=sk)
-            if i % 3 == 0 and cache is not None:
-                if p0 == 0:
-                    cache[i] = ops.split_empty(B * L * hw, 2 * Cc, sk, dev) if qs else torch.empty(B * L * hw, 2 * Cc, device=dev, dtype=F32)
-                kv = cache[i]
-                q = qkv.view(-1)[:M * m_ * Cc].view(M, m_ * Cc)             # q of the new positions, packed [M, C]
-                self._lin_s(xn, d, p + ".in_proj", q, M=M, N=Cc, K=Cc, lo=0, hi=Cc, ldy=m_ * Cc, y_split=qs)
-                self._lin_s(xn, d, p + ".in_proj", kv, M=M, N=2 * Cc, K=Cc, lo=Cc, hi=3 * Cc, ldy=m_ * 2 * Cc, out_w=P * hw,
-                            y_img_stride=L * hw, y_off=p0 * hw, y_split=qs)
-                k, v, ldq, ldkv = kv, kv[:, m_ * Cc:], m_ * Cc, m_ * 2 * Cc
-            else:
-                self._lin_s(xn, d, p + ".in_proj", qkv, M=M, N=3 * Cc, K=Cc, y_split=qs)
-                q, k, v, ldq, ldkv = qkv, qkv[:, m_ * Cc:], qkv[:, m_ * 2 * Cc:], m_ * 3 * Cc, m_ * 3 * Cc
-            ops.attention(q, k, v, ao, ldq=ldq, ldk=ldkv, ldv=ldkv, ldo=2 * Cc, out_split=sk, split_kind=sk if qs else 0, **geo[i % 3])
-            self._lin_s(ao, d, p + ".out_proj", x, M=M, N=Cc, K=Cc, residual=x, ldr=Cc)
-            ops.layernorm(x, d[p + ".ln_2.w"], d[p + ".ln_2.b"], xn, 1e-5, split_kind=sk)
-            self._lin_s(xn, d, p + ".c_fc", hdn, M=M, N=4 * Cc, K=Cc, act=ops.ACT_QUICKGELU, y_split=True)
-            if i == self.layers - 1 and self.use_cids:       # only the head reads the last x: it leaves the epilogue as split rows
-                self._lin_s(hdn, d, p + ".c_proj", xn, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc, y_split=True)
-            else:
-                self._lin_s(hdn, d, p + ".c_proj", x, M=M, N=Cc, K=4 * Cc, residual=x, ldr=Cc)
-        return self._head(d, xn if self.use_cids else x, B=B, hw=hw, P=P, nf=nf if nh is None else nh, split=True)
 
     def forward(self, motion: torch.Tensor, imgs: torch.Tensor) -> torch.Tensor:
         """motion [B,H,W,Cc], imgs [B,L-1,H,W,Ci] -> logits [B,L-1,H,W,out] fp32."""
@@ -1035,7 +997,7 @@ class MAGE(nn.Module):
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self.precision = precision
         self.generate_model.compute_dtype, self.generate_model.split_kind = PRECISIONS[precision]
-        # the once-per-clip prologue: exact-fp32 MFMA chains only in 'fp32' mode, f16x3 split operands otherwise (_lin_fp32)
+        # the once-per-clip prologue: exact-fp32 MFMA chains only in 'fp32' mode, f16x3 split operands otherwise (_linear)
         self.ma_encoder.split_kind = self.text_encoder.split_kind = 0 if precision == "fp32" else ops.F16X3
         if hasattr(self.first_stage_model, "set_precision"):     # an external latent first stage (MAGE+) has no such switch
             self.first_stage_model.set_precision(precision)
