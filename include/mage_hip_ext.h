@@ -347,7 +347,13 @@ int mage_token_logprob_bwd(const float* logits, int64_t rows, int32_t K, int64_t
  * output rows may be regrouped whole frames at a time (out_w % 256 == 0, y_img_stride, y_off) as mage_gemm regroups them.  axis 1 = H (a
  * sequence is a column of the frame), 2 = W (a row).  C % 128 == 0 (N % 384 == 0), K % 128 == 0 in [256, 1024], dtype MAGE_BF16 or MAGE_F16,
  * act none, no other epilogue stage.  `scale` is mage_attn_desc::scale.  Per output element the operations are those of the replaced pair
- * in their order: Y holds the same bits as mage_gemm followed by mage_attention.  Anything else: MAGE_EINVAL, nothing launched. */
+ * in their order: Y holds the same bits as mage_gemm followed by mage_attention.  Anything else: MAGE_EINVAL, nothing launched.
+ * axis 0 = T, the temporal blocks of a full pass over clips of exactly 16 slots (causal: slot i attends to the slots <= i, mage_attn_desc::causal
+ * with nq == nk == 16): rows [clip][slot][hw], and desc->out_w carries hw, the rows of one slot (in_w, a_img_stride and y_img_stride equal it:
+ * the rows are described as groups of hw, nothing is regrouped).  hw % 16 == 0, M % (16 hw) == 0, a_off and y_off whole clips (multiples of
+ * 16 hw), (15 hw + 16) * lda * 2 + 16384 < 2^32 (the kernel's 32-bit lane offsets inside a clip); a y_img_stride other than out_w (regrouped
+ * output rows) is refused for this axis.  A tile is then 16 adjacent positions x the 16 slots of one clip; everything else as for axes 1 and 2,
+ * the same bits as mage_gemm followed by mage_attention with q_axis_stride = kv_axis_stride = hw, outer strides 16 hw, causal. */
 int mage_gemm_attn_fused_qkv(const mage_gemm_desc* desc, int32_t axis, float scale, void* stream);
 /* The symbol of the kernel mage_gemm_attn_fused_qkv(desc, axis, ...) launches. */
 int mage_gemm_attn_fused_qkv_kernel_name(const mage_gemm_desc* desc, int32_t axis, char* buf, int32_t len);

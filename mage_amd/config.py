@@ -27,6 +27,8 @@ class Config:
     # ---- decoder stack (modules/mage_model.py)
     qk_fuse: bool = True              # 16-bit LayerNorm-fold path, 16 x 16 frames, calls large enough: the H / W attention inside the in_proj GEMM, one launch
                                       # per block (q, k, v never stored; False: QKV GEMM + mage_attention, the same bits)
+    tqkv_fuse: bool = True            # the same launch for the temporal blocks of a full pass over 16 slots (causal; False: they keep QKV GEMM + mage_attention, the
+                                      # same bits; qk_fuse = False turns both off)
     mlp_fuse: bool = True             # 16-bit LayerNorm-fold path with the 16-bit stream, C = 512, calls large enough: c_fc, QuickGELU and c_proj of a block in one
                                       # launch (the hidden rows never stored; False: the two GEMMs, the same bits)
     ln_fold: bool = True              # LayerNorm folded around the 16-bit GEMMs (producer partial sums + consumer epilogue)
@@ -56,6 +58,7 @@ class Config:
 ENV = {
     "ln_fold": ("MAGE_NO_LN_FOLD", False),
     "qk_fuse": ("MAGE_NO_QK_FUSE", False),
+    "tqkv_fuse": ("MAGE_NO_TQKV_FUSE", False),
     "mlp_fuse": ("MAGE_NO_MLP_FUSE", False),
     "stream_16bit": ("MAGE_STREAM_FP32", False),
     "attn_split": ("MAGE_ATTN_SPLIT_FP32", False),

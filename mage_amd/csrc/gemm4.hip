@@ -63,7 +63,8 @@ struct Gemm4Args {
     // the fused H / W axial attention entry (QF, see gemm4_body): 1 = H axis | 2 = W axis, softmax scale, the regrouping of the output rows
     // (out_w rows at a time, y_img_stride apart).  On a 16-byte boundary: the fused kernel fetches the four with one s_load_dwordx4 of their
     // own.  Packed directly behind stagger_sleeps, hipcc merges the argument loads differently and the hand-scheduled kernel's scalar
-    // registers fall differently from there on (profiles/r19_retire_two_launch_pair.txt)
+    // registers fall differently from there on (profiles/r19_retire_two_launch_pair.txt).  The temporal form (TX, gemm4_tattn_kernel) regroups no
+    // rows and carries its own two numbers in the last two: out_w = hw, the rows between two slots of a clip; y_img_stride = hw / 16, tiles per clip
     alignas(16) int attn_axis;
     float attn_scale;
     int out_w, y_img_stride;
@@ -121,6 +122,11 @@ __device__ __forceinline__ void g4_mfma32(const u32x4& w, const u32x4& x) {
 //     (lane = head dim, register = key).  Same epilogue arithmetic per element, then den, P = hi + lo, O^T = V^T P_hi^T + V^T P_lo^T, the lane
 //     swap, 1 / den and the 16-byte row stores of attention_mfma_kernel.  The lane that computed a numerator is the lane that multiplies it.
 // The row statistics are fetched once per entry.  Every element takes the unfused pair's operations in the pair's order: the same bits in `ao`.
+// TX (the temporal blocks of a full pass over clips of 16 slots, gemm4_tattn_kernel): the same entry with another row map and a mask.  A tile is 16
+// adjacent positions of one clip x its 16 slots -- tile row R = slot * 16 + position reads row (R & 15) * hw + (R >> 4) behind the tile's first row
+// (clip * 16 hw + position block * 16), so that an m-fragment is again one sequence, lane l15 = its slot; every row is still one contiguous piece
+// for the loader.  The scores pass attention_mfma_kernel's causal select (key slot 4 grp + e <= query slot l15, else -inf; a masked numerator is
+// +0) before and after the maximum; the slab schedule, the panel replay, the staging window and the stores are the H / W form's.
 // The epilogue MFMAs of the fused attention entry (QF): attention_mfma_kernel's instructions (attn_mfma_qk / attn_mfma_pv in attn_mfma.h) on the
 // same operands, but as inline asm on VGPRs: given the builtins, hipcc puts their results into the accumulator registers it believes free
 // (a[0:3] -- live accumulators of the tile).  Wait states inside the strings: a just-written operand (1), the result before any reader (16);
@@ -152,9 +158,10 @@ __device__ __forceinline__ void g4_mm(const u32x4& w, const u32x4& x) {
     else g4_mfma<I, ZERO, CLOB, HF>(w, x);
 }
 // (the body of both kernels below: gemm4_kernel = plain GEMM, gemm4_attn_kernel = QF, the fused attention entry)
-template <int ACT, int EK, int LN, bool RB, bool HF, bool QF>
+template <int ACT, int EK, int LN, bool RB, bool HF, bool QF, bool TX = false>
 __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     static_assert(EK != EK_GENERAL, "lean epilogue kinds");
+    static_assert(!TX || QF, "the temporal row map belongs to the fused attention entry");
     static_assert(!QF || (LN == LN_CONSUME && ACT == MAGE_ACT_NONE), "fused attention: the LayerNorm-consuming in_proj");
     static_assert(!HF || (LN != LN_DUAL && LN != LN_GELUBWD), "f16 form: the generation path's epilogues");
     typedef std::conditional_t<HF, f16_t, unsigned short> H16;
@@ -184,15 +191,28 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
     const int lr = lane >> 3, lp = lane & 7;
     unsigned voffA[8], voffW[8];
     // QF: tile row R (0..255) -> row of the frame (H axis: sequences run down the columns of the 16 x 16 frame)
-    [[maybe_unused]] auto frame_row = [&](int R) { return g.attn_axis == 1 ? ((R & 15) << 4) + (R >> 4) : R; };
+    // TX: tile row R = slot * 16 + position -> row of the tile's 16 positions x 16 slots (slots g.out_w = hw rows apart)
+    [[maybe_unused]] auto frame_row = [&](int R) {
+        if constexpr (TX) return (R & 15) * g.out_w + (R >> 4);
+        else return g.attn_axis == 1 ? ((R & 15) << 4) + (R >> 4) : R;
+    };
+    // TX: first row of row tile tm = position block tm % tpc of clip tm / tpc (tpc = g.y_img_stride = hw / 16 tiles per clip of 16 * hw rows)
+    [[maybe_unused]] auto tile_row0 = [&](int tm_) {
+        const int clip = tm_ / g.y_img_stride;
+        return (long)clip * 16 * g.out_w + (tm_ - clip * g.y_img_stride) * 16;
+    };
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int r = u * 8 + lr;
         const int ch = lp ^ ((r >> 1) & 7);
-        voffA[u] = (unsigned)((QF ? frame_row(wave * 64 + r) : r) * g.lda * 2 + ch * 16 + 8192 - u * 1024);
+        if constexpr (TX) voffA[u] = (unsigned)frame_row(wave * 64 + r) * (unsigned)(g.lda * 2) + (unsigned)(ch * 16 + 8192 - u * 1024);     // < 2^32 (host)
+        else voffA[u] = (unsigned)((QF ? frame_row(wave * 64 + r) : r) * g.lda * 2 + ch * 16 + 8192 - u * 1024);
         voffW[u] = (unsigned)(r * g.ldw * 2 + ch * 16 + 8192 - u * 1024);
     }
-    auto a_base = [&](int tile) { return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + (QF ? 0 : wave * 64)) + g.a_off) * g.lda * 2 - 4096; };
+    auto a_base = [&](int tile) {
+        if constexpr (TX) return (const char*)g.A + (tile_row0(tile / g.ntiles_n) + g.a_off) * g.lda * 2 - 4096;
+        else return (const char*)g.A + ((long)((tile / g.ntiles_n) * 256 + (QF ? 0 : wave * 64)) + g.a_off) * g.lda * 2 - 4096;
+    };
     auto w_base = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * (QF ? 384 : 256) + wave * 64) * g.ldw * 2 - 4096; };
     // QF: the 128 v rows behind a group's 256 [q | k] rows -- 4 units (32 rows) per wave, LDS rows wave*32 .. +31 of the W half of a stage
     [[maybe_unused]] auto w_base_v = [&](int tile) { return (const char*)g.W + (long)((tile % g.ntiles_n) * 384 + 256 + wave * 32) * g.ldw * 2 - 4096; };
@@ -278,6 +298,8 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
         const int tm = c_tile / g.ntiles_n, tn = c_tile - tm * g.ntiles_n;
         MAGE_DASSERT(c_tile >= 0 && c_tile < g.ntiles && tm * 256 < g.M && tn * (QF ? 384 : 256) < g.N);
         [[maybe_unused]] float ln_mean[8], ln_rstd[8];
+        [[maybe_unused]] long row0 = 0;                    // TX: the entry's first row, once per entry (statistics rows, output rows, the panel replay)
+        if constexpr (TX) row0 = tile_row0(tm);
         // One tile of kind PH.  Plain GEMM: the entry is this one tile, PH = 0.  QF: the entry (frame, group of 4 heads) is a PH = 1 tile (the
         // 256 packed [q | k] columns of the group; KEEP: the softmax numerators stay in this wave's registers) followed by a PH = 2 tile of HALF width
         // over the same rows (the group's 128 v columns; wave (wm, wn) takes the 64 columns of the two heads whose q and k it has just multiplied).
@@ -292,7 +314,8 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
             const int n0 = QF ? tn * 384 + (HALF ? 256 + wn * 64 : wn * 128) : ((MAGE4_ABL & 32) ? 0 : tn) * 256 + wn * 128;
             [[maybe_unused]] const int ny0 = HALF ? tn * 128 + wn * 64 : n0;
             if constexpr (KEEP) {                          // the V part replays the frame's panel (from L2: the frame's groups stream it together)
-                a_next = a_base(c_tile);
+                if constexpr (TX) a_next = (const char*)g.A + (row0 + g.a_off) * g.lda * 2 - 4096;
+                else a_next = a_base(c_tile);
                 w_next = w_base_v(c_tile);
             } else {
                 const int nt_tile = c_tile + nwg8 > last_tile ? last_tile : c_tile + nwg8;     // past the end: re-fetch the last tile (never read)
@@ -384,7 +407,9 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                     if constexpr (LN == LN_CONSUME && !HALF) {      // (HALF: the Q K part's are kept)
 #pragma unroll
                         for (int a = 0; a < 8; ++a) {
-                            const long row = QF ? (long)tm * 256 + frame_row(wm * 128 + a * 16 + ql15) : (long)(m0 + a * 16 + l15);
+                            long row;
+                            if constexpr (TX) row = row0 + frame_row(wm * 128 + a * 16 + ql15);
+                            else row = QF ? (long)tm * 256 + frame_row(wm * 128 + a * 16 + ql15) : (long)(m0 + a * 16 + l15);
                             const float2 st = *(const float2*)(g.ln_stats + 2 * row);
                             ln_mean[a] = st.x;
                             ln_rstd[a] = st.y;
@@ -569,19 +594,26 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
                                 float mx = -INFINITY;
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
-                                    st[e] = st[e] * g.attn_scale;
+                                    // TX: attention_mfma_kernel's causal select -- slot l15 sees the slots 4 grp + e <= l15
+                                    if constexpr (TX) st[e] = (4 * qgrp + e <= ql15) ? st[e] * g.attn_scale : -INFINITY;
+                                    else st[e] = st[e] * g.attn_scale;
                                     mx = fmaxf(mx, st[e]);
                                 }
                                 mx = fmaxf(mx, __shfl_xor(mx, 16));
                                 mx = fmaxf(mx, __shfl_xor(mx, 32));
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) p[e] = expf(st[e] - mx);
+                                for (int e = 0; e < 4; ++e) {
+                                    if constexpr (TX) p[e] = (4 * qgrp + e <= ql15) ? expf(st[e] - mx) : 0.f;
+                                    else p[e] = expf(st[e] - mx);
+                                }
                             }
                             pl[mt][0] = p;
                         }
                         g4_for<4>([&](auto mt_) { g4_acc_write<c * 4 + decltype(mt_)::value>(pl[decltype(mt_)::value][0]); });
                     } else {
-                        const long shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
+                        long shift;
+                        if constexpr (TX) shift = g.y_off;                                                         // (rows not regrouped: host)
+                        else shift = (long)(tm * 256 / g.out_w) * (g.y_img_stride - g.out_w) + g.y_off;       // out_w % 256 == 0 (host): one group per tile
                         // the two heads' 16 rows x 64 B through the wave's staging window (epilogue_lean's swizzle; a wave's DS operations execute in order):
                         // stored as 2 x (8 rows x 128 B) instead of 2 x (16 rows x 64 B)
                         const int srow = (qgrp * 16 + ql15) >> 3, scc = ql15 & 7;
@@ -637,7 +669,9 @@ __device__ __forceinline__ void gemm4_body(const Gemm4Args& g) {
 #pragma unroll
                             for (int i = 0; i < 2; ++i) {
                                 const int r = srow + 8 * i;
-                                const long yrow = (long)tm * 256 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
+                                long yrow;
+                                if constexpr (TX) yrow = row0 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
+                                else yrow = (long)tm * 256 + frame_row(wm * 128 + mh * 64 + mt * 16 + r) + shift;
                                 *(u32x4*)(op + yrow * g.ldy) = *(const u32x4*)(win + r * 128 + ((scc ^ ((r >> 1) & 7)) << 4));
                             }
                         }
@@ -724,14 +758,20 @@ template <bool HF>
 __global__ __launch_bounds__(256) void gemm4_attn_kernel(const Gemm4Args g) {
     gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, true>(g);
 }
+// the same entry for the temporal blocks (TX): a tile is 16 adjacent positions x the 16 slots of one clip, causal along the slots
+template <bool HF>
+__global__ __launch_bounds__(256) void gemm4_tattn_kernel(const Gemm4Args g) {
+    gemm4_body<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, HF, true, true>(g);
+}
 
-template <int ACT, int EK, int LN, bool RB, bool HF = false, bool QF = false>
+template <int ACT, int EK, int LN, bool RB, bool HF = false, bool QF = false, bool TX = false>
 int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, int attn_axis = 0, float attn_scale = 0.f) {
     Gemm4Args a;
     a.attn_axis = attn_axis;
     a.attn_scale = attn_scale;
     a.out_w = d->out_w;
     a.y_img_stride = d->y_img_stride;
+    if constexpr (TX) a.y_img_stride = d->out_w / 16;  // (out_w = hw, the slot stride; nothing is regrouped, so the second field carries the tiles per clip)
     a.A = d->A;
     a.W = d->W;
     a.Y = d->Y;
@@ -766,7 +806,8 @@ int launch4(const mage_gemm_desc* d, hipStream_t s, int n_cu, int attn_axis = 0,
         a.stagger_sleeps = (int)(period * st_percent / 100 / st_groups / 1024);
     }
     int r;
-    if constexpr (QF) r = mage_gemm_launch<gemm4_attn_kernel<HF>>(grid, 256, G4_LDS, s, a);
+    if constexpr (TX) r = mage_gemm_launch<gemm4_tattn_kernel<HF>>(grid, 256, G4_LDS, s, a);
+    else if constexpr (QF) r = mage_gemm_launch<gemm4_attn_kernel<HF>>(grid, 256, G4_LDS, s, a);
     else r = mage_gemm_launch<gemm4_kernel<ACT, EK, LN, RB, HF>>(grid, 256, G4_LDS, s, a);
     return r < 0 ? r : 1;
 }
@@ -1057,14 +1098,28 @@ int mage_gemm4_try(const mage_gemm_desc* d, hipStream_t s) {
 // The fused H / W axial attention (include/mage_hip_ext.h): N = 3C, W / bias / ln_colsum packed per group of 4 heads, ao out
 extern "C" int mage_gemm_attn_fused_qkv(const mage_gemm_desc* d, int32_t axis, float scale, void* stream) {
     MAGE_CHECK_ARG(d != nullptr, "mage_gemm_attn_fused_qkv: null descriptor");
-    MAGE_CHECK_ARG(axis == 1 || axis == 2, "mage_gemm_attn_fused_qkv: axis %d (1 = H, 2 = W of 16 x 16 frames)", (int)axis);
+    MAGE_CHECK_ARG(axis >= 0 && axis <= 2, "mage_gemm_attn_fused_qkv: axis %d (0 = T of clips of 16 slots, 1 = H, 2 = W of 16 x 16 frames)", (int)axis);
+    if (axis == 0) {
+        // T: the rows come as slots of out_w = hw rows (in_w, a_img_stride and y_img_stride say the same: nothing is regrouped), 16 slots per clip.
+        // A tile is 16 adjacent positions x the 16 slots of one clip; a lane's offset inside a tile reaches row 15 hw + 15
+        const long hw = d->out_w;
+        MAGE_CHECK_ARG(hw >= 16 && hw % 16 == 0 && d->M > 0 && d->M % (16 * hw) == 0,
+                       "mage_gemm_attn_fused_qkv: axis 0: out_w=%d (the rows of one slot) a multiple of 16, M=%d whole clips of 16 slots", d->out_w, d->M);
+        MAGE_CHECK_ARG(d->y_img_stride == d->out_w && d->a_img_stride == d->out_w,
+                       "mage_gemm_attn_fused_qkv: axis 0: rows are not regrouped (y_img_stride=%d, a_img_stride=%d must equal out_w=%d)", d->y_img_stride,
+                       d->a_img_stride, d->out_w);
+        MAGE_CHECK_ARG(d->a_off % (16 * hw) == 0 && d->y_off % (16 * hw) == 0, "mage_gemm_attn_fused_qkv: axis 0: a_off=%d and y_off=%d must be whole clips", d->a_off,
+                       d->y_off);
+        MAGE_CHECK_ARG(d->lda > 0 && (15 * hw + 16) * d->lda * 2 + 16384 < (1L << 32),
+                       "mage_gemm_attn_fused_qkv: axis 0: a clip's rows beyond the kernel's 32-bit lane offsets");
+    }
     MAGE_CHECK_ARG(d->dtype == MAGE_BF16 || d->dtype == MAGE_F16, "mage_gemm_attn_fused_qkv: bf16 or f16 operands");
     MAGE_CHECK_ARG(d->A && d->W && d->Y && d->bias && d->ln_stats && d->ln_colsum, "mage_gemm_attn_fused_qkv: A, W, Y, bias, ln_stats, ln_colsum must be given");
     MAGE_CHECK_ARG(d->M > 0 && d->M % 256 == 0 && d->N > 0 && d->N % 384 == 0 && d->K % 128 == 0 && d->K >= 256 && d->K <= 1024,
                    "mage_gemm_attn_fused_qkv: M=%d a multiple of 256 (whole 16 x 16 frames), N=%d = 3C a multiple of 384 (groups of 4 heads of width 32), K=%d a "
                    "multiple of 128 in [256, 1024]", d->M, d->N, d->K);
     MAGE_CHECK_ARG(d->taps_h * d->taps_w == 1 && d->stride == 1 && !d->dy0 && !d->dx0 && d->in_h == 1 && d->out_h == 1 && d->in_w == d->out_w && !d->a_half &&
-                       d->y_mul_x == 1 && (d->out_w >= d->M || (d->out_w % 256 == 0 && d->a_img_stride == d->out_w)) && d->a_off % 256 == 0 && d->a_off >= 0,
+                       d->y_mul_x == 1 && (axis == 0 || d->out_w >= d->M || (d->out_w % 256 == 0 && d->a_img_stride == d->out_w)) && d->a_off % 256 == 0 && d->a_off >= 0,
                    "mage_gemm_attn_fused_qkv: plain rows in (a_off a multiple of 256), output rows regrouped whole frames at a time");
     MAGE_CHECK_ARG(!d->scale && !d->shift && !d->rowadd && !d->residual && !d->post_relu && !d->res_half && !d->y2 && !d->ln_part && !d->head_w && !d->a_relu &&
                        d->n_split <= 1 && d->act == MAGE_ACT_NONE,
@@ -1079,8 +1134,13 @@ extern "C" int mage_gemm_attn_fused_qkv(const mage_gemm_desc* d, int32_t axis, f
                    "mage_gemm_attn_fused_qkv: operands beyond the kernel's 32-bit lane offsets");
     hipStream_t s = (hipStream_t)stream;
     const int n_cu = mage_gemm_cu_count();
-    const int r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, true>(d, s, n_cu, axis, scale)
-                                       : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, true>(d, s, n_cu, axis, scale);
+    int r;
+    if (axis == 0)
+        r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, true, true>(d, s, n_cu, axis, scale)
+                                 : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, true, true>(d, s, n_cu, axis, scale);
+    else
+        r = d->dtype == MAGE_F16 ? launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, true, true>(d, s, n_cu, axis, scale)
+                                 : launch4<MAGE_ACT_NONE, EK_BIAS, LN_CONSUME, false, false, true>(d, s, n_cu, axis, scale);
     return r < 0 ? r : MAGE_OK;
 }
 

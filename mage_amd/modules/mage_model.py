@@ -526,6 +526,20 @@ class FlatAxialDecoder(nn.Module):
             return False
         return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 8) * torch.cuda.get_device_properties(xb.device).multi_processor_count
 
+    def _tqkv_fuse(self, xb, M: int, hw: int, P: int, p0: int, stats_rows: bool, cache) -> bool:
+        """The temporal blocks of a pass take the same launch (ops.gemm_attn_fused_qkv, axis 0: a tile is 16 adjacent positions x the 16 slots of a
+        clip, attention_mfma_kernel's causal select in the epilogue): _qkv_fuse's conditions without the 16 x 16 frame shape -- the 16-bit
+        LayerNorm-fold path with (mean, rstd) rows, no cache, use_cids, the same widths and the same size rule qkv_fuse_tiles (a tile list of the
+        same length) -- for a full window of exactly 16 slots (P == 16, p0 == 0) of hw % 16 == 0 rows each.  Every other window (the incremental
+        loop, set_context's prefill, frames_length != 16, generation past L) keeps the QKV GEMM + attention pair, which writes the same bits.
+        Timed at the cfg2 full loop only.  config tqkv_fuse = False (MAGE_NO_TQKV_FUSE=1) turns it off alone, qk_fuse = False with the H / W blocks'."""
+        Cc, cfg = self.model_channels, config.get()
+        if not (stats_rows and cache is None and P == 16 and p0 == 0 and hw % 16 == 0 and self.use_cids and cfg.qk_fuse and cfg.tqkv_fuse):
+            return False
+        if Cc % 256 or not 256 <= Cc <= 1024 or M % (16 * hw) or (M + 8) * Cc * 2 >= 2 ** 32 or (15 * hw + 16) * Cc * 2 + 16384 >= 2 ** 32:
+            return False
+        return (M // 256) * (Cc // 128) >= getattr(self, "qkv_fuse_tiles", 8) * torch.cuda.get_device_properties(xb.device).multi_processor_count
+
     def _mlp_fuse(self, xb, M: int, stats_rows: bool, sb: bool) -> bool:
         """The blocks of a pass run c_fc, QuickGELU and c_proj in ONE launch (ops.mlp_fused, csrc/gemm4m.hip: the hidden rows never reach memory): the
         16-bit LayerNorm-fold path with (mean, rstd) rows and the 16-bit stream, C = 512 (the width the kernel is built for), whole 128-row tiles,
@@ -692,9 +706,13 @@ class FlatAxialDecoder(nn.Module):
             """m operand rows of n columns: split rows in the split modes (or where `split` says), else rows in the compute dtype."""
             return ops.split_empty(m, n, sk, dev) if split else torch.empty(m, n, device=dev, dtype=dt)
 
-        xn, qkv, ao = rows(Cc), rows(3 * Cc, qs), rows(Cc)
         geo = [self._axial_geo(a, B, hh, ww, P, p0, cached=cache is not None, q_cached=cache is not None and not sk) for a in range(3)]
         fuse = not sk and self._qkv_fuse(xb, M, hh, ww, fold and not inl, cache)
+        tfuse = not sk and self._tqkv_fuse(xb, M, hw, P, p0, fold and not inl, cache)
+        # per block: its attention runs inside its in_proj launch (a temporal block 0 needs the fill's statistics rows, ln0)
+        fused = [(fuse if i % 3 else tfuse and (i > 0 or ln0 is not None)) for i in range(self.layers)]
+        xn, ao = rows(Cc), rows(Cc)
+        qkv = None if all(fused) else rows(3 * Cc, qs)      # (every block fused: q, k and v are stored nowhere)
         mfuse = not sk and self._mlp_fuse(xb, M, fold and not inl, sb)
         hdn = None if mfuse else rows(4 * Cc)
         for i in range(self.layers):
@@ -702,12 +720,13 @@ class FlatAxialDecoder(nn.Module):
             ln1 = ln if i else ln0
             if ln1 is None:
                 ops.layernorm(x, d[p + ".ln_1.w"], d[p + ".ln_1.b"], xn, 1e-5, split_kind=sk)
-            if fuse and i % 3:
-                # H / W blocks: the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): per (frame, group of 4 heads) a Q K tile that
-                # keeps the softmax numerators in registers, then a V tile that finishes P V -- the same bits in ao as the QKV GEMM +
-                # ops.attention below, q, k and v never stored
+            if fused[i]:
+                # the attention inside the in_proj GEMM's epilogues (csrc/gemm4.hip, QF): per (row tile, group of 4 heads) a Q K tile that keeps
+                # the softmax numerators in registers, then a V tile that finishes P V -- the same bits in ao as the QKV GEMM + ops.attention
+                # below, q, k and v never stored.  H / W blocks: a tile is a frame; temporal blocks: 16 positions x the clip's 16 slots, causal
                 f = self._qkv_fuse_w(d, p, dt)
-                ops.gemm_attn_fused_qkv(xb, f["w"], ao, axis=i % 3, M=M, C_=Cc, K=Cc, lda=Cc, ldy=Cc, bias=f["c"], ln_stats=stats, ln_colsum=f["s"])
+                ops.gemm_attn_fused_qkv(xb, f["w"], ao, axis=i % 3, M=M, C_=Cc, K=Cc, lda=Cc, ldy=Cc, bias=f["c"], ln_stats=stats, ln_colsum=f["s"],
+                                        out_w=None if i % 3 else hw)
             elif i % 3 == 0 and cache is not None and not sk:
                 # one row [q | k | v] per (clip, slot, pixel): the new positions' QKV projection is ONE launch writing straight into their
                 # slots, and the attention reads q back from there (1.5x the K,V bytes of a cache that is 0.8 GB at cfg2)
@@ -729,7 +748,7 @@ class FlatAxialDecoder(nn.Module):
             else:
                 q, k, v = qkv, qkv[:, cw:], qkv[:, 2 * cw:]
                 self._ln_linear(d, p, "in_proj", xn, xb, ln1, qkv, M=M, N=3 * Cc, sk=sk)
-            if not (fuse and i % 3):
+            if not fused[i]:
                 ops.attention(q, k, v, ao, ldq=q.stride(0), ldk=k.stride(0), ldv=v.stride(0), ldo=ao.stride(0), out_split=sk,
                               split_kind=sk if qs else 0, **geo[i % 3])
             _linear(ao, d, p + ".out_proj", x, dt, M=M, N=Cc, K=Cc, sk=sk, **res)

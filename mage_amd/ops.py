@@ -319,9 +319,11 @@ def qkv_pack_rows(C_: int, device=None) -> torch.Tensor:
 def gemm_attn_fused_qkv(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, axis: int, M: int, C_: int, K: int, lda: int, bias, ln_stats, ln_colsum,
                         ldy: int, scale: Optional[float] = None, a_off: int = 0, out_w: Optional[int] = None, y_img_stride: Optional[int] = None,
                         y_off: int = 0):
-    """The H / W axial attention inside the in_proj GEMM, one launch (mage_gemm_attn_fused_qkv): w, bias and ln_colsum are the 3 C_ rows of the
+    """The axial attention inside the in_proj GEMM, one launch (mage_gemm_attn_fused_qkv): w, bias and ln_colsum are the 3 C_ rows of the
     LayerNorm-folded in_proj in qkv_pack_rows' order; writes the attention output rows y [.., C_] -- the bits of ops.gemm (QKV) followed by
-    ops.attention.  axis 1 = H, 2 = W of 16 x 16 frames; scale as ops.attention's."""
+    ops.attention.  axis 1 = H, 2 = W of 16 x 16 frames (out_w, y_img_stride, y_off regroup the output rows whole frames at a time); axis 0 = T,
+    causal, over whole clips of 16 slots: rows [clip, slot, hw] with out_w = hw, the rows of one slot, a multiple of 16 (a_off and y_off whole
+    clips; y_img_stride stays out_w: the rows are not regrouped); scale as ops.attention's."""
     l, s = _dev(a)
     assert w.dtype == a.dtype and y.dtype == a.dtype, (w.dtype, y.dtype)
     out_w = M if out_w is None else out_w
