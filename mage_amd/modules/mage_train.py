@@ -47,9 +47,11 @@ def _wt(d: Dict[str, torch.Tensor], name: str, dt) -> torch.Tensor:
 
 
 class _Run:
-    """Per-call state: compute dtype, dropout probability and seeds."""
+    """Per-call state: compute dtype, dropout probability and seeds; sk / split_w: the split kind of the fp32 products (_gemm32; 0: exact fp32)
+    and the split weight copies of this call."""
 
     def __init__(self, dt, p: float, training: bool):
+        self.sk, self.split_w = 0, {}
         self.dt = dt
         self.p = float(p) if training else 0.0
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.p > 0 else 0
@@ -65,33 +67,32 @@ class _Run:
 # ----------------------------------------------------------------------------------------------------------------- GEMM helpers
 # fp32 products of the text / motion-anchor encoders (activations, gradients and weights stay fp32 there in every mode).  In bf16 training
 # mode they run on f16x3 split operands (three f16 MFMA products per K slab, fp32-class result: include/mage_hip.h) instead of the
-# exact-fp32 MFMA chain, 3x its rate -- as in generation (mage_model._lin_fp32); precision 'fp32' keeps the exact chain, which is what the
-# 1e-4 gradient gates against the oracle are stated for.  _SPLIT32 is set by train_forward / train_backward.
-_SPLIT32 = {"sk": 0, "w": {}}
+# exact-fp32 MFMA chain, 3x its rate -- as in generation (mage_model._linear under split_kind); precision 'fp32' keeps the exact chain, which
+# is what the 1e-4 gradient gates against the oracle are stated for.  train_forward sets run32.sk; the tape carries run32 to train_backward.
 def _f32_branch() -> bool:
     """fp32 branch rows / LayerNorm-output gradients in bf16 mode too (the round-2 form; config.train_f32_branch)."""
     return config.get().train_f32_branch
 
 
-def _gemm32(a, w, y, *, M, N, K, lda=None, **kw):
-    """ops.gemm for fp32 operands; plain products (bias / fp32 residual / QuickGELU only) go through split copies when _SPLIT32 says so."""
-    sk = _SPLIT32["sk"]
+def _gemm32(run: _Run, a, w, y, *, M, N, K, lda=None, **kw):
+    """ops.gemm for fp32 operands; plain products (bias / fp32 residual / QuickGELU only) go through split copies when run.sk says so."""
+    sk = run.sk
     lda = K if lda is None else lda
     ldy = kw.pop("ldy", N)
     if (sk and a.dtype == F32 and w.dtype == F32 and K % 64 == 0 and N % 8 == 0 and lda == K and ldy == N and a.dim() == 2 and a.stride(1) == 1
             and w.dim() == 2 and w.is_contiguous() and set(kw) <= {"bias", "residual", "ldr", "act"}
             and kw.get("act", ops.ACT_NONE) in (ops.ACT_NONE, ops.ACT_QUICKGELU) and (kw.get("residual") is None or kw.get("act", 0) == ops.ACT_NONE)):
         key = (w.data_ptr(), tuple(w.shape), w._version)
-        ws = _SPLIT32["w"].get(key)
+        ws = run.split_w.get(key)
         if ws is None:
-            ws = _SPLIT32["w"][key] = (ops.split(w, sk), w)          # keeps w alive: the key is its address
+            ws = run.split_w[key] = (ops.split(w, sk), w)          # keeps w alive: the key is its address
         return ops.gemm(ops.split(a[:M], sk), ws[0], y, M=M, N=N, K=K, lda=2 * K, ldy=N, split_kind=sk, **kw)
     return ops.gemm(a, w, y, M=M, N=N, K=K, lda=lda, ldy=ldy, **kw)
 
 
-def _gemm_x(a, wT, y, *, M, N, K, lda=None, **kw):
+def _gemm_x(run: _Run, a, wT, y, *, M, N, K, lda=None, **kw):
     """y[M, N] = a[M, K] @ wT[N, K]^T (no bias): dX of a Linear, or any plain product."""
-    return _gemm32(a, wT, y, M=M, N=N, K=K, lda=lda, **kw)
+    return _gemm32(run, a, wT, y, M=M, N=N, K=K, lda=lda, **kw)
 
 
 def _split_plan(M: int, N: int, K: int):
@@ -101,38 +102,84 @@ def _split_plan(M: int, N: int, K: int):
     return S, Mc
 
 
+TAPS3 = tuple((ky - 1, kx - 1) for ky in range(3) for kx in range(3))       # a 3 x 3 convolution's (dy, dx)
+
+
+def _wgrad_taps(dy, x, *, M: int, N: int, Cin: int, taps=((0, 0),), ld_dy: Optional[int] = None, ld_x: Optional[int] = None,
+                dy_geo: Optional[dict] = None, x_geo: Optional[dict] = None, want_bias: bool = True, colsum: bool = False, dyT=None):
+    """dW[N, len(taps) * Cin] (tap-major, ci fastest: the GEMM weight layout; fp32) = sum_m dy[row(m), :N]^T x[gather_tap(m), :Cin] and
+    db[N] = sum_m dy[row(m), :]: dy transposed once, one gathered transpose of x per tap stacked below each other, ONE split-K GEMM whose
+    partials are summed in a fixed order.  taps: the (dy, dx) shifts of x's gather; x_geo: the grid it runs over and where x's images lie, in
+    ops.transpose's own keywords (out_h, out_w, in_h, in_w, stride, img_stride, a_off; None: plain rows); dy_geo: a row map for dy, likewise;
+    ld_dy / ld_x: the operands' leading dimensions (N / Cin).  colsum: db may come from the pass that transposes dy (bf16; dy_geo then has
+    out_w, img_stride, a_off at the most).  dyT: the transposed dy of an earlier call on the same dy.  Returns (dW, db or None, dyT)."""
+    assert dy.dtype == x.dtype
+    dev, dt, K = dy.device, dy.dtype, len(taps) * Cin
+    ld_dy = N if ld_dy is None else ld_dy
+    S, Mc = _split_plan(M, N, K)
+    Mp = S * Mc
+    db = None
+    if dyT is None:
+        dyT = torch.empty(N, Mp, device=dev, dtype=dt)
+        if colsum and want_bias and dt == BF16 and N % 8 == 0 and ld_dy % 8 == 0 and Mp % 8 == 0:
+            db = ops.transpose_colsum(dy, dyT, M=M, Mp=Mp, C=N, ldx=ld_dy, ldy=Mp, **(dy_geo or {}))
+        else:
+            ops.transpose(dy, dyT, M=M, Mp=Mp, C=N, ldx=ld_dy, ldy=Mp, **(dy_geo or {}))
+    xT = torch.empty(K, Mp, device=dev, dtype=dt)
+    for i, (sy, sx) in enumerate(taps):
+        ops.transpose(x, xT, M=M, Mp=Mp, C=Cin, ldx=Cin if ld_x is None else ld_x, ldy=Mp, y_row0=i * Cin, dy=sy, dx=sx, **(x_geo or {}))
+    part = torch.empty(S, N, K, device=dev, dtype=F32)
+    ops.gemm(dyT, xT, part, M=N, N=K, K=Mc, lda=Mp, ldy=K, ldw=Mp, n_split=S, a_split_stride=Mc, w_split_stride=Mc, y_split_stride=N * K)
+    dW = part[0] if S == 1 else ops.sum_partials(part, torch.empty(N, K, device=dev, dtype=F32), stride=N * K, n_part=S, n=N * K)
+    if want_bias and db is None:
+        db = ops.row_sum(dyT, torch.empty(N, device=dev, dtype=F32), ld=Mp, n=M, rows=N)
+    return dW, db, dyT
+
+
 def _wgrad(dy, x, *, M: int, N: int, K: int, ld_dy: int, ld_x: int, dy_geo: Optional[dict] = None, x_geo: Optional[dict] = None,
            want_bias: bool = True):
     """dW[N, K] = sum_m dy[m, :N]^T x[m, :K] (fp32) and db[N] = sum_m dy[m, :].  dy and x are row sets of the same M logical rows
     (optionally regrouped views: dict(out_w, img_stride, a_off), the [:, 1:] / [:, 0] slices of [B, L, hw, C] streams), same
     dtype (the compute dtype)."""
     assert dy.dtype == x.dtype
-    dev, dt = dy.device, dy.dtype
-    if (dt == BF16 and dy_geo is None and x_geo is None and N % 256 == 0 and K % 256 == 0 and M >= 4096 and ld_dy % 8 == 0 and ld_x % 8 == 0
-            and not config.get().train_wgrad_transpose):
+    if (dy.dtype == BF16 and dy_geo is None and x_geo is None and N % 256 == 0 and K % 256 == 0 and M >= 4096 and ld_dy % 8 == 0
+            and ld_x % 8 == 0 and not config.get().train_wgrad_transpose):
         # the decoder stack's Linear layers: dW = dY^T X straight from the row-major operands (mage_gemm_tn: transposing LDS loads),
         # no dY^T / X^T copies (they were 11.8 ms of a 92 ms step at cfg2)
         return ops.gemm_tn(dy, x, T=M, N=N, K=K, ld_dy=ld_dy, ld_x=ld_x, want_bias=want_bias)
-    S, Mc = _split_plan(M, N, K)
-    Mp = S * Mc
-    dyT = torch.empty(N, Mp, device=dev, dtype=dt)
-    db = None
-    fused = want_bias and dt == BF16 and N % 8 == 0 and ld_dy % 8 == 0 and Mp % 8 == 0
-    if fused:                                       # db in the same pass as the transposed copy (bf16)
-        db = ops.transpose_colsum(dy, dyT, M=M, Mp=Mp, C=N, ldx=ld_dy, ldy=Mp, **(dy_geo or {}))
-    else:
-        ops.transpose(dy, dyT, M=M, Mp=Mp, C=N, ldx=ld_dy, ldy=Mp, **(dy_geo or {}))
-    xT = torch.empty(K, Mp, device=dev, dtype=dt)
-    ops.transpose(x, xT, M=M, Mp=Mp, C=K, ldx=ld_x, ldy=Mp, **(x_geo or {}))
-    part = torch.empty(S, N, K, device=dev, dtype=F32)
-    ops.gemm(dyT, xT, part, M=N, N=K, K=Mc, lda=Mp, ldy=K, ldw=Mp, n_split=S, a_split_stride=Mc, w_split_stride=Mc, y_split_stride=N * K)
-    if S == 1:
-        dW = part[0]
-    else:
-        dW = ops.sum_partials(part, torch.empty(N, K, device=dev, dtype=F32), stride=N * K, n_part=S, n=N * K)
-    if want_bias and not fused:
-        db = ops.row_sum(dyT, torch.empty(N, device=dev, dtype=F32), ld=Mp, n=M, rows=N)
-    return dW, db
+    return _wgrad_taps(dy, x, M=M, N=N, Cin=K, ld_dy=ld_dy, ld_x=ld_x, dy_geo=dy_geo, x_geo=x_geo, want_bias=want_bias, colsum=True)[:2]
+
+
+def _flipped(w: torch.Tensor, cout: int, k: int, cin: int) -> torch.Tensor:
+    """GEMM weight [cin, k*k*cout] of the input-gradient convolution of the k x k convolution with GEMM weight w ([cout, k, k, cin]
+    flattened): Wf[ci, (ky, kx), co] = W[co, (k-1-ky, k-1-kx), ci]."""
+    return w.reshape(cout, k, k, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, k * k * cout).contiguous()
+
+
+def _linear_bwd(run: _Run, d, grads, name: str, key: str, dy, x, *, M: int, N: int, K: int, geo: Optional[dict] = None, out_dt=None, out=None,
+                **gemm_kw):
+    """Backward of the Linear y[M, N] = x[M, K] W^T + b (W: d[key + suffix]; dy and x in the compute dtype): the gradients into
+    grads[name + 'weight'] / grads[name + 'bias'] (geo: _wgrad's dy_geo / x_geo), then dx = dy W, which is returned: a fresh [M, K] in out_dt,
+    or `out` (gemm_kw: the product's epilogue or row maps).  Neither out_dt nor out: the weight gradient only."""
+    grads[name + "weight"], grads[name + "bias"] = _wgrad(dy, x, M=M, N=N, K=K, ld_dy=N, ld_x=K, **(geo or {}))
+    if out is None and out_dt is None:
+        return None
+    if out is None:
+        out = torch.empty(M, K, device=dy.device, dtype=out_dt)
+    return _gemm_x(run, dy, _wt(d, key, dy.dtype), out, M=M, N=K, K=N, **gemm_kw)
+
+
+def _self_attn_bwd(run: _Run, d, grads, name: str, p: str, dbr, t, x_in, *, M: int, C: int, geo: dict, out_dt, **last_kw):
+    """Backward of the self-attention branch out_proj(attention(in_proj(x_in))) with packed [q | k | v] rows (t['qkv'], t['ao'] of the
+    forward pass): out_proj, attention_bwd on the three column views, in_proj.  dbr: the branch's output gradient as a GEMM operand;
+    name: the nn.MultiheadAttention's state_dict prefix; geo: attention_bwd's keywords.  Returns the gradient of x_in in out_dt (last_kw:
+    that product's residual)."""
+    dt, qkv = dbr.dtype, t["qkv"]
+    dao = _linear_bwd(run, d, grads, name + "out_proj.", p + ".out_proj", dbr, t["ao"], M=M, N=C, K=C, out_dt=dt)
+    dqkv = torch.empty(M, 3 * C, device=dbr.device, dtype=dt)
+    ops.attention_bwd(qkv, qkv[:, C:], qkv[:, 2 * C:], dao, dqkv, dqkv[:, C:], dqkv[:, 2 * C:], ldq=3 * C, ldk=3 * C, ldv=3 * C, ldo=C,
+                      ld_dq=3 * C, ld_dk=3 * C, ld_dv=3 * C, **geo)
+    return _linear_bwd(run, d, grads, name + "in_proj_", p + ".in_proj", dqkv, x_in, M=M, N=3 * C, K=C, out_dt=out_dt, **last_kw)
 
 
 def _to_dt(run: _Run, g32: torch.Tensor, seed: Optional[int] = None) -> torch.Tensor:
@@ -150,13 +197,13 @@ def _res_linear(run: _Run, a, d, name, x_old, dt, *, M, N, K, seed, ln=None, cas
     the mask-and-add pass and the norm are one launch (mage_dropout_add_layernorm)."""
     w, b = d[name + _sfx(dt)], d.get(name + ".b")
     if run.p == 0:
-        x_new = _gemm32(a, w, torch.empty_like(x_old), M=M, N=N, K=K, lda=K, ldy=N, bias=b, residual=x_old, ldr=N)
+        x_new = _gemm32(run, a, w, torch.empty_like(x_old), M=M, N=N, K=K, lda=K, ldy=N, bias=b, residual=x_old, ldr=N)
         if ln is None:
             return x_new if cast_to is None else (x_new, ops.cast(x_new, torch.empty(M, N, device=a.device, dtype=cast_to)))
         return x_new, ops.layernorm(x_new, ln[0], ln[1], torch.empty(M, N, device=a.device, dtype=ln[2]), 1e-5)
     # the branch rows leave the GEMM in the compute dtype (bf16 mode: half the bytes written here and read by the mask-and-add pass;
     # the stream x itself stays fp32).  MAGE_TRAIN_F32_BRANCH=1 keeps fp32 branch rows.
-    br = _gemm32(a, w, torch.empty(M, N, device=a.device, dtype=F32 if _f32_branch() else a.dtype), M=M, N=N, K=K, lda=K, ldy=N, bias=b)
+    br = _gemm32(run, a, w, torch.empty(M, N, device=a.device, dtype=F32 if _f32_branch() else a.dtype), M=M, N=N, K=K, lda=K, ldy=N, bias=b)
     if ln is None:
         if cast_to is not None:                      # the last block: its rows also as the head GEMM's bf16 operand
             xb = torch.empty(M, N, device=a.device, dtype=cast_to)
@@ -246,32 +293,27 @@ def _emit_next(run, dx, emit):
     return dxb, dict(dx_bf16=dxb, p=run.p if seed is not None else 0.0, seed=seed or 0)
 
 
-def _block_mlp_bwd(run, d, p, pre, grads, dx, x1, xn2, hpre, M, Cc, seed, ln_key="ln_2", fc="c_fc", proj="c_proj", act=ops.ACT_QUICKGELU,
-                   names=None, hdn=None, dxb=None, emit=None):
-    """Backward of x2 = x1 + drop(proj(act(fc(LN(x1))))) given dx = d/dx2 (fp32, updated in place to d/dx1).  dxb: dx as this branch's
-    GEMM operand if the caller already holds it; emit = (seed,): returns the updated dx as the NEXT branch's operand (see _emit_next)."""
+def _block_mlp_bwd(run, d, p, pre, grads, dx, x1, xn2, hpre, M, Cc, seed, hdn=None, dxb=None, emit=None):
+    """Backward of x2 = x1 + drop(c_proj(QuickGELU(c_fc(ln_2(x1))))) given dx = d/dx2 (fp32, updated in place to d/dx1).  dxb: dx as this
+    branch's GEMM operand if the caller already holds it; emit = (seed,): returns the updated dx as the NEXT branch's operand (see _emit_next)."""
     dt, dev = run.dt, dx.device
-    names = names or {"fc_w": f"{pre}.mlp.c_fc.weight", "fc_b": f"{pre}.mlp.c_fc.bias", "proj_w": f"{pre}.mlp.c_proj.weight",
-                      "proj_b": f"{pre}.mlp.c_proj.bias", "ln_w": f"{pre}.ln_2.weight", "ln_b": f"{pre}.ln_2.bias"}
     if dxb is None:
         dxb = _to_dt(run, dx, seed)
     if hdn is None:
-        hdn = ops.act(hpre, torch.empty_like(hpre), act)
-    grads[names["proj_w"]], grads[names["proj_b"]] = _wgrad(dxb, hdn, M=M, N=Cc, K=4 * Cc, ld_dy=Cc, ld_x=4 * Cc)
+        hdn = ops.act(hpre, torch.empty_like(hpre), ops.ACT_QUICKGELU)
+    _linear_bwd(run, d, grads, f"{pre}.mlp.c_proj.", f"{p}.c_proj", dxb, hdn, M=M, N=Cc, K=4 * Cc)      # hdn is released before dh exists
     del hdn
-    if dt != F32 and act == ops.ACT_QUICKGELU and M % 256 == 0 and Cc % 64 == 0 and config.get().train_dual:
-        # d/d(pre-activation) straight from the data-gradient GEMM: its epilogue multiplies the accumulators by QuickGELU'(hpre)
-        dh = ops.gemm(dxb, _wt(d, f"{p}.{proj}", dt), torch.empty(M, 4 * Cc, device=dev, dtype=dt), M=M, N=4 * Cc, K=Cc, lda=Cc, ldy=4 * Cc,
-                      act=ops.ACT_QUICKGELU_GRAD, y2=hpre, ldy2=4 * Cc)
-    else:
-        dh = _gemm_x(dxb, _wt(d, f"{p}.{proj}", dt), torch.empty(M, 4 * Cc, device=dev, dtype=dt), M=M, N=4 * Cc, K=Cc)
-        ops.act_bwd(hpre, dh, dh, act)
-    grads[names["fc_w"]], grads[names["fc_b"]] = _wgrad(dh, xn2, M=M, N=4 * Cc, K=Cc, ld_dy=4 * Cc, ld_x=Cc)
+    # d/d(pre-activation) straight from the data-gradient GEMM where its epilogue can multiply the accumulators by QuickGELU'(hpre)
+    dual = dt != F32 and M % 256 == 0 and Cc % 64 == 0 and config.get().train_dual
+    dh = _gemm_x(run, dxb, _wt(d, f"{p}.c_proj", dt), torch.empty(M, 4 * Cc, device=dev, dtype=dt), M=M, N=4 * Cc, K=Cc,
+                 **(dict(act=ops.ACT_QUICKGELU_GRAD, y2=hpre, ldy2=4 * Cc) if dual else {}))
+    if not dual:
+        ops.act_bwd(hpre, dh, dh, ops.ACT_QUICKGELU)
     # d/d(LayerNorm output) in the compute dtype: layernorm_bwd reads it once (its dx stream stays fp32)
-    dxn = _gemm_x(dh, _wt(d, f"{p}.{fc}", dt), torch.empty(M, Cc, device=dev, dtype=F32 if _f32_branch() else dt), M=M, N=Cc, K=4 * Cc)
+    dxn = _linear_bwd(run, d, grads, f"{pre}.mlp.c_fc.", f"{p}.c_fc", dh, xn2, M=M, N=4 * Cc, K=Cc, out_dt=F32 if _f32_branch() else dt)
     del dh, dxb
     nxt, kw = _emit_next(run, dx, emit)
-    grads[names["ln_w"]], grads[names["ln_b"]] = ops.layernorm_bwd(x1, d[f"{p}.{ln_key}.w"], dxn, dx, eps=1e-5, accumulate=True, **kw)
+    grads[f"{pre}.ln_2.weight"], grads[f"{pre}.ln_2.bias"] = ops.layernorm_bwd(x1, d[f"{p}.ln_2.w"], dxn, dx, eps=1e-5, accumulate=True, **kw)
     return nxt
 
 
@@ -284,13 +326,13 @@ def _dec_backward(gm, run: _Run, tape, dlogits, grads: Dict[str, torch.Tensor], 
     tail = dict(out_w=(L - 1) * hw, img_stride=L * hw, a_off=hw)            # the x[:, 1:] rows of a [B, L, hw, C] stream
     dx = torch.zeros(M, Cc, device=dev, dtype=F32)
     if gm.use_cids:
-        grads[pre + ".out.weight"], grads[pre + ".out.bias"] = _wgrad(dlogits, tape["xa"], M=M1, N=Kc, K=Cc, ld_dy=Kc, ld_x=Cc, x_geo=tail)
-        _gemm_x(dlogits, _wt(d, "out", dt), dx, M=M1, N=Cc, K=Kc, out_w=(L - 1) * hw, y_img_stride=L * hw, y_off=hw)
+        _linear_bwd(run, d, grads, pre + ".out.", "out", dlogits, tape["xa"], M=M1, N=Kc, K=Cc, geo=dict(x_geo=tail), out=dx, out_w=(L - 1) * hw,
+                    y_img_stride=L * hw, y_off=hw)
     else:                                                                    # dlogits = d loss / d pred [M1, n8] (padding columns zero)
         n8 = d["out.f32"].shape[0]
         dWo, dbo = _wgrad(dlogits, tape["y"], M=M1, N=n8, K=Cc, ld_dy=n8, ld_x=Cc)
         grads[pre + ".out.2.weight"], grads[pre + ".out.2.bias"] = dWo[:Kc].reshape(Kc, Cc, 1, 1, 1), dbo[:Kc]
-        dy = _gemm_x(dlogits, _wt(d, "out", dt), torch.empty(M1, Cc, device=dev, dtype=F32), M=M1, N=Cc, K=n8)
+        dy = _gemm_x(run, dlogits, _wt(d, "out", dt), torch.empty(M1, Cc, device=dev, dtype=F32), M=M1, N=Cc, K=n8)
         dg, db, _ = ops.groupnorm_bwd(tape["x_last"], d["gn.w"], d["gn.b"], tape["gn_stats"], dy, dx, n_samples=B, rows_per_sample=(L - 1) * hw,
                                       sample_stride_rows=L * hw, row_off=hw, groups=32, act=2)       # slot 0 rows stay zero
         grads[pre + ".out.0.weight"], grads[pre + ".out.0.bias"] = dg, db
@@ -302,16 +344,8 @@ def _dec_backward(gm, run: _Run, tape, dlogits, grads: Dict[str, torch.Tensor], 
                              emit=(t["s_attn"],))
         if dxb is None:
             dxb = _to_dt(run, dx, t["s_attn"])
-        grads[bp + ".attn.out_proj.weight"], grads[bp + ".attn.out_proj.bias"] = _wgrad(dxb, t["ao"], M=M, N=Cc, K=Cc, ld_dy=Cc, ld_x=Cc)
-        dao = _gemm_x(dxb, _wt(d, p + ".out_proj", dt), torch.empty(M, Cc, device=dev, dtype=dt), M=M, N=Cc, K=Cc)
-        qkv = t["qkv"]
-        dqkv = torch.empty(M, 3 * Cc, device=dev, dtype=dt)
-        ops.attention_bwd(qkv, qkv[:, Cc:], qkv[:, 2 * Cc:], dao, dqkv, dqkv[:, Cc:], dqkv[:, 2 * Cc:], ldq=3 * Cc, ldk=3 * Cc, ldv=3 * Cc,
-                          ldo=Cc, ld_dq=3 * Cc, ld_dk=3 * Cc, ld_dv=3 * Cc, **t["geo"])
-        grads[bp + ".attn.in_proj_weight"], grads[bp + ".attn.in_proj_bias"] = _wgrad(dqkv, t["xn1"], M=M, N=3 * Cc, K=Cc, ld_dy=3 * Cc,
-                                                                                     ld_x=Cc)
-        dxn = _gemm_x(dqkv, _wt(d, p + ".in_proj", dt), torch.empty(M, Cc, device=dev, dtype=F32 if _f32_branch() else dt), M=M, N=Cc, K=3 * Cc)
-        del dxb, dao, dqkv
+        dxn = _self_attn_bwd(run, d, grads, bp + ".attn.", p, dxb, t, t["xn1"], M=M, C=Cc, geo=t["geo"], out_dt=F32 if _f32_branch() else dt)
+        del dxb
         dxb, kw = _emit_next(run, dx, (tape["blocks"][i - 1]["s_mlp"] if i > 0 else None,))
         grads[bp + ".ln_1.weight"], grads[bp + ".ln_1.bias"] = ops.layernorm_bwd(t["x0"], d[p + ".ln_1.w"], dxn, dx, eps=1e-5, accumulate=True, **kw)
         tape["blocks"][i] = None                                             # release the block's activations
@@ -321,15 +355,13 @@ def _dec_backward(gm, run: _Run, tape, dlogits, grads: Dict[str, torch.Tensor], 
     if dxb is None:
         dxb = _to_dt(run, dx)
     head = dict(out_w=hw, img_stride=L * hw, a_off=0)                        # the x[:, 0] rows
-    grads[pre + ".in_linear.weight"], grads[pre + ".in_linear.bias"] = _wgrad(dxb, tape["feats"], M=M1, N=Cc, K=gm.in_channels, ld_dy=Cc,
-                                                                             ld_x=gm.in_channels, dy_geo=tail)
-    grads[pre + ".context_linear.weight"], grads[pre + ".context_linear.bias"] = _wgrad(dxb, tape["motion"], M=B * hw, N=Cc,
-                                                                                       K=gm.context_channels, ld_dy=Cc,
-                                                                                       ld_x=gm.context_channels, dy_geo=head)
-    dfeats = _gemm_x(dxb, _wt(d, "in_linear", dt), torch.empty(M1, gm.in_channels, device=dev, dtype=F32), M=M1, N=gm.in_channels, K=Cc,
-                     out_w=(L - 1) * hw, a_img_stride=L * hw, a_off=hw)
-    dmotion = _gemm_x(dxb, _wt(d, "context_linear", dt), torch.empty(B * hw, gm.context_channels, device=dev, dtype=F32), M=B * hw,
-                      N=gm.context_channels, K=Cc, out_w=hw, a_img_stride=L * hw, a_off=0)
+    Ki, Kx = gm.in_channels, gm.context_channels                             # both weight gradients first, then both input gradients
+    _linear_bwd(run, d, grads, pre + ".in_linear.", "in_linear", dxb, tape["feats"], M=M1, N=Cc, K=Ki, geo=dict(dy_geo=tail))
+    _linear_bwd(run, d, grads, pre + ".context_linear.", "context_linear", dxb, tape["motion"], M=B * hw, N=Cc, K=Kx, geo=dict(dy_geo=head))
+    dfeats = _gemm_x(run, dxb, _wt(d, "in_linear", dt), torch.empty(M1, Ki, device=dev, dtype=F32), M=M1, N=Ki, K=Cc, out_w=(L - 1) * hw,
+                     a_img_stride=L * hw, a_off=hw)
+    dmotion = _gemm_x(run, dxb, _wt(d, "context_linear", dt), torch.empty(B * hw, Kx, device=dev, dtype=F32), M=B * hw, N=Kx, K=Cc, out_w=hw,
+                      a_img_stride=L * hw, a_off=0)
     return dfeats, dmotion
 
 
@@ -338,9 +370,7 @@ def _conv_flip(model, d, dt):
     """Weight of the input-gradient convolution: Wf[ci, (ky, kx), co] = W[co, (2-ky, 2-kx), ci]."""
     key = "conv.flip" + _sfx(dt)
     if key not in d:
-        Cc = model.vision_width
-        w = d["conv" + _sfx(dt)].view(Cc, 3, 3, Cc)
-        d[key] = w.flip(1, 2).permute(3, 1, 2, 0).reshape(Cc, 9 * Cc).contiguous()
+        d[key] = _flipped(d["conv" + _sfx(dt)], model.vision_width, 3, model.vision_width)
     return d[key]
 
 
@@ -370,23 +400,10 @@ def _frame_backward(model, run_dt, tok_rows, emb, dfeats, grads, acc, lat_rows=N
     else:
         dfe = dfeats if run_dt == F32 else ops.cast(dfeats, torch.empty(rows, Cc, device=dev, dtype=run_dt))
         dfe_geo = {}
-    # dW[co, tap, ci] = sum_p dfeats[p, co] * emb[shift_tap(p), ci]: nine shifted transposes stacked, one split-K GEMM
-    S, Mc = _split_plan(rows, Cc, 9 * Cc)
-    Mp = S * Mc
-    dyT = torch.empty(Cc, Mp, device=dev, dtype=run_dt)
-    ops.transpose(dfe, dyT, M=rows, Mp=Mp, C=Cc, ldx=Cc, ldy=Mp, **dfe_geo)
-    xT = torch.empty(9 * Cc, Mp, device=dev, dtype=run_dt)
-    for ky in range(3):
-        for kx in range(3):
-            ops.transpose(emb, xT, M=rows, Mp=Mp, C=Cc, ldx=Cc, ldy=Mp, y_row0=(ky * 3 + kx) * Cc, out_h=R, out_w=R, in_h=R, in_w=R,
-                          img_stride=hw, dy=ky - 1, dx=kx - 1)
-    part = torch.empty(S, Cc, 9 * Cc, device=dev, dtype=F32)
-    ops.gemm(dyT, xT, part, M=Cc, N=9 * Cc, K=Mc, lda=Mp, ldy=9 * Cc, ldw=Mp, n_split=S, a_split_stride=Mc, w_split_stride=Mc,
-             y_split_stride=Cc * 9 * Cc)
-    dW = part[0] if S == 1 else ops.sum_partials(part, torch.empty(Cc, 9 * Cc, device=dev, dtype=F32), stride=Cc * 9 * Cc, n_part=S,
-                                                 n=Cc * 9 * Cc)
+    # dW[co, tap, ci] = sum_p dfeats[p, co] * emb[shift_tap(p), ci]
+    dW = _wgrad_taps(dfe, emb, M=rows, N=Cc, Cin=Cc, taps=TAPS3, dy_geo=dfe_geo, x_geo=dict(out_h=R, out_w=R, in_h=R, in_w=R, img_stride=hw),
+                     want_bias=False)[0]
     acc["conv"] = dW if acc.get("conv") is None else acc["conv"] + dW
-    del dyT, xT, part
     # d emb = the transposed convolution of dfeats
     if taps:
         demb = ops.gemm(dfe, _conv_flip(model, d, run_dt), torch.empty(rows, Cc, device=dev, dtype=F32), M=rows, N=Cc, K=9 * Cc, lda=Cc, ldy=Cc,
@@ -419,15 +436,15 @@ def _ma_forward(ma, run: _Run, q, kv, B: int, nq: int, nk: int):
         if ma.mage_plus:                                                     # the ln_q / ln_kv line of mage_model.py:93 (MAGE+)
             qin = ops.layernorm(x, d[p + ".ln_q.w"], d[p + ".ln_q.b"], torch.empty_like(x), 1e-5)
             kvin = ops.layernorm(kv, d[p + ".ln_kv.w"], d[p + ".ln_kv.b"], torch.empty_like(kv), 1e-5)
-        qp = _gemm32(qin, w[:Cc], torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc, lda=Cc, ldy=Cc, bias=b[:Cc])
-        kvp = _gemm32(kvin, w[Cc:], torch.empty(B * nk, 2 * Cc, device=dev, dtype=F32), M=B * nk, N=2 * Cc, K=Cc, lda=Cc, ldy=2 * Cc, bias=b[Cc:])
+        qp = _gemm32(run, qin, w[:Cc], torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc, lda=Cc, ldy=Cc, bias=b[:Cc])
+        kvp = _gemm32(run, kvin, w[Cc:], torch.empty(B * nk, 2 * Cc, device=dev, dtype=F32), M=B * nk, N=2 * Cc, K=Cc, lda=Cc, ldy=2 * Cc, bias=b[Cc:])
         geo = dict(n_seq=B, inner=1, nq=nq, nk=nk, n_head=H, q_outer_stride=nq, q_axis_stride=1, kv_outer_stride=nk, kv_axis_stride=1)
         ao = torch.empty(B * nq, Cc, device=dev, dtype=F32)
         ops.attention(qp, kvp, kvp[:, Cc:], ao, ldq=Cc, ldk=2 * Cc, ldv=2 * Cc, ldo=Cc, **geo)
         s_attn, s_mlp = run.next_seed(), run.next_seed()
         x1 = _res_linear(run, ao, d, p + ".out_proj", x, F32, M=B * nq, N=Cc, K=Cc, seed=s_attn)
         xn = ops.layernorm(x1, d[p + ".ln_2.w"], d[p + ".ln_2.b"], torch.empty_like(x1), 1e-5)
-        hpre = _gemm32(xn, d[p + ".c_fc.f32"], torch.empty(B * nq, 4 * Cc, device=dev, dtype=F32), M=B * nq, N=4 * Cc, K=Cc, lda=Cc,
+        hpre = _gemm32(run, xn, d[p + ".c_fc.f32"], torch.empty(B * nq, 4 * Cc, device=dev, dtype=F32), M=B * nq, N=4 * Cc, K=Cc, lda=Cc,
                        ldy=4 * Cc, bias=d[p + ".c_fc.b"])
         hdn = ops.act(hpre, torch.empty_like(hpre), ops.ACT_QUICKGELU)
         x2 = _res_linear(run, hdn, d, p + ".c_proj", x1, F32, M=B * nq, N=Cc, K=4 * Cc, seed=s_mlp)
@@ -446,13 +463,14 @@ def _ma_backward(ma, run32: _Run, tape, dx, grads, pre: str = "ma_encoder"):
         p, bp, t = f"b{i}", f"{pre}.blocks.{i}", tape["layers"][i]
         _block_mlp_bwd(run32, d, p, bp, grads, dx, t["x1"], t["xn"], t["hpre"], B * nq, Cc, t["s_mlp"])
         dbr = _to_dt(run32, dx, t["s_attn"])
-        grads[bp + ".attn.out_proj.weight"], grads[bp + ".attn.out_proj.bias"] = _wgrad(dbr, t["ao"], M=B * nq, N=Cc, K=Cc, ld_dy=Cc, ld_x=Cc)
-        dao = _gemm_x(dbr, _wt(d, p + ".out_proj", F32), torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc)
+        dao = _linear_bwd(run32, d, grads, bp + ".attn.out_proj.", p + ".out_proj", dbr, t["ao"], M=B * nq, N=Cc, K=Cc, out_dt=F32)
         dqp = torch.empty(B * nq, Cc, device=dev, dtype=F32)
         dkvp = torch.empty(B * nk, 2 * Cc, device=dev, dtype=F32)
         kvp = t["kvp"]
         ops.attention_bwd(t["qp"], kvp, kvp[:, Cc:], dao, dqp, dkvp, dkvp[:, Cc:], ldq=Cc, ldk=2 * Cc, ldv=2 * Cc, ldo=Cc, ld_dq=Cc,
                           ld_dk=2 * Cc, ld_dv=2 * Cc, **t["geo"])
+        # in_proj is two Linears over the rows of one weight (q of x, k | v of the text): their gradients are assembled, their dx products
+        # read column slices of the transposed copy
         dWq, dbq = _wgrad(dqp, t["qin"], M=B * nq, N=Cc, K=Cc, ld_dy=Cc, ld_x=Cc)
         dWkv, dbkv = _wgrad(dkvp, t["kvin"], M=B * nk, N=2 * Cc, K=Cc, ld_dy=2 * Cc, ld_x=Cc)
         grads[bp + ".attn.in_proj_weight"] = torch.cat([dWq, dWkv], 0)                      # [3C, C] assembly (layout plumbing)
@@ -460,15 +478,15 @@ def _ma_backward(ma, run32: _Run, tape, dx, grads, pre: str = "ma_encoder"):
         wT = _wt(d, p + ".in_proj", F32)                                                    # [C, 3C]
         wqT, wkvT = wT[:, :Cc].contiguous(), wT[:, Cc:].contiguous()
         if ma.mage_plus:
-            dqin = _gemm_x(dqp, wqT, torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc)
+            dqin = _gemm_x(run32, dqp, wqT, torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc)
             grads[bp + ".ln_q.weight"], grads[bp + ".ln_q.bias"] = ops.layernorm_bwd(t["x0"], d[p + ".ln_q.w"], dqin, dx, eps=1e-5, accumulate=True)
-            dkvin = _gemm_x(dkvp, wkvT, torch.empty(B * nk, Cc, device=dev, dtype=F32), M=B * nk, N=Cc, K=2 * Cc)
+            dkvin = _gemm_x(run32, dkvp, wkvT, torch.empty(B * nk, Cc, device=dev, dtype=F32), M=B * nk, N=Cc, K=2 * Cc)
             dkv = torch.empty_like(dkvin)
             grads[bp + ".ln_kv.weight"], grads[bp + ".ln_kv.bias"] = ops.layernorm_bwd(kv, d[p + ".ln_kv.w"], dkvin, dkv, eps=1e-5,
                                                                                       accumulate=False)
         else:
-            dx = _gemm_x(dqp, wqT, torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc, residual=dx, ldr=Cc)
-            dkv = _gemm_x(dkvp, wkvT, torch.empty(B * nk, Cc, device=dev, dtype=F32), M=B * nk, N=Cc, K=2 * Cc)
+            dx = _gemm_x(run32, dqp, wqT, torch.empty(B * nq, Cc, device=dev, dtype=F32), M=B * nq, N=Cc, K=Cc, residual=dx, ldr=Cc)
+            dkv = _gemm_x(run32, dkvp, wkvT, torch.empty(B * nk, Cc, device=dev, dtype=F32), M=B * nk, N=Cc, K=2 * Cc)
             # ln_q / ln_kv exist in the checkpoint but are not applied by MAGE (mage_model.py:92): zero gradients
         dkv_total = dkv if dkv_total is None else dkv_total + dkv
     return dx, dkv_total
@@ -495,7 +513,7 @@ def _text_forward(te, run: _Run, text):
     layers = []
     for i in range(te.transformer_layers):
         p = f"l{i}"
-        qkv = _gemm32(x, d[p + ".in_proj.f32"], torch.empty(B * S, 3 * Wd, device=dev, dtype=F32), M=B * S, N=3 * Wd, K=Wd, lda=Wd,
+        qkv = _gemm32(run, x, d[p + ".in_proj.f32"], torch.empty(B * S, 3 * Wd, device=dev, dtype=F32), M=B * S, N=3 * Wd, K=Wd, lda=Wd,
                       ldy=3 * Wd, bias=d[p + ".in_proj.b"])
         ao = torch.empty(B * S, Wd, device=dev, dtype=F32)
         # nn.TransformerEncoderLayer(dropout=p) also drops attention PROBABILITIES in train() (mage_model.py:193-199)
@@ -504,7 +522,7 @@ def _text_forward(te, run: _Run, text):
         s1_seed, sh_seed, s2_seed = run.next_seed(), run.next_seed(), run.next_seed()
         s1 = _res_linear(run, ao, d, p + ".out_proj", x, F32, M=B * S, N=Wd, K=Wd, seed=s1_seed)
         x1 = ops.layernorm(s1, d[p + ".norm1.w"], d[p + ".norm1.b"], torch.empty_like(s1), d[p + ".norm1.eps"])
-        hpre = _gemm32(x1, d[p + ".fc1.f32"], torch.empty(B * S, 4 * Wd, device=dev, dtype=F32), M=B * S, N=4 * Wd, K=Wd, lda=Wd,
+        hpre = _gemm32(run, x1, d[p + ".fc1.f32"], torch.empty(B * S, 4 * Wd, device=dev, dtype=F32), M=B * S, N=4 * Wd, K=Wd, lda=Wd,
                        ldy=4 * Wd, bias=d[p + ".fc1.b"])
         hdn = ops.act(hpre, torch.empty_like(hpre), ops.ACT_GELU_ERF)
         if run.p > 0:
@@ -514,7 +532,7 @@ def _text_forward(te, run: _Run, text):
         layers.append(dict(x_in=x, qkv=qkv, ao=ao, s1=s1, x1=x1, hpre=hpre, s2=s2, seeds=(s1_seed, sh_seed, s2_seed), sa_seed=sa_seed))
         x = x2
     xf = ops.layernorm(x, d["ln_text_final.w"], d["ln_text_final.b"], torch.empty_like(x), te.ln_text_final.eps)
-    out = _gemm32(xf, d["proj.f32"], torch.empty(B * S, te.output_dim, device=dev, dtype=F32), M=B * S, N=te.output_dim, K=Wd, lda=Wd,
+    out = _gemm32(run, xf, d["proj.f32"], torch.empty(B * S, te.output_dim, device=dev, dtype=F32), M=B * S, N=te.output_dim, K=Wd, lda=Wd,
                    ldy=te.output_dim, bias=d["proj.b"])
     return out, dict(ids=ids, keepf=keepf, e=e, s_emb=s_emb, layers=layers, x_last=x, xf=xf, geo=geo, B=B, S=S)
 
@@ -523,9 +541,7 @@ def _text_backward(te, run32: _Run, tape, dout, grads, pre: str = "text_encoder"
     d = te._derived.get(te._build)
     B, S = tape["B"], tape["S"]
     Wd, dev, R = te.transformer_width, dout.device, tape["B"] * tape["S"]
-    grads[pre + ".text_projection.weight"], grads[pre + ".text_projection.bias"] = _wgrad(dout, tape["xf"], M=R, N=te.output_dim, K=Wd,
-                                                                                         ld_dy=te.output_dim, ld_x=Wd)
-    dxf = _gemm_x(dout, _wt(d, "proj", F32), torch.empty(R, Wd, device=dev, dtype=F32), M=R, N=Wd, K=te.output_dim)
+    dxf = _linear_bwd(run32, d, grads, pre + ".text_projection.", "proj", dout, tape["xf"], M=R, N=te.output_dim, K=Wd, out_dt=F32)
     dx = torch.empty(R, Wd, device=dev, dtype=F32)
     grads[pre + ".ln_text_final.weight"], grads[pre + ".ln_text_final.bias"] = ops.layernorm_bwd(tape["x_last"], d["ln_text_final.w"], dxf,
                                                                                                 dx, eps=te.ln_text_final.eps,
@@ -536,30 +552,22 @@ def _text_backward(te, run32: _Run, tape, dout, grads, pre: str = "text_encoder"
         ds2 = torch.empty(R, Wd, device=dev, dtype=F32)
         grads[lp + ".norm2.weight"], grads[lp + ".norm2.bias"] = ops.layernorm_bwd(t["s2"], d[p + ".norm2.w"], dx, ds2, eps=d[p + ".norm2.eps"],
                                                                                   accumulate=False)
+        # the MLP half is written out: post-norm order, GELU(erf), and a dropout of the hidden rows in both directions
         dbr = _to_dt(run32, ds2, s2_seed)
         hdn = ops.act(t["hpre"], torch.empty_like(t["hpre"]), ops.ACT_GELU_ERF)
         if run32.p > 0:
             hdn = ops.dropout(hdn, torch.empty_like(hdn), run32.p, sh_seed)
-        grads[lp + ".linear2.weight"], grads[lp + ".linear2.bias"] = _wgrad(dbr, hdn, M=R, N=Wd, K=4 * Wd, ld_dy=Wd, ld_x=4 * Wd)
-        dh = _gemm_x(dbr, _wt(d, p + ".fc2", F32), torch.empty(R, 4 * Wd, device=dev, dtype=F32), M=R, N=4 * Wd, K=Wd)
+        dh = _linear_bwd(run32, d, grads, lp + ".linear2.", p + ".fc2", dbr, hdn, M=R, N=Wd, K=4 * Wd, out_dt=F32)
         if run32.p > 0:
             dh = ops.dropout(dh, torch.empty_like(dh), run32.p, sh_seed)
         ops.act_bwd(t["hpre"], dh, dh, ops.ACT_GELU_ERF)
-        grads[lp + ".linear1.weight"], grads[lp + ".linear1.bias"] = _wgrad(dh, t["x1"], M=R, N=4 * Wd, K=Wd, ld_dy=4 * Wd, ld_x=Wd)
-        dx1 = _gemm_x(dh, _wt(d, p + ".fc1", F32), torch.empty(R, Wd, device=dev, dtype=F32), M=R, N=Wd, K=4 * Wd, residual=ds2, ldr=Wd)
+        dx1 = _linear_bwd(run32, d, grads, lp + ".linear1.", p + ".fc1", dh, t["x1"], M=R, N=4 * Wd, K=Wd, out_dt=F32, residual=ds2, ldr=Wd)
         ds1 = torch.empty(R, Wd, device=dev, dtype=F32)
         grads[lp + ".norm1.weight"], grads[lp + ".norm1.bias"] = ops.layernorm_bwd(t["s1"], d[p + ".norm1.w"], dx1, ds1, eps=d[p + ".norm1.eps"],
                                                                                   accumulate=False)
         dbr = _to_dt(run32, ds1, s1_seed)
-        grads[lp + ".self_attn.out_proj.weight"], grads[lp + ".self_attn.out_proj.bias"] = _wgrad(dbr, t["ao"], M=R, N=Wd, K=Wd, ld_dy=Wd, ld_x=Wd)
-        dao = _gemm_x(dbr, _wt(d, p + ".out_proj", F32), torch.empty(R, Wd, device=dev, dtype=F32), M=R, N=Wd, K=Wd)
-        qkv = t["qkv"]
-        dqkv = torch.empty(R, 3 * Wd, device=dev, dtype=F32)
-        ops.attention_bwd(qkv, qkv[:, Wd:], qkv[:, 2 * Wd:], dao, dqkv, dqkv[:, Wd:], dqkv[:, 2 * Wd:], ldq=3 * Wd, ldk=3 * Wd, ldv=3 * Wd,
-                          ldo=Wd, ld_dq=3 * Wd, ld_dk=3 * Wd, ld_dv=3 * Wd, drop_p=run32.p, drop_seed=t["sa_seed"], **tape["geo"])
-        grads[lp + ".self_attn.in_proj_weight"], grads[lp + ".self_attn.in_proj_bias"] = _wgrad(dqkv, t["x_in"], M=R, N=3 * Wd, K=Wd,
-                                                                                               ld_dy=3 * Wd, ld_x=Wd)
-        dx = _gemm_x(dqkv, _wt(d, p + ".in_proj", F32), torch.empty(R, Wd, device=dev, dtype=F32), M=R, N=Wd, K=3 * Wd, residual=ds1, ldr=Wd)
+        dx = _self_attn_bwd(run32, d, grads, lp + ".self_attn.", p, dbr, t, t["x_in"], M=R, C=Wd, out_dt=F32, residual=ds1, ldr=Wd,
+                            geo=dict(tape["geo"], drop_p=run32.p, drop_seed=t["sa_seed"]))
     ops.row_affine(dx, tape["keepf"], None)                                   # x = dropout(LN(e)) * keep
     if run32.p > 0:
         dx = ops.dropout(dx, torch.empty_like(dx), run32.p, tape["s_emb"])
@@ -728,7 +736,6 @@ def train_forward(model, batch, head=None):
     run32.seed, run32.p = run.seed, run.p
     run32.site = 1 << 20            # its own stream of dropout sites: the decoder's and the encoders' layers never share a seed
     run32.sk = ops.F16X3 if (dt != F32 and config.get().train_enc_split) else 0
-    _SPLIT32["sk"], _SPLIT32["w"] = run32.sk, {}
     d = model._derived.get(model._build)
     dev = images.device
     tok = tok_in = tok0 = lat_all = lat_in = lat0 = None
@@ -815,7 +822,6 @@ def train_forward(model, batch, head=None):
 def train_backward(model, tape, grad_out: torch.Tensor) -> Dict[str, torch.Tensor]:
     """Gradients of every trainable parameter, keyed by state_dict name (fp32, the parameter's shape)."""
     run, run32 = tape["run"], tape["run32"]
-    _SPLIT32["sk"] = getattr(run32, "sk", 0)
     dt = run.dt
     R, L, Cc, B = model.image_resolution, model.frames_length, model.vision_width, tape["B"]
     hw = R * R

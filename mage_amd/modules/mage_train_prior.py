@@ -22,7 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
-from .mage_train import _split_plan, _wgrad
+from .mage_train import TAPS3, _flipped, _wgrad, _wgrad_taps
 from .vqvae_model import VectorQuantizedVAE
 
 F32 = torch.float32
@@ -36,7 +36,7 @@ def _flip(d: Dict[str, torch.Tensor], key: str, cin: int, cout: int, dt=F32) -> 
     Wf[ci, (ky, kx), co] = W[co, (2 - ky, 2 - kx), ci]  (a derived copy in dt, cached with the others)."""
     k = key + (".flip" if dt == F32 else ".flip.bf16")
     if k not in d:
-        d[k] = d[key].reshape(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, 9 * cout).to(dt).contiguous()
+        d[k] = _flipped(d[key], cout, 3, cin).to(dt)
     return d[k]
 
 
@@ -45,25 +45,8 @@ def _conv_wgrad(dy, x, *, n_img: int, R: int, cin: int, cout: int, x_img_stride:
     """dW [cout, 9*cin] (tap-major, ci fastest: the GEMM weight layout) = sum over output pixels of dy^T gathered(x), and db.
     dy [n_img*R*R, cout] plain rows; x is read as image i -> rows i*x_img_stride + x_off (a frame of the padded buffer).
     Returns (dW, db, dyT): the transposed dy can be reused for the other temporal taps."""
-    dev, dt = dy.device, dy.dtype
-    assert x.dtype == dt
-    hw = R * R
-    M = n_img * hw
-    S, Mc = _split_plan(M, cout, 9 * cin)
-    Mp = S * Mc
-    if dyT is None:
-        dyT = torch.empty(cout, Mp, device=dev, dtype=dt)
-        ops.transpose(dy, dyT, M=M, Mp=Mp, C=cout, ldx=cout, ldy=Mp)
-    xT = torch.empty(9 * cin, Mp, device=dev, dtype=dt)
-    for t in range(9):
-        ops.transpose(x, xT, M=M, Mp=Mp, C=cin, ldx=cin, ldy=Mp, y_row0=t * cin, out_h=R, out_w=R, in_h=R, in_w=R,
-                      img_stride=hw if x_img_stride is None else x_img_stride, a_off=x_off, dy=t // 3 - 1, dx=t % 3 - 1)
-    K = 9 * cin
-    part = torch.empty(S, cout, K, device=dev, dtype=F32)
-    ops.gemm(dyT, xT, part, M=cout, N=K, K=Mc, lda=Mp, ldy=K, ldw=Mp, n_split=S, a_split_stride=Mc, w_split_stride=Mc, y_split_stride=cout * K)
-    dW = part[0] if S == 1 else ops.sum_partials(part, torch.empty(cout, K, device=dev, dtype=F32), stride=cout * K, n_part=S, n=cout * K)
-    db = ops.row_sum(dyT, torch.empty(cout, device=dev, dtype=F32), ld=Mp, n=M, rows=cout) if want_bias else None
-    return dW, db, dyT
+    geo = dict(out_h=R, out_w=R, in_h=R, in_w=R, img_stride=R * R if x_img_stride is None else x_img_stride, a_off=x_off)
+    return _wgrad_taps(dy, x, M=n_img * R * R, N=cout, Cin=cin, taps=TAPS3, x_geo=geo, want_bias=want_bias, dyT=dyT)
 
 
 def _w4(dW: torch.Tensor, cout: int, cin: int) -> torch.Tensor:

@@ -9,7 +9,7 @@ back-propagates into it, and its ``backward`` produces every parameter gradient 
   passes to z_e unchanged, the codebook receives ``index_add`` of the gradient of z_q_x (a scatter kernel);
 * every convolution gradient as MFMA GEMMs: data gradients are the forward implicit-GEMM kernel on re-laid weights (a stride-2
   convolution's is four sub-pixel GEMMs, a transposed convolution's is a stride-2 gather GEMM), weight gradients are gathered
-  transposes + one split-K launch (mage_train._wgrad machinery);
+  transposes + one split-K launch (mage_train._wgrad_taps);
 * the in-place-ReLU quirk of ResBlock (out = relu(x) + f(relu(x)), vqvae_model.py:111-124) exactly as in inference.
 
 fp32 throughout (stage-1 training is small: 2 x 2.4 M parameters).
@@ -28,7 +28,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .mage_train import _split_plan
+from .mage_train import TAPS3, _flipped, _wgrad_taps
+from .vqvae_model import VectorQuantizedVAE
 
 F32 = torch.float32
 
@@ -36,35 +37,13 @@ __all__ = ["VQVAEForwardFn", "vq_train_forward", "vq_train_backward", "vq8_train
 
 
 # ----------------------------------------------------------------------------------------------------------------- helpers
-def _conv(a, wgt, y, *, n_img, H, W, cin, cout, k, stride=1, pad=None, OH=None, OW=None, **epi):
-    pad = k // 2 if pad is None else pad
-    OH = H if OH is None else OH
-    OW = W if OW is None else OW
-    return ops.gemm(a, wgt, y, M=n_img * OH * OW, N=cout, K=k * k * cin, lda=cin, ldy=cout, out_h=OH, out_w=OW, in_h=H, in_w=W,
-                    taps_h=k, taps_w=k, cin=cin, stride=stride, dy0=-pad, dx0=-pad, **epi)
+_conv = VectorQuantizedVAE._conv
 
 
-def _wgrad_taps(dy, x, *, M: int, N: int, Cin: int, taps, grid, dy_geo=None, x_ld=None):
-    """dW[N, ntaps*Cin] = sum_m dy[m, :]^T x[gather_tap(m), :] and db[N]: `taps` = list of dict(dy, dx) gathers of x over the output
-    grid `grid` = dict(out_h, out_w, in_h, in_w, stride) (x is [n_img*in_h*in_w, Cin] channels-last); dy_geo optionally gathers the
-    rows of dy itself (the sub-pixel positions of a transposed convolution's output)."""
-    dev = dy.device
-    nt = len(taps)
-    S, Mc = _split_plan(M, N, nt * Cin)
-    Mp = S * Mc
-    dyT = torch.empty(N, Mp, device=dev, dtype=F32)
-    ops.transpose(dy, dyT, M=M, Mp=Mp, C=N, ldx=N, ldy=Mp, **(dy_geo or {}))
-    xT = torch.empty(nt * Cin, Mp, device=dev, dtype=F32)
-    for i, t in enumerate(taps):
-        ops.transpose(x, xT, M=M, Mp=Mp, C=Cin, ldx=Cin if x_ld is None else x_ld, ldy=Mp, y_row0=i * Cin, out_h=grid["out_h"],
-                      out_w=grid["out_w"], in_h=grid["in_h"], in_w=grid["in_w"], img_stride=grid["in_h"] * grid["in_w"], dy=t["dy"], dx=t["dx"],
-                      stride=grid.get("stride", 1))
-    K = nt * Cin
-    part = torch.empty(S, N, K, device=dev, dtype=F32)
-    ops.gemm(dyT, xT, part, M=N, N=K, K=Mc, lda=Mp, ldy=K, ldw=Mp, n_split=S, a_split_stride=Mc, w_split_stride=Mc, y_split_stride=N * K)
-    dW = part[0] if S == 1 else ops.sum_partials(part, torch.empty(N, K, device=dev, dtype=F32), stride=N * K, n_part=S, n=N * K)
-    db = ops.row_sum(dyT, torch.empty(N, device=dev, dtype=F32), ld=Mp, n=M, rows=N)
-    return dW, db
+def _grid(OH: int, OW: int, H: int = None, W: int = None, stride: int = 1) -> dict:
+    """_wgrad_taps' x_geo for channels-last images [n_img, H, W, .] gathered over an OH x OW output grid (H, W: the grid's own)."""
+    H, W = OH if H is None else H, OW if W is None else W
+    return dict(out_h=OH, out_w=OW, in_h=H, in_w=W, img_stride=H * W, stride=stride)
 
 
 def _bn_forward(bn: nn.BatchNorm2d, x_rows, relu: bool, residual=None):
@@ -93,9 +72,6 @@ def _res_forward(vq, w, p: str, rb, r, n_img: int, H: int, W: int, post_relu: bo
     return out, dict(r=r, t=t, s3=s3, s1=s1, out=out, post_relu=post_relu)
 
 
-_TAPS3 = [dict(dy=ky - 1, dx=kx - 1) for ky in range(3) for kx in range(3)]
-
-
 def _res_backward(vq, w, p: str, rb, key: str, tape, dout, n_img: int, H: int, W: int, grads: Dict[str, torch.Tensor]):
     """Returns d/dr (r = the block's ReLU'd input); fills the block's parameter gradients (keys `key`.block.{1,2,4,5}.*)."""
     D, dev = vq.dim, dout.device
@@ -104,18 +80,17 @@ def _res_backward(vq, w, p: str, rb, key: str, tape, dout, n_img: int, H: int, W
     s1, s3 = tape["s1"], tape["s3"]
     dc1 = torch.empty_like(do)
     grads[f"{key}.block.5.weight"], grads[f"{key}.block.5.bias"] = ops.bn_backward(s1["x"], do, s1["mean"], s1["rstd"], s1["gamma"], dc1)
-    dW1, db1 = _wgrad_taps(dc1, tape["t"], M=M, N=D, Cin=D, taps=[dict(dy=0, dx=0)], grid=dict(out_h=H, out_w=W, in_h=H, in_w=W))
+    dW1, db1, _ = _wgrad_taps(dc1, tape["t"], M=M, N=D, Cin=D, x_geo=_grid(H, W))
     grads[f"{key}.block.4.weight"], grads[f"{key}.block.4.bias"] = dW1.view(D, D, 1, 1), db1
     w1T = w[p + ".w1.f32"].t().contiguous()                                     # [Cin, Cout]: dX = dY W
     dt = ops.gemm(dc1, w1T, torch.empty_like(do), M=M, N=D, K=D, lda=D, ldy=D)
     dc3 = torch.empty_like(do)
     grads[f"{key}.block.2.weight"], grads[f"{key}.block.2.bias"] = ops.bn_backward(s3["x"], dt, s3["mean"], s3["rstd"], s3["gamma"], dc3,
                                                                                   mask=tape["t"])
-    dW3, db3 = _wgrad_taps(dc3, tape["r"], M=M, N=D, Cin=D, taps=_TAPS3, grid=dict(out_h=H, out_w=W, in_h=H, in_w=W))
+    dW3, db3, _ = _wgrad_taps(dc3, tape["r"], M=M, N=D, Cin=D, taps=TAPS3, x_geo=_grid(H, W))
     grads[f"{key}.block.1.weight"] = dW3.view(D, 3, 3, D).permute(0, 3, 1, 2).contiguous()       # [Cout, Cin, kh, kw]
     grads[f"{key}.block.1.bias"] = db3
-    w3f = w[p + ".w3.f32"].view(D, 3, 3, D).flip(1, 2).permute(3, 1, 2, 0).reshape(D, 9 * D).contiguous()   # input-gradient conv
-    return _conv(dc3, w3f, torch.empty_like(do), n_img=n_img, H=H, W=W, cin=D, cout=D, k=3, residual=do, ldr=D)
+    return _conv(dc3, _flipped(w[p + ".w3.f32"], D, 3, D), torch.empty_like(do), n_img=n_img, H=H, W=W, cin=D, cout=D, k=3, residual=do, ldr=D)
 
 
 def _subpixel_weights(wt: torch.Tensor):
@@ -197,8 +172,7 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
         grads["decoder.6.bias"] = ops.row_sum(ds, torch.empty(N * Cin, device=dev, dtype=F32), ld=H * W, n=H * W,
                                               rows=N * Cin).view(N, Cin).sum(0)                    # [N, Cin] -> [Cin] (tiny)
         dtaps = ops.convt_unfold_tanh_bwd(ds, None, torch.empty(M4, nt, device=dev, dtype=F32), N=N, IH=2 * h, IW=2 * wd, cout=Cin)
-        dW16, _ = _wgrad_taps(dtaps, tape["v"], M=M4, N=nt, Cin=D, taps=[dict(dy=0, dx=0)], grid=dict(out_h=2 * h, out_w=2 * wd, in_h=2 * h,
-                                                                                                  in_w=2 * wd))
+        dW16 = _wgrad_taps(dtaps, tape["v"], M=M4, N=nt, Cin=D, x_geo=_grid(2 * h, 2 * wd))[0]
         grads["decoder.6.weight"] = dW16.view(4, 4, Cin, D).permute(3, 2, 0, 1).contiguous()       # [cin, cout, ky, kx]
         w16T = w["d6.w16.f32"].t().contiguous()                                                    # [D, 16*Cin]
         dv = ops.gemm(dtaps, w16T, torch.empty(M4, D, device=dev, dtype=F32), M=M4, N=D, K=nt, lda=nt, ldy=D)
@@ -211,8 +185,8 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
         du = None
         for (py, px), (ws, kys, kxs) in tape["subw"].items():
             sub_rows = dict(out_h=h, out_w=wd, in_h=2 * h, in_w=2 * wd, img_stride=4 * h * wd, dy=py, dx=px, stride=2)   # dct at (2oy+py, 2ox+px)
-            taps = [dict(dy=py - k2y, dx=px - k2x) for k2y in range(2) for k2x in range(2)]
-            dWs, _ = _wgrad_taps(dct, tape["u"], M=M, N=D, Cin=D, taps=taps, grid=dict(out_h=h, out_w=wd, in_h=h, in_w=wd), dy_geo=sub_rows)
+            taps = [(py - k2y, px - k2x) for k2y in range(2) for k2x in range(2)]
+            dWs = _wgrad_taps(dct, tape["u"], M=M, N=D, Cin=D, taps=taps, x_geo=_grid(h, wd), dy_geo=sub_rows)[0]
             dWs = dWs.view(D, 2, 2, D)                                                             # [co, k2y, k2x, ci]
             for k2y in range(2):
                 for k2x in range(2):
@@ -235,8 +209,8 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
     dr1 = _res_backward(vq, w, "e4", enc[4], "encoder.4", tape["t4"], dr2, N, h, wd, grads)
     da3 = ops.act_bwd(tape["r1"], dr1, torch.empty_like(dr1), ops.ACT_RELU)
     H2, W2 = H // 2, W // 2
-    taps16 = [dict(dy=ky - 1, dx=kx - 1) for ky in range(4) for kx in range(4)]
-    dW3, db3 = _wgrad_taps(da3, tape["h0"], M=M, N=D, Cin=D, taps=taps16, grid=dict(out_h=h, out_w=wd, in_h=H2, in_w=W2, stride=2))
+    taps16 = [(ky - 1, kx - 1) for ky in range(4) for kx in range(4)]
+    dW3, db3, _ = _wgrad_taps(da3, tape["h0"], M=M, N=D, Cin=D, taps=taps16, x_geo=_grid(h, wd, H2, W2, stride=2))
     grads["encoder.3.weight"] = dW3.view(D, 4, 4, D).permute(0, 3, 1, 2).contiguous()
     grads["encoder.3.bias"] = db3
     # input gradient of the stride-2 convolution = the transposed convolution with the same weight tensor read as [cin_T = co, cout_T = ci]
@@ -253,7 +227,7 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
         Cp = 8
         xr = torch.zeros(N * H * W, Cp, device=dev, dtype=F32)
         xr[:, :Cin] = tape["x"].permute(0, 2, 3, 1).reshape(N * H * W, Cin)
-    dW0, db0 = _wgrad_taps(da0, xr, M=M0, N=D, Cin=Cp, taps=taps16, grid=dict(out_h=H2, out_w=W2, in_h=H, in_w=W, stride=2), x_ld=Cp)
+    dW0, db0, _ = _wgrad_taps(da0, xr, M=M0, N=D, Cin=Cp, taps=taps16, x_geo=_grid(H2, W2, H, W, stride=2))
     grads["encoder.0.weight"] = dW0.view(D, 4, 4, Cp)[..., :Cin].permute(0, 3, 1, 2).contiguous()
     grads["encoder.0.bias"] = db0
     return grads
@@ -263,8 +237,8 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
 def _kconv_bwd(w, wkey: str, dy, x, *, n_img: int, H: int, W: int, cin: int, cout: int, k: int, want_dx: bool = True, dx_res=None):
     """Backward of y = Conv2d(cin, cout, k, 1, k // 2)(x) on channels-last rows: (dW [cout, cin, k, k], db, dx [+ dx_res])."""
     M, r = n_img * H * W, k // 2
-    taps = [dict(dy=ky - r, dx=kx - r) for ky in range(k) for kx in range(k)]
-    dW, db = _wgrad_taps(dy, x, M=M, N=cout, Cin=cin, taps=taps, grid=dict(out_h=H, out_w=W, in_h=H, in_w=W))
+    taps = [(ky - r, kx - r) for ky in range(k) for kx in range(k)]
+    dW, db, _ = _wgrad_taps(dy, x, M=M, N=cout, Cin=cin, taps=taps, x_geo=_grid(H, W))
     dW = dW.view(cout, k, k, cin).permute(0, 3, 1, 2).contiguous()
     dx = None
     if want_dx:
@@ -273,8 +247,7 @@ def _kconv_bwd(w, wkey: str, dy, x, *, n_img: int, H: int, W: int, cin: int, cou
         if k == 1:
             ops.gemm(dy, w[wkey].t().contiguous(), dx, M=M, N=cin, K=cout, lda=cout, ldy=cin, **extra)
         else:
-            wf = w[wkey].view(cout, k, k, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, k * k * cout).contiguous()
-            _conv(dy, wf, dx, n_img=n_img, H=H, W=W, cin=cout, cout=cin, k=k, **extra)
+            _conv(dy, _flipped(w[wkey], cout, k, cin), dx, n_img=n_img, H=H, W=W, cin=cout, cout=cin, k=k, **extra)
     return dW, db, dx
 
 
@@ -378,7 +351,7 @@ def vq8_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.
                                               rows=N * Cin).view(N, Cin).sum(0)
         dsr = torch.zeros(M, 8, device=dev, dtype=F32)                                              # channels-last rows, padded to 8 (plumbing)
         dsr[:, :Cin] = ds.permute(0, 2, 3, 1).reshape(M, Cin)
-        dW8, _ = _wgrad_taps(dsr, tape["last"], M=M, N=8, Cin=dim, taps=[dict(dy=0, dx=0)], grid=dict(out_h=H, out_w=W, in_h=H, in_w=W))
+        dW8 = _wgrad_taps(dsr, tape["last"], M=M, N=8, Cin=dim, x_geo=_grid(H, W))[0]
         grads["decoder.8.weight"] = dW8[:Cin].reshape(Cin, dim, 1, 1).contiguous()
         w8 = torch.zeros(8, dim, device=dev, dtype=F32)
         w8[:Cin] = w["d8.wt"]
@@ -402,8 +375,8 @@ def vq8_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.
     M = N * H * W
     xr = torch.zeros(M, 8, device=dev, dtype=F32)
     xr[:, :Cin] = tape["x"].permute(0, 2, 3, 1).reshape(M, Cin)
-    taps = [dict(dy=ky - 3, dx=kx - 3) for ky in range(7) for kx in range(7)]
-    dW0, db0 = _wgrad_taps(g, xr, M=M, N=dim, Cin=8, taps=taps, grid=dict(out_h=H, out_w=W, in_h=H, in_w=W))
+    taps = [(ky - 3, kx - 3) for ky in range(7) for kx in range(7)]
+    dW0, db0, _ = _wgrad_taps(g, xr, M=M, N=dim, Cin=8, taps=taps, x_geo=_grid(H, W))
     grads["encoder.0.weight"] = dW0.view(dim, 7, 7, 8)[..., :Cin].permute(0, 3, 1, 2).contiguous()
     grads["encoder.0.bias"] = db0
     return grads
