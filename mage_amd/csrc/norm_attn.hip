@@ -174,8 +174,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const mage_attn_desc d, 
 }
 
 // ------------------------------------------------------------------------------------ attention on the matrix cores
-// bf16, nq <= 32 and nk <= 32 (every axial attention of the decoder, frames_length up to 32): one wave per (sequence, head),
-// three MFMA steps per block of 16 queries (and per block of 16 keys).
+// 16-bit or f16x3 rows, nq <= 32 and nk <= 32 (every axial attention of the decoder, frames_length up to 32): one wave per (sequence,
+// head), three MFMA steps per block of 16 queries (and per block of 16 keys).  The workgroup-per-sequence kernel is written once over
+// an operand policy (attn_mfma.h) and described here with the bf16 policy's instructions; its wave-per-sequence forms for nq <= 2 follow.
 //   S^T = K Q^T   (v_mfma_f32_16x16x32_bf16, operands straight from global: lane (r = lane&15, g = lane>>4) loads the 16
 //                  bytes [g*8, g*8+8) of row r of K resp. Q): the result lane (i = lane&15, g) holds S^T[j = 4g+e][i], e=0..3,
 //                  i.e. four consecutive keys of ITS query -- exactly the B-operand layout of the next MFMA (swapped-QK idiom).
@@ -188,11 +189,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const mage_attn_desc d, 
 // NKB = key blocks of 16 (nk <= 16*NKB); queries are walked in blocks of 16 (nq <= 32 at the call sites: frames_length 32).
 // MAXH = heads per wave (ceil(n_head / 4) rounded up to 2, 4 or 8): sizes the preloaded fragment registers; 16 heads -> 4, which
 // keeps the kernel at a register count that lets 4-5 workgroups share a CU (a memory-bound kernel lives off that).
-template <int NKB, int MAXH, typename HT = unsigned short>
+// Ops = the operand policy (attn_mfma.h): attn_ops_plain<unsigned short | f16_t> for bf16 / f16 rows, attn_ops_f16x3 for split rows of
+// f16 pieces (the fast parity mode, in place of the thread-per-(query, head) fp32 kernel: 540 vs ~200 us per launch at cfg2).  The
+// geometry, the mask, the softmax and the row store below are the same code for all three.
+template <int NKB, int MAXH, typename Ops>
 __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_desc d) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned short* vs = (unsigned short*)smem_raw;     // [16*NKB][n_head*32 + 16]: rows >= nk are zero
-    const int rowf = d.n_head * 32, vpitch = rowf + 16;
+    unsigned short* vs = (unsigned short*)smem_raw;     // [16*NKB][n_head*COLS + 16]: V rows as they lie in memory; rows >= nk are zero
+    const int rowf = d.n_head * Ops::COLS, vpitch = rowf + 16;
     const int s = blockIdx.x;
     const int outer = s / d.inner, in = s - outer * d.inner;
     const long q_base = (long)outer * d.q_outer_stride + in;
@@ -202,7 +206,8 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
     const unsigned short* qp = (const unsigned short*)d.q;
     const unsigned short* kp = (const unsigned short*)d.k;
     const unsigned short* vp = (const unsigned short*)d.v;
-    HT* op = (HT*)d.out;
+    typename Ops::out_t* op = (typename Ops::out_t*)d.out;
+    const int ldo = Ops::ldo(d.ldo);
     const int vec_per_row = rowf / 8;
     for (int e = threadIdx.x; e < 16 * NKB * vec_per_row; e += 256) {
         const int j = e / vec_per_row, c = (e - j * vec_per_row) * 8;
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
     // all of this wave's K fragments up front (independent 16-byte loads; out-of-range keys clamped, masked below)
-    uint4 kf[MAXH][NKB];
+    typename Ops::frag kf[MAXH][NKB];
 #pragma unroll
     for (int t = 0; t < MAXH; ++t) {
         const int h = wave + 4 * t;
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 const long krow = kv_base + (long)min(kb * 16 + r, d.nk - 1) * d.kv_axis_stride;
-                kf[t][kb] = *(const uint4*)(kp + krow * d.ldk + h * 32 + g * 8);
+                kf[t][kb] = Ops::load(kp + krow * d.ldk, h * 32 + g * 8);
             }
         }
     }
@@ -233,11 +238,11 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
         const int qi = qb * 16 + r;                                           // this lane's query
         const long qrow = q_base + (long)min(qi, d.nq - 1) * d.q_axis_stride;
         const int jmax = d.causal ? min(klen, qi + 1 + (d.nk - d.nq)) : klen;  // query qi sees keys j < jmax
-        uint4 qf[MAXH];
+        typename Ops::frag qf[MAXH];
 #pragma unroll
         for (int t = 0; t < MAXH; ++t) {
             const int h = wave + 4 * t;
-            if (h < d.n_head) qf[t] = *(const uint4*)(qp + qrow * d.ldq + h * 32 + g * 8);
+            if (h < d.n_head) qf[t] = Ops::load(qp + qrow * d.ldq, h * 32 + g * 8);
         }
 #pragma unroll
         for (int t = 0; t < MAXH; ++t) {
@@ -247,25 +252,22 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
             float mx = -INFINITY;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
-                st[kb] = attn_mfma_qk<HT>(kf[t][kb], qf[t]);
+                st[kb] = Ops::qk(kf[t][kb], qf[t]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    st[kb][e] = (kb * 16 + 4 * g + e < jmax) ? st[kb][e] * d.scale : -INFINITY;
-                    mx = fmaxf(mx, st[kb][e]);
-                }
+                for (int e = 0; e < 4; ++e) mx = fmaxf(mx, (kb * 16 + 4 * g + e < jmax) ? st[kb][e] * d.scale : -INFINITY);
             }
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
             float den = 0.f;
-            ashort4 phi[NKB], plo[NKB];                                       // P = hi + lo in bf16 (lo = the truncation residue)
+            typename Ops::p4 phi[NKB], plo[NKB];                              // P = hi + lo (lo = the residue, in the policy's pieces)
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float p = (kb * 16 + 4 * g + e < jmax) ? expf(st[kb][e] - mx) : 0.f;
+                    const float p = (kb * 16 + 4 * g + e < jmax) ? expf(Ops::template exp_arg<NKB>(st[kb][e], d.scale, mx)) : 0.f;
                     den += p;
-                    short ph, pl;
-                    attn_p_split<HT>(p, ph, pl);
+                    typename Ops::pe ph, pl;
+                    Ops::psplit(p, ph, pl);
                     phi[kb][e] = ph;
                     plo[kb][e] = pl;
                 }
@@ -274,16 +276,11 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
             f32x4 o[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+                typename Ops::vt4 vt[NKB];
 #pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                    const unsigned short* vr = vs + (kb * 16 + 4 * g) * vpitch + h * 32 + b * 16 + r;
-                    ashort4 vt;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) vt[e] = (short)vr[e * vpitch];
-                    o[b] = attn_mfma_pv<HT>(vt, phi[kb], o[b]);
-                    o[b] = attn_mfma_pv<HT>(vt, plo[kb], o[b]);
-                }
+                for (int kb = 0; kb < NKB; ++kb)
+                    vt[kb] = Ops::vt(vs + (kb * 16 + 4 * g) * vpitch + Ops::col(h * 32 + b * 16 + r), vpitch, Ops::LO);
+                o[b] = Ops::template pv<NKB>(vt, phi, plo);
             }
             // lane (i = r, g) holds O[i][b*16 + 4g + e]; swap halves between neighbouring lane groups: 8 consecutive dims per lane
             const float inv = 1.0f / den;
@@ -296,14 +293,14 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const mage_attn_des
             }
             if (qi < d.nq) {
                 const int col = h * 32 + 16 * (g & 1) + 8 * (g >> 1);
-                store8(op + (o_base + (long)qi * o_step) * d.ldo + col, v0, v1);
+                store8(op + (o_base + (long)qi * o_step) * ldo + col, v0, v1);
             }
         }
     }
 }
 
 // Few queries, many sequences (the incremental AR step's temporal attention: nq = 1 or 2 new positions against a K,V cache of up to
-// 32, 16384 sequences at cfg2): one WAVE per sequence, no LDS, no barrier.  Per (sequence, head) the SAME instruction sequence on the
+// 32, 16384 sequences at cfg2): one WAVE per sequence, no workgroup barrier.  Per (sequence, head) the SAME instruction sequence on the
 // same operand values as attention_mfma_kernel (S^T = K Q^T by one 16x16x32 MFMA, in-lane softmax + two xor-shuffles, P = hi + lo,
 // O^T = V^T P^T by 16x16x16 MFMAs) -- the incremental loop's tokens stay bit-identical to the full pass's -- with the V rows in a
 // wave-private LDS tile (rows beyond nk are clamped copies: their probabilities are exactly 0) and four heads' loads in flight before
@@ -328,6 +325,7 @@ template <int N> __device__ __forceinline__ ashort4 row_shl_s4(ashort4 src) {
 
 template <int NKB, typename HT = unsigned short>
 __global__ __launch_bounds__(256) void attention_mfma_fewq_kernel(const mage_attn_desc d) {
+    typedef attn_ops_plain<HT> Ops;
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (s >= d.n_seq) return;
@@ -410,10 +408,7 @@ __global__ __launch_bounds__(256) void attention_mfma_fewq_kernel(const mage_att
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sp[kb][e] = (kb * 16 + 4 * g + e < jmax_p) ? sp[kb][e] * d.scale : -INFINITY;
-                mx = fmaxf(mx, sp[kb][e]);
-            }
+            for (int e = 0; e < 4; ++e) mx = fmaxf(mx, (kb * 16 + 4 * g + e < jmax_p) ? sp[kb][e] * d.scale : -INFINITY);
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float den = 0.f;
@@ -422,7 +417,7 @@ __global__ __launch_bounds__(256) void attention_mfma_fewq_kernel(const mage_att
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float p = (kb * 16 + 4 * g + e < jmax_p) ? expf(sp[kb][e] - mx) : 0.f;
+                const float p = (kb * 16 + 4 * g + e < jmax_p) ? expf(Ops::template exp_arg<NKB>(sp[kb][e], d.scale, mx)) : 0.f;
                 den += p;
                 short ph, pl;
                 attn_p_split<HT>(p, ph, pl);
@@ -476,151 +471,13 @@ __global__ __launch_bounds__(256) void attention_mfma_fewq_kernel(const mage_att
     }
 }
 
-// The fast parity mode's axial attention (q, k, v and out are SPLIT rows of f16 pieces, common.h): attention_mfma_kernel's structure
-// with every product as three f16 MFMA passes -- S^T = (K_hi Q_lo^T + K_lo Q_hi^T) 2^-11 + K_hi Q_hi^T by v_mfma_f32_16x16x32_f16,
-// softmax in fp32, P = hi + lo 2^-11 in f16 pieces, O^T = (V_hi^T P_lo^T + V_lo^T P_hi^T) 2^-11 + V_hi^T P_hi^T by 16x16x16 --
-// 22-bit operands, fp32 accumulation: fp32-class like the split GEMMs, in place of the thread-per-(query, head) fp32 kernel (540 vs
-// ~200 us per launch at cfg2).  Logical column c of a split row sits at 16-bit index (c / 64) * 128 + piece * 64 + c % 64.
-__device__ __forceinline__ int split_col(int c, int piece) { return ((c >> 6) << 7) + (piece << 6) + (c & 63); }
-
-template <int NKB, int MAXH>
-__global__ __launch_bounds__(256) void attention_mfma_split_kernel(const mage_attn_desc d) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned short* vs = (unsigned short*)smem_raw;     // [16*NKB][2*n_head*32 + 16]: physical (split) V rows; rows >= nk are zero
-    const int prow = d.n_head * 64, vpitch = prow + 16;
-    const int s = blockIdx.x;
-    const int outer = s / d.inner, in = s - outer * d.inner;
-    const long q_base = (long)outer * d.q_outer_stride + in;
-    const long o_base = d.o_axis_stride ? (long)outer * d.o_outer_stride + in : q_base;      // out: q's row map unless the descriptor gives its own
-    const long o_step = d.o_axis_stride ? d.o_axis_stride : d.q_axis_stride;
-    const long kv_base = (long)outer * d.kv_outer_stride + in;
-    const unsigned short* qp = (const unsigned short*)d.q;
-    const unsigned short* kp = (const unsigned short*)d.k;
-    const unsigned short* vp = (const unsigned short*)d.v;
-    split_f16* op = (split_f16*)d.out;
-    const int ldo = d.ldo >> 1;
-    const int vec_per_row = prow / 8;
-    for (int e = threadIdx.x; e < 16 * NKB * vec_per_row; e += 256) {
-        const int j = e / vec_per_row, c = (e - j * vec_per_row) * 8;
-        uint4 val = uint4{0u, 0u, 0u, 0u};
-        if (j < d.nk) val = *(const uint4*)(vp + (kv_base + (long)j * d.kv_axis_stride) * d.ldv + c);
-        *(uint4*)(vs + j * vpitch + c) = val;
-    }
-    int klen = d.nk;
-    if (d.kv_len) klen = min(klen, d.kv_len[s / d.kv_len_div]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    constexpr float LO = 1.0f / MAGE_F16_LO_SCALE;
-    uint4 kf[MAXH][NKB][2];
-#pragma unroll
-    for (int t = 0; t < MAXH; ++t) {
-        const int h = wave + 4 * t;
-        if (h < d.n_head) {
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) {
-                const long krow = (kv_base + (long)min(kb * 16 + r, d.nk - 1) * d.kv_axis_stride) * d.ldk;
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) kf[t][kb][pc] = *(const uint4*)(kp + krow + split_col(h * 32 + g * 8, pc));
-            }
-        }
-    }
-    __syncthreads();
-    const int nqb = (d.nq + 15) >> 4;
-    for (int qb = 0; qb < nqb; ++qb) {
-        const int qi = qb * 16 + r;
-        const long qrow = (q_base + (long)min(qi, d.nq - 1) * d.q_axis_stride) * d.ldq;
-        const int jmax = d.causal ? min(klen, qi + 1 + (d.nk - d.nq)) : klen;
-        uint4 qf[MAXH][2];
-#pragma unroll
-        for (int t = 0; t < MAXH; ++t) {
-            const int h = wave + 4 * t;
-            if (h < d.n_head) {
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) qf[t][pc] = *(const uint4*)(qp + qrow + split_col(h * 32 + g * 8, pc));
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < MAXH; ++t) {
-            const int h = wave + 4 * t;
-            if (h >= d.n_head) break;
-            f32x4 st[NKB];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb) {
-                f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][0]), __builtin_bit_cast(f16x8, qf[t][1]),
-                                                                 f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][1]), __builtin_bit_cast(f16x8, qf[t][0]), a, 0, 0, 0);
-                a *= LO;
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][0]), __builtin_bit_cast(f16x8, qf[t][0]), a, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    a[e] = (kb * 16 + 4 * g + e < jmax) ? a[e] * d.scale : -INFINITY;
-                    mx = fmaxf(mx, a[e]);
-                }
-                st[kb] = a;
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            float den = 0.f;
-            ahalf4 phi[NKB], plo[NKB];
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = (kb * 16 + 4 * g + e < jmax) ? expf(st[kb][e] - mx) : 0.f;
-                    den += p;
-                    const _Float16 ph = (_Float16)p;
-                    phi[kb][e] = ph;
-                    plo[kb][e] = (_Float16)((p - (float)ph) * MAGE_F16_LO_SCALE);
-                }
-            den += __shfl_xor(den, 16);
-            den += __shfl_xor(den, 32);
-            f32x4 o[2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                ahalf4 vth[NKB], vtl[NKB];
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                    const unsigned short* vr = vs + (kb * 16 + 4 * g) * vpitch;
-                    const int ch = split_col(h * 32 + b * 16 + r, 0), cl = split_col(h * 32 + b * 16 + r, 1);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        vth[kb][e] = __builtin_bit_cast(_Float16, vr[e * vpitch + ch]);
-                        vtl[kb][e] = __builtin_bit_cast(_Float16, vr[e * vpitch + cl]);
-                    }
-                }
-                f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                    a = __builtin_amdgcn_mfma_f32_16x16x16f16(vth[kb], plo[kb], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x16f16(vtl[kb], phi[kb], a, 0, 0, 0);
-                }
-                a *= LO;
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) a = __builtin_amdgcn_mfma_f32_16x16x16f16(vth[kb], phi[kb], a, 0, 0, 0);
-                o[b] = a;
-            }
-            const float inv = 1.0f / den;
-            f32x4 v0, v1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[0][e]), __float_as_uint(o[1][e]), false, false);
-                v0[e] = __uint_as_float(sw[0]) * inv;
-                v1[e] = __uint_as_float(sw[1]) * inv;
-            }
-            if (qi < d.nq) {
-                const int col = h * 32 + 16 * (g & 1) + 8 * (g >> 1);
-                store8(op + (o_base + (long)qi * o_step) * ldo + col, v0, v1);
-            }
-        }
-    }
-}
-
-// The few-query form of attention_mfma_split_kernel (the incremental step's temporal attention in f16x3 mode): wave per sequence, the V
-// pieces in a wave-private LDS tile, per (sequence, head) the same instruction sequence as the workgroup-per-sequence kernel (the
-// incremental loop's tokens stay bit-identical to the full pass's).
+// The few-query form of attention_mfma_kernel over attn_ops_f16x3 (the incremental step's temporal attention in f16x3 mode): wave per
+// sequence, the V pieces in a wave-private LDS tile, per (sequence, head) the policy's operations in the workgroup kernel's order (the
+// incremental loop's tokens stay bit-identical to the full pass's).  Chunks of two heads; the V^T fragments are read where a head's P V
+// product needs them (read in the load phase as above they cost this kernel two of its seven waves per SIMD).
 template <int NKB>
 __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const mage_attn_desc d) {
+    typedef attn_ops_f16x3 Ops;
     constexpr int CH = 2, VP = 40;
     __shared__ unsigned short vsm[4][CH][2][NKB * 16][VP];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -634,15 +491,14 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
     const unsigned short* qp = (const unsigned short*)d.q;
     const unsigned short* kp = (const unsigned short*)d.k;
     const unsigned short* vp = (const unsigned short*)d.v;
-    split_f16* op = (split_f16*)d.out;
-    const int ldo = d.ldo >> 1;
+    Ops::out_t* op = (Ops::out_t*)d.out;
+    const int ldo = Ops::ldo(d.ldo);
     int klen = d.nk;
     if (d.kv_len) klen = min(klen, d.kv_len[s / d.kv_len_div]);
     const int r = lane & 15, g = lane >> 4;
     const int qi = r;
     const long qrow = (q_base + (long)min(qi, d.nq - 1) * d.q_axis_stride) * d.ldq;
     const int jmax_p = d.causal ? min(klen, (r & 1) + 1 + (d.nk - d.nq)) : klen;      // packed lanes: query = lane parity
-    constexpr float LO = 1.0f / MAGE_F16_LO_SCALE;
     long krow[NKB], vrow[NKB];
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
@@ -650,19 +506,17 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
         vrow[kb] = (kv_base + (long)min(kb * 16 + r, d.nk - 1) * d.kv_axis_stride) * d.ldv;
     }
     for (int h0 = 0; h0 < d.n_head; h0 += CH) {
-        uint4 kf[CH][NKB][2], qf[CH][2];
+        Ops::frag kf[CH][NKB], qf[CH];
 #pragma unroll
         for (int t = 0; t < CH; ++t) {
             const int h = min(h0 + t, d.n_head - 1);
+            qf[t] = Ops::load(qp + qrow, h * 32 + g * 8);
 #pragma unroll
-            for (int pc = 0; pc < 2; ++pc) {
-                const int c = split_col(h * 32 + g * 8, pc);
-                qf[t][pc] = *(const uint4*)(qp + qrow + c);
+            for (int kb = 0; kb < NKB; ++kb) {
+                kf[t][kb] = Ops::load(kp + krow[kb], h * 32 + g * 8);
+                const Ops::frag vf = Ops::load(vp + vrow[kb], h * 32 + g * 8);
 #pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                    kf[t][kb][pc] = *(const uint4*)(kp + krow[kb] + c);
-                    *(uint4*)&vsm[wv][t][pc][kb * 16 + r][g * 8] = *(const uint4*)(vp + vrow[kb] + c);
-                }
+                for (int pc = 0; pc < 2; ++pc) *(uint4*)&vsm[wv][t][pc][kb * 16 + r][g * 8] = vf.p[pc];
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -672,11 +526,7 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
             constexpr int t = decltype(T)::value;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
-                f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][0]), __builtin_bit_cast(f16x8, qf[t][1]),
-                                                                 f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][1]), __builtin_bit_cast(f16x8, qf[t][0]), a, 0, 0, 0);
-                a *= LO;
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[t][kb][0]), __builtin_bit_cast(f16x8, qf[t][0]), a, 0, 0, 0);
+                const f32x4 a = Ops::qk(kf[t][kb], qf[t]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sp[kb][e] = row_shr_f<2 * t>(sp[kb][e], a[e]);
             }
@@ -687,23 +537,21 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sp[kb][e] = (kb * 16 + 4 * g + e < jmax_p) ? sp[kb][e] * d.scale : -INFINITY;
-                mx = fmaxf(mx, sp[kb][e]);
-            }
+            for (int e = 0; e < 4; ++e) mx = fmaxf(mx, (kb * 16 + 4 * g + e < jmax_p) ? sp[kb][e] * d.scale : -INFINITY);
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float den = 0.f;
-        ahalf4 phi_p[NKB], plo_p[NKB];
+        Ops::p4 phi_p[NKB], plo_p[NKB];
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float p = (kb * 16 + 4 * g + e < jmax_p) ? expf(sp[kb][e] - mx) : 0.f;
+                const float p = (kb * 16 + 4 * g + e < jmax_p) ? expf(Ops::exp_arg<NKB>(sp[kb][e], d.scale, mx)) : 0.f;
                 den += p;
-                const _Float16 ph = (_Float16)p;
+                Ops::pe ph, pl;
+                Ops::psplit(p, ph, pl);
                 phi_p[kb][e] = ph;
-                plo_p[kb][e] = (_Float16)((p - (float)ph) * MAGE_F16_LO_SCALE);
+                plo_p[kb][e] = pl;
             }
         den += __shfl_xor(den, 16);
         den += __shfl_xor(den, 32);
@@ -712,7 +560,7 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
             constexpr int t = decltype(T)::value;
             const int h = h0 + t;
             if (h >= d.n_head) return;
-            ahalf4 phi[NKB], plo[NKB];
+            Ops::p4 phi[NKB], plo[NKB];
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 phi[kb] = __builtin_bit_cast(ahalf4, row_shl_s4<2 * t>(__builtin_bit_cast(ashort4, phi_p[kb])));
@@ -722,24 +570,10 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
             f32x4 o[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                ahalf4 vth[NKB], vtl[NKB];
+                Ops::vt4 vt[NKB];                                             // hi at piece 0 of the tile, lo one piece further
 #pragma unroll
-                for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        vth[kb][e] = __builtin_bit_cast(_Float16, vsm[wv][t][0][kb * 16 + 4 * g + e][b * 16 + r]);
-                        vtl[kb][e] = __builtin_bit_cast(_Float16, vsm[wv][t][1][kb * 16 + 4 * g + e][b * 16 + r]);
-                    }
-                f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) {
-                    a = __builtin_amdgcn_mfma_f32_16x16x16f16(vth[kb], plo[kb], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x16f16(vtl[kb], phi[kb], a, 0, 0, 0);
-                }
-                a *= LO;
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb) a = __builtin_amdgcn_mfma_f32_16x16x16f16(vth[kb], phi[kb], a, 0, 0, 0);
-                o[b] = a;
+                for (int kb = 0; kb < NKB; ++kb) vt[kb] = Ops::vt(&vsm[wv][t][0][kb * 16 + 4 * g][b * 16 + r], VP, NKB * 16 * VP);
+                o[b] = Ops::pv<NKB>(vt, phi, plo);
             }
             f32x4 v0, v1;
 #pragma unroll
@@ -823,28 +657,44 @@ int ln_launch(const float* x, const float* g, const float* b, void* y, int64_t r
     return MAGE_OK;
 }
 
+// The matrix-core kernels (nq, nk, n_head <= 32), for either operand policy: the few-query kernel of the policy's mode for the incremental
+// step's temporal attention, else the workgroup kernel on its (NKB, MAXH) ladder.  n_head = 32 with nk > 16 stages more than 64 KiB of
+// V: the kernel's dynamic LDS limit is raised for such a launch.
+template <typename Ops>
+int attn_mfma_launch(const mage_attn_desc* d, hipStream_t s) {
+    const int nkb = d->nk <= 16 ? 1 : 2;
+    if (d->nq <= 2 && d->n_seq >= 1024 && !mage_options().attn_no_fewq) {      // the incremental step's temporal attention
+        const dim3 grid((unsigned)((d->n_seq + 3) / 4));
+        if constexpr (Ops::PIECES == 2) {
+            if (nkb == 1) hipLaunchKernelGGL((attention_mfma_split_fewq_kernel<1>), grid, dim3(256), 0, s, *d);
+            else hipLaunchKernelGGL((attention_mfma_split_fewq_kernel<2>), grid, dim3(256), 0, s, *d);
+        } else {
+            if (nkb == 1) hipLaunchKernelGGL((attention_mfma_fewq_kernel<1, typename Ops::out_t>), grid, dim3(256), 0, s, *d);
+            else hipLaunchKernelGGL((attention_mfma_fewq_kernel<2, typename Ops::out_t>), grid, dim3(256), 0, s, *d);
+        }
+        MAGE_CHECK_LAUNCH("mage_attention");
+        return MAGE_OK;
+    }
+    const size_t lds = (size_t)16 * nkb * (d->n_head * Ops::COLS + 16) * 2;
+    const int hpw = (d->n_head + 3) / 4;
+#define ATTN_MFMA(NKB, MH) \
+    do { \
+        if (lds > 64 * 1024) \
+            (void)hipFuncSetAttribute((const void*)attention_mfma_kernel<NKB, MH, Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        hipLaunchKernelGGL((attention_mfma_kernel<NKB, MH, Ops>), dim3(d->n_seq), dim3(256), lds, s, *d); \
+    } while (0)
+    if (nkb == 1) { if (hpw <= 2) ATTN_MFMA(1, 2); else if (hpw <= 4) ATTN_MFMA(1, 4); else ATTN_MFMA(1, 8); }
+    else { if (hpw <= 2) ATTN_MFMA(2, 2); else if (hpw <= 4) ATTN_MFMA(2, 4); else ATTN_MFMA(2, 8); }
+#undef ATTN_MFMA
+    MAGE_CHECK_LAUNCH("mage_attention");
+    return MAGE_OK;
+}
+
 template <typename T>
 int attn_launch(const mage_attn_desc* d, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
         // the axial attentions: short sequences on the matrix cores
-        if (d->nq <= 32 && d->nk <= 32 && d->n_head <= 32 && !mage_options().attn_no_mfma) {
-            const int nkb = d->nk <= 16 ? 1 : 2;
-            if (d->nq <= 2 && d->n_seq >= 1024 && !mage_options().attn_no_fewq) {      // the incremental step's temporal attention
-                const dim3 grid((unsigned)((d->n_seq + 3) / 4));
-                if (nkb == 1) hipLaunchKernelGGL((attention_mfma_fewq_kernel<1, T>), grid, dim3(256), 0, s, *d);
-                else hipLaunchKernelGGL((attention_mfma_fewq_kernel<2, T>), grid, dim3(256), 0, s, *d);
-                MAGE_CHECK_LAUNCH("mage_attention");
-                return MAGE_OK;
-            }
-            const size_t lds = (size_t)16 * nkb * (d->n_head * 32 + 16) * 2;
-            const int hpw = (d->n_head + 3) / 4;
-#define ATTN_MFMA(NKB, MH) hipLaunchKernelGGL((attention_mfma_kernel<NKB, MH, T>), dim3(d->n_seq), dim3(256), lds, s, *d)
-            if (nkb == 1) { if (hpw <= 2) ATTN_MFMA(1, 2); else if (hpw <= 4) ATTN_MFMA(1, 4); else ATTN_MFMA(1, 8); }
-            else { if (hpw <= 2) ATTN_MFMA(2, 2); else if (hpw <= 4) ATTN_MFMA(2, 4); else ATTN_MFMA(2, 8); }
-#undef ATTN_MFMA
-            MAGE_CHECK_LAUNCH("mage_attention");
-            return MAGE_OK;
-        }
+        if (d->nq <= 32 && d->nk <= 32 && d->n_head <= 32 && !mage_options().attn_no_mfma) return attn_mfma_launch<attn_ops_plain<T>>(d, s);
     }
     // heads per workgroup: all of them if K,V fit 64 KiB of LDS, else halved while even; an odd group that still does not fit takes
     // its largest divisor that does (1 always does: nk <= 64), so every head count runs
@@ -972,26 +822,7 @@ int attn_split_launch(const mage_attn_desc* d, hipStream_t s) {
                    "mage_attention: split (f16x3) q/k/v: nq, nk <= 32, an even head count, split output");
     MAGE_CHECK_ARG((d->ldq | d->ldk | d->ldv | d->ldo) % 128 == 0 && ((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->out) & 255) == 0),
                    "mage_attention: split operands need leading dimensions that are multiples of 128 16-bit elements and 256-byte aligned bases");
-    const int nkb = d->nk <= 16 ? 1 : 2;
-    if (d->nq <= 2 && d->n_seq >= 1024 && !mage_options().attn_no_fewq) {      // the incremental step's temporal attention
-        const dim3 grid((unsigned)((d->n_seq + 3) / 4));
-        if (nkb == 1) hipLaunchKernelGGL((attention_mfma_split_fewq_kernel<1>), grid, dim3(256), 0, s, *d);
-        else hipLaunchKernelGGL((attention_mfma_split_fewq_kernel<2>), grid, dim3(256), 0, s, *d);
-        MAGE_CHECK_LAUNCH("mage_attention");
-        return MAGE_OK;
-    }
-    const size_t lds = (size_t)16 * nkb * (d->n_head * 64 + 16) * 2;
-    const int hpw = (d->n_head + 3) / 4;
-#define ATTN_S(NKB, MH) \
-    do { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attention_mfma_split_kernel<NKB, MH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((attention_mfma_split_kernel<NKB, MH>), dim3(d->n_seq), dim3(256), lds, s, *d); \
-    } while (0)
-    if (nkb == 1) { if (hpw <= 2) ATTN_S(1, 2); else if (hpw <= 4) ATTN_S(1, 4); else ATTN_S(1, 8); }
-    else { if (hpw <= 2) ATTN_S(2, 2); else if (hpw <= 4) ATTN_S(2, 4); else ATTN_S(2, 8); }
-#undef ATTN_S
-    MAGE_CHECK_LAUNCH("mage_attention");
-    return MAGE_OK;
+    return attn_mfma_launch<attn_ops_f16x3>(d, s);
 }
 }  // namespace
 

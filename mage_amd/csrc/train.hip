@@ -6,6 +6,7 @@
 // mage_sum_partials adds in a fixed order.  Everything here is deterministic except mage_embedding_bwd (fp32 atomics, like the
 // reference's own nn.Embedding backward on a GPU).
 #include "common.h"
+#include "attn_mfma.h"      // attn_p_split and the MFMA operand typedefs of the forward kernels
 
 namespace {
 
@@ -1230,15 +1231,6 @@ namespace {
 //                the lanes that own those queries;  dV^T += dO^T P, dK^T += Q^T dS  (A = dO^T / Q^T from LDS).
 // P and dS enter the 16x16x16 MFMAs as bf16 hi + lo pairs (fp32-class weights, as in the forward).  dK / dV accumulate over the query
 // blocks in registers; every output row leaves as one 16-byte store per lane (lane-group swap as in the forward).
-typedef __attribute__((ext_vector_type(8))) __bf16 tbf16x8;
-typedef __attribute__((ext_vector_type(4))) short tshort4;
-
-__device__ __forceinline__ void split_hi_lo(float v, short& hi, short& lo) {
-    const unsigned hb = __float_as_uint(v) & 0xffff0000u;
-    hi = (short)(hb >> 16);
-    lo = (short)(__float_as_uint(v - __uint_as_float(hb)) >> 16);
-}
-
 template <int NKB>
 __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn_desc d, const unsigned short* __restrict__ dout,
                                                                  unsigned short* __restrict__ dq, unsigned short* __restrict__ dk,
@@ -1309,8 +1301,8 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
         float mx = -INFINITY;
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
-            st[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tbf16x8, kf[kb]), __builtin_bit_cast(tbf16x8, qf), zero4, 0, 0, 0);
-            dpt[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tbf16x8, vf[kb]), __builtin_bit_cast(tbf16x8, gf), zero4, 0, 0, 0);
+            st[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(abf16x8, kf[kb]), __builtin_bit_cast(abf16x8, qf), zero4, 0, 0, 0);
+            dpt[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(abf16x8, vf[kb]), __builtin_bit_cast(abf16x8, gf), zero4, 0, 0, 0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 st[kb][e] = (kb * 16 + 4 * g + e < jmax) ? st[kb][e] * d.scale : -INFINITY;
@@ -1340,13 +1332,13 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
             }
         dsum += __shfl_xor(dsum, 16);
         dsum += __shfl_xor(dsum, 32);
-        tshort4 shi[NKB], slo[NKB];
+        ashort4 shi[NKB], slo[NKB];
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 short hi, lo;
-                split_hi_lo(st[kb][e] * (dpt[kb][e] - dsum) * d.scale, hi, lo);    // dS
+                attn_p_split<unsigned short>(st[kb][e] * (dpt[kb][e] - dsum) * d.scale, hi, lo);    // dS
                 shi[kb][e] = hi;
                 slo[kb][e] = lo;
             }
@@ -1357,7 +1349,7 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 const unsigned short* kr = ks + (kb * 16 + 4 * g) * PITCH + b * 16 + r;
-                tshort4 kt;
+                ashort4 kt;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) kt[e] = (short)kr[e * PITCH];
                 o[b] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kt, shi[kb], o[b], 0, 0, 0);
@@ -1387,18 +1379,18 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
         }
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
-            const f32x4 s2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tbf16x8, qf), __builtin_bit_cast(tbf16x8, kf[kb]), zero4, 0, 0, 0);
-            const f32x4 dp2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tbf16x8, gf), __builtin_bit_cast(tbf16x8, vf[kb]), zero4, 0, 0, 0);
-            tshort4 phi, plo, dhi, dlo;
+            const f32x4 s2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(abf16x8, qf), __builtin_bit_cast(abf16x8, kf[kb]), zero4, 0, 0, 0);
+            const f32x4 dp2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(abf16x8, gf), __builtin_bit_cast(abf16x8, vf[kb]), zero4, 0, 0, 0);
+            ashort4 phi, plo, dhi, dlo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 // a query that sees no key (jmq <= 0) has P = NaN on every key, as in the query-major half (0 * (1 / 0)): dv is NaN too
                 const float p = (kb * 16 + r < jmq[e]) ? expf(s2[e] * d.scale - mxq[e]) * invq[e] : (jmq[e] > 0 ? 0.f : NAN);
                 short hi, lo;
-                split_hi_lo(p, hi, lo);
+                attn_p_split<unsigned short>(p, hi, lo);
                 phi[e] = hi;
                 plo[e] = lo;
-                split_hi_lo(p * (dp2[e] - dsq[e]) * d.scale, hi, lo);
+                attn_p_split<unsigned short>(p * (dp2[e] - dsq[e]) * d.scale, hi, lo);
                 dhi[e] = hi;
                 dlo[e] = lo;
             }
@@ -1406,7 +1398,7 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const mage_attn
             for (int b = 0; b < 2; ++b) {
                 const unsigned short* gr = gs + (qb * 16 + 4 * g) * PITCH + b * 16 + r;
                 const unsigned short* qr = qs + (qb * 16 + 4 * g) * PITCH + b * 16 + r;
-                tshort4 gt, qt;
+                ashort4 gt, qt;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     gt[e] = (short)gr[e * PITCH];

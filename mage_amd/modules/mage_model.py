@@ -805,7 +805,7 @@ class FlatAxialDecoder(nn.Module):
             _wsplit(d, n, self.split_kind)
 
     def _attn_split(self) -> bool:
-        """f16x3: the axial attentions read split q, k, v on the matrix cores (attention_mfma_split_kernel); sequences up to 32."""
+        """f16x3: the axial attentions read split q, k, v on the matrix cores (attention_mfma_kernel over the f16x3 operand policy); sequences up to 32."""
         return (self.split_kind == ops.F16X3 and self.frames_length <= 32 and (self.model_channels // 32) % 2 == 0
                 and config.get().attn_split)
 

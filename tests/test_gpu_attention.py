@@ -1,5 +1,5 @@
 """GPU: every kernel behind mage_attention (csrc/norm_attn.hip) against an fp64 restatement of the descriptor contract
-(include/mage_hip.h, mage_attn_desc), at the edges of its dispatch (attn_launch / attn_split_launch).
+(include/mage_hip.h, mage_attn_desc), at the edges of its dispatch (attn_launch, attn_split_launch and attn_mfma_launch beneath both).
 
 Which kernel a descriptor reaches, and the cases of CASES / test_fewq_bit_identical_to_the_workgroup_kernel that reach it:
   attention_kernel<float, 16 | 32 | 64>                fp32: f32_nk1, f32_nk15_nq16, f32_axial_nk16 | f32_axial_nk17, f32_nk31_hg3, f32_nk32 |
@@ -13,12 +13,13 @@ Which kernel a descriptor reaches, and the cases of CASES / test_fewq_bit_identi
                                                        (32), bf16_axial_nk33, f16_nk64_hg8, f16_nk64_h9_hg3,
                                                        bf16_nk64 (64); through attn_no_mfma in
                                                        test_fewq_bit_identical_to_the_workgroup_kernel: bf16 16 and 32, f16 16 and 32
-  attention_mfma_kernel<NKB, MAXH, bf16 | f16>         16-bit, nq, nk, n_head <= 32: NKB = 1 for nk <= 16, else 2; MAXH = 2 for n_head <= 8,
-                                                       4 for 9..16, 8 for 17..32: mfma_<dtype>_nkb<NKB>_h<n_head>.  n_head = 32 with nk > 16
-                                                       (mfma_*_nkb2_h32) stages 66 560 bytes of V in LDS, above 64 KiB: it launches on
-                                                       gfx950 without raising the kernel's limit
-  attention_mfma_fewq_kernel<NKB, bf16 | f16>          as above with nq <= 2 and n_seq >= 1024 (the incremental step): fewq_*
-  attention_mfma_split_kernel<NKB, MAXH>               f16x3 q/k/v: split_nkb<NKB>_h<n_head>
+  attention_mfma_kernel<NKB, MAXH, Ops>                nq, nk, n_head <= 32: NKB = 1 for nk <= 16, else 2; MAXH = 2 for n_head <= 8, 4 for
+                                                       9..16, 8 for 17..32.  Ops = the operand policy (csrc/attn_mfma.h):
+    Ops = attn_ops_plain<bf16 | f16>                   16-bit q/k/v: mfma_<dtype>_nkb<NKB>_h<n_head>.  n_head = 32 with nk > 16
+                                                       (mfma_*_nkb2_h32) stages 66 560 bytes of V in LDS, above 64 KiB: the launcher
+                                                       raises the kernel's dynamic LDS limit for such a launch, in either policy
+    Ops = attn_ops_f16x3                               f16x3 q/k/v: split_nkb<NKB>_h<n_head>
+  attention_mfma_fewq_kernel<NKB, bf16 | f16>          16-bit as above with nq <= 2 and n_seq >= 1024 (the incremental step): fewq_*
   attention_mfma_split_fewq_kernel<NKB>                f16x3, nq <= 2, n_seq >= 1024: split_fewq_*
 
 Rows that see no key (kv_len = 0, or a causal query i < nq - nk): every kernel computes NaN there (its probabilities are all 0, the
@@ -87,7 +88,7 @@ CASES = [
     case("bf16_nk64", "bf16", 64, 64, 2, 3, causal=True, lens="edge0"),
     case("bf16_nq33_nk15", "bf16", 33, 15, 3, 7),
     case("f16_nq33_nk32", "f16", 33, 32, 1, 7, causal=True),                          # causal nq > nk: query 0 sees no key
-    # attention_mfma_kernel<NKB, MAXH, bf16 | f16>
+    # attention_mfma_kernel<NKB, MAXH, attn_ops_plain<bf16 | f16>>
     case("mfma_bf16_nkb1_h1", "bf16", 16, 16, 1, 7, causal=True),
     case("mfma_f16_nkb1_h3", "f16", 1, 1, 3, 7),
     case("mfma_bf16_nkb2_h8", "bf16", 3, 17, 8, 9, causal=True, lens="edge0", div=3),
@@ -106,7 +107,7 @@ CASES = [
     case("fewq_f16_nkb1_h5", "f16", 2, 15, 5, 1025, inner=5, causal=True, omap=True),
     case("fewq_bf16_nkb2_h3", "bf16", 2, 32, 3, 4099, inner=7, causal=True, spread=2),
     case("fewq_f16_nkb2_h9", "f16", 1, 17, 9, 4099, lens="edge0", div=3),
-    # attention_mfma_split_kernel<NKB, MAXH>
+    # attention_mfma_kernel<NKB, MAXH, attn_ops_f16x3>
     case("split_nkb1_h2", "f16x3", 16, 16, 2, 7, causal=True, geo="axial"),
     case("split_nkb1_h10", "f16x3", 3, 15, 10, 9, lens="edge0", div=3),
     case("split_nkb1_h18", "f16x3", 1, 16, 18, 7),

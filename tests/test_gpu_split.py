@@ -112,7 +112,7 @@ def test_split_row_producers_match_fp32_twins(kind):
 
 @pytest.mark.parametrize("nq,nk,causal", [(16, 16, False), (16, 16, True), (24, 24, True), (32, 32, False), (2, 20, True), (1, 9, True)])
 def test_split_attention_on_the_matrix_cores_against_fp32_attention(nq, nk, causal):
-    """attention_mfma_split_kernel (q, k, v, out as f16x3 split rows; one and two key blocks; the incremental step's query-block-appended-
+    """attention_mfma_kernel over attn_ops_f16x3 (q, k, v, out as f16x3 split rows; one and two key blocks; the incremental step's query-block-appended-
     to-a-cache shape) against the fp32 thread-per-query kernel on the same values."""
     kind = ops.F16X3
     g = torch.Generator().manual_seed(nq * 100 + nk)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Compare the kernels of two `hipcc -save-temps` assembly files function by function.
 
-    tools/asm_kernel_diff.py OLD.s NEW.s
+    tools/asm_kernel_diff.py OLD.s NEW.s [MAP]
+
+MAP, optional, is a file of `old_symbol=new_symbol` lines: a renamed instantiation is compared with its ancestor (and listed under its new name).
 
 Per kernel symbol (a `.globl` function whose body ends at its `.Lfunc_end` label): the number of lines in each file and the number of
 differing lines after local labels (.LBB<n>_<m>, .Lfunc_end<n>, ...) are renumbered per function, so that a kernel added in front of another
@@ -65,6 +67,9 @@ def figures(path, name):
 def main():
     old_p, new_p = sys.argv[1:3]
     old, new = kernels(old_p), kernels(new_p)
+    if len(sys.argv) > 3:                   # MAP: lines `old_symbol=new_symbol`; such a kernel of OLD.s is compared under its new name
+        renamed = dict(s.split("=") for s in open(sys.argv[3]).read().split())
+        old = {renamed.get(k, k): v for k, v in old.items()}
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name in old and name in new:
