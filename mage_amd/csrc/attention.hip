@@ -1,58 +1,12 @@
-// LayerNorm, short-sequence multi-head attention (axial / text / cross), ADAIN, speed-embedding add.
+// Short-sequence multi-head attention (axial / text / cross), forward: the thread-per-(query, head) kernel, the matrix-core kernel over an
+// operand policy and its two few-query forms, behind mage_attention.  The backward kernels are in attention_bwd.hip.
 // All HBM-bound: one pass over the data, 16-byte vector accesses, fp32 arithmetic.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "attn_mfma.h"      // the MFMA attention kernels' operand helpers, shared with the fused Q K / P V epilogues of gemm4.hip
 
 namespace {
-
-// ------------------------------------------------------------------------------------ LayerNorm
-// One wave per row; two-pass (mean, then centred variance) entirely in registers.
-template <typename OT, int VPL>   // VPL = float4 vectors per lane (C <= 256*VPL)
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, OT* __restrict__ y, long rows,
-                                                        int C, float eps) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* xr = x + row * C;
-    f32x4 v[VPL];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        const int c = j * 256 + lane * 4;
-        v[j] = (c < C) ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        const int c = j * 256 + lane * 4;
-        if (c < C) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float dlt = v[j][e] - mean;
-                q += dlt * dlt;
-            }
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
-    OT* yr = y + row * C;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        const int c = j * 256 + lane * 4;
-        if (c < C) {
-            const f32x4 gm = *(const f32x4*)(gamma + c), bt = *(const f32x4*)(beta + c);
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (v[j][e] - mean) * rstd * gm[e] + bt[e];
-            store4(yr + c, o);
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------ attention
 // Workgroup = (sequence, head group).  K and V of the head group are staged once in LDS in their storage type
@@ -154,7 +108,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const mage_attn_desc d, 
                 den += pj;
                 if (drop_thresh) {                   // dropout on the probabilities (train() of the text encoder): the sum stays unmasked
                     const unsigned long long idx = (((unsigned long long)s * d.n_head + (h0 + hl)) * d.nq + i) * d.nk + j;
-                    pj = hash32(d.drop_seed * 0x9e3779b97f4a7c15ULL + idx) >= drop_thresh ? pj * inv_keep : 0.f;
+                    pj = drop_keep(d.drop_seed * 0x9e3779b97f4a7c15ULL, idx, drop_thresh) ? pj * inv_keep : 0.f;
                 }
                 const T* vr = vs + j * rowf + hl * 32;
 #pragma unroll
@@ -593,70 +547,6 @@ __global__ __launch_bounds__(256) void attention_mfma_split_fewq_kernel(const ma
     }
 }
 
-// ------------------------------------------------------------------------------------ ADAIN
-// grid = (B, C/64); block 256 = 64 channels x 4 position phases.
-__global__ __launch_bounds__(256) void adain_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                    const float* __restrict__ beta, float* __restrict__ out, int P,
-                                                    int C, float eps) {
-    __shared__ float red[2][4][64];
-    const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
-    const long base = (long)b * P * C + c;
-    float s = 0.f;
-    for (int p = ph; p < P; p += 4) s += x[base + (long)p * C];
-    red[0][ph][threadIdx.x & 63] = s;
-    __syncthreads();
-    const float mean = (red[0][0][threadIdx.x & 63] + red[0][1][threadIdx.x & 63] + red[0][2][threadIdx.x & 63] +
-                        red[0][3][threadIdx.x & 63]) / (float)P;
-    float q = 0.f;
-    for (int p = ph; p < P; p += 4) {
-        const float dlt = x[base + (long)p * C] - mean;
-        q += dlt * dlt;
-    }
-    red[1][ph][threadIdx.x & 63] = q;
-    __syncthreads();
-    const float var = (red[1][0][threadIdx.x & 63] + red[1][1][threadIdx.x & 63] + red[1][2][threadIdx.x & 63] +
-                       red[1][3][threadIdx.x & 63]) / (float)P;
-    const float rstd = 1.0f / sqrtf(var + eps);
-    for (int p = ph; p < P; p += 4) {
-        const long i = base + (long)p * C;
-        out[i] = gamma[i] * ((x[i] - mean) * rstd) + beta[i];
-    }
-}
-
-__global__ void add_scaled_rowvec_kernel(float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ vec,
-                                         long per_b, int C, long total) {
-    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= total) return;
-    const long b = i / per_b;
-    const int c = (int)(i % C);
-    f32x4 v = *(f32x4*)(x + i);
-    v += s[b] * *(const f32x4*)(vec + c);
-    *(f32x4*)(x + i) = v;
-}
-
-__global__ void row_affine_kernel(float* __restrict__ x, const float* __restrict__ rs, const float* __restrict__ table,
-                                  long rows, int C, int div, int mod) {
-    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= rows * C) return;
-    const long r = i / C;
-    const int c = (int)(i - r * C);
-    f32x4 v = *(f32x4*)(x + i);
-    if (rs) v *= rs[r];
-    if (table) v += *(const f32x4*)(table + ((r / div) % mod) * (long)C + c);
-    *(f32x4*)(x + i) = v;
-}
-
-template <typename OT>
-int ln_launch(const float* x, const float* g, const float* b, void* y, int64_t rows, int C, float eps, hipStream_t s) {
-    const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
-    if (C <= 256) hipLaunchKernelGGL((layernorm_kernel<OT, 1>), grid, blk, 0, s, x, g, b, (OT*)y, (long)rows, C, eps);
-    else if (C <= 512) hipLaunchKernelGGL((layernorm_kernel<OT, 2>), grid, blk, 0, s, x, g, b, (OT*)y, (long)rows, C, eps);
-    else if (C <= 1024) hipLaunchKernelGGL((layernorm_kernel<OT, 4>), grid, blk, 0, s, x, g, b, (OT*)y, (long)rows, C, eps);
-    else hipLaunchKernelGGL((layernorm_kernel<OT, 8>), grid, blk, 0, s, x, g, b, (OT*)y, (long)rows, C, eps);
-    MAGE_CHECK_LAUNCH("mage_layernorm");
-    return MAGE_OK;
-}
-
 // The matrix-core kernels (nq, nk, n_head <= 32), for either operand policy: the few-query kernel of the policy's mode for the incremental
 // step's temporal attention, else the workgroup kernel on its (NKB, MAXH) ladder.  n_head = 32 with nk > 16 stages more than 64 KiB of
 // V: the kernel's dynamic LDS limit is raised for such a launch.
@@ -731,91 +621,6 @@ int attn_launch(const mage_attn_desc* d, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int mage_layernorm(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype,
-                              int64_t rows, int32_t C, float eps, void* stream) {
-    MAGE_CHECK_ARG(x && gamma && beta && y, "mage_layernorm: null pointer");
-    MAGE_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 2048, "mage_layernorm: rows=%ld C=%d unsupported", (long)rows, C);
-    if (y_dtype == MAGE_F32) return ln_launch<float>(x, gamma, beta, y, rows, C, eps, (hipStream_t)stream);
-    if (y_dtype == MAGE_BF16) return ln_launch<unsigned short>(x, gamma, beta, y, rows, C, eps, (hipStream_t)stream);
-    if (y_dtype == MAGE_F16) return ln_launch<f16_t>(x, gamma, beta, y, rows, C, eps, (hipStream_t)stream);
-    if (y_dtype == MAGE_BF16X3 || y_dtype == MAGE_F16X3) {
-        MAGE_CHECK_ARG(C % 64 == 0 && (((uintptr_t)y) & 255) == 0, "mage_layernorm: split output needs C %% 64 == 0 and y 256-byte aligned");
-        if (y_dtype == MAGE_BF16X3) return ln_launch<split_bf16>(x, gamma, beta, y, rows, C, eps, (hipStream_t)stream);
-        return ln_launch<split_f16>(x, gamma, beta, y, rows, C, eps, (hipStream_t)stream);
-    }
-    mage_set_error("mage_layernorm: bad y_dtype %d", y_dtype);
-    return MAGE_EINVAL;
-}
-
-// ------------------------------------------------------------------------------------ fp32 rows -> split-precision rows
-namespace {
-template <typename OT>
-__global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ x, long ldx, OT* __restrict__ y, long ldy, long rows, int C) {
-    const int vpr = C >> 2;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * vpr) return;
-    const long r = i / vpr;
-    const int c = (int)(i - r * vpr) << 2;
-    store4(y + r * ldy + c, *(const f32x4*)(x + r * ldx + c));
-}
-}  // namespace
-
-namespace {
-template <typename OT>
-__global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ x, long ldx, OT* __restrict__ y, long rows, int C, int relu,
-                                                         long group, long group_stride, long off, long inner, long inner_stride,
-                                                         float* __restrict__ x_relu) {
-    const int vpr = C >> 2;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * vpr) return;
-    const long r = i / vpr;
-    const int c = (int)(i - r * vpr) << 2;
-    f32x4 v = *(const f32x4*)(x + r * ldx + c);
-    if (relu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    if (x_relu) *(f32x4*)(x_relu + r * ldx + c) = v;
-    const long ig = r % group;
-    const long orow = (r / group) * group_stride + (ig / inner) * inner_stride + (ig % inner) + off;
-    store4(y + orow * C + c, v);
-}
-}  // namespace
-
-extern "C" int mage_split_rows(const float* x, int64_t ldx, void* y, int64_t rows, int32_t C, int32_t kind, int32_t relu, int64_t group,
-                               int64_t group_stride, int64_t off, int64_t inner, int64_t inner_stride, float* x_relu, void* stream) {
-    MAGE_CHECK_ARG(x && y && rows > 0 && C > 0 && C % 64 == 0 && ldx % 4 == 0 && group > 0, "mage_split_rows: C=%d must be a multiple of 64", C);
-    MAGE_CHECK_ARG(((((uintptr_t)y) & 255) | (((uintptr_t)x) & 15)) == 0, "mage_split_rows: y must be 256-byte aligned, x 16-byte aligned");
-    MAGE_CHECK_ARG(kind == MAGE_BF16X3 || kind == MAGE_F16X3, "mage_split_rows: kind %d is not a split kind", kind);
-    if (inner <= 0) {
-        inner = group;
-        inner_stride = group;
-    }
-    const dim3 grid((unsigned)((rows * (C >> 2) + 255) / 256));
-    if (kind == MAGE_BF16X3)
-        hipLaunchKernelGGL((split_rows_kernel<split_bf16>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (split_bf16*)y, (long)rows, C, relu,
-                           (long)group, (long)group_stride, (long)off, (long)inner, (long)inner_stride, x_relu);
-    else
-        hipLaunchKernelGGL((split_rows_kernel<split_f16>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (split_f16*)y, (long)rows, C, relu,
-                           (long)group, (long)group_stride, (long)off, (long)inner, (long)inner_stride, x_relu);
-    MAGE_CHECK_LAUNCH("mage_split_rows");
-    return MAGE_OK;
-}
-
-extern "C" int mage_split(const float* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int32_t C, int32_t kind, void* stream) {
-    MAGE_CHECK_ARG(x && y && rows > 0 && C > 0 && C % 64 == 0 && ldx % 4 == 0 && ldy % 128 == 0 && ldy >= 2 * (int64_t)C,
-                   "mage_split: C=%d must be a multiple of 64, ldy a multiple of 128 16-bit elements (>= 2C)", C);
-    MAGE_CHECK_ARG(((((uintptr_t)y) & 255) | (((uintptr_t)x) & 15)) == 0, "mage_split: y must be 256-byte aligned, x 16-byte aligned");
-    MAGE_CHECK_ARG(kind == MAGE_BF16X3 || kind == MAGE_F16X3, "mage_split: kind %d is not a split kind", kind);
-    const dim3 grid((unsigned)((rows * (C >> 2) + 255) / 256));
-    if (kind == MAGE_BF16X3)
-        hipLaunchKernelGGL((split_kernel<split_bf16>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (split_bf16*)y, (long)(ldy >> 1), (long)rows, C);
-    else
-        hipLaunchKernelGGL((split_kernel<split_f16>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (split_f16*)y, (long)(ldy >> 1), (long)rows, C);
-    MAGE_CHECK_LAUNCH("mage_split");
-    return MAGE_OK;
-}
-
 namespace {
 int attn_split_launch(const mage_attn_desc* d, hipStream_t s) {
     MAGE_CHECK_ARG(d->nq <= 32 && d->nk <= 32 && d->n_head <= 32 && d->n_head % 2 == 0 && d->out_split == MAGE_F16X3 && d->drop_p == 0.f,
@@ -846,325 +651,4 @@ extern "C" int mage_attention(const mage_attn_desc* d, void* stream) {
     if (d->dtype == MAGE_F16X3) return attn_split_launch(d, (hipStream_t)stream);
     mage_set_error("mage_attention: bad dtype %d", d->dtype);
     return MAGE_EINVAL;
-}
-
-extern "C" int mage_adain(const float* x, const float* gamma, const float* beta, float* out, int32_t B, int32_t P,
-                          int32_t C, float eps, void* stream) {
-    MAGE_CHECK_ARG(x && gamma && beta && out, "mage_adain: null pointer");
-    MAGE_CHECK_ARG(B > 0 && P > 0 && C > 0 && C % 64 == 0, "mage_adain: C=%d must be a multiple of 64", C);
-    hipLaunchKernelGGL(adain_kernel, dim3(B, C / 64), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, out, P, C, eps);
-    MAGE_CHECK_LAUNCH("mage_adain");
-    return MAGE_OK;
-}
-
-extern "C" int mage_add_scaled_rowvec(float* x, const float* s, const float* vec, int32_t B, int32_t P, int32_t C,
-                                      void* stream) {
-    MAGE_CHECK_ARG(x && s && vec, "mage_add_scaled_rowvec: null pointer");
-    MAGE_CHECK_ARG(B > 0 && P > 0 && C > 0 && C % 4 == 0, "mage_add_scaled_rowvec: C=%d must be a multiple of 4", C);
-    const long total = (long)B * P * C;
-    hipLaunchKernelGGL(add_scaled_rowvec_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, x, s, vec, (long)P * C, C, total);
-    MAGE_CHECK_LAUNCH("mage_add_scaled_rowvec");
-    return MAGE_OK;
-}
-
-// Caption bookkeeping of the text encoder in one launch (mage_model.py:233-239: `text != padding_idx`, its row sums): keep[b*S + s] = 1.0 where
-// ids[b][s] != padding_idx else 0.0 (the row scale that zeroes padded rows), kv_len[b] = number of kept tokens (the key-padding length).
-namespace {
-__global__ __launch_bounds__(64) void caption_mask_kernel(const int64_t* __restrict__ ids, int S, long padding_idx, int* __restrict__ kv_len,
-                                                          float* __restrict__ keep) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int cnt = 0;
-    for (int s0 = 0; s0 < S; s0 += 64) {
-        const int s = s0 + lane;
-        const bool k = s < S && ids[(long)b * S + s] != padding_idx;
-        if (s < S && keep) keep[(long)b * S + s] = k ? 1.0f : 0.0f;
-        cnt += __popcll(__ballot(k));
-    }
-    if (lane == 0 && kv_len) kv_len[b] = cnt;
-}
-}  // namespace
-
-extern "C" int mage_caption_mask(const int64_t* ids, int32_t B, int32_t S, int64_t padding_idx, int32_t* kv_len, float* keep, void* stream) {
-    MAGE_CHECK_ARG(ids && B > 0 && S > 0 && (kv_len || keep), "mage_caption_mask: bad arguments");
-    hipLaunchKernelGGL(caption_mask_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, ids, S, (long)padding_idx, kv_len, keep);
-    MAGE_CHECK_LAUNCH("mage_caption_mask");
-    return MAGE_OK;
-}
-
-// Strided block copy on the stream (hipMemcpy2DAsync, device to device): `height` rows of `width_bytes`, row pitches in bytes.  Output
-// assembly without a compute kernel: the passed-through first frame and the decoded frames into the [B, L, C, H, W] result (mage_model.py:691).
-extern "C" int mage_copy2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch, int64_t width_bytes, int64_t height, void* stream) {
-    MAGE_CHECK_ARG(dst && src && width_bytes > 0 && height > 0 && dst_pitch >= width_bytes && src_pitch >= width_bytes, "mage_copy2d: bad arguments");
-    const hipError_t e = hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)width_bytes, (size_t)height, hipMemcpyDeviceToDevice,
-                                          (hipStream_t)stream);
-    if (e != hipSuccess) {
-        mage_set_error("mage_copy2d: %s", hipGetErrorString(e));
-        return MAGE_EHIP;
-    }
-    return MAGE_OK;
-}
-
-extern "C" int mage_row_affine(float* x, const float* rs, const float* table, int64_t rows, int32_t C, int32_t div, int32_t mod,
-                               void* stream) {
-    MAGE_CHECK_ARG(x && rows > 0 && C > 0 && C % 4 == 0, "mage_row_affine: bad arguments");
-    MAGE_CHECK_ARG(!table || (div >= 1 && mod >= 1), "mage_row_affine: bad div/mod");
-    const long total = (long)rows * C;
-    hipLaunchKernelGGL(row_affine_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, rs,
-                       table, (long)rows, C, div, mod);
-    MAGE_CHECK_LAUNCH("mage_row_affine");
-    return MAGE_OK;
-}
-
-// ------------------------------------------------------------------------------------ GroupNorm + SiLU (MAGE+ head)
-namespace {
-
-// stats[b][g] = {mean, rstd} over rows_per_sample rows x (C/groups) channels; one workgroup per (b, g), two passes,
-// fixed-order reductions (deterministic).
-__global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, long sample_stride_rows, long row_off,
-                                                       int rows_per_sample, int C, int groups, float eps,
-                                                       float* __restrict__ stats) {
-    __shared__ double red[4];
-    const int b = blockIdx.x, g = blockIdx.y, cpg = C / groups;
-    const float* base = x + ((long)b * sample_stride_rows + row_off) * C + g * cpg;
-    const long n = (long)rows_per_sample * cpg;
-    auto block_sum = [&](double v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        return red[0] + red[1] + red[2] + red[3];
-    };
-    double s = 0.0;
-    for (int r = threadIdx.x; r < rows_per_sample; r += 256)
-        for (int c = 0; c < cpg; ++c) s += (double)base[(long)r * C + c];
-    const double mean = block_sum(s) / (double)n;
-    double q = 0.0;
-    for (int r = threadIdx.x; r < rows_per_sample; r += 256)
-        for (int c = 0; c < cpg; ++c) {
-            const double dlt = (double)base[(long)r * C + c] - mean;
-            q += dlt * dlt;
-        }
-    const double var = block_sum(q) / (double)n;
-    if (threadIdx.x == 0) {
-        stats[((long)b * groups + g) * 2] = (float)mean;
-        stats[((long)b * groups + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-}
-
-// act: 0 none, 1 ReLU, 2 SiLU.  residual (optional, fp32, packed like the logical output) is added after the affine, before act.
-// Output row of (sample b, row r): b*y_sample_stride_rows + y_row_off + r.
-template <typename OT>
-__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, long sample_stride_rows, long row_off,
-                                                       int rows_per_sample, int C, int groups, const float* __restrict__ stats,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       const float* __restrict__ residual, int act, OT* __restrict__ y,
-                                                       long y_sample_stride_rows, long y_row_off, long total) {
-    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= total) return;
-    const long orow = i / C;
-    const int c = (int)(i - orow * C);
-    const long b = orow / rows_per_sample, r = orow - b * rows_per_sample;
-    const int cpg = C / groups;
-    const f32x4 v = *(const f32x4*)(x + ((b * sample_stride_rows + row_off + r) * C + c));
-    const f32x4 gm = *(const f32x4*)(gamma + c), bt = *(const f32x4*)(beta + c);
-    f32x4 res = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (residual) res = *(const f32x4*)(residual + i);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int g = (c + e) / cpg;                                  // a vector may straddle groups when C/groups < 4
-        const float mean = stats[(b * groups + g) * 2], rstd = stats[(b * groups + g) * 2 + 1];
-        const float t = (v[e] - mean) * rstd * gm[e] + bt[e] + res[e];
-        o[e] = act == 2 ? t / (1.0f + expf(-t)) : act == 1 ? fmaxf(t, 0.f) : t;
-    }
-    store4(y + ((b * y_sample_stride_rows + y_row_off + r) * C + c), o);
-}
-
-int gn_launch(const char* who, const float* x, int64_t sample_stride_rows, int64_t row_off, int32_t n_samples, int32_t rows_per_sample,
-              int32_t C, int32_t groups, const float* gamma, const float* beta, float eps, float* stats, const float* residual,
-              int32_t act, void* y, int32_t y_dtype, int64_t y_sample_stride_rows, int64_t y_row_off, hipStream_t s) {
-    if (y_dtype != MAGE_F32 && y_dtype != MAGE_BF16 && y_dtype != MAGE_F16) {      // refuse before the statistics kernel writes stats
-        mage_set_error("%s: bad y_dtype %d", who, y_dtype);
-        return MAGE_EINVAL;
-    }
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(n_samples, groups), dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
-                       rows_per_sample, C, groups, eps, stats);
-    const long total = (long)n_samples * rows_per_sample * C;
-    const dim3 grid((unsigned)((total / 4 + 255) / 256));
-    if (y_dtype == MAGE_F32)
-        hipLaunchKernelGGL((gn_apply_kernel<float>), grid, dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off, rows_per_sample,
-                           C, groups, stats, gamma, beta, residual, act, (float*)y, (long)y_sample_stride_rows, (long)y_row_off, total);
-    else if (y_dtype == MAGE_BF16)
-        hipLaunchKernelGGL((gn_apply_kernel<unsigned short>), grid, dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
-                           rows_per_sample, C, groups, stats, gamma, beta, residual, act, (unsigned short*)y,
-                           (long)y_sample_stride_rows, (long)y_row_off, total);
-    else                                               // the f16 mode on the latent (MAGE+) path: the GroupNorm + SiLU head's rows (round 6)
-        hipLaunchKernelGGL((gn_apply_kernel<f16_t>), grid, dim3(256), 0, s, x, (long)sample_stride_rows, (long)row_off,
-                           rows_per_sample, C, groups, stats, gamma, beta, residual, act, (f16_t*)y,
-                           (long)y_sample_stride_rows, (long)y_row_off, total);
-    MAGE_CHECK_LAUNCH(who);
-    return MAGE_OK;
-}
-
-}  // namespace
-
-extern "C" int mage_groupnorm_silu(const float* x, int64_t sample_stride_rows, int64_t row_off, int32_t n_samples,
-                                   int32_t rows_per_sample, int32_t C, int32_t groups, const float* gamma, const float* beta,
-                                   float eps, float* stats, void* y, int32_t y_dtype, void* stream) {
-    MAGE_CHECK_ARG(x && gamma && beta && stats && y, "mage_groupnorm_silu: null pointer");
-    MAGE_CHECK_ARG(n_samples > 0 && rows_per_sample > 0 && groups > 0 && C % groups == 0 && C % 4 == 0,
-                   "mage_groupnorm_silu: C=%d groups=%d unsupported", C, groups);
-    return gn_launch("mage_groupnorm_silu", x, sample_stride_rows, row_off, n_samples, rows_per_sample, C, groups, gamma, beta, eps,
-                     stats, nullptr, 2, y, y_dtype, rows_per_sample, 0, (hipStream_t)stream);
-}
-
-extern "C" int mage_groupnorm_act(const float* x, int64_t sample_stride_rows, int64_t row_off, int32_t n_samples,
-                                  int32_t rows_per_sample, int32_t C, int32_t groups, const float* gamma, const float* beta,
-                                  float eps, float* stats, const float* residual, int32_t act, void* y, int32_t y_dtype,
-                                  int64_t y_sample_stride_rows, int64_t y_row_off, void* stream) {
-    MAGE_CHECK_ARG(x && gamma && beta && stats && y, "mage_groupnorm_act: null pointer");
-    MAGE_CHECK_ARG(n_samples > 0 && rows_per_sample > 0 && groups > 0 && C % groups == 0 && C % 4 == 0,
-                   "mage_groupnorm_act: C=%d groups=%d unsupported", C, groups);
-    MAGE_CHECK_ARG(act >= 0 && act <= 2, "mage_groupnorm_act: act=%d (0 none, 1 relu, 2 silu)", act);
-    return gn_launch("mage_groupnorm_act", x, sample_stride_rows, row_off, n_samples, rows_per_sample, C, groups, gamma, beta, eps,
-                     stats, residual, act, y, y_dtype, y_sample_stride_rows, y_row_off, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------ reparameterisation + KL summand
-namespace {
-__global__ __launch_bounds__(256) void reparam_kl_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
-                                                         const float* __restrict__ eps, float* __restrict__ out,
-                                                         float* __restrict__ kl_sum, long n) {
-    __shared__ double red[4];
-    const long base = (long)blockIdx.x * n;
-    double acc = 0.0;
-    for (long i = threadIdx.x; i < n; i += 256) {
-        const float m = mu[base + i], lv = logvar[base + i];
-        out[base + i] = eps[base + i] * expf(0.5f * lv) + m;
-        acc += (double)(1.0f + lv - m * m - expf(lv));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) kl_sum[blockIdx.x] = (float)(red[0] + red[1] + red[2] + red[3]);
-}
-}  // namespace
-
-extern "C" int mage_reparam_kl(const float* mu, const float* logvar, const float* eps, float* out, float* kl_sum, int32_t B,
-                               int64_t n, void* stream) {
-    MAGE_CHECK_ARG(mu && logvar && eps && out && kl_sum && B > 0 && n > 0, "mage_reparam_kl: bad arguments");
-    hipLaunchKernelGGL(reparam_kl_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, mu, logvar, eps, out, kl_sum, (long)n);
-    MAGE_CHECK_LAUNCH("mage_reparam_kl");
-    return MAGE_OK;
-}
-
-// ------------------------------------------------------------------------------------ mean squared error (MAGE+ latent loss)
-namespace {
-__global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ a, long lda, const float* __restrict__ b, long ldb,
-                                                          long rows, int cols, double* __restrict__ partial) {
-    __shared__ double red[4];
-    double acc = 0.0;
-    const long total = rows * cols;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / cols;
-        const int c = (int)(i - r * cols);
-        const float dlt = a[r * lda + c] - b[r * ldb + c];
-        acc += (double)(dlt * dlt);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ void mse_final_kernel(const double* __restrict__ partial, int n, double inv_count, float* __restrict__ out) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += partial[i];          // fixed order: deterministic
-    out[0] = (float)(s * inv_count);
-}
-}  // namespace
-
-extern "C" int mage_mse(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int32_t cols, double* workspace,
-                        float* out, void* stream) {
-    MAGE_CHECK_ARG(a && b && workspace && out && rows > 0 && cols > 0, "mage_mse: bad arguments");
-    MAGE_CHECK_ARG(lda >= cols && ldb >= cols, "mage_mse: lda=%ld ldb=%ld must be at least cols=%d", (long)lda, (long)ldb, cols);
-    const int nblk = (int)((rows * cols + 255) / 256 < 256 ? (rows * cols + 255) / 256 : 256);
-    hipLaunchKernelGGL(mse_partial_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, (long)lda, b, (long)ldb, (long)rows, cols,
-                       workspace);
-    hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, workspace, nblk, 1.0 / ((double)rows * cols), out);
-    MAGE_CHECK_LAUNCH("mage_mse");
-    return MAGE_OK;
-}
-
-// ------------------------------------------------------------------------------------ LayerNorm statistics from GEMM partial sums
-namespace {
-__global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ part, long rows, int n_slices, float inv_c, float eps,
-                                                       float* __restrict__ stats) {
-    const long r = (long)blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    float mean, rstd;
-    mage_ln_stats_row((const float2*)part + r, rows, n_slices, inv_c, eps, mean, rstd);          // slice-major: each slice's loads are coalesced
-    *(float2*)(stats + 2 * r) = float2{mean, rstd};
-}
-}  // namespace
-
-// (mean, rstd) of bf16 rows, one wave per row: the first LayerNorm of a decoder pass when the residual stream starts in bf16 (the frame
-// fill and context_linear write bf16 rows; the Linear that follows takes (rows, stats) like every later one).  Sums in fp32 in a fixed
-// order (lane: its 8-column groups left to right; then the xor tree), the closing formula is mage_ln_stats'.
-namespace {
-template <typename HT>                                  // unsigned short = bf16 rows, f16_t = f16 rows
-__global__ __launch_bounds__(256) void row_stats_kernel(const unsigned short* __restrict__ x, long rows, int C, long ldx, float inv_c, float eps,
-                                                        float* __restrict__ stats) {
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const unsigned short* p = x + r * ldx;
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = lane * 8; c < C; c += 512) {
-        const uint4 v = *(const uint4*)(p + c);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float2 ab = unpack16x2<HT>(w[j]);
-            const float a = ab.x, b = ab.y;
-            s1 = __fadd_rn(s1, __fadd_rn(a, b));
-            s2 = __fadd_rn(s2, __fmaf_rn(a, a, __fmul_rn(b, b)));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 = __fadd_rn(s1, __shfl_xor(s1, o));
-        s2 = __fadd_rn(s2, __shfl_xor(s2, o));
-    }
-    if (lane == 0) {
-        const float mean = __fmul_rn(s1, inv_c);
-        const float var = fmaxf(__fmaf_rn(-mean, mean, __fmul_rn(s2, inv_c)), 0.f);
-        *(float2*)(stats + 2 * r) = float2{mean, __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, eps)))};
-    }
-}
-}  // namespace
-
-extern "C" int mage_row_stats(const void* x, int32_t dtype, int64_t rows, int32_t C, int64_t ldx, float eps, float* stats, void* stream) {
-    MAGE_CHECK_ARG(x && stats && rows > 0 && C > 0 && C % 8 == 0 && ldx >= C && ldx % 8 == 0 && (((uintptr_t)x) & 15) == 0 &&
-                       (dtype == MAGE_BF16 || dtype == MAGE_F16),
-                   "mage_row_stats: bf16 or f16 rows, C and ldx multiples of 8, x 16-byte aligned");
-    if (dtype == MAGE_F16)
-        hipLaunchKernelGGL(row_stats_kernel<f16_t>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
-                           (long)rows, C, (long)ldx, 1.0f / (float)C, eps, stats);
-    else
-        hipLaunchKernelGGL(row_stats_kernel<unsigned short>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                           (const unsigned short*)x, (long)rows, C, (long)ldx, 1.0f / (float)C, eps, stats);
-    MAGE_CHECK_LAUNCH("mage_row_stats");
-    return MAGE_OK;
-}
-
-extern "C" int mage_ln_stats(const float* part, int64_t rows, int32_t n_slices, int32_t C, float eps, float* stats, void* stream) {
-    MAGE_CHECK_ARG(part && stats && rows > 0 && n_slices > 0 && C > 0, "mage_ln_stats: bad arguments");
-    hipLaunchKernelGGL(ln_stats_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, (long)rows, n_slices,
-                       1.0f / (float)C, eps, stats);
-    MAGE_CHECK_LAUNCH("mage_ln_stats");
-    return MAGE_OK;
 }

@@ -1,4 +1,4 @@
-// Operand helpers of the matrix-core attention kernels (norm_attn.hip: attention_mfma_kernel and its few-query form) -- shared with the
+// Operand helpers of the matrix-core attention kernels (attention.hip: attention_mfma_kernel and its few-query form) -- shared with the
 // fused Q K / P V epilogues of gemm4.hip, which must produce the same bits from the same values: ONE definition of the P = hi + lo split
 // and of the two MFMA calls -- and the two operand policies (bf16 / f16 rows, f16x3 split rows) attention_mfma_kernel is written over.
 #pragma once
@@ -37,7 +37,7 @@ template <typename HT> __device__ __forceinline__ f32x4 attn_mfma_qk(const uint4
 // Logical column c of a split row (common.h) sits at 16-bit index (c / 64) * 128 + piece * 64 + c % 64.
 __device__ __forceinline__ int split_col(int c, int piece) { return ((c >> 6) << 7) + (piece << 6) + (c & 63); }
 
-// Operand policies of attention_mfma_kernel and of the f16x3 few-query kernel (norm_attn.hip): everything in which the f16x3 mode
+// Operand policies of attention_mfma_kernel and of the f16x3 few-query kernel (attention.hip): everything in which the f16x3 mode
 // differs from the bf16 / f16 one, and nothing else -- how a Q / K / V fragment is loaded, the Q K product, the exponent's argument, the
 // P = hi + lo split, how V^T is read from staged V rows, the P V product with its accumulation order over the key blocks, and the
 // output rows.

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/mage_hip.h"
 
 typedef __bf16 bf16_t;
@@ -74,6 +75,15 @@ __device__ __forceinline__ void mage_raise(int* word, int code, long value, int 
             mage_set_error("%s: launch failed: %s", name, hipGetErrorString(e_));       \
             return MAGE_EHIP;                                                           \
         }                                                                               \
+    } while (0)
+
+// an entry point's fp32 / bf16 fork: returns what the instantiation for `dtype` returns
+#define DT_DISPATCH(dtype, CALL_F32, CALL_BF16, who)                  \
+    do {                                                              \
+        if ((dtype) == MAGE_F32) return CALL_F32;                     \
+        if ((dtype) == MAGE_BF16) return CALL_BF16;                   \
+        mage_set_error("%s: bad dtype %d", who, (int)(dtype));        \
+        return MAGE_EINVAL;                                           \
     } while (0)
 
 // ---- the one launch path of the kernels mage_gemm dispatches to (gemm_impl.h, gemm4.hip, gemm4h.hip, conv_tile.hip)
@@ -153,6 +163,16 @@ __device__ __forceinline__ void mage_ln_stats_row(const float2* __restrict__ p, 
     mean = __fmul_rn(s1, inv_c);
     const float var = fmaxf(__fmaf_rn(-mean, mean, __fmul_rn(s2, inv_c)), 0.f);
     rstd = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, eps)));
+}
+
+// The LayerNorm kernels that hold a row in registers (norm.hip) are instantiated on VPL = float4 vectors per lane, C <= 256 * VPL: the one
+// ladder of their launchers.  f(std::integral_constant<int, VPL>) launches.
+template <typename F>
+void ln_vpl(int C, F&& f) {
+    if (C <= 256) f(std::integral_constant<int, 1>{});
+    else if (C <= 512) f(std::integral_constant<int, 2>{});
+    else if (C <= 1024) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
 }
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
@@ -286,6 +306,16 @@ __device__ __forceinline__ unsigned hash32(unsigned long long v) {
     v ^= v >> 33;
     return (unsigned)v;
 }
+// element i of the mask is kept; seedmul = seed * 0x9e3779b97f4a7c15, thresh = p * 2^32 (DropMask)
+__device__ __forceinline__ bool drop_keep(unsigned long long seedmul, unsigned long long i, unsigned thresh) { return hash32(seedmul + i) >= thresh; }
+// the three numbers of a mask that the launchers hand to the kernels (host side)
+struct DropMask {
+    unsigned thresh;                 // p * 2^32
+    float inv_keep;                  // 1 / (1 - p)
+    unsigned long long seedmul;      // seed * 0x9e3779b97f4a7c15
+    DropMask(float p, uint64_t seed)
+        : thresh((unsigned)((double)p * 4294967296.0)), inv_keep(1.0f / (1.0f - p)), seedmul((unsigned long long)seed * 0x9e3779b97f4a7c15ULL) {}
+};
 // -log(u) of the 24-bit uniform u = (m + 0.5) 2^-24, never rounded: u itself is exact in fp32 below 1/2, 1 - u above (where log1p takes it)
 __device__ __forceinline__ float sample_neglog_u(unsigned m) {
     return m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f) : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));

@@ -8,8 +8,9 @@ walks the graph by hand and hands autograd one gradient per parameter -- so ``.g
 
 Dense gradients are MFMA GEMMs: dX = dY W runs the forward kernel on a transposed weight copy; dW = dY^T X contracts over all
 tokens into a small [N, K] matrix, so both operands are transposed once (mage_transpose) and multiplied in ONE split-K launch
-(mage_gemm n_split) whose partials are summed in a fixed order.  LayerNorm / attention / activation / cross-entropy backward,
-the embedding scatter and the positional-table reductions are the kernels of csrc/train.hip.
+(mage_gemm n_split) whose partials are summed in a fixed order.  The activation and cross-entropy backward, the embedding scatter and
+the positional-table reductions are the kernels of csrc/train.hip; the LayerNorm backward is in csrc/norm.hip, attention's in
+csrc/attention_bwd.hip.
 
 Built for every config family of the reference: the MNIST configs of BASELINE cfg1-3; with the randomness branch of
 modules/mage_train_prior.py (Conv3d video prior, reparameterisation + KL, ADAIN) config/mage_caterv1.yaml / mage_caterv2.yaml; and

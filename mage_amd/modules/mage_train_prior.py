@@ -10,7 +10,7 @@
 Forward = the inference kernels (MAGE._video_prior with a tape, the implicit-GEMM 3x3 convolutions, mage_adain, mage_reparam_kl);
 backward = the same GEMM kernel on flipped / transposed weights for the input gradients (a Conv3d's temporal taps are three
 accumulating launches into the zero-padded frame buffer its forward read from), transposes + one split-K GEMM per weight gradient,
-and mage_groupnorm_bwd / mage_adain_bwd / mage_reparam_kl_bwd (csrc/train.hip).  In bf16 training the Conv3d video prior (the bulk of
+and mage_groupnorm_bwd / mage_adain_bwd / mage_reparam_kl_bwd (csrc/norm.hip, rows.hip).  In bf16 training the Conv3d video prior (the bulk of
 the branch: 36 temporal-tap convolutions over all frames, forward and twice backward) stores its activations and weights in bf16 for
 the matrix cores (convolution outputs, GroupNorm statistics and every gradient stream stay fp32); the per-clip 3x3 heads and ADAIN are
 fp32 in both modes, like the once-per-clip prologue of the inference path.

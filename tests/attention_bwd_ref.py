@@ -1,4 +1,4 @@
-"""fp64 restatement of mage_attention_bwd (include/mage_hip.h; kernels in mage_amd/csrc/train.hip) on the logical rows of a
+"""fp64 restatement of mage_attention_bwd (include/mage_hip.h; kernels in mage_amd/csrc/attention_bwd.hip) on the logical rows of a
 mage_attn_desc, as closed formulas, with the per-element error bounds of the three kernel families.
 
 For one (sequence s, head h), queries i, keys j, 32 columns c, mask as in the forward (causal aligned to the last key, then

@@ -1,6 +1,6 @@
 """numpy / fp64 references of the kernels that make or score the discrete decisions, with their case tables and checkers:
     mage_vq_prepare, mage_vq_nearest (mage_amd/csrc/vq.hip), mage_argmax, mage_cross_entropy (token_heads.hip), mage_caption_mask,
-    mage_row_affine (norm_attn.hip).
+    mage_row_affine (rows.hip).
 Every reference takes the exact fp32 values the kernel reads and returns, beside the expected values (and a bound where the result is not
 exact), the flat index of every element the kernel must write: the footprint.  The checkers take the kernel's whole output buffers, which
 start filled with a sentinel (F32_SENT: the NaN of tests/helpers.py SENTINEL; I64_SENT, I32_SENT) and carry TAIL elements of slack: outside

@@ -1,5 +1,5 @@
 """fp64 restatements of the norm and loss entry points of the randomness branch, the MAGE+ head and the stage-1 VQ-VAE (include/mage_hip.h;
-kernels in mage_amd/csrc/norm_attn.hip and train.hip) as closed formulas on their logical rows, with a per-element error bound for every output:
+kernels in mage_amd/csrc/norm.hip and rows.hip) as closed formulas on their logical rows, with a per-element error bound for every output:
     mage_groupnorm_act / mage_groupnorm_silu, mage_groupnorm_bwd, mage_adain, mage_adain_bwd, mage_add_scaled_rowvec, mage_bn_colreduce,
     mage_bn_apply, mage_bn_bwd_apply, mage_reparam_kl, mage_reparam_kl_bwd, mage_mse, mage_mse_bwd.
 The references take the exact fp32 values the kernels read.  (mean, rstd) are INPUTS of mage_groupnorm_bwd, of mage_bn_colreduce modes 1 and 2

@@ -1,4 +1,4 @@
-"""GPU: every kernel behind mage_attention (csrc/norm_attn.hip) against an fp64 restatement of the descriptor contract
+"""GPU: every kernel behind mage_attention (csrc/attention.hip) against an fp64 restatement of the descriptor contract
 (include/mage_hip.h, mage_attn_desc), at the edges of its dispatch (attn_launch, attn_split_launch and attn_mfma_launch beneath both).
 
 Which kernel a descriptor reaches, and the cases of CASES / test_fewq_bit_identical_to_the_workgroup_kernel that reach it:
@@ -257,7 +257,7 @@ FEWQ_IDENTITY = [
 
 @pytest.mark.parametrize("c", FEWQ_IDENTITY)
 def test_fewq_bit_identical_to_the_workgroup_kernel(c):
-    """norm_attn.hip's claim under attention_mfma_fewq_kernel: per (sequence, head) the same operations on the same values as
+    """attention.hip's claim under attention_mfma_fewq_kernel: per (sequence, head) the same operations on the same values as
     attention_mfma_kernel (and the split pair likewise), so the incremental loop's rows equal the full pass's bit for bit.  The
     thread-per-query kernel behind attn_no_mfma has its own arithmetic: it must meet the same fp64 bound."""
     out, inputs, g, lens, scale = launch(c)

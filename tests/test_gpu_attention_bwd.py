@@ -1,4 +1,4 @@
-"""GPU: every kernel behind mage_attention_bwd (csrc/train.hip) against the fp64 restatement of tests/attention_bwd_ref.py (formulas
+"""GPU: every kernel behind mage_attention_bwd (csrc/attention_bwd.hip) against the fp64 restatement of tests/attention_bwd_ref.py (formulas
 and the derivation of the per-element bounds are in that module's docstring), at the edges of its dispatch.
 
 Which kernel a descriptor reaches, and the cases that reach it:

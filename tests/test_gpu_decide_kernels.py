@@ -1,5 +1,5 @@
 """GPU: the kernels that make or score the discrete decisions -- the codebook quantiser and its caches (mage_amd/csrc/vq.hip), the row argmax and the
-forward cross entropy (token_heads.hip), the caption mask and the row affine (norm_attn.hip) -- against the numpy / fp64 references of
+forward cross entropy (token_heads.hip), the caption mask and the row affine (rows.hip) -- against the numpy / fp64 references of
 tests/decide_ref.py (formulas, case tables and the derivation of every bound are in that module's docstring), at the edges of their dispatch.
 The C entry points are called through mage_amd._lib: mage_amd.ops allocates the outputs itself and hides ld, the row maps and the null outputs.
 

@@ -1,5 +1,5 @@
 """GPU: the GroupNorm, BatchNorm, ADAIN, KL and MSE kernels of the randomness branch, the MAGE+ head and the stage-1 VQ-VAE
-(mage_amd/csrc/norm_attn.hip, train.hip) against the fp64 restatements of tests/norm_ref.py (formulas and the derivation of every per-element
+(mage_amd/csrc/norm.hip, rows.hip) against the fp64 restatements of tests/norm_ref.py (formulas and the derivation of every per-element
 bound are in that module's docstring), at the edges of their dispatch.  The C entry points are called through mage_amd._lib where mage_amd.ops
 hides a parameter (n_part, stats, red, the partial buffers).
 

@@ -1,4 +1,4 @@
-"""GPU: the norm, loss, scatter and row-sum kernels of the decoder's backward pass (mage_amd/csrc/train.hip, norm_attn.hip) against the fp64
+"""GPU: the norm, loss, scatter and row-sum kernels of the decoder's backward pass (mage_amd/csrc/train.hip, norm.hip) against the fp64
 restatements of tests/train_ref.py (formulas and the derivation of every per-element bound are in that module's docstring), at the edges of
 their dispatch.  The C entry points are called through mage_amd._lib where mage_amd.ops hides a parameter (n_part, n_chunk, scratch).
 

@@ -1,4 +1,4 @@
-"""GPU: the weight-gradient, activation, dropout and Adam kernels of the training path (mage_amd/csrc/train.hip, gemm_tn.hip, gemm4.hip) against
+"""GPU: the weight-gradient, activation, dropout and Adam kernels of the training path (mage_amd/csrc/train.hip, optim.hip, gemm_tn.hip, gemm4.hip) against
 the fp64 restatements of tests/wgrad_ref.py (formulas and the derivation of every per-element bound are in that module's docstring), at the
 edges of their dispatch.  The C entry points are called through mage_amd._lib, which shows every parameter (n_split, tokens_per_split, n_part).
 

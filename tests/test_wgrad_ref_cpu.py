@@ -1,6 +1,6 @@
 """CPU: the fp64 restatements and bounds of tests/wgrad_ref.py.  Each reference is pinned against torch (autograd of F.gelu, x * sigmoid(1.702 x),
 relu and tanh; torch.optim.Adam in float64; dy.double().t() @ x.double(); F.unfold and plain indexing for the gathers).  Float32 emulations of
-the kernels in the summation order their comments in train.hip / gemm_tn.hip state must meet every bound on every case of
+the kernels in the summation order their comments in train.hip / optim.hip / gemm_tn.hip state must meet every bound on every case of
 tests/test_gpu_wgrad_kernels.py, and eleven subtly wrong kernels ("mutants") must each leave a bound, or break a bit-exact check, on the case
 named in their test."""
 import math

@@ -1,5 +1,5 @@
 """fp64 restatements of six entry points of the decoder's backward pass (include/mage_hip.h; kernels in mage_amd/csrc/train.hip and
-norm_attn.hip) as closed formulas on their logical rows, with a per-element error bound for every output:
+norm.hip) as closed formulas on their logical rows, with a per-element error bound for every output:
     mage_layernorm, mage_dropout_add_layernorm, mage_layernorm_bwd, mage_cross_entropy_bwd, mage_embedding_bwd, mage_group_rowsum,
     mage_row_sum.
 The references take the exact values the kernels read (16-bit inputs converted from their stored bits).  Dropout masks are

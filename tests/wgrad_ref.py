@@ -1,5 +1,5 @@
-"""fp64 restatements of nine entry points of the training path (include/mage_hip.h; kernels in mage_amd/csrc/train.hip, gemm_tn.hip,
-gemm4.hip), written from the header's words, with a per-element error bound for every output:
+"""fp64 restatements of nine entry points of the training path (include/mage_hip.h; kernels in mage_amd/csrc/train.hip, optim.hip,
+gemm_tn.hip, gemm4.hip), written from the header's words, with a per-element error bound for every output:
     mage_transpose, mage_transpose_colsum, mage_gemm_tn, mage_colsum, mage_sum_partials, mage_act, mage_act_bwd,
     mage_dropout / mage_dropout_add (mask and exact values: tests/train_ref.py keep_mask, inv_keep, dropout_add_exact), mage_adam.
 The references take the exact values the kernels read: 16-bit inputs from their stored bits, the fp32-rounded lr, beta1, beta2, eps,

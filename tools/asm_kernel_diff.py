@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Compare the kernels of two `hipcc -save-temps` assembly files function by function.
 
-    tools/asm_kernel_diff.py OLD.s NEW.s [MAP]
+    tools/asm_kernel_diff.py OLD NEW [MAP]
 
+OLD and NEW are each one assembly file or a directory: every `*.s` of a directory is read into one symbol table (kernels that moved between
+translation units pair up by name; a symbol defined twice with different bodies is an error).
 MAP, optional, is a file of `old_symbol=new_symbol` lines: a renamed instantiation is compared with its ancestor (and listed under its new name).
 
 Per kernel symbol (a `.globl` function whose body ends at its `.Lfunc_end` label): the number of lines in each file and the number of
@@ -10,11 +12,24 @@ differing lines after local labels (.LBB<n>_<m>, .Lfunc_end<n>, ...) are renumbe
 does not show as a change.  Kernels present in one file only are listed with their register figures (from the .amdhsa_ directives and the
 metadata comment block behind the body).  Exit status 1 when a kernel common to both files differs."""
 import difflib
+import glob
+import os
 import re
 import sys
 
+where = {}                                  # (directory, symbol) -> the file of the directory that defines it
+
 
 def kernels(path):
+    if os.path.isdir(path):                 # every *.s of the directory in one symbol table; `where` remembers each symbol's file for figures()
+        out = {}
+        for f in sorted(glob.glob(os.path.join(path, "*.s"))):
+            for name, body in kernels(f).items():
+                if name in out and normalise(out[name]) != normalise(body):
+                    sys.exit(f"{name}: defined in {where[path, name]} and in {f} with different bodies")
+                out[name] = body
+                where[path, name] = f
+        return out
     out, name, body = {}, None, []
     for line in open(path):
         s = line.rstrip("\n")
@@ -47,7 +62,7 @@ def normalise(body):
 
 
 def figures(path, name):
-    text = open(path).read()
+    text = open(where.get((path, name), path)).read()
     i = text.find(f".amdhsa_kernel {name}")
     blk = text[i:text.find(".end_amdhsa_kernel", i)] if i >= 0 else ""
     got = {}
