@@ -20,10 +20,12 @@
 // registers = 4 consecutive columns), which is what epilogue_lean expects.
 //
 // Schedule of chunk c (two phases of 64 MFMAs, one barrier in the middle of each; rings of two stages for W1 and for W2, 32 KB per stage):
-//     Pa(c): GEMM 1 (c)      || pack of chunk c-1 (8 converts)      second half: LDS-DMA of W2(c),   first fragments of GEMM 2 (c-1)
-//     Pb(c): GEMM 2 (c-1)    || activation of chunk c (in place)     second half: LDS-DMA of W1(c+2), first fragments of GEMM 1 (c+1)
+//     Pa(c): GEMM 1 (c)      || activation of chunk c-1, block t = 1, and its pack   second half: LDS-DMA of W2(c),   first fragments of GEMM 2 (c-1)
+//     Pb(c): GEMM 2 (c-1)    || activation of chunk c, block t = 0 (in place)         second half: LDS-DMA of W1(c+2), first fragments of GEMM 1 (c+1)
 // A stage is requested one whole chunk before the barrier that publishes it (s_waitcnt vmcnt(8): the 8 pieces of the other ring are younger).
-// The epilogue arithmetic is single-instruction asm statements between the MFMA statements (gemm4h's way), two per MFMA slot.
+// The epilogue arithmetic is single-instruction asm statements between the MFMA statements (gemm4h's way), ONE per MFMA slot: what a wave issues
+// for free beside a 16-cycle MFMA is 8 cycles, one transcendental or convert or two plain operations (profiles/r06_mfma_valu_coissue.txt), and
+// the chunk's 120 operations fit the 128 slots of Pb(c) and Pa(c + 1) one by one (m_act_pos below).
 // LDS: 128 KB of rings, 16 KB of c_fc's epilogue constants (colsum, bias: loaded once per workgroup), 4 x 4 KB staging for the closing epilogue
 // (per wave: 2 KB for the transposed output rows, 2 KB for the residual fragments on their way into the accumulator layout) = 160 KB.
 #include "gemm_shared.h"
@@ -51,22 +53,113 @@ constexpr int M_LDS = M_STGOFF + 4 * 4096;              // 160 KB
 
 #ifdef MAGE4M_STAMP
 // tuning build (tools/probes/gemm4m_probe.hip): wave 0 of each workgroup takes five 100 MHz wall-clock stamps per tile -- 0 tile start, 1 chunk loop done
-// (before the last pack), 2 last GEMM 2 done, 3 closing epilogue done, 4 tile end (where the kernel used to request the rest of the next tile's rows
+// (before the last chunk's block 1 and pack), 2 last GEMM 2 done, 3 closing epilogue done, 4 tile end (where the kernel used to request the rest of the next tile's rows
 // after the epilogue; nothing lies between 3 and 4 now) -- into scalar registers and writes them at the tile's end: the stores are older than every
 // LDS-DMA piece of the next tile, so no counted wait of the chunk loop sees them.  [workgroup][tile of the workgroup][5]
-constexpr int M_STAMP_WG = 256, M_STAMP_TILES = 16;
+// Stamps 0 and 1 take the shader clock (s_memtime) beside the wall clock: the clock under the chunk loop.  Inside the chunk loop the chunk pairs
+// (8, 9) and (32, 33) of every tile are stamped with the shader clock: per phase k = 3 ph + {0 phase start, 1 in front of the mid-phase s_waitcnt,
+// 2 behind the s_barrier}, ph = 0 Pa(c), 1 Pb(c), 2 Pa(c + 1), 3 Pb(c + 1); k = 12 is the start of the next chunk's Pa.  The two pairs are copies
+// of the loop body of their own (template parameter ST = 0 | 1; ST = -1: no stamps), so the other chunks run the release code: a scalar branch on
+// c at every stamp point cost a quarter of the loop's time.  A stamp is requested at its point and stays in a scalar register until the next
+// point, where it moves into a lane of ONE vector register (v_writelane: the kernel's scalar registers already spill into such lanes, 30 more
+// would go to scratch), so nothing waits for the clock's answer where it is taken.  The low 32 bits are kept (a segment is a few thousand cycles,
+// the chunk loop some 250 000): lane 13 ST + k, lanes 26 and 27 for stamps 0 and 1.  [workgroup][tile of the workgroup][32]
+constexpr int M_STAMP_WG = 256, M_STAMP_TILES = 16, M_CSTAMP_N = 13, M_CSTAMP_LANES = 32, M_CSTAMP_C0 = 8, M_CSTAMP_C1 = 32;
 __device__ unsigned long long m_stamps[M_STAMP_WG * M_STAMP_TILES * 5];
-#define M_STAMP(k)                                         \
-    do {                                                   \
-        fence();                                           \
-        stamp[k] = __builtin_amdgcn_s_memrealtime();       \
-        fence();                                           \
+__device__ unsigned m_cstamps[M_STAMP_WG * M_STAMP_TILES * M_CSTAMP_LANES];
+#define M_CSTAMP_PUT(lane_) asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(cstamp) : "s"(cpend), "i"(lane_))
+#define M_STAMP(k)                                                        \
+    do {                                                                  \
+        fence();                                                          \
+        stamp[k] = __builtin_amdgcn_s_memrealtime();                      \
+        if constexpr ((k) < 2) {                                          \
+            cpend = (unsigned)__builtin_amdgcn_s_memtime();               \
+            M_CSTAMP_PUT(2 * M_CSTAMP_N + (k));                           \
+        }                                                                 \
+        fence();                                                          \
+    } while (0)
+#define M_CSTAMP(ST_, k)                                                                      \
+    do {                                                                                      \
+        if constexpr (decltype(ST_)::value >= 0) {                                            \
+            fence();                                                                          \
+            if constexpr ((k) > 0) M_CSTAMP_PUT(M_CSTAMP_N * decltype(ST_)::value + (k) - 1); \
+            cpend = (unsigned)__builtin_amdgcn_s_memtime();                                   \
+            if constexpr ((k) == M_CSTAMP_N - 1) M_CSTAMP_PUT(M_CSTAMP_N * decltype(ST_)::value + (k)); \
+            fence();                                                                          \
+        }                                                                                     \
     } while (0)
 #else
 #define M_STAMP(k) \
     do {           \
     } while (0)
+#define M_CSTAMP(ST_, k) \
+    do {                 \
+    } while (0)
 #endif
+
+// ---- The chunk epilogue's schedule.  A chunk has 112 activation ops o = 28 G + K -- group G = accumulator block (block t = G >> 1 of the chunk,
+// 16-row tile mt = G & 1), K = 4 a + j: row a of the 7 operations (0, 1 the LayerNorm fold, 2 the scaling, 3 exp, 4 (+ 1), 5 rcp, 6 the product) on
+// value j of the block's 4 -- and 8 packs I (tile I >> 2, word I & 3).  They are issued one per MFMA slot at POSITIONS 0 .. 127: 0 .. 63 the slots of
+// Pb(c), 64 .. 127 the slots of Pa(c + 1).  A row takes one UNIT of 4 slots; odd units are the slots k = 4 .. 7 of an 8-MFMA batch, which hold no
+// fragment read, and every exp / rcp row and every pack sits on an odd unit (the plain rows share their slots with the ds_read_b128s):
+//     Pb(c)    :  -  a0  a1  b0  a2 [a3] a4 [a5] a6  b1  b2 [b3] b4 [b5] b6  -          a = group 0, b = group 1 (block 0; tiles 0, 1)
+//     Pa(c + 1):  c0 c1  c2 [c3] c4 [c5] c6 [P0] d0  d1  d2 [d3] d4 [d5] d6 [P1]        c = group 2, d = group 3 (block 1); P = the 4 packs of a tile
+// Tile 0's words are packed as soon as group 2 is through; group 0 starts at slot 4 of Pb(c), 8 MFMAs behind the MFMA that wrote it, as it always has.
+constexpr int M_NACT = 112, M_NPACK = 8, M_NPOS = 128;
+constexpr int M_ROW_UNIT[4][7] = {{1, 2, 4, 5, 6, 7, 8}, {3, 9, 10, 11, 12, 13, 14}, {16, 17, 18, 19, 20, 21, 22}, {24, 25, 26, 27, 28, 29, 30}};
+constexpr int M_PACK_UNIT[2] = {23, 31};
+constexpr int M_CRD_SLOT[2] = {45, 47};          // the slots of Pb(c) that read block 1's (column sums, bias) and of Pa(c + 1) that read block 0's of chunk c + 1
+constexpr int m_act_pos(int o) { return 4 * M_ROW_UNIT[o / 28][(o % 28) >> 2] + (o & 3); }
+constexpr int m_pack_pos(int I) { return 4 * M_PACK_UNIT[I >> 2] + (I & 3); }
+constexpr int m_act_at(int p) {                  // the activation op at position p, or -1
+    for (int o = 0; o < M_NACT; ++o)
+        if (m_act_pos(o) == p) return o;
+    return -1;
+}
+constexpr int m_pack_at(int p) {
+    for (int I = 0; I < M_NPACK; ++I)
+        if (m_pack_pos(I) == p) return I;
+    return -1;
+}
+constexpr bool m_heavy(int o) { return ((o % 28) >> 2) == 3 || ((o % 28) >> 2) == 5; }          // v_exp_f32, v_rcp_f32: 8 issue cycles; plain VALU 4; v_cvt_pk 8
+constexpr int m_slot_cycles(int p) { return (m_act_at(p) >= 0 ? (m_heavy(m_act_at(p)) ? 8 : 4) : 0) + (m_pack_at(p) >= 0 ? 8 : 0); }
+constexpr bool m_sched_once() {                  // every op at a position of its own, every position at most 8 issue cycles of vector work
+    int n = 0;
+    for (int p = 0; p < M_NPOS; ++p) {
+        if (m_slot_cycles(p) > 8) return false;
+        n += (m_act_at(p) >= 0) + (m_pack_at(p) >= 0);
+    }
+    for (int o = 0; o < M_NACT; ++o)
+        if (m_act_pos(o) < 0 || m_act_pos(o) >= M_NPOS || m_act_at(m_act_pos(o)) != o) return false;
+    for (int I = 0; I < M_NPACK; ++I)
+        if (m_pack_pos(I) < 0 || m_pack_pos(I) >= M_NPOS || m_pack_at(m_pack_pos(I)) != I) return false;
+    return n == M_NACT + M_NPACK;
+}
+constexpr bool m_sched_order() {                 // producer -> consumer
+    for (int G = 0; G < 4; ++G)
+        for (int K = 0; K < 28; ++K) {
+            const int p = m_act_pos(28 * G + K);
+            // GEMM 1's last MFMA into group G is slot 60 + G of Pa(c) = position G - 4: its result is read no sooner than 8 MFMAs later
+            if (p - (G - 4) < 8) return false;
+            // a value's operations in order; a transcendental's result is read no sooner than 4 instructions later
+            if (K >= 4 && p - m_act_pos(28 * G + K - 4) < (m_heavy(28 * G + K - 4) ? 4 : 1)) return false;
+            // eu[] is one set of 4 registers (written by row 2, last read by row 6): the groups take it one after the other
+            if (G > 0 && K >= 8 && p < m_act_pos(28 * (G - 1) + 27)) return false;
+            // sv / cv hold block 0's constants from Pa(c)'s M_CRD_SLOT to Pb(c)'s, where block 1's replace them until Pa(c + 1)'s M_CRD_SLOT
+            if (K < 8 && G < 2 && p >= M_CRD_SLOT[0]) return false;
+            if (K < 8 && G >= 2 && (p <= M_CRD_SLOT[1] || p >= 64 + M_CRD_SLOT[0])) return false;
+        }
+    for (int I = 0; I < M_NPACK; ++I) {
+        const int mt = I >> 2, w = I & 3, G = 2 * (w >> 1) + mt, p = m_pack_pos(I);
+        // a pack reads two finished values of group G; hpk[mt] is GEMM 2's operand from slot mt of Pb(c + 1) = position 128 + mt (an MFMA in
+        // between covers the VALU -> MFMA operand wait states) and was Pb(c)'s operand until position 63
+        if (p <= m_act_pos(28 * G + 24 + 2 * (w & 1)) || p <= m_act_pos(28 * G + 25 + 2 * (w & 1))) return false;
+        if (p < 64 || M_NPOS + mt - p < 2) return false;
+    }
+    return true;
+}
+static_assert(m_sched_once(), "gemm4m: every activation op and every pack exactly once per chunk, at most 8 issue cycles of vector work per MFMA slot");
+static_assert(m_sched_order(), "gemm4m: a producer -> consumer distance of the chunk epilogue's schedule is broken");
 
 // one LDS-DMA piece: 64 lanes x 16 B from (scalar base + per-lane offset) to LDS lds .. lds + 1023
 __device__ __forceinline__ void m_dma(unsigned lds, unsigned voff, const char* base) {
@@ -158,6 +251,12 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
     // gemm4h's operations in gemm4h's order.  Group G (block t = G >> 1, tile mt = G & 1: one accumulator block, 4 values j) has 28 ops K = 4 a + j:
     // a = 0, 1 the LayerNorm fold, 2 the scaling, 3 exp, 4 (+ 1), 5 rcp, 6 the product -- a transcendental's result is read 4 instructions later.
     float eu[4];
+#ifdef MAGE4M_STAMP
+    unsigned long long stamp[5];
+    int cstamp = 0;
+    unsigned cpend = 0;
+    int stamp_tile = 0;
+#endif
     auto act_op = [&](auto PAR_, auto G_, auto K_) __attribute__((always_inline)) {
         constexpr int PAR = decltype(PAR_)::value, G = decltype(G_)::value, K = decltype(K_)::value;
         constexpr int t = G >> 1, mt = G & 1, a = K >> 2, j = K & 3;
@@ -185,47 +284,64 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
         else sv = *(const f32x4*)p;
     };
 
-    // Pa(c): GEMM 1 of chunk c (parity PAR) || pack of chunk c - 1.  PACK = false: the tile's first chunk.
-    auto phase_a = [&](auto PAR_, auto PACK_, int c) __attribute__((always_inline)) {
+    auto sched_ops = [&](auto PAR_, auto P_) __attribute__((always_inline)) {          // the op of position P, on the chunk of parity PAR
+        constexpr int o = m_act_at(decltype(P_)::value), I = m_pack_at(decltype(P_)::value);
+        if constexpr (o >= 0 || I >= 0) fence();
+        if constexpr (o >= 0) act_op(PAR_, std::integral_constant<int, o / 28>{}, std::integral_constant<int, o % 28>{});
+        if constexpr (I >= 0) pack_op(PAR_, std::integral_constant<int, I>{});
+    };
+    // Pa(c): GEMM 1 of chunk c (parity PAR) || positions 64 .. 127 of chunk c - 1: its block 1 and its pack.  ACT = false: the tile's first chunk.
+    auto phase_a = [&](auto PAR_, auto ACT_, auto ST_, int c) __attribute__((always_inline)) {
         constexpr int PAR = decltype(PAR_)::value;
-        constexpr bool PACK = decltype(PACK_)::value;
+        constexpr bool ACT = decltype(ACT_)::value;
         g4_for<64>([&](auto i_) {
             constexpr int i = decltype(i_)::value, b = i >> 3, k = i & 7, j = k >> 1, mt = k & 1, ks = 2 * b + (j >> 1), t = j & 1;
+            if constexpr (i == 0) M_CSTAMP(ST_, 6 * PAR);
             m_mfma1<ks == 0, k == 0, HF>(hacc[PAR][mt][t], wf[b & 1][j], xf[mt][ks]);
             fence();
+            if constexpr (ACT && (i == M_CRD_SLOT[0] || i == M_CRD_SLOT[1])) consts_rd(c, 0, i == M_CRD_SLOT[1]);      // this chunk's block 0, for Pb(c)
             if constexpr (k < 4 && b < 7) rd_w1((b + 1) & 1, PAR, b + 1, k);
-            if constexpr (k < 4 && b == 7 && PACK) rd_w2(0, PAR ^ 1, 0, k);          // GEMM 2 (c - 1): W2 stage of parity PAR ^ 1
-            if constexpr (PACK && i >= 8 && i < 16) pack_op(std::integral_constant<int, PAR ^ 1>{}, std::integral_constant<int, i - 8>{});
+            if constexpr (k < 4 && b == 7 && ACT) rd_w2(0, PAR ^ 1, 0, k);           // GEMM 2 (c - 1): W2 stage of parity PAR ^ 1
+            if constexpr (ACT) sched_ops(std::integral_constant<int, PAR ^ 1>{}, std::integral_constant<int, 64 + i>{});
             if constexpr (b >= 4 && (k == 4 || k == 6)) dma_w2(PAR, c, (b - 4) * 2 + (k == 6));
             fence();
-            if constexpr (i == 31) wait_barrier();
+            if constexpr (i == 31) {
+                M_CSTAMP(ST_, 6 * PAR + 1);
+                wait_barrier();
+                M_CSTAMP(ST_, 6 * PAR + 2);
+            }
         });
     };
-    // Pb(c): GEMM 2 of chunk c - 1 (ZERO: the tile's first k-step) || activation of chunk c (parity PAR)
-    auto phase_b = [&](auto PAR_, auto ZERO_, int c) __attribute__((always_inline)) {
+    // Pb(c): GEMM 2 of chunk c - 1 (ZERO: the tile's first k-step) || positions 0 .. 63 of chunk c (parity PAR): its block 0
+    auto phase_b = [&](auto PAR_, auto ZERO_, auto ST_, int c) __attribute__((always_inline)) {
         constexpr int PAR = decltype(PAR_)::value;
         constexpr bool ZERO = decltype(ZERO_)::value;
         g4_for<64>([&](auto i_) {
             constexpr int i = decltype(i_)::value, b = i >> 3, k = i & 7, j = k >> 1, mt = k & 1, nb = 4 * b + j;
+            if constexpr (i == 0) M_CSTAMP(ST_, 6 * PAR + 3);
             g4_mfma<mt * 32 + nb, ZERO, k == 0, HF>(wf[b & 1][j], hpk[mt]);
             fence();
-            if constexpr (i == 23 || i == 24) consts_rd(c, 1, i - 23);                         // block 1's constants, behind block 0's last use (slot 21)
-            if constexpr (i == 56 || i == 57) consts_rd((c + 1) & (M_NCH - 1), 0, i - 56);     // the next chunk's, behind block 1's last use (slot 49)
+            if constexpr (i == M_CRD_SLOT[0] || i == M_CRD_SLOT[1]) consts_rd(c, 1, i == M_CRD_SLOT[1]);               // block 1's constants, for Pa(c + 1)
             if constexpr (k < 4 && b < 7) rd_w2((b + 1) & 1, PAR ^ 1, b + 1, k);
             if constexpr (k < 4 && b == 7) rd_w1(0, PAR ^ 1, 0, k);                  // GEMM 1 (c + 1)
-            if constexpr (i >= 4 && i < 60) {                                         // two ops per slot
-                constexpr int o = 2 * (i - 4);
-                fence();
-                act_op(PAR_, std::integral_constant<int, o / 28>{}, std::integral_constant<int, o % 28>{});
-                act_op(PAR_, std::integral_constant<int, (o + 1) / 28>{}, std::integral_constant<int, (o + 1) % 28>{});
-            }
+            sched_ops(PAR_, i_);
             if constexpr (b >= 4 && (k == 4 || k == 6)) dma_w1(PAR, (c + 2) & (M_NCH - 1), (b - 4) * 2 + (k == 6));
             fence();
-            if constexpr (i == 31) wait_barrier();
+            if constexpr (i == 31) {
+                M_CSTAMP(ST_, 6 * PAR + 4);
+                wait_barrier();
+                M_CSTAMP(ST_, 6 * PAR + 5);
+            }
+        });
+    };
+    auto act_block = [&](auto PAR_, auto T_) __attribute__((always_inline)) {          // block T's two groups with no MFMA beside them (the tile's first and last chunk)
+        g4_for<56>([&](auto k_) {
+            act_op(PAR_, std::integral_constant<int, 2 * decltype(T_)::value + decltype(k_)::value / 28>{}, std::integral_constant<int, decltype(k_)::value % 28>{});
         });
     };
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
+    typedef std::integral_constant<int, -1> NST;              // a chunk without stamps
 
     // ---- prologue: c_fc's epilogue constants, W1(0), W1(1); the first tile's rows
     for (int i = tid; i < M_HID / 4; i += 256) {
@@ -241,10 +357,6 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
     ring_barrier();
     fence();
 
-#ifdef MAGE4M_STAMP
-    unsigned long long stamp[5];
-    int stamp_tile = 0;
-#endif
     for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
         MAGE_DASSERT(tile >= 0 && tile < g.ntiles);
         M_STAMP(0);
@@ -255,23 +367,18 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
             mean[mt] = st.x;
             rstd[mt] = st.y;
         }
-        // ---- chunk 0: GEMM 1 alone, then its activation alone
+        // ---- chunk 0: GEMM 1 alone, then its block 0 alone; its block 1 runs under GEMM 1 (1) like every other chunk's
         g4_for<4>([&](auto j_) { rd_w1(0, 0, 0, decltype(j_)::value); });
         fence();
-        phase_a(I0{}, std::false_type{}, 0);
+        phase_a(I0{}, std::false_type{}, NST{}, 0);
         consts_rd(0, 0, 0);
         consts_rd(0, 0, 1);
         asm volatile("s_nop 15" ::: "memory");         // the last MFMA's result -> VALU
         fence();
-        g4_for<56>([&](auto k_) { act_op(I0{}, std::integral_constant<int, decltype(k_)::value / 28>{}, std::integral_constant<int, decltype(k_)::value % 28>{}); });
+        act_block(I0{}, I0{});
         fence();
         consts_rd(0, 1, 0);
         consts_rd(0, 1, 1);
-        fence();
-        g4_for<56>([&](auto k_) { act_op(I0{}, std::integral_constant<int, 2 + decltype(k_)::value / 28>{}, std::integral_constant<int, decltype(k_)::value % 28>{}); });
-        fence();
-        consts_rd(1, 0, 0);
-        consts_rd(1, 0, 1);
         fence();
         wait_barrier();
 #pragma unroll
@@ -279,17 +386,35 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
         g4_for<4>([&](auto j_) { rd_w1(0, 1, 0, decltype(j_)::value); });
         fence();
         // ---- chunk 1: its GEMM 2 is the tile's first k-step
-        phase_a(I1{}, std::true_type{}, 1);
-        phase_b(I1{}, std::true_type{}, 1);
+        phase_a(I1{}, std::true_type{}, NST{}, 1);
+        phase_b(I1{}, std::true_type{}, NST{}, 1);
+#ifdef MAGE4M_STAMP
+        auto chunk_pair = [&](auto ST_, int c) __attribute__((always_inline)) {
+            phase_a(I0{}, std::true_type{}, ST_, c);
+            phase_b(I0{}, std::false_type{}, ST_, c);
+            phase_a(I1{}, std::true_type{}, ST_, c + 1);
+            phase_b(I1{}, std::false_type{}, ST_, c + 1);
+            M_CSTAMP(ST_, 12);
+        };
+        for (int c = 2; c < M_CSTAMP_C0; c += 2) chunk_pair(NST{}, c);
+        chunk_pair(I0{}, M_CSTAMP_C0);
+        for (int c = M_CSTAMP_C0 + 2; c < M_CSTAMP_C1; c += 2) chunk_pair(NST{}, c);
+        chunk_pair(I1{}, M_CSTAMP_C1);
+        for (int c = M_CSTAMP_C1 + 2; c < M_NCH; c += 2) chunk_pair(NST{}, c);
+#else
         for (int c = 2; c < M_NCH; c += 2) {
-            phase_a(I0{}, std::true_type{}, c);
-            phase_b(I0{}, std::false_type{}, c);
-            phase_a(I1{}, std::true_type{}, c + 1);
-            phase_b(I1{}, std::false_type{}, c + 1);
+            phase_a(I0{}, std::true_type{}, NST{}, c);
+            phase_b(I0{}, std::false_type{}, NST{}, c);
+            phase_a(I1{}, std::true_type{}, NST{}, c + 1);
+            phase_b(I1{}, std::false_type{}, NST{}, c + 1);
         }
+#endif
         M_STAMP(1);
-        // ---- the last chunk's pack and GEMM 2 (W2 stage 1); the closing epilogue's first bias values are requested under it
+        // ---- the last chunk's block 1 (its constants were read in Pb(63)), pack and GEMM 2 (W2 stage 1); the closing epilogue's first bias values
+        // are requested under it
         asm volatile("s_nop 15" ::: "memory");
+        fence();
+        act_block(I1{}, I1{});
         fence();
         g4_for<8>([&](auto i_) { pack_op(I1{}, i_); });
         fence();
@@ -421,6 +546,10 @@ __global__ __launch_bounds__(256) void gemm4m_kernel(const Gemm4mArgs g) {
         if (tid == 0 && blockIdx.x < M_STAMP_WG && stamp_tile < M_STAMP_TILES) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) m_stamps[((int)blockIdx.x * M_STAMP_TILES + stamp_tile) * 5 + k] = stamp[k];
+        }
+        if (tid < M_CSTAMP_LANES && blockIdx.x < M_STAMP_WG && stamp_tile < M_STAMP_TILES) {
+            MAGE_DASSERT(((int)blockIdx.x * M_STAMP_TILES + stamp_tile) * M_CSTAMP_LANES + tid < M_STAMP_WG * M_STAMP_TILES * M_CSTAMP_LANES);
+            m_cstamps[((int)blockIdx.x * M_STAMP_TILES + stamp_tile) * M_CSTAMP_LANES + tid] = (unsigned)cstamp;
         }
         ++stamp_tile;
         fence();

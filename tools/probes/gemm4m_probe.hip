@@ -1,6 +1,8 @@
 // Stamp probe of the fused decoder MLP launch (mage_amd/csrc/gemm4m.hip; this file compiles its own copy, so -DMAGE4M_STAMP and other tuning flags
 // work) against the library's mage_mlp_fused: bitwise comparison of the output rows and of ln_part, HIP-event times of both, and -- with
-// -DMAGE4M_STAMP -- where a tile's time goes: wave 0 of every workgroup stamps the 100 MHz wall clock at five points of each tile.
+// -DMAGE4M_STAMP -- where a tile's time goes: wave 0 of every workgroup stamps the 100 MHz wall clock at five points of each tile, and the shader
+// clock at the phase starts, in front of the mid-phase waits and behind the barriers of the chunk pairs (8, 9) and (32, 33): per phase kind
+// (Pa / Pb) the first half, the wait + barrier and the second half in shader cycles, and the clock under the chunk loop (shader / wall clock).
 // build (from the repo root; the library must be built first):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DMAGE4M_STAMP tools/probes/gemm4m_probe.hip -Lmage_amd/lib -lmage_hip -Wl,-rpath,'$ORIGIN/../../mage_amd/lib' -o tools/probes/gemm4m_probe.bin
 // run:  timeout -k 10 300 tools/probes/gemm4m_probe.bin [rounds = 5] [M = 262144]
@@ -72,17 +74,27 @@ static Dist dist(std::vector<double>& v) {
 }
 static int stamp_table(int grid, int tiles_per_wg_max, int ntiles) {
     std::vector<unsigned long long> st((size_t)M_STAMP_WG * M_STAMP_TILES * 5);
-    if (hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(m_stamps), st.size() * 8) != hipSuccess) {
+    std::vector<unsigned> cs((size_t)M_STAMP_WG * M_STAMP_TILES * M_CSTAMP_LANES);
+    if (hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(m_stamps), st.size() * 8) != hipSuccess ||
+        hipMemcpyFromSymbol(cs.data(), HIP_SYMBOL(m_cstamps), cs.size() * 4) != hipSuccess) {
         printf("stamps: copy back failed\n");
         return 1;
     }
     const char* names[6] = {"chunk loop (64 chunks)", "last pack + GEMM 2", "closing epilogue", "trailing row loads issued", "hand-over to next tile", "whole tile (start to start)"};
-    std::vector<double> seg[6], share;
+    std::vector<double> seg[6], share, ghz, ph[2][3], chunk;          // ph[0 Pa | 1 Pb][0 first half | 1 wait + barrier | 2 second half], shader cycles
     for (int wg = 0; wg < grid && wg < M_STAMP_WG; ++wg) {
         const int n_my = (ntiles - wg + grid - 1) / grid;
         for (int t = 0; t < n_my && t < M_STAMP_TILES; ++t) {
             const unsigned long long* s = &st[((size_t)wg * M_STAMP_TILES + t) * 5];
+            const unsigned* cl = &cs[((size_t)wg * M_STAMP_TILES + t) * M_CSTAMP_LANES];
             for (int k = 0; k < 4; ++k) seg[k].push_back((double)(s[k + 1] - s[k]) * 10.0);
+            ghz.push_back((double)(unsigned)(cl[2 * M_CSTAMP_N + 1] - cl[2 * M_CSTAMP_N]) / ((double)(s[1] - s[0]) * 10.0));
+            for (int p = 0; p < 2; ++p) {
+                const unsigned* c = cl + p * M_CSTAMP_N;
+                for (int q = 0; q < 4; ++q)                      // phases Pa(c), Pb(c), Pa(c + 1), Pb(c + 1); unsigned differences survive a wrap of the low word
+                    for (int h = 0; h < 3; ++h) ph[q & 1][h].push_back((double)(unsigned)(c[3 * q + h + 1] - c[3 * q + h]));
+                for (int q = 0; q < 2; ++q) chunk.push_back((double)(unsigned)(c[6 * q + 6] - c[6 * q]));
+            }
             if (t + 1 < n_my && t + 1 < M_STAMP_TILES) {
                 seg[4].push_back((double)(s[5] - s[4]) * 10.0);
                 seg[5].push_back((double)(s[5] - s[0]) * 10.0);
@@ -103,6 +115,27 @@ static int stamp_table(int grid, int tiles_per_wg_max, int ntiles) {
     }
     const Dist ds = dist(share);
     printf("    closing epilogue / whole tile, per tile: median %.2f%% (p10 %.2f%%, p90 %.2f%%)\n", 100 * ds.med, 100 * ds.p10, 100 * ds.p90);
+    const Dist dg = dist(ghz);
+    printf("    clock under the chunk loop (shader clock / wall clock, per tile): median %.3f GHz (p10 %.3f, p90 %.3f)\n", dg.med, dg.p10, dg.p90);
+    printf("    chunks %d, %d, %d, %d of every tile, shader cycles (a phase = 64 MFMAs; 64 x 16.63 = 1064)\n", M_CSTAMP_C0, M_CSTAMP_C0 + 1, M_CSTAMP_C1, M_CSTAMP_C1 + 1);
+    printf("    %-30s %9s %9s %9s\n", "segment", "median", "p10", "p90");
+    const char* pn[2] = {"Pa", "Pb"};
+    const char* hn[3] = {"first half (32 MFMAs)", "wait + barrier", "second half (32 MFMAs)"};
+    double med[2][3];
+    for (int q = 0; q < 2; ++q)
+        for (int h = 0; h < 3; ++h) {
+            const Dist d = dist(ph[q][h]);
+            med[q][h] = d.med;
+            char nm[64];
+            snprintf(nm, sizeof nm, "%s %s", pn[q], hn[h]);
+            printf("    %-30s %9.0f %9.0f %9.0f\n", nm, d.med, d.p10, d.p90);
+        }
+    const Dist dc = dist(chunk);
+    printf("    %-30s %9.0f %9.0f %9.0f   = %.2f cycles per MFMA\n", "chunk (Pa + Pb)", dc.med, dc.p10, dc.p90, dc.med / 128);
+    const double ideal = 128 * 16.63, over = med[0][0] + med[0][1] + med[0][2] + med[1][0] + med[1][1] + med[1][2] - ideal;
+    printf("    overhead above 128 x 16.63 = %.0f cycles (sum of the medians): %.0f -- Pa halves %.0f (%.0f%%), Pb halves %.0f (%.0f%%), waits + barriers %.0f (%.0f%%)\n", ideal,
+           over, med[0][0] + med[0][2] - ideal / 2, 100 * (med[0][0] + med[0][2] - ideal / 2) / over, med[1][0] + med[1][2] - ideal / 2,
+           100 * (med[1][0] + med[1][2] - ideal / 2) / over, med[0][1] + med[1][1], 100 * (med[0][1] + med[1][1]) / over);
     return 0;
 }
 #endif
