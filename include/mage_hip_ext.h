@@ -525,6 +525,62 @@ int mage_distill_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t 
                           int32_t mode, const uint8_t* given, const float* row_kl, const float* grad_out, const float* norm, void* dlogits,
                           int32_t dl_dtype, void* stream);
 
+/* Per-code counts and row sums of a quantised batch: no site in the reference (its codebook moves by the gradient of
+ * mse(z_q_x, z_e_x.detach()) alone and nothing reports its use).  Serves VectorQuantizedVAE.set_codebook_update('ema') (every training
+ * forward, right after mage_vq_nearest) and VectorQuantizedVAE.code_usage (mage_amd/modules/vqvae_model.py).
+ * ids int64 [rows]; z fp32 rows [rows, ldz], of which the first D columns are read.
+ *   counts (int64 [K])    counts[k] = the number of rows with ids == k, exact (integer adds);
+ *   sums   (fp32 [K, D])  sums[k, :] = the sum of those rows of z.
+ * z and sums may both be null: the counts-only form (D and ldz are then not looked at).  An id outside [0, K) is recorded for
+ * mage_check_device_errors (as mage_token_logprob's bad token is) and counted nowhere: neither in counts nor in sums.
+ * THE SUMS HAVE ONE ORDER.  The rows are cut into n_chunk = min(64, ceil(rows / 4096)) chunks of R = ceil(rows / n_chunk) rounded up to a
+ * multiple of 8 rows: chunk c owns rows [c R, min(rows, (c + 1) R)) -- a function of `rows` alone.  Inside a chunk the rows of code k are
+ * added to +0 one after the other in ascending row order, in fp32 (one LDS add per row, issued by the one wave that owns the channel);
+ * sums[k, d] is then +0 + chunk 0's sum + chunk 1's sum + ..., chunks ascending, in fp32.  There is no floating-point atomic between
+ * waves: two launches give the same bits, and the bits of sums[k, :] depend on the positions and values of code k's rows alone (the rows
+ * of other codes may be permuted among themselves).  Error: a sum of n_k terms plus the n_chunk stage,
+ * |err| <= (n_k + n_chunk) 2^-24 sum |z|.
+ * scratch: 16-byte aligned, at least n_chunk * K * (D + 1) * 4 bytes (n_chunk * K * 4 for the counts-only form): the chunks' partial
+ * tables, written before they are read.
+ * Geometry: mage_embedding_bwd's deterministic form (a workgroup owns a chunk and a channel slice, an LDS table of the slice, its eight
+ * waves split the slice's channels) with any D % 4 == 0, a 32-channel slice above 512 codes (K x slice x 4 B within 128 KiB), a row stride,
+ * and one more workgroup per chunk that counts; a second launch adds the chunks.
+ * rows in [1, 2^31), K in [1, 1024], with sums D % 4 == 0, D in [4, 1024], ldz >= D; ids and counts 8-byte, z 4-byte, sums and scratch
+ * 16-byte aligned; scratch_bytes as above: MAGE_EINVAL otherwise, nothing launched. */
+int mage_code_stats(const int64_t* ids, const float* z, int64_t rows, int32_t D, int64_t ldz, int32_t K, int64_t* counts, float* sums,
+                    void* scratch, int64_t scratch_bytes, void* stream);
+
+/* Exponential-moving-average codebook update (van den Oord et al. 2017, appendix A.1) with Laplace smoothing, the restart of dead codes
+ * from encoder rows, and usage statistics: no site in the reference.  Serves VectorQuantizedVAE.set_codebook_update('ema'), after
+ * mage_code_stats on the same (ids, z).
+ * One launch updates in place codebook (fp32 [K, D]: e_k), cluster_size (fp32 [K]: N_k) and embed_sum (fp32 [K, D]: m_k) from counts
+ * (int64 [K]) and sums (fp32 [K, D]).  With g = (double)decay, every right-hand side evaluated in fp64 from the fp32 (int64) operands, each
+ * operation rounded on its own (no contraction), and rounded once to fp32 where it is stored:
+ *   1. N_k' = (float)(g N_k + (1 - g) counts[k]);
+ *   2. m_k' = (float)(g m_k + (1 - g) sums[k]), elementwise;
+ *   3. n = sum_k N_k' over the stored fp32 values, in fp64, k ascending from 0.0;
+ *   4. Nhat_k = (N_k' + eps) / (n + K eps) * n                                   (fp64, not stored);
+ *   5. e_k = (float)(m_k' / Nhat_k).
+ * Every workgroup derives n itself from the K values in that order: no cross-workgroup reduction, no floating-point atomic, the same bits
+ * from every launch.  (One integer ticket orders the write of the K new sizes after every workgroup's read of the old ones: the workgroup
+ * that arrives last writes them from its own copy.  No value passes between workgroups.  The ticket is one word per device: calls of
+ * mage_codebook_ema on one device must be ordered -- one stream, or events.)
+ * Restart, after steps 1 to 5, when restart_below > 0: a code with N_k' < restart_below (fp32 compare) is dead and takes an encoder row,
+ *   r_k = ((uint64)hash32(seed * 0x9e3779b97f4a7c15 + step * K + k) * rows) >> 32   (uint64 wrap-around; hash32 and the seed multiplier
+ *         are the dropout masks' and the sampler's: csrc/common.h),
+ *   e_k = z[r_k, :D] copied bit for bit, N_k = restart_size, m_k = (float)((double)restart_size * z[r_k]).
+ * Two dead codes may draw the same row: the quantiser's first-minimum rule then never picks the second one, which stays dead and draws
+ * again at the next step (`step` changes the counter).  z (fp32 rows [rows, ldz]), rows and ldz are looked at only when restart_below > 0.
+ * stats (fp64 [4], device, written by one thread): [0] perplexity exp(-sum_k p_k ln p_k), p_k = counts[k] / sum counts, k ascending in
+ * fp64, a zero count adding 0 (never 0 * inf); [1] the number of codes with counts[k] > 0; [2] the number of codes restarted; [3] sum counts.
+ * sum counts == 0 (every id was invalid): the state is left untouched, perplexity is NaN, the other three are 0.
+ * K in [1, 1024]; D % 4 == 0, D in [4, 1024]; decay in [0, 1), eps > 0, restart_below >= 0, restart_size > 0, all finite; with
+ * restart_below > 0 z non-null, rows in [1, 2^31), ldz >= D; codebook, embed_sum, sums 16-byte, counts and stats 8-byte, cluster_size and z
+ * 4-byte aligned: MAGE_EINVAL otherwise, nothing launched.  Nothing is read on the host. */
+int mage_codebook_ema(float* codebook, float* cluster_size, float* embed_sum, const int64_t* counts, const float* sums, const float* z,
+                      int64_t rows, int64_t ldz, int32_t K, int32_t D, float decay, float eps, float restart_below, float restart_size,
+                      uint64_t seed, uint64_t step, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

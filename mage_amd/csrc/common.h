@@ -19,7 +19,7 @@ int mage_device_index();               // current HIP device, or -1 (per-device 
 const void* mage_zero_page();          // device pointer, 16384 zero bytes (padding source of the gather loads; a zero bias vector of up to 4096
                                        // columns); null before mage_init
 int* mage_error_word();                // device pointer to the deferred-error word of the current device (mage_check_device_errors)
-enum { MAGE_DEVERR_EMBEDDING_ID = 1, MAGE_DEVERR_CE_TARGET = 2, MAGE_DEVERR_TOKEN_ID = 3, MAGE_DEVERR_PAIR_ID = 4 };
+enum { MAGE_DEVERR_EMBEDDING_ID = 1, MAGE_DEVERR_CE_TARGET = 2, MAGE_DEVERR_TOKEN_ID = 3, MAGE_DEVERR_PAIR_ID = 4, MAGE_DEVERR_CODE_ID = 5 };
 // Kernel-selection switches (tuning, A/B tests, bisecting): ONE table, filled once from the MAGE_* environment variables of the same names
 // (upper-cased, "MAGE_" prefix) the first time it is asked for, changed at run time only through mage_set_option (include/mage_hip.h lists
 // them).  No dispatch function reads the environment.

@@ -180,6 +180,7 @@ extern "C" int mage_check_device_errors(void* stream) {
                        : host[0] == MAGE_DEVERR_CE_TARGET ? "mage_cross_entropy: target out of range"
                        : host[0] == MAGE_DEVERR_TOKEN_ID ? "mage_token_logprob: token out of range"
                        : host[0] == MAGE_DEVERR_PAIR_ID ? "mage_preference_loss: pair index out of range"
+                       : host[0] == MAGE_DEVERR_CODE_ID ? "mage_code_stats: code id out of range"
                                                           : "device-side argument error";
     mage_set_error("%s (value %d, valid range [0, %d))", what, host[1], host[2]);
     return MAGE_EINVAL;

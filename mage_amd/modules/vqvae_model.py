@@ -42,6 +42,10 @@ def _no_torch_forward(self, *a, **k):
                        "through VectorQuantizedVAE.encode/decode/forward")
 
 
+# buffers of the codebook holder in EMA mode (VectorQuantizedVAE.set_codebook_update): registered only then, so the default state_dict is the reference's
+EMA_BUFFERS = ("ema_cluster_size", "ema_embed_sum", "ema_step")
+
+
 class VQEmbedding(nn.Module):
     """Codebook holder: ``embedding.weight`` [K, D] ~ U(-1/K, 1/K) (vqvae_model.py:87-91)."""
 
@@ -204,6 +208,9 @@ class VectorQuantizedVAE(nn.Module):
         self.decode_chunk = 1024                   # frames per decode launch group (bounds workspace: 0.8 GB at dim 256)
         self._pad_bufs = {}                        # zero-padded frame buffers of the bf16 decode, keyed by (frames, grid, device, stream)
         self._derived = _Derived(self)
+        self.codebook_update = "grad"              # 'ema': set_codebook_update
+        self._ema = None                           # EMA mode's settings and the host's copy of the step counter
+        self.last_codebook_stats = None            # EMA mode: device tensors of the last training forward (counts, perplexity, active, restarted)
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
@@ -217,6 +224,15 @@ class VectorQuantizedVAE(nn.Module):
         self.load_state_dict(sd, strict=False)
         print(f"Restored from {path}")
 
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """nn.Module.load_state_dict; a checkpoint saved in EMA mode needs set_codebook_update('ema', ...) first (strict=False drops its EMA state)."""
+        found = [k for k in ("codebook." + n for n in EMA_BUFFERS) if k in state_dict]
+        if found and strict and self.codebook_update != "ema":
+            raise RuntimeError(f"the checkpoint carries EMA codebook state ({', '.join(found)}) but this model updates its codebook by the "
+                               "gradient: call set_codebook_update('ema', ...) before load_state_dict, or load with strict=False to drop the "
+                               "EMA state")
+        return super().load_state_dict(state_dict, strict, **kw)
+
     def set_precision(self, precision: str) -> "VectorQuantizedVAE":
         """'fp32' (parity: exact-fp32 MFMA), 'bf16' (decode stack on bf16 MFMA; encode + VQ stay fp32-class so token indices stay
         bit-exact), or 'f16x3' / 'bf16x3' (the fast parity modes: the f4 decode stack on split-precision operands, fp32-class frames)."""
@@ -229,6 +245,103 @@ class VectorQuantizedVAE(nn.Module):
         # against the reference because of the 7e-7 the split operands move z_e by; the other modes take the split encoder
         self.encode_split = precision != "fp32"
         return self
+
+    # ------------------------------------------------------------------ codebook update rule
+    def set_codebook_update(self, mode: str = "grad", *, decay: float = 0.99, eps: float = 1e-5, restart_below: float = 0.0,
+                            restart_size: Optional[float] = None, seed: int = 0) -> "VectorQuantizedVAE":
+        """How training moves the codebook.  'grad' (the default, the reference's rule): the gradient of mse(z_q_x, z_e_x.detach()) and the
+        caller's optimizer.  'ema': every training-mode forward updates the codebook itself -- exponential moving averages of the per-code
+        counts and encoder-row sums (decay), Laplace smoothing (eps), and with restart_below > 0 a code whose averaged count falls below
+        it restarts from an encoder row of the batch with size restart_size (None: restart_below), chosen by (seed, step)
+        (include/mage_hip_ext.h: mage_codebook_ema states the rule).  The codebook then takes no gradient: the middle term of the
+        reference's three-term loss has no effect.
+        'ema' registers codebook.ema_cluster_size (ones), codebook.ema_embed_sum (a copy of the codebook, so that an unused code keeps
+        m / N = e) and codebook.ema_step (int64) and switches the codebook's requires_grad off; 'grad' removes them and restores it.  A
+        checkpoint saved in EMA mode carries the three keys: call set_codebook_update('ema', ...) before loading it.  Calling 'ema' again
+        changes the settings and keeps the state."""
+        if mode not in ("grad", "ema"):
+            raise ValueError(f"set_codebook_update: mode must be 'grad' or 'ema', got {mode!r}")
+        cbm, w = self.codebook, self.codebook.embedding.weight
+        if mode == "grad":
+            if self.codebook_update == "ema":
+                for n in EMA_BUFFERS:
+                    del cbm._buffers[n]
+                w.requires_grad_(self._ema["requires_grad"])
+            self.codebook_update, self._ema, self.last_codebook_stats = "grad", None, None
+            return self
+        import math
+        rs = restart_below if restart_size is None else restart_size
+        if not (math.isfinite(decay) and 0.0 <= decay < 1.0):
+            raise ValueError(f"set_codebook_update: decay={decay} outside [0, 1)")
+        if not (math.isfinite(eps) and eps > 0.0):
+            raise ValueError(f"set_codebook_update: eps={eps} must be finite and > 0")
+        if not (math.isfinite(restart_below) and restart_below >= 0.0):
+            raise ValueError(f"set_codebook_update: restart_below={restart_below} must be finite and >= 0")
+        if restart_below > 0.0 and not (math.isfinite(rs) and rs > 0.0):
+            raise ValueError(f"set_codebook_update: restart_size={restart_size} must be finite and > 0")
+        if self.K > 1024 or w.shape[1] > 1024 or w.shape[1] % 4:
+            raise ValueError(f"set_codebook_update: the EMA kernels take K <= 1024 and D % 4 == 0, D <= 1024 (K={self.K}, D={w.shape[1]})")
+        self._check_one_process()
+        keep = self._ema["requires_grad"] if self.codebook_update == "ema" else w.requires_grad
+        if self.codebook_update != "ema":
+            with torch.no_grad():
+                cbm.register_buffer("ema_cluster_size", torch.ones(self.K, device=w.device, dtype=torch.float32))
+                cbm.register_buffer("ema_embed_sum", w.detach().float().clone())
+                cbm.register_buffer("ema_step", torch.zeros((), device=w.device, dtype=torch.int64))
+        w.requires_grad_(False)
+        self.codebook_update = "ema"
+        self._ema = dict(decay=float(decay), eps=float(eps), restart_below=float(restart_below), restart_size=float(rs) if restart_below > 0.0 else 1.0,
+                         seed=int(seed), requires_grad=keep, step=0, step_sig=None)
+        return self
+
+    @staticmethod
+    def _check_one_process() -> None:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError("EMA codebook updates run per process: with torch.distributed at world size "
+                               f"{dist.get_world_size()} every rank would average its own batch and restart dead codes from its own rows, and the "
+                               "ranks' codebooks would drift apart.  An all-reduced form is out of scope: train the first stage in one process, or "
+                               "use set_codebook_update('grad')")
+
+    def _ema_update(self, ids: torch.Tensor, z_e: torch.Tensor) -> None:
+        """One EMA step from a training forward's ids (int64 [rows]) and encoder rows z_e (fp32 [rows, D]): mage_code_stats, then
+        mage_codebook_ema in place on the codebook parameter and the three buffers.  The launches follow the forward's own reads of the
+        codebook on the stream, so that call's outputs come from the codebook before the update."""
+        if _frozen_token():
+            raise RuntimeError("EMA codebook update inside a weights_frozen() region: the region promises that no parameter changes; call the "
+                               "training forward outside it")
+        self._check_one_process()
+        cfg, cbm, w = self._ema, self.codebook, self.codebook.embedding.weight
+        if w.dtype != torch.float32 or not w.is_contiguous():
+            raise RuntimeError("EMA codebook update: the codebook must be a contiguous fp32 parameter")
+        with torch.no_grad():
+            step_buf = cbm.ema_step
+            if cfg["step_sig"] != (step_buf.data_ptr(), step_buf._version):     # first step, or the buffer was loaded / moved: read it once
+                cfg["step"] = int(step_buf.item())
+            ids = ids.reshape(-1)
+            counts, sums = ops.code_stats(ids, z_e, K=self.K)
+            stats = ops.codebook_ema(w.data, cbm.ema_cluster_size, cbm.ema_embed_sum, counts, sums, z_e if cfg["restart_below"] > 0.0 else None,
+                                     decay=cfg["decay"], eps=cfg["eps"], restart_below=cfg["restart_below"], restart_size=cfg["restart_size"],
+                                     seed=cfg["seed"], step=cfg["step"])
+            step_buf.add_(1)
+            cfg["step"] += 1
+            cfg["step_sig"] = (step_buf.data_ptr(), step_buf._version)
+        bump_weights_epoch()                       # the kernel wrote the parameter behind its version counter: cb, cbt, c2, the decode tables
+        self.last_codebook_stats = dict(counts=counts, perplexity=stats[0], active=stats[1], restarted=stats[2])
+
+    @torch.no_grad()
+    def code_usage(self, ids: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """How a batch of tokens uses the codebook: counts (int64 [K], mage_code_stats' counts-only form), perplexity exp(-sum p ln p) and
+        the number of active codes, device tensors, no host sync.  ids: any int64 tensor of codes (encode(x), MAGE.last_tokens); works in
+        any mode.  A collapsed codebook shows as a perplexity and an active count far below K."""
+        if ids.dtype != torch.int64:
+            raise TypeError(f"code_usage: ids must be int64, got {ids.dtype}")
+        if not ids.is_cuda:
+            raise RuntimeError("code_usage counts with a libmage_hip.so kernel: move the ids to a ROCm GPU (there is no CPU fallback)")
+        with torch.cuda.device(ids.device):
+            counts, _ = ops.code_stats(ids.contiguous().view(-1), K=self.K)
+        p = counts.double() / counts.sum()                                      # [K] bookkeeping; all ids invalid: 0 / 0, a NaN perplexity
+        return dict(counts=counts, perplexity=torch.exp(-torch.xlogy(p, p).sum()), active=(counts > 0).sum())
 
     # ------------------------------------------------------------------ derived weights
     def _build(self) -> Dict[str, torch.Tensor]:
@@ -785,4 +898,7 @@ class VectorQuantizedVAE(nn.Module):
         D = z.shape[1]
         z_q = ops.embedding(ids, w["cb"], torch.empty(N * hh * ww, D, device=x.device, dtype=torch.float32))
         x_tilde = self._decode_nocheck(ids)
+        if self.training and self.codebook_update == "ema":        # train() without the training graph (no_grad, f8): the update still runs
+            with torch.cuda.device(x.device):
+                self._ema_update(ids, z)
         return x_tilde, z.view(N, hh, ww, D).permute(0, 3, 1, 2), z_q.view(N, hh, ww, D).permute(0, 3, 1, 2)

@@ -137,6 +137,8 @@ def vq_train_forward(vq, x: torch.Tensor):
     z_e, t5 = _res_forward(vq, w, "e5", enc[5], r2, N, h, wd, post_relu=False)
     ids = ops.vq_nearest(z_e, w["cbt"], w["c2"])
     zq = ops.embedding(ids, w["cb"], torch.empty(N * h * wd, D, device=dev, dtype=F32))
+    if vq.training and vq.codebook_update == "ema":                                      # behind the gather: this call's z_q is the old codebook's
+        vq._ema_update(ids, z_e)
     rd = ops.relu(zq, torch.empty_like(zq))                                              # decoder[0]'s in-place ReLU on z_q_x_st
     rd1, td0 = _res_forward(vq, w, "d0", dec[0], rd, N, h, wd, post_relu=True)
     u, td1 = _res_forward(vq, w, "d1", dec[1], rd1, N, h, wd, post_relu=True)            # decoder[2] ReLU folded
@@ -161,7 +163,7 @@ def vq_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.T
     grads: Dict[str, torch.Tensor] = {}
     M = N * h * wd
     dz_e = g_ze_rows.clone() if g_ze_rows is not None else torch.zeros(M, D, device=dev, dtype=F32)
-    if g_zq_rows is not None:                                      # z_q_x_bar: index_add into the codebook (vqvae_model.py:54-62)
+    if g_zq_rows is not None and vq.codebook_update != "ema":      # z_q_x_bar: index_add into the codebook (vqvae_model.py:54-62); EMA mode: no gradient
         gcb = torch.zeros(vq.K, D, device=dev, dtype=F32)
         ops.embedding_bwd(tape["ids"].reshape(-1), g_zq_rows, gcb)
         grads["codebook.embedding.weight"] = gcb
@@ -315,6 +317,8 @@ def vq8_train_forward(vq, x: torch.Tensor):
     z_e, D = h, 4 * dim
     ids = ops.vq_nearest(z_e, w["cbt"], w["c2"])
     zq = ops.embedding(ids, w["cb"], torch.empty(N * hh * ww, D, device=dev, dtype=F32))
+    if vq.training and vq.codebook_update == "ema":                                      # behind the gather: this call's z_q is the old codebook's
+        vq._ema_update(ids, z_e)
     dec_t, ups = [], []
     h = zq
     for bi, ci, co in _F8_DEC:
@@ -339,7 +343,7 @@ def vq8_train_backward(vq, tape, g_xt, g_ze_rows, g_zq_rows) -> Dict[str, torch.
     grads: Dict[str, torch.Tensor] = {}
     M8 = N * tape["h"] * tape["wd"]
     dz_e = g_ze_rows.clone() if g_ze_rows is not None else torch.zeros(M8, D, device=dev, dtype=F32)
-    if g_zq_rows is not None:                                      # z_q_x_bar: index_add into the codebook (vqvae_model.py:54-62)
+    if g_zq_rows is not None and vq.codebook_update != "ema":      # z_q_x_bar: index_add into the codebook (vqvae_model.py:54-62); EMA mode: no gradient
         gcb = torch.zeros(vq.K, D, device=dev, dtype=F32)
         ops.embedding_bwd(tape["ids"].reshape(-1), g_zq_rows, gcb)
         grads["codebook.embedding.weight"] = gcb

@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT_RELU, ACT_TANH, BF16, BF16X3, F16, F16X3, F32, AttnDesc, GemmDesc
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
-           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "adam_guarded", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
+           "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "code_stats", "code_stats_chunks", "codebook_ema", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "adam_guarded", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
            "token_logprob", "clip_scores", "video_metrics", "group_advantages", "frame_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
@@ -1400,6 +1400,66 @@ def embedding_bwd(ids, dout, dtable, *, padding_idx: int = -1, group: Optional[i
     _lib.check(l.mage_embedding_bwd(ids.data_ptr(), dout.data_ptr(), code(dout), dtable.data_ptr(), n, dtable.shape[1], dtable.shape[0],
                                     padding_idx, group, group_stride, off, _p(scratch), 0 if scratch is None else scratch.numel(), s), l)
     return dtable
+
+
+def code_stats_chunks(rows: int) -> int:
+    """The number of row chunks mage_code_stats cuts `rows` into (include/mage_hip_ext.h states the formula): its scratch is sized from it."""
+    return min(64, (rows + 4095) // 4096)
+
+
+def code_stats(ids: torch.Tensor, z: Optional[torch.Tensor] = None, *, K: int, D: Optional[int] = None, counts: Optional[torch.Tensor] = None,
+               sums: Optional[torch.Tensor] = None):
+    """mage_code_stats: (counts int64 [K], sums fp32 [K, D] or None) of ids (int64, any shape) and the encoder rows z [rows, >= D] fp32 (row
+    stride z.stride(0)).  counts[k] = the number of rows with id k, sums[k] = the fixed-order fp32 sum of those rows of z.  z None: the
+    counts-only form.  An id outside [0, K) is counted nowhere and reported by check_device_errors."""
+    l, s = _dev(ids)
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() > 0
+    rows, dev = ids.numel(), ids.device
+    if counts is None:
+        counts = torch.empty(K, device=dev, dtype=torch.int64)
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == K and counts.device == dev
+    ldz = 0
+    if z is not None:
+        assert z.dtype == torch.float32 and z.dim() == 2 and z.stride(1) == 1 and z.shape[0] == rows and z.device == dev
+        D = z.shape[1] if D is None else D
+        ldz = z.stride(0)
+        assert 0 < D <= z.shape[1]
+        if sums is None:
+            sums = torch.empty(K, D, device=dev, dtype=torch.float32)
+        assert sums.dtype == torch.float32 and sums.is_contiguous() and tuple(sums.shape) == (K, D) and sums.device == dev
+    else:
+        assert sums is None
+        D = 0
+    scratch = torch.empty(code_stats_chunks(rows) * K * (D + 1), device=dev, dtype=torch.float32)
+    _lib.check(l.mage_code_stats(ids.data_ptr(), _p(z), rows, D, ldz, K, counts.data_ptr(), _p(sums), scratch.data_ptr(), scratch.numel() * 4, s), l)
+    return counts, sums
+
+
+def codebook_ema(codebook: torch.Tensor, cluster_size: torch.Tensor, embed_sum: torch.Tensor, counts: torch.Tensor, sums: torch.Tensor,
+                 z: Optional[torch.Tensor] = None, *, decay: float = 0.99, eps: float = 1e-5, restart_below: float = 0.0,
+                 restart_size: Optional[float] = None, seed: int = 0, step: int = 0, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mage_codebook_ema: one launch updates codebook [K, D], cluster_size [K] and embed_sum [K, D] (fp32, in place) from code_stats' counts
+    and sums; with restart_below > 0 a code whose new size is below it takes a row of z (fp32 [rows, >= D], row stride z.stride(0)) chosen by
+    (seed, step).  Returns stats, fp64 [4] on the device: perplexity, codes used, codes restarted, rows counted.  The writes go behind
+    autograd's version counters: the caller invalidates what it derived from the codebook."""
+    l, s = _dev(codebook)
+    K, D = codebook.shape
+    dev = codebook.device
+    for t_, shape in ((codebook, (K, D)), (embed_sum, (K, D)), (sums, (K, D)), (cluster_size, (K,))):
+        assert t_.dtype == torch.float32 and t_.is_contiguous() and tuple(t_.shape) == shape and t_.device == dev
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == K and counts.device == dev
+    rows = ldz = 0
+    if z is not None:
+        assert z.dtype == torch.float32 and z.dim() == 2 and z.stride(1) == 1 and z.shape[1] >= D and z.device == dev
+        rows, ldz = z.shape[0], z.stride(0)
+    if stats is None:
+        stats = torch.empty(4, device=dev, dtype=torch.float64)
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 4 and stats.device == dev
+    restart_size = (restart_below if restart_below > 0 else 1.0) if restart_size is None else restart_size      # unused without a restart
+    _lib.check(l.mage_codebook_ema(codebook.data_ptr(), cluster_size.data_ptr(), embed_sum.data_ptr(), counts.data_ptr(), sums.data_ptr(), _p(z),
+                                   rows, ldz, K, D, float(decay), float(eps), float(restart_below), float(restart_size),
+                                   int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), stats.data_ptr(), s), l)
+    return stats
 
 
 def group_rowsum(x, out, *, rows: int, C: int, div: int, mod: int, row_scale=None, row_scale_div: int = 1):
