@@ -525,6 +525,64 @@ int mage_distill_loss_bwd(const float* logits, int64_t rows, int32_t K, int64_t 
                           int32_t mode, const uint8_t* given, const float* row_kl, const float* grad_out, const float* norm, void* dlogits,
                           int32_t dl_dtype, void* stream);
 
+/* Supervised cross entropy of one target code per row with class weights, label smoothing, a z-loss and a mask, and what the row predicts:
+ * the reference's objective is F.cross_entropy(logits, target) with no option (mage_model.py:618, mage_cross_entropy here); this is
+ * F.cross_entropy(weight=, label_smoothing=, ignore_index=) per row, plus the z-loss of PaLM (Chowdhery et al. 2022: zeta * log^2 Z) and the
+ * rank of the target.  Serves MAGE.forward after MAGE.set_loss or with batch['given'] (mage_amd/modules/mage_train.py: SupervisedHead) and
+ * MAGE.evaluate.
+ * Row i is the K fp32 logits z at logits + i*ld and the target y = target[i] (int64; outside [0, K): recorded for
+ * mage_check_device_errors as mage_token_logprob's bad token is, and clamped).  w = class_weight (fp32 [K], 16-byte aligned; null: all
+ * ones), eps = label_smoothing, zeta = z_loss; c1 = (float)(1 - eps) and c2 = (float)(eps / K) are formed on the host in fp64.  The rule for
+ * one free row, in fp32, one wave per row in csrc/token_row.h's layout:
+ *   mx, Z       row_logsumexp's maximum and sum, so lse = mx + logf(Z) (row_lse) carries mage_token_logprob's bits;
+ *   row_nll     = -(z_y - lse): THE NEGATION OF mage_token_logprob's VALUE ON THE SAME ROW, BIT FOR BIT (the same difference with its sign
+ *               turned, so a token that holds all the mass gives -0 where the log-probability is +0);
+ *   smooth      = sum_{k < K} w_k (lse - z_k), formed only when eps > 0: a lane adds its own codes in register order, each step one
+ *               fma(w_k, lse - z_k, sum) on the rounded difference, and the lanes meet in the xor butterfly;
+ *   row_loss    = fma(c2, smooth, (c1 w_y) nll) with eps > 0, (c1 w_y) nll (two products) otherwise: with eps = 0 and no weights row_loss
+ *               has row_nll's bits.  The z-loss term zeta lse^2 is NOT in row_loss: it enters summary[0] and the gradient only;
+ *   rank        = #{j < K : z_j > z_y} + #{j < y : z_j == z_y} (int32; may be null), counted exactly by ballots on the sampler's keys
+ *               (sample_key at inv_t = 1: -0 == +0, a NaN logit is never above), so rank == 0 exactly where mage_argmax picks y; a NaN
+ *               z_y gives rank K.
+ *   Edges follow F.cross_entropy, nothing is clamped: a -inf logit with eps > 0 makes row_loss +inf (NaN if its weight is 0: 0 * inf, as
+ *   in torch), z_y = -inf makes row_nll +inf, a NaN logit or a row of -inf only makes row_lse, row_nll and row_loss NaN.
+ * given (uint8 [rows], may be null: every row free; a torch.bool tensor as it is): mage_distill_loss's contract.  A given row is never read
+ *   (a NaN there does not show, its target is not range-checked); its row_loss, row_nll and row_lse are +0, its rank 0 and its dlogits row
+ *   +0, written with the stores the free rows use.  A free row's bits depend on the row, its target and the weights alone.
+ * norm [2]: norm[0] = (float)(1 / sum_free w_y), norm[1] = (float)(1 / n_free), each 0 when its sum is 0 (the means are then +0 and nothing
+ *   is NaN); sum_free w_y is an fp64 sum and n_free an exact count from the same pass.  Without class weights norm[0] == norm[1] ==
+ *   1.0f / (float)n_free.
+ * summary [5], each rounded once from fp64:
+ *   [0] (sum row_loss) / (sum_free w_y) + zeta (sum lse^2) / n_free: the objective, F.cross_entropy's 'mean' reduction plus the z-loss
+ *       (the z term is formed only when zeta > 0);
+ *   [1] the mean of row_nll over the free rows, unweighted;  [2] the share of free rows with rank == 0;  [3] the mean of lse^2;
+ *   [4] the share of given rows over `rows`.
+ *   The sums are fp64 in ONE order, mage_distill_loss's two-launch geometry: workgroup b of the row-reading launch owns the row quads b,
+ *   b + G, ... (G = min(ceil(rows / 4), 16384)), a wave adds its rows in ascending order, the four waves meet in order; a second launch adds
+ *   the G partial sums the same way through a per-device buffer of the library (calls of mage_token_xent on one device must be ordered: one
+ *   stream, or events).  The geometry depends on rows alone: two launches give the same bits; no floating-point atomics.
+ * mage_token_xent_bwd: dlogits [rows, K] contiguous, MAGE_F32 or MAGE_BF16, the gradient of grad_out[0] * summary[0].  With g = grad_out[0],
+ *   p_k = expf(z_k - mx) * (1 / Z) recomputed by the forward call's operations and W = sum_k w_k in smooth's order ((float)K without
+ *   weights):
+ *     d_k = g [ norm[0] ((1 - eps) w_y (p_k - 1[k = y]) + (eps / K) (W p_k - w_k)) + norm[1] 2 zeta lse p_k ],   evaluated as
+ *     B = (g norm[0]) (c1 w_y),  C = (g norm[0]) c2,  A = fma((g norm[1]) (2 zeta), lse, fma(C, W, B)),
+ *     d_k = fma(-C, w_k, fma(A, p_k, -B 1[k = y]))        (the C and zeta steps only with eps > 0 and zeta > 0).
+ *   Rows are not special-cased: a NaN row's gradient is NaN.  A row is read once with 16-byte loads and written once (fp32: 16 bytes,
+ *   bf16: 8 bytes per lane and chunk), with vector stores.
+ * Registers (VGPRs per lane of the NV = 4, 8, 16, 32, 64 instances; no instance has scratch or a spill): forward 58, 60, 77, 109, 171
+ *   without smoothing and 58, 65, 89, 150, 256 + 14 AGPRs with it (a lane keeps its NV class weights across the rows of its wave);
+ *   backward (fp32) 22, 31, 41, 61, 101 without smoothing and 23, 33, 51, 87, 159 with it.
+ * mage_token_stats' size rules (rows > 0, K % 4 == 0, 0 < K <= MAGE_SAMPLE_MAX_K, ld % 4 == 0 and >= K, logits 16-byte aligned); target
+ * non-null and 8-byte aligned; class_weight 16-byte aligned; label_smoothing in [0, 1); z_loss finite and >= 0; row_loss, row_nll,
+ * row_lse, summary, norm, grad_out non-null and 4-byte aligned; dlogits 16-byte aligned, dl_dtype MAGE_F32 or MAGE_BF16: MAGE_EINVAL
+ * otherwise, nothing launched. */
+int mage_token_xent(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* target, const float* class_weight,
+                    float label_smoothing, float z_loss, const uint8_t* given, float* row_loss, float* row_nll, float* row_lse, int32_t* rank,
+                    float* summary, float* norm, void* stream);
+int mage_token_xent_bwd(const float* logits, int64_t rows, int32_t K, int64_t ld, const int64_t* target, const float* class_weight,
+                        float label_smoothing, float z_loss, const uint8_t* given, const float* grad_out, const float* norm, void* dlogits,
+                        int32_t dl_dtype, void* stream);
+
 /* Per-code counts and row sums of a quantised batch: no site in the reference (its codebook moves by the gradient of
  * mse(z_q_x, z_e_x.detach()) alone and nothing reports its use).  Serves VectorQuantizedVAE.set_codebook_update('ema') (every training
  * forward, right after mage_vq_nearest) and VectorQuantizedVAE.code_usage (mage_amd/modules/vqvae_model.py).

@@ -158,6 +158,8 @@ EXT_SIGNATURES = {
     "mage_token_logprob_bwd_masked": (C.c_int, [vp, i64, i32, i64, vp, vp, i64, vp, vp, i32, vp, vp]),
     "mage_distill_loss": (C.c_int, [vp, i64, i32, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp]),
     "mage_distill_loss_bwd": (C.c_int, [vp, i64, i32, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "mage_token_xent": (C.c_int, [vp, i64, i32, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mage_token_xent_bwd": (C.c_int, [vp, i64, i32, i64, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp]),
     "mage_code_stats": (C.c_int, [vp, vp, i64, i32, i64, i32, vp, vp, vp, i64, vp]),
     "mage_codebook_ema": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, f32, f32, f32, f32, C.c_uint64, C.c_uint64, vp, vp]),
 }

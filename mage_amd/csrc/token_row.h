@@ -1,5 +1,5 @@
 // One row of logits in the registers of one wave: the layout, the sampling filter and the fixed-order sums that the token heads share
-// (token_heads.hip: sampling, log-probabilities, statistics; policy_loss.hip; preference.hip: the log-probabilities' backward; distill.hip: two rows per wave).
+// (token_heads.hip: sampling, log-probabilities, statistics; policy_loss.hip; preference.hip: the log-probabilities' backward; distill.hip: two rows per wave; xent.hip: the supervised loss).
 // A workgroup of 256 threads takes four rows, wave by wave.  A lane holds NV values of its row as NV/4 chunks of 16 bytes: code
 // k = c*256 + lane*4 + e is element e of chunk c, register c*4 + e.  NV = 4, 8, 16, 32, 64 covers K <= 256 .. 4096 (MAGE_ROW_LADDER).
 // Every sum has one order: a lane adds its own terms in register order with explicit roundings, the lanes meet in an xor butterfly, so

@@ -996,6 +996,7 @@ class MAGE(nn.Module):
         self.context_frames = 1        # set_context: frames 0 .. k-1 of batch['images'] are given; 1: only frame 0 (off)
         self.context_prefill = True    # incremental mode: the given frames enter as ONE window; False: one position at a time, no pick
         self.last_known_mask: Optional[torch.Tensor] = None              # bool [B, L-1, h, w]: the slots the last generation was given
+        self.loss_options: Optional[dict] = None                         # set_loss: forward's supervised-loss options; None: the plain cross entropy
         self.caption_dropout = 0.0     # forward in training mode: the probability that a clip's caption is replaced by the null caption
         self.last_caption_drop: Optional[torch.Tensor] = None            # bool [B]: the clips whose caption the last forward dropped
 
@@ -1291,6 +1292,103 @@ class MAGE(nn.Module):
                 self.last_clip_policy_logprob = ops.clip_scores(st["policy_logprob"], n_clips=B)[0].view(B)
             ops.check_device_errors(images.device)
         return scores.view(B)
+
+    def _refuse_no_rows(self, who: str) -> None:
+        """The supervised-loss kernel reads rows of codebook_size logits as 16-byte vectors: a token model whose codebook is a multiple of 4."""
+        if not self.use_cids:
+            raise ValueError(f"{who}: a use_cids=False (MAGE+) model regresses continuous latents; it has no token probabilities")
+        if self.codebook_size % 4 != 0:
+            raise ValueError(f"{who}: codebook_size={self.codebook_size} must be a multiple of 4 (mage_token_xent reads 16-byte vectors)")
+
+    def set_loss(self, label_smoothing: float = 0.0, z_loss: float = 0.0, class_weights: Optional[torch.Tensor] = None) -> "MAGE":
+        """The options of forward's supervised next-token loss (mage_token_xent, include/mage_hip_ext.h), F.cross_entropy's own:
+        label_smoothing in [0, 1): every token's target is (1 - eps) one-hot + eps / K uniform;
+        z_loss >= 0: the loss gains z_loss * mean(logsumexp(logits)^2), which keeps the logits' scale near log Z = 0;
+        class_weights fp32 [codebook_size], finite, >= 0, at least one > 0 (mage_amd.utils.glue.balanced_class_weights): token k's term is
+        weighted by class_weights[k] and the mean is a weighted mean (F.cross_entropy's weight=).  They are kept on the model's device.
+        With any of them set, forward ends in the SupervisedHead (modules/mage_train.py) in both grad modes and its loss dict gains 'nll' (the
+        plain mean negative log-likelihood, comparable across settings) and 'accuracy'.  set_loss() restores the defaults: forward is then
+        the plain cross entropy again, launch for launch.  evaluate ignores these options: it measures the model, not the objective."""
+        for name, v, hi in (("label_smoothing", label_smoothing, 1.0), ("z_loss", z_loss, 3.4e38)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and 0.0 <= v < hi):
+                raise ValueError(f"set_loss: {name} must be a finite number in [0, {'1' if hi == 1.0 else 'inf'}), got {v!r}")
+        w = class_weights
+        if w is not None:
+            K = self.codebook_size
+            if not (torch.is_tensor(w) and w.dtype == F32 and tuple(w.shape) == (K,) and bool(torch.isfinite(w).all()) and bool((w >= 0).all())
+                    and bool((w > 0).any())):
+                raise ValueError(f"set_loss: class_weights must be fp32 [{K}], finite, >= 0 and somewhere > 0")
+        if label_smoothing == 0 and z_loss == 0 and w is None:
+            self.loss_options = None
+            return self
+        self._refuse_no_rows("set_loss")
+        if w is not None:
+            w = w.detach().to(next(self.parameters()).device).contiguous().clone()
+        self.loss_options = dict(label_smoothing=float(label_smoothing), z_loss=float(z_loss), class_weights=w)
+        return self
+
+    def _supervised_head(self, batch):
+        """forward's loss head: None (the model's own: the plain cross entropy or MSE) unless set_loss set an option or the batch carries
+        'given' (bool [B, L-1, h, w], last_known_mask's layout: the slots left out of the loss); then the SupervisedHead.  Refusals before
+        any launch."""
+        given = batch.get("given")
+        if self.loss_options is None and given is None:
+            return None
+        from . import mage_train
+        self._refuse_no_rows("forward")
+        images = batch["images"]
+        given = self._given_mask("forward", given, (images.shape[0], self.frames_length - 1, self.image_resolution, self.image_resolution),
+                                 images.device if images.is_cuda else None)
+        o = dict(self.loss_options or {})
+        w = o.get("class_weights")
+        if w is not None and w.device != images.device:
+            w = w.to(images.device)
+            self.loss_options["class_weights"] = w       # (the model has moved since set_loss)
+            o["class_weights"] = w
+        return mage_train.SupervisedHead(None, given=None if given is None else given.reshape(-1), **o)
+
+    @torch.no_grad()
+    def evaluate(self, batch, topk=(1, 5), given=None) -> dict:
+        """What the model predicts on the batch's own video, token by token: one teacher-forced pass (score's) ending in mage_token_xent with
+        every option off, under no_grad.  Returns device tensors:
+          'nll' (the mean negative log-likelihood of the free tokens, nats), 'perplexity' (exp nll), 'accuracy' (the share of free tokens the
+          argmax predicts), 'mean_rank' (the mean rank of the true code among the K logits; 0: always first), all 0-dim fp32;
+          'topk_accuracy': {k: 0-dim fp32, the share of free tokens whose true code is among the k largest logits} for k in topk;
+          'frame_nll', 'frame_accuracy': fp32 [L-1], the same means per frame over the frame's free tokens (a frame without one: 0) -- how
+          exposure bias shows along a clip;
+          'token_nll' fp32 and 'token_rank' int32, [B, L-1, h, w]: -last_token_logprobs of score, bit for bit, and each true code's rank.
+        given (bool [B, L-1, h, w], slot i is frame i + 1): slots to leave out, e.g. the context of a continuation; their token values are 0.
+        set_loss is ignored (the model is measured, not the objective); guidance and given frames or tokens are refused as by score.  The
+        per-frame and top-k reductions are torch ops on the per-token tensors."""
+        self._refuse_no_rows("evaluate")
+        self._refuse_guided("evaluate")
+        self._refuse_known("evaluate", batch)
+        K = self.codebook_size
+        if not (isinstance(topk, (tuple, list)) and len(topk) > 0
+                and all(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= K for k in topk)):
+            raise ValueError(f"evaluate: topk must be a non-empty tuple of ints in [1, {K}], got {topk!r}")
+        images = batch["images"]
+        B, Lm1, R = images.shape[0], self.frames_length - 1, self.image_resolution
+        given = self._given_mask("evaluate", given, (B, Lm1, R, R), images.device if images.is_cuda else None)
+        if not images.is_cuda:
+            raise ValueError("evaluate: batch['images'] must be on the model's ROCm GPU (there is no CPU / PyTorch fallback)")
+        with torch.cuda.device(images.device), weights_frozen():
+            tok, logits = self.teacher_forced_logits(batch)
+            tgt = tok[:, 1:].reshape(-1).contiguous()
+            res = ops.token_xent(logits.reshape(-1, K), tgt, given=None if given is None else given.reshape(-1))
+            ops.check_device_errors(images.device)
+            tshape = (B, Lm1, R, R)
+            nll_t, rank_t = res["row_nll"].view(tshape), res["rank"].view(tshape)
+            free = torch.ones(tshape, device=images.device, dtype=torch.bool) if given is None else ~given
+            # (integer counts and fp64 sums of a few thousand values, rounded once to fp32)
+            n_all, n_frame = free.sum().clamp(min=1).double(), free.sum((0, 2, 3)).clamp(min=1).double()
+            hit = lambda k: free & (rank_t < k)      # noqa: E731
+            nll = res["summary"][1].clone()
+            return {"nll": nll, "perplexity": nll.exp(), "accuracy": res["summary"][2].clone(),
+                    "mean_rank": ((rank_t * free).sum().double() / n_all).to(F32),
+                    "topk_accuracy": {int(k): (hit(k).sum().double() / n_all).to(F32) for k in topk},
+                    "frame_nll": ((nll_t.double() * free).sum((0, 2, 3)) / n_frame).to(F32),
+                    "frame_accuracy": (hit(1).sum((0, 2, 3)).double() / n_frame).to(F32), "token_nll": nll_t, "token_rank": rank_t}
 
     def policy_loss(self, batch, tokens, advantages, behaviour_logprobs=None, *, clip=0.2, entropy_coef: float = 0.0, reference_logprobs=None,
                     kl_coef: float = 0.0, given=None, ratio: str = "token"):
@@ -2681,12 +2779,12 @@ class MAGE(nn.Module):
         tgt = rows[:, 1:L].contiguous().view(-1, LD)
         return ops.mse(pred, tgt, rows=B * (L - 1) * hw, cols=E, lda=pred.shape[1], ldb=LD), pred
 
-    def _forward_with_graph(self, batch):
+    def _forward_with_graph(self, batch, head=None):
         """Grad mode (the training loop, main_mage.py:150-153): the same pass as one autograd node whose inputs are the trainable
         parameters (mage_train.MageLossFn, through _run_head), so that ``loss.backward()`` fills every ``.grad`` from the HIP backward kernels."""
         _need_gpu(batch["images"], "MAGE.forward")
         with torch.cuda.device(batch["images"].device):
-            loss, (parts, _) = self._run_head(batch, None)
+            loss, (parts, _) = self._run_head(batch, head)
             prefix = "train" if self.training else "val"
             ops.check_device_errors(batch["images"].device)
         return loss, {f"{prefix}/{k}": v for k, v in parts.items()}
@@ -2728,21 +2826,28 @@ class MAGE(nn.Module):
         batch['caption_drop'] (bool [B], optional) replaces the draw and applies in either mode.  last_caption_drop keeps the mask (None when
         nothing was dropped or drawn).  p = 0 (the default) and no mask: the call is the one it was."""
         batch = self._drop_captions(batch)
+        head = self._supervised_head(batch)              # None: the plain loss; set_loss / batch['given']: mage_token_xent (see set_loss)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if test_flag and self.randomness:
                 raise NotImplementedError("forward(test_flag=True) is an evaluation switch (mage_model.py:604): call it under torch.no_grad()")
-            return self._forward_with_graph(batch)
+            return self._forward_with_graph(batch, head)
         batch = dict(batch, _test_flag=bool(test_flag and self.randomness))      # :604: the video embedding is replaced by noise
         extras: dict = {}
         L = self.frames_length
         if self.use_cids:
             tok, logits = self.teacher_forced_logits(batch, extras)
-            recon = ops.cross_entropy(logits.reshape(-1, self.codebook_size), tok[:, 1:L].reshape(-1).contiguous())   # :618
+            logits, tgt, more = logits.reshape(-1, self.codebook_size), tok[:, 1:L].reshape(-1).contiguous(), {}
+            if head is None:
+                recon = ops.cross_entropy(logits, tgt)                                                                # :618
+            else:
+                recon, more, _ = head.forward(self, logits, tgt, batch["images"].shape[0])
         else:
             _need_gpu(batch["images"], "MAGE.forward")
             recon, self.last_logits = self._forward_latent(batch, extras)                                            # :620
         prefix = "train" if self.training else "val"
         ld = {f"{prefix}/prediction": recon.item()}
+        if self.use_cids:
+            ld.update({f"{prefix}/{k}": v for k, v in more.items()})       # the SupervisedHead's parts ('prediction' again, 'nll', 'accuracy', ...)
         final = recon
         if self.randomness:
             kl = -0.5 * extras["kl_sum"].mean()                                               # :623 (a [B]-element reduction)

@@ -613,6 +613,29 @@ class CrossEntropyHead:
         return ops.cross_entropy_bwd(logits, target, gout, _dlogits(logits, dt))
 
 
+class SupervisedHead:
+    """forward on a use_cids model after MAGE.set_loss, or with batch['given']: mage_token_xent (include/mage_hip_ext.h) -- the cross entropy
+    of CrossEntropyHead with class_weights (fp32 [K] or None), label_smoothing, a z_loss and given (bool per token, or None: the token's row
+    is left out, F.cross_entropy's ignore_index).  tokens None: the pass runs over the batch's own video and forward's randomness terms are
+    added on top, as for CrossEntropyHead.  parts: 'prediction' (the objective), 'nll' (the plain mean negative log-likelihood of the free
+    tokens), 'accuracy' (the share of them the argmax predicts) and, with a mask, 'given_fraction'.  saved: the kernel's results."""
+
+    def __init__(self, tokens=None, *, label_smoothing=0.0, z_loss=0.0, class_weights=None, given=None):
+        self.tokens, self.given = tokens, given
+        self.opts = dict(label_smoothing=float(label_smoothing), z_loss=float(z_loss), class_weight=class_weights)
+
+    def forward(self, model, logits, target, B):
+        res = ops.token_xent(logits, target, given=self.given, rank=False, **self.opts)
+        s = res["summary"].tolist()
+        parts = {"prediction": s[0], "nll": s[1], "accuracy": s[2]}
+        if self.given is not None:
+            parts["given_fraction"] = s[4]
+        return res["summary"][0], parts, res
+
+    def backward(self, logits, target, saved, gout, dt):
+        return ops.token_xent_bwd(logits, target, saved["norm"], gout, _dlogits(logits, dt), given=self.given, **self.opts)
+
+
 class MseHead:
     """forward on a MAGE+ model (mage_model.py:620): `logits` are the predicted latents, kept as model.last_logits."""
     tokens = None

@@ -16,7 +16,7 @@ from ._lib import ACT_GELU_ERF, ACT_NONE, ACT_QUICKGELU, ACT_QUICKGELU_GRAD, ACT
 
 __all__ = ["gemm", "layernorm", "attention", "embedding", "table_conv", "split_rows", "vq_prepare", "vq_nearest", "argmax", "cross_entropy",
            "conv_in", "conv_out", "convt_fold_tanh", "row_affine", "groupnorm_silu", "groupnorm_act", "reparam_kl", "mse", "check_device_errors", "graph_events_supported", "transpose", "row_sum", "sum_partials", "layernorm_bwd", "dropout_add_layernorm", "act", "act_bwd", "cross_entropy_bwd", "embedding_bwd", "code_stats", "code_stats_chunks", "codebook_ema", "group_rowsum", "attention_bwd", "dropout", "adam", "adam_clipped", "adam_guarded", "sumsq", "bn_train_stats", "bn_apply", "bn_backward", "convt_unfold_tanh_bwd", "maxpool2", "upsample2", "relu", "cast", "adain", "add_scaled_rowvec",
-           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "frame_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
+           "token_logprob", "clip_scores", "video_metrics", "group_advantages", "frame_advantages", "policy_loss", "policy_loss_bwd", "preference_loss", "token_logprob_bwd", "distill_loss", "distill_loss_bwd", "token_xent", "token_xent_bwd", "split", "split_empty", "split_dtype", "PROFILE", "F32", "BF16", "F16", "BF16X3", "F16X3", "ACT_NONE", "ACT_RELU", "ACT_QUICKGELU", "ACT_GELU_ERF", "ACT_TANH", "tdtype", "code"]
 
 
 def code(t: torch.Tensor) -> int:
@@ -956,6 +956,52 @@ def distill_loss_bwd(logits: torch.Tensor, teacher: torch.Tensor, row_kl: torch.
     _lib.check(l.mage_distill_loss_bwd(logits.data_ptr(), rows, K, logits.stride(0), teacher.data_ptr(), teacher.stride(0), float(temperature),
                                        int(mode), _p(given), row_kl.data_ptr(), grad_out.data_ptr(), norm.data_ptr(), dlogits.data_ptr(),
                                        code(dlogits), s), l)
+    return dlogits
+
+
+def _xent_args(logits, target, class_weight, given):
+    """The asserts token_xent and token_xent_bwd share; returns (rows, K)."""
+    _given_rows(given, logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows, K = logits.shape
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows and target.device == logits.device
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and class_weight.is_contiguous() and tuple(class_weight.shape) == (K,)
+        assert class_weight.device == logits.device
+    return rows, K
+
+
+def token_xent(logits: torch.Tensor, target: torch.Tensor, *, class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+               z_loss: float = 0.0, given: Optional[torch.Tensor] = None, rank: bool = True) -> dict:
+    """mage_token_xent over logits [rows, K] fp32 (row stride >= K) and target int64 [rows]: F.cross_entropy(weight=class_weight (fp32 [K]),
+    label_smoothing=) per row with the rows of `given` (bool [rows]) left out as by ignore_index, plus z_loss * mean(logsumexp^2).  Returns
+    fp32 'row_loss', 'row_nll' (= -token_logprob, bit for bit), 'row_lse' [rows], int32 'rank' [rows] (the target's rank among the row's
+    logits, 0: the argmax; None with rank=False), 'summary' [5] (the objective, the mean nll, the accuracy, the mean lse^2, the given share)
+    and 'norm' [2] (1 / the free rows' weight, 1 / their number), token_xent_bwd's input."""
+    rows, K = _xent_args(logits, target, class_weight, given)
+    l, s = _dev(logits)
+    mk = lambda n: torch.empty(n, device=logits.device, dtype=torch.float32)      # noqa: E731
+    out = dict(row_loss=mk(rows), row_nll=mk(rows), row_lse=mk(rows),
+               rank=torch.empty(rows, device=logits.device, dtype=torch.int32) if rank else None, summary=mk(5), norm=mk(2))
+    _lib.check(l.mage_token_xent(logits.data_ptr(), rows, K, logits.stride(0), target.data_ptr(), _p(class_weight), float(label_smoothing),
+                                 float(z_loss), _p(given), out["row_loss"].data_ptr(), out["row_nll"].data_ptr(), out["row_lse"].data_ptr(),
+                                 _p(out["rank"]), out["summary"].data_ptr(), out["norm"].data_ptr(), s), l)
+    return out
+
+
+def token_xent_bwd(logits: torch.Tensor, target: torch.Tensor, norm: torch.Tensor, grad_out: torch.Tensor, dlogits: torch.Tensor, *,
+                   class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0, z_loss: float = 0.0,
+                   given: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mage_token_xent_bwd: dlogits [rows, K] contiguous fp32 or bf16, the gradient of grad_out (fp32 [1]) times token_xent's summary[0] with
+    respect to the logits, from token_xent's inputs and its 'norm'."""
+    rows, K = _xent_args(logits, target, class_weight, given)
+    l, s = _dev(logits)
+    assert norm.dtype == torch.float32 and norm.numel() == 2 and norm.is_contiguous() and norm.device == logits.device
+    assert grad_out.dtype == torch.float32 and grad_out.numel() == 1 and grad_out.device == logits.device
+    assert dlogits.dtype in (torch.float32, torch.bfloat16) and dlogits.is_contiguous() and dlogits.numel() == rows * K
+    assert dlogits.device == logits.device
+    _lib.check(l.mage_token_xent_bwd(logits.data_ptr(), rows, K, logits.stride(0), target.data_ptr(), _p(class_weight), float(label_smoothing),
+                                     float(z_loss), _p(given), grad_out.data_ptr(), norm.data_ptr(), dlogits.data_ptr(), code(dlogits), s), l)
     return dlogits
 
 

@@ -86,6 +86,24 @@ def null_caption(text: torch.Tensor, padding_idx: int = 0) -> torch.Tensor:
     return torch.where(keep.sum(1, keepdim=True) >= 2, null, text)
 
 
+def balanced_class_weights(counts: torch.Tensor, power: float = 0.5) -> torch.Tensor:
+    """Class weights for MAGE.set_loss from how often each code occurs (VectorQuantizedVAE.code_usage(ids)['counts'], int64 [K]): fp32 [K]
+    on the counts' device with w_k proportional to count_k ** -power over the codes that occur and w_k = 0 for the others, scaled so that the
+    count-weighted mean weight is 1 (sum_k count_k w_k == sum_k count_k: the weighted loss keeps the unweighted one's scale).  power = 0
+    leaves every used code at 1, power = 1 gives every used code the same total weight; 0.5 lies between.  A few elementwise torch ops in
+    fp64: nothing is read on the host."""
+    if not (torch.is_tensor(counts) and counts.dim() == 1 and counts.numel() > 0 and not counts.is_floating_point() and not counts.is_complex()
+            and counts.dtype != torch.bool):
+        raise ValueError("balanced_class_weights: counts must be an integer tensor [K] (code_usage(ids)['counts'])")
+    if isinstance(power, bool) or not isinstance(power, (int, float)) or not (np.isfinite(power) and power >= 0):
+        raise ValueError(f"balanced_class_weights: power must be finite and >= 0, got {power!r}")
+    c = counts.to(torch.float64)
+    used = c > 0
+    w = torch.where(used, c.clamp(min=1.0) ** -float(power), torch.zeros_like(c))
+    total = (c * w).sum()
+    return (w * (c.sum() / total.clamp(min=1e-300))).to(torch.float32)
+
+
 _MOTIONS = ["up then down", "left then right", "down then up", "right then left"]        # data/mnist_caption_single.py:30
 
 
